@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the VidToMe token-merging hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 Metric (BASELINE.json): denoising steps/sec for a 16-frame 512x512 SD-1.5 chunk, merge ratio 0.5.
 A *step* is one pass of the hot path over one chunk: the patched self-attention segment
@@ -80,6 +80,7 @@ HEADLINE_REGIME = "corr01"
 # read its counters a call later; in a real run that happens once per 256 calls of a level, in a ten-pass region it would be a
 # tenth of the time
 REGIME_WARMUP = 5
+DUMP_BYTES = 48 << 20             # --dump-outputs: total size of the written arrays (float32)
 REGIME_NOTES = {
     "n01": "h ~ N(0,1), frames uncorrelated (SURVEY 8d)",
     "corr01": "h[f] = base + 0.1 N(0,1) (SURVEY 8d: realistic cross-frame cosine)",
@@ -148,7 +149,38 @@ def parse():
                          "phase, peer) and exits with code 3 (0 = off)")
     ap.add_argument("--event-every", type=int, default=5,
                     help="record HIP events around the hot launches on every k-th timed pass (the others are event-free)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the headline region, write what its LAST timed pass returned (the output of every site) as "
+                         "DIR/<name>.npy in float32 (whole when small, else a fixed seeded sample of token rows, all channels; "
+                         f"{DUMP_BYTES >> 20} MB in all) plus DIR/moments.npy over every element.  Same arguments -> same "
+                         "inputs, so two builds compare output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def dump_outputs(outs, site_list, out_dir: str, rank: int, world: int) -> None:
+    """`outs`: the per-site (B*F, N, C) outputs of one pass.  Each site gets an equal share of DUMP_BYTES (split over the
+    ranks too); a site whose output is larger keeps the token rows numpy.random.default_rng(site index) picks, in row
+    order -- the same rows for the same shapes on every run.  `moments.npy` (float64, one row per site: sum, sum |x|,
+    sum x^2, max |x|) covers every element of the outputs, sampled or not."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // (len(outs) * world)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    moments = []
+    for i, (o, s_) in enumerate(zip(outs, site_list)):
+        rows = o.reshape(-1, o.shape[-1])
+        x = rows.double()
+        moments.append([x.sum().item(), x.abs().sum().item(), (x * x).sum().item(), x.abs().max().item()])
+        del x
+        keep = max(1, share // (4 * rows.shape[1]))
+        if keep < rows.shape[0]:
+            pick = np.sort(np.random.default_rng(i).choice(rows.shape[0], keep, replace=False))
+            rows = rows[torch.from_numpy(pick).to(rows.device)]
+        np.save(os.path.join(out_dir, f"{prefix}site{i:02d}_{s_.name}.npy"), rows.float().cpu().numpy())
+    np.save(os.path.join(out_dir, f"{prefix}moments.npy"), np.array(moments, dtype=np.float64))
 
 
 def self_launch(args) -> int:
@@ -685,10 +717,11 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def run_region(regime, steps, warmup, xmode, with_box, inflight=1):
+    def run_region(regime, steps, warmup, xmode, with_box, inflight=1, dump=False):
         """One measured region: a fresh chunk stream of `regime`, anchors populated, `warmup` untimed and `steps` timed passes
         between two fences (barrier + synchronize), HIP events on every `every`-th pass, one extra untimed pass for the
-        matcher's device-side counters.  Returns everything the line is built from."""
+        matcher's device-side counters.  Returns everything the line is built from.  With `dump`, what the last timed pass
+        returned goes to --dump-outputs."""
         total_passes = 1 + warmup + steps
         for b in unet.blocks:                       # a region starts like a denoising step: no anchors
             b.global_tokens = None
@@ -751,13 +784,18 @@ def main():
                 if mt.enabled:                        # ... bracketed as a whole too: what the itemised kernels leave is gaps
                     pe0, pe1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     pe0.record()
-                step()
+                if dump and i == steps - 1:      # (earlier passes' outputs are dropped at once, as without the dump)
+                    last = step()
+                else:
+                    step()
                 if mt.enabled:
                     pe1.record()
                     pass_events.append((pe0, pe1))
             mt.enabled = False
             fence()
             dt = time.perf_counter() - t0
+            if dump:                                  # sampled before the counter pass below can touch any shared buffer
+                dump_outputs(last, site_list, args.dump_outputs, rank, world)
             event_pass_ms = sum(a.elapsed_time(b) for a, b in pass_events) / max(1, len(pass_events))
             if ex is None:                            # one untimed pass for the matcher's counters (N = 1: the chunk stream
                 mt.count = True                       # of an exchange has no spare chunk)
@@ -799,7 +837,8 @@ def main():
                 "pruned_block_fraction": cnt.get("pruned_block_fraction"),
                 "executed_mfma_fraction": cnt.get("executed_mfma_fraction")}
 
-    head = run_region(args.data, args.steps, args.warmup, mode, True, inflight=max(1, args.inflight) if world == 1 else 1)
+    head = run_region(args.data, args.steps, args.warmup, mode, True, inflight=max(1, args.inflight) if world == 1 else 1,
+                      dump=args.dump_outputs is not None)
     mt, dt, box = head["mt"], head["dt"], head["box"]
     timed_passes, total_passes, event_pass_ms = head["timed_passes"], head["total_passes"], head["event_pass_ms"]
     aflops, ams, an = mt.summary("attention")

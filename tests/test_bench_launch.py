@@ -131,3 +131,49 @@ def test_bench_secondary_workloads(workload):
     assert d["config"]["batch"] == (3 if workload == "cfg3" else 2)
     assert d["roofline"]["achieved"] > 0 and d["matching"]["matching_ms_per_step"] > 0
     assert d["components_ms_per_step"]["attention"] > 0
+
+
+def test_dump_outputs_is_bounded_and_repeatable(tmp_path):
+    """--dump-outputs on cfg-2-shaped host tensors: float32 samples under the 64 MB bound, the same rows on every call, and
+    moments over every element."""
+    import importlib.util
+    import numpy as np
+    from vidtome_amd import sites
+    spec = importlib.util.spec_from_file_location("bench_under_test", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    site_list = sites.sd15_sites()
+    g = torch.Generator().manual_seed(0)
+    outs = [torch.randn(32, (64 // s.downsample) ** 2, s.channels, generator=g).half() for s in site_list]
+    for d in ("a", "b"):
+        bench.dump_outputs(outs, site_list, str(tmp_path / d), 0, 1)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert len(names) == len(site_list) + 1 and names == sorted(os.listdir(tmp_path / "b"))
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 << 20
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == (np.float64 if n == "moments.npy" else np.float32) and np.array_equal(a, b), n
+    m = np.load(tmp_path / "a" / "moments.npy")
+    for i, o in enumerate(outs):
+        x = o.double()
+        assert np.allclose(m[i], [x.sum(), x.abs().sum(), (x * x).sum(), x.abs().max()]), i
+        rows = np.load(tmp_path / "a" / f"site{i:02d}_{site_list[i].name}.npy")
+        flat = o.reshape(-1, o.shape[-1]).float().numpy()
+        assert rows.shape[1] == flat.shape[1] and (flat[:, None, :] == rows[None, :8, :]).all(-1).any(0).all(), i
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_same_inputs_same_outputs(tmp_path):
+    """Two runs with the same arguments dump the same last-pass outputs; --steps is the number of timed passes."""
+    import numpy as np
+    argv = ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--regimes", "none", "--workloads", "none",
+            "--no-inflight-line", "--dump-outputs"]
+    for d in ("a", "b"):
+        line = _line(_run(argv + [str(tmp_path / d)]))
+        assert line["steps"] == 2 and line["timing"].startswith("value = 2 passes")
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert len(names) == 17 and names == sorted(os.listdir(tmp_path / "b"))
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 << 20
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all() and np.array_equal(a, b), n
