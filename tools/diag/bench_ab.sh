@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of environment switches on the headline bench region, same box, interleaved repetitions.
-#   bash tools/diag/bench_ab.sh "VTM_ATT16=0" "VTM_ATT16=1" ...
+#   bash tools/diag/bench_ab.sh "VIDTOME_FOLD_KEYS=0" "VIDTOME_FOLD_KEYS=1" ...
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 for rep in 1 2 3; do
   for env in "$@"; do

@@ -621,67 +621,10 @@ __global__ __launch_bounds__(waves_for(D) * 64, (D <= 48 ? 4 : D <= 96 ? 4 : 1))
         write_output<T, D>(o, l_run, out, ldo, b, h, q0, M, Mp, l31, hi);
 }
 
-// Tail plan.  All workgroups of a launch take the same time, so the launch runs in "rounds" of as many workgroups
-// as the chip holds (slots); the last, partly filled round leaves most CUs idle for a whole workgroup time (cfg-2
-// mid blocks: 272 workgroups on 256 slots -> two rounds for 6 % more work than one; top blocks: 4.25 rounds).  The
-// work items of that last round are therefore split along the key axis into `nsplit` shorter workgroups that fill
-// the chip -- in the SAME launch, behind the whole ones, so they start as the slots of the last whole round free
-// up -- and merged by attention_combine_kernel.
-// `bounded`: the launch carries a device-side query count (vtm_attention_kv_bounded: compacted live queries).  How many
-// of its workgroups do real work is not known when it is launched -- the cfg-2 top block launches 2 176 for ~1 800 live
-// ones, 3.5 rounds of 512 that cost 4 -- so the round structure cannot be planned.  It is made finer instead: EVERY
-// work item is split in two along the key axis (split-major order), the live ones then fill 7 half-length rounds
-// (profiles/r04_attention_split_all.txt); the price is one partial record per workgroup for attention_combine_kernel.
-template <int D>
-TailPlan plan_tail(int64_t B, int64_t h, int64_t Mq, int64_t Mk, bool bounded = false) {
-    constexpr int WAVES = waves_for(D), QB = WAVES * QW;
-    constexpr int wg_per_cu = D <= 48 ? 2 : 1;   // resident workgroups per CU (launch bounds / LDS)
-    TailPlan p;
-    p.nqb = vtm::cdiv(Mq, QB);
-    p.total = p.nqb * h * B;
-    const int64_t slots = (int64_t)vtm::device_cus() * wg_per_cu;
-    p.full = p.total / slots * slots;
-    const int64_t rem = p.total - p.full, ntiles = vtm::cdiv(Mk, KV);
-    p.nsplit = 1;
-    p.ws_bytes = 0;
-    p.split_all = false;
-    if (bounded && p.total >= 2 * slots && ntiles >= 64 && p.total % 8 == 0) {
-        p.full = 0;
-        p.nsplit = 2;
-        p.split_all = true;
-        p.ws_bytes = (size_t)p.total * 2 * rec_floats(D) * (WAVES * 64) * sizeof(float);
-        return p;
-    }
-    // worth it only behind at least one whole round, for long key axes, and when the last round is at most a
-    // quarter full (a workgroup that has its CU to itself already runs about twice as fast as in a full round;
-    // measured: 128 of 512 -> -7 %, 16 of 256 -> -18 %, 192 or 256 of 512 -> no gain)
-    if (p.full > 0 && rem > 0 && rem * 4 <= slots && ntiles >= 32) {
-        int64_t ns = slots / rem;
-        if (ns > 16) ns = 16;
-        if (ns > ntiles / 8) ns = ntiles / 8;
-        if (ns >= 2) {
-            p.nsplit = (int)ns;
-            p.ws_bytes = (size_t)rem * ns * rec_floats(D) * (WAVES * 64) * sizeof(float);
-        }
-    }
-    if (p.nsplit == 1) p.full = p.total;
-    return p;
-}
-
-bool devplan_on() {
-    static const bool on = [] {
-        const char *e = getenv("VTM_ATT_DEVPLAN");      // A/B hook, read once per process
-        return e == nullptr || atoi(e) != 0;
-    }();
-    return on;
-}
-// workspace of a device-planned query-bounded launch of attention_kernel<D>
-template <int D>
-size_t devplan_ws(int64_t Mk) {
-    if (!devplan_on() || vtm::cdiv(Mk, KV) < 16) return 0;
-    const int slots = vtm::device_cus() * (D <= 48 ? 2 : 1);
-    return 256 + (size_t)plan_tail_wgs(slots) * rec_floats(D) * (waves_for(D) * 64) * sizeof(float);
-}
+// attention_kernel<D> for the planners: resident workgroups per CU (launch bounds / LDS), the partial record of a key-split
+// workgroup
+constexpr int wg_per_cu_for(int D) { return D <= 48 ? 2 : 1; }
+constexpr size_t rec_bytes_for(int D) { return (size_t)rec_floats(D) * (waves_for(D) * 64) * sizeof(float); }
 
 template <typename T, int D, bool FOLD = false>
 int launch(const void *q, int64_t ldq, const void *k, int64_t ldk, const void *vt, int64_t ldvt, void *out,
@@ -701,43 +644,40 @@ int launch(const void *q, int64_t ldq, const void *k, int64_t ldk, const void *v
             attr_set[dev].store(true, std::memory_order_release);
         }
     }
-    constexpr int WAVES = waves_for(D);
-    const float scale_log2e_ = scale * 1.4426950408889634f;
+    constexpr int WAVES = waves_for(D), QB = WAVES * QW;
+    const float scale_log2e = scale * 1.4426950408889634f;
     // (round 6) a query-bounded launch is planned ON THE DEVICE from the live counts when the workspace holds the plan and
     // the records of the largest tail a plan can have (vtm_attention_kv_bounded_ws_bytes): whole items, then tiers split
-    // 2 .. 16 ways -- rounds 4-5 split every item in two (VTM_ATT_DEVPLAN=0 keeps that plan)
-    if (q_count != nullptr && ws != nullptr && devplan_on()) {
-        const int slots = vtm::device_cus() * (D <= 48 ? 2 : 1);
-        const size_t rec_bytes = (size_t)rec_floats(D) * (WAVES * 64) * sizeof(float);
-        constexpr int QB = WAVES * QW;
-        // (launches of at least two rounds: the oversized grid and the two small launches of a plan cost 50-70 us, which a
-        // one-round launch does not get back -- profiles/r06_k_devplan_attention_kernel.txt)
-        if (ws_bytes >= 256 + (size_t)plan_tail_wgs(slots) * rec_bytes && vtm::cdiv(M, QB) * h * B >= 2 * slots) {
-            DevPlan *plan = reinterpret_cast<DevPlan *>(ws);
-            float *records = reinterpret_cast<float *>(static_cast<char *>(ws) + 256);
-            const int64_t nqb_max = vtm::cdiv(M, QB), total = nqb_max * h * B, tail_max = plan_tail_wgs(slots);
-            VTM_REQUIRE(total + tail_max < (1ll << 31) / 16, "vtm_attention: grid too large");
-            const int xcd_pairs = (B * h) % 8 == 0 ? (int)(B * h / 8) : 0;
-            hipLaunchKernelGGL(attention16_plan_kernel, dim3(1), dim3(64), 0, s, q_count, (int)B, (int)h, QB, slots,
-                               (int)vtm::cdiv(Mk, KV), plan);
-            hipLaunchKernelGGL((attention_kernel<T, D, FOLD>), dim3((unsigned)(total + tail_max)), dim3(WAVES * 64), lds, s,
-                               (const T *)q, ldq, (const T *)k, ldk, (const T *)vt, ldvt, (T *)out, ldo, h, M, Mp, Mk, Mkp,
-                               scale_log2e_, B / share_groups, nqb_max, total, 1, records, xcd_pairs, q_count, (int64_t)0, k_count,
-                               k_bias, ldkb, (const DevPlan *)plan);
-            hipLaunchKernelGGL((attention_combine_kernel<T, D>), dim3((unsigned)plan_split_items(slots)), dim3(WAVES * 64), 0, s,
-                               (const float *)records, (T *)out, ldo, h, M, Mp, nqb_max, total, 1, xcd_pairs, q_count,
-                               (const DevPlan *)plan);
-            return vtm::launch_status("vtm_attention");
-        }
+    // 2 .. 16 ways -- rounds 4-5 split every item in two (plan_tail's `bounded`, still the plan of a smaller workspace)
+    // (launches of at least two rounds: the oversized grid and the two small launches of a plan cost 50-70 us, which a
+    // one-round launch does not get back -- profiles/r06_k_devplan_attention_kernel.txt)
+    const int slots = vtm::device_cus() * wg_per_cu_for(D);
+    if (q_count != nullptr && ws != nullptr && ws_bytes >= devplan_ws_bytes(slots, rec_bytes_for(D)) &&
+        vtm::cdiv(M, QB) * h * B >= 2 * slots) {
+        DevPlan *plan = reinterpret_cast<DevPlan *>(ws);
+        float *records = reinterpret_cast<float *>(static_cast<char *>(ws) + DEVPLAN_HEADER);
+        const int64_t nqb_max = vtm::cdiv(M, QB), total = nqb_max * h * B, tail_max = plan_tail_wgs(slots);
+        VTM_REQUIRE(total + tail_max < (1ll << 31) / 16, "vtm_attention: grid too large");
+        const int xcd_pairs = (B * h) % 8 == 0 ? (int)(B * h / 8) : 0;
+        hipLaunchKernelGGL(attention16_plan_kernel, dim3(1), dim3(64), 0, s, q_count, (int)B, (int)h, QB, slots,
+                           (int)vtm::cdiv(Mk, KV), plan);
+        hipLaunchKernelGGL((attention_kernel<T, D, FOLD>), dim3((unsigned)(total + tail_max)), dim3(WAVES * 64), lds, s,
+                           (const T *)q, ldq, (const T *)k, ldk, (const T *)vt, ldvt, (T *)out, ldo, h, M, Mp, Mk, Mkp,
+                           scale_log2e, B / share_groups, nqb_max, total, 1, records, xcd_pairs, q_count,
+                           (int64_t)0, k_count, k_bias, ldkb, (const DevPlan *)plan);
+        hipLaunchKernelGGL((attention_combine_kernel<T, D>), dim3((unsigned)plan_split_items(slots)), dim3(WAVES * 64), 0, s,
+                           (const float *)records, (T *)out, ldo, h, M, Mp, nqb_max, total, 1, xcd_pairs, q_count,
+                           (const DevPlan *)plan);
+        return vtm::launch_status("vtm_attention");
     }
-    TailPlan p = plan_tail<D>(B, h, M, Mk, q_count != nullptr);
-    if (p.split_all && (!ws || ws_bytes < p.ws_bytes)) p = plan_tail<D>(B, h, M, Mk);   // not enough workspace: the plain plan
+    TailPlan p = plan_tail(B, h, M, Mk, QB, wg_per_cu_for(D), rec_bytes_for(D), q_count != nullptr);
+    if (p.split_all && (!ws || ws_bytes < p.ws_bytes))   // not enough workspace: the plain plan
+        p = plan_tail(B, h, M, Mk, QB, wg_per_cu_for(D), rec_bytes_for(D), false);
     if (p.nsplit > 1 && (!ws || ws_bytes < p.ws_bytes)) {   // no workspace: plain single launch
         p.nsplit = 1;
         p.full = p.total;
         p.split_all = false;
     }
-    const float scale_log2e = scale * 1.4426950408889634f;
     const int64_t src_batch = B / share_groups;
     VTM_REQUIRE(p.total < (1ll << 31) / 16, "vtm_attention: grid too large");
     // one launch: the whole workgroups first, the key-split ones of the last round behind them (they start as the
@@ -773,40 +713,12 @@ int launch(const void *q, int64_t ldq, const void *k, int64_t ldk, const void *v
     return vtm::launch_status("vtm_attention");
 }
 
-// Which d = 40 launches go to the wide-tile kernel of attention16.hip, and in which shape (round 6).  VTM_ATT16=0 keeps
-// everything on attention_kernel; VTM_ATT16_NQ=1 does the same for the plain (one value group) shape only, VTM_ATT16_SKEW=0
-// selects the un-skewed kernels (4-wave workgroups were measured 18 % slower -- register spills -- and are not built).  Read
-// once per process.  Both kernels compute the same sums in the same per-tile order for a query (the split plans differ),
-// so results agree to the tolerance of the key-split combine, not bit for bit.
-struct Policy16 {
-    bool on, skew;
-    int nq, waves;
-};
-const Policy16 &policy16() {
-    static const Policy16 p = [] {
-        Policy16 v{true, true, 2, 8};
-        if (const char *e = getenv("VTM_ATT16")) v.on = atoi(e) != 0;
-        if (const char *e = getenv("VTM_ATT16_SKEW")) v.skew = atoi(e) != 0;
-        if (const char *e = getenv("VTM_ATT16_NQ")) v.nq = atoi(e) == 1 ? 1 : 2;
-        if (v.nq == 1) v.waves = 8;
-        return v;
-    }();
-    return p;
-}
-// -> true and the shape when this launch is the wide kernel's
-bool shape16_for(int64_t d, int share_groups, bool fold, Shape16 *sh) {
-    const Policy16 &p = policy16();
-    if (!p.on || d != 40) return false;
-    if (share_groups == 1) {
-        if (p.nq == 1) return false;               // (one sub-tile, one group IS attention_kernel)
-        *sh = Shape16{p.nq, 1, p.waves, p.skew};
-        return true;
-    }
-    if (!fold && (share_groups == 2 || share_groups == 3)) {   // shared probabilities: P once, one PV per sample
-        *sh = Shape16{1, share_groups, 8, p.skew};   // (skew: attention16g.hip, else attention16_kernel<NQ = 1, NG>)
-        return true;
-    }
-    return false;
+// Which launches go to the wide-tile d = 40 kernels (round 6): self-attention to attention16s_kernel (attention16.hip, which
+// also takes every folded d = 40 launch: vtm_attention_kv_folded), shared probabilities of 2 or 3 groups to attention16g_kernel
+// (attention16g.hip).  -> the value groups per wave of the wide kernel, 0 for attention_kernel
+int shape16_for(int64_t d, int share_groups, int dtype) {
+    if (d != 40 || (dtype != VTM_F16 && dtype != VTM_BF16)) return 0;
+    return share_groups <= 3 ? share_groups : 0;
 }
 
 template <typename T>
@@ -828,50 +740,45 @@ int dispatch(int64_t d, const void *q, int64_t ldq, const void *k, int64_t ldk, 
                      (long long)d);
 }
 
-}  // namespace
-
-// (d = 40: the caller does not say how the launch will share its probabilities -- the largest plan any shape could choose)
-static size_t ws16_max(int64_t B, int64_t h, int64_t Mq, int64_t Mk, bool bounded) {
-    size_t n = 0;
-    Shape16 sh;
-    for (int sg = 1; sg <= 3; ++sg)
-        if (B % sg == 0 && shape16_for(40, sg, false, &sh)) {
-            const size_t w = ws_bytes16(sh, sh.ng > 1 ? B / sg : B, h, Mq, Mk, bounded);
-            n = w > n ? w : n;
-        }
+// workspace of attention_kernel<D>: its host tail plan, or a device plan for a bounded launch over at least 16 key tiles
+template <int D>
+size_t ws_bytes_for(int64_t B, int64_t h, int64_t Mq, int64_t Mk, bool bounded) {
+    size_t n = plan_tail(B, h, Mq, Mk, waves_for(D) * QW, wg_per_cu_for(D), rec_bytes_for(D), bounded).ws_bytes;
+    if (bounded && vtm::cdiv(Mk, KV) >= 16)
+        n = std::max(n, devplan_ws_bytes(vtm::device_cus() * wg_per_cu_for(D), rec_bytes_for(D)));
     return n;
 }
 
-VTM_EXPORT size_t vtm_attention_ws_bytes(int64_t B, int64_t h, int64_t Mq, int64_t Mk, int64_t d) {
+// d = 40: the caller does not say how the launch will share its probabilities -- the largest plan any kernel could choose
+size_t ws_bytes_any(int64_t B, int64_t h, int64_t Mq, int64_t Mk, int64_t d, bool bounded) {
     if (B <= 0 || h <= 0 || Mq <= 0 || Mk <= 0) return 0;
     switch (d) {
-        case 40: return std::max(plan_tail<40>(B, h, Mq, Mk).ws_bytes, ws16_max(B, h, Mq, Mk, false));
-        case 64: return plan_tail<64>(B, h, Mq, Mk).ws_bytes;
-        case 80: return plan_tail<80>(B, h, Mq, Mk).ws_bytes;
-        case 160: return plan_tail<160>(B, h, Mq, Mk).ws_bytes;
-        case 8: return plan_tail<8>(B, h, Mq, Mk).ws_bytes;
-        case 16: return plan_tail<16>(B, h, Mq, Mk).ws_bytes;
-        case 32: return plan_tail<32>(B, h, Mq, Mk).ws_bytes;
-        case 96: return plan_tail<96>(B, h, Mq, Mk).ws_bytes;
-        case 128: return plan_tail<128>(B, h, Mq, Mk).ws_bytes;
+        case 40: {
+            size_t n = std::max(ws_bytes_for<40>(B, h, Mq, Mk, bounded), ws_bytes16(B, h, Mq, Mk, bounded));
+            for (int ng = 2; ng <= 3; ++ng)
+                if (B % ng == 0) n = std::max(n, ws_bytes16g(ng, B / ng, h, Mq, Mk, bounded));
+            return n;
+        }
+        case 64: return ws_bytes_for<64>(B, h, Mq, Mk, bounded);
+        case 80: return ws_bytes_for<80>(B, h, Mq, Mk, bounded);
+        case 160: return ws_bytes_for<160>(B, h, Mq, Mk, bounded);
+        case 8: return ws_bytes_for<8>(B, h, Mq, Mk, bounded);
+        case 16: return ws_bytes_for<16>(B, h, Mq, Mk, bounded);
+        case 32: return ws_bytes_for<32>(B, h, Mq, Mk, bounded);
+        case 96: return ws_bytes_for<96>(B, h, Mq, Mk, bounded);
+        case 128: return ws_bytes_for<128>(B, h, Mq, Mk, bounded);
     }
     return 0;
 }
 
+}  // namespace
+
+VTM_EXPORT size_t vtm_attention_ws_bytes(int64_t B, int64_t h, int64_t Mq, int64_t Mk, int64_t d) {
+    return ws_bytes_any(B, h, Mq, Mk, d, false);
+}
+
 VTM_EXPORT size_t vtm_attention_kv_bounded_ws_bytes(int64_t B, int64_t h, int64_t Mq, int64_t Mk, int64_t d) {
-    if (B <= 0 || h <= 0 || Mq <= 0 || Mk <= 0) return 0;
-    switch (d) {
-        case 40: return std::max(std::max(plan_tail<40>(B, h, Mq, Mk, true).ws_bytes, devplan_ws<40>(Mk)), ws16_max(B, h, Mq, Mk, true));
-        case 64: return std::max(plan_tail<64>(B, h, Mq, Mk, true).ws_bytes, devplan_ws<64>(Mk));
-        case 80: return std::max(plan_tail<80>(B, h, Mq, Mk, true).ws_bytes, devplan_ws<80>(Mk));
-        case 160: return std::max(plan_tail<160>(B, h, Mq, Mk, true).ws_bytes, devplan_ws<160>(Mk));
-        case 8: return std::max(plan_tail<8>(B, h, Mq, Mk, true).ws_bytes, devplan_ws<8>(Mk));
-        case 16: return std::max(plan_tail<16>(B, h, Mq, Mk, true).ws_bytes, devplan_ws<16>(Mk));
-        case 32: return std::max(plan_tail<32>(B, h, Mq, Mk, true).ws_bytes, devplan_ws<32>(Mk));
-        case 96: return std::max(plan_tail<96>(B, h, Mq, Mk, true).ws_bytes, devplan_ws<96>(Mk));
-        case 128: return std::max(plan_tail<128>(B, h, Mq, Mk, true).ws_bytes, devplan_ws<128>(Mk));
-    }
-    return 0;
+    return ws_bytes_any(B, h, Mq, Mk, d, true);
 }
 
 static int attention_any(const void *q, int64_t ldq, const void *k, int64_t ldk, const void *vt, int64_t ldvt,
@@ -887,15 +794,12 @@ static int attention_any(const void *q, int64_t ldq, const void *k, int64_t ldk,
     VTM_REQUIRE((Mkp * ldk + d) * 2 < (1ll << 31) && (d * ldvt + Mkp) * 2 < (1ll << 31),
                 "vtm_attention: a (sample, head) slice of K or V^T must stay below 2 GiB");
     hipStream_t s = vtm::as_stream(stream);
-    Shape16 sh;
-    if ((dtype == VTM_F16 || dtype == VTM_BF16) && shape16_for(d, share_groups, false, &sh)) {
-        // the value groups of one (source sample, head) share a buffer descriptor: the sample stride rides in the offset
-        if (sh.ng == 1 || (sh.ng * (B / share_groups) * h * d * ldvt) * 2 < (1ll << 31)) {
-            const Args16 a{q, ldq, k, ldk, vt, ldvt, out, ldo, dtype, B, h, Mq, Mqp, Mk, Mkp, scale, share_groups, ws, ws_bytes,
-                           q_count, s, false, nullptr, nullptr, 0};
-            return attention16(a, sh);
-        }
-    }
+    const Args16 a{q, ldq, k, ldk, vt, ldvt, out, ldo, dtype, B, h, Mq, Mqp, Mk, Mkp, scale, share_groups, ws, ws_bytes,
+                   q_count, s, false, nullptr, nullptr, 0};
+    const int ng = shape16_for(d, share_groups, dtype);
+    if (ng == 1) return attention16(a);
+    // the value groups of one (source sample, head) share a buffer descriptor: the sample stride rides in the offset
+    if (ng > 1 && (ng * (B / share_groups) * h * d * ldvt) * 2 < (1ll << 31)) return attention16g(a, ng);
     if (dtype == VTM_F16)
         return dispatch<__half>(d, q, ldq, k, ldk, vt, ldvt, out, ldo, B, h, Mq, Mqp, Mk, Mkp, scale, share_groups, ws,
                                 ws_bytes, q_count, s);
@@ -947,18 +851,17 @@ VTM_EXPORT int vtm_attention_kv_folded(const void *q, int64_t ldq, const void *k
     VTM_REQUIRE((Mkp * ldk + d) * 2 < (1ll << 31) && (d * ldvt + Mkp) * 2 < (1ll << 31) && Mkp * 4 < (1ll << 31),
                 "vtm_attention_kv_folded: a (sample, head) slice of K or V^T must stay below 2 GiB");
     hipStream_t s = vtm::as_stream(stream);
-    Shape16 sh;
-    if ((dtype == VTM_F16 || dtype == VTM_BF16) && shape16_for(d, 1, true, &sh)) {
+    if (dtype != VTM_F16 && dtype != VTM_BF16) return vtm::fail(VTM_EINVAL, "vtm_attention_kv_folded: dtype must be VTM_F16 or VTM_BF16");
+    if (d == 40) {   // attention16s_kernel; d = 8: attention_kernel
         const Args16 a{q, ldq, k, ldk, vt, ldvt, out, ldo, dtype, B, h, Mq, Mqp, Mk, Mkp, scale, 1, ws, ws_bytes,
                        q_count, s, true, k_count, k_bias, ldkb};
-        return attention16(a, sh);
+        return attention16(a);
     }
-#define VTM_FOLDED(T, D) launch<T, D, true>(q, ldq, k, ldk, vt, ldvt, out, ldo, B, h, Mq, Mqp, Mk, Mkp, scale, 1, ws, ws_bytes, q_count, s, \
-                                            k_count, k_bias, ldkb)
-    if (dtype == VTM_F16) return d == 40 ? VTM_FOLDED(__half, 40) : VTM_FOLDED(__half, 8);
-    if (dtype == VTM_BF16) return d == 40 ? VTM_FOLDED(vtm_bf16, 40) : VTM_FOLDED(vtm_bf16, 8);
-#undef VTM_FOLDED
-    return vtm::fail(VTM_EINVAL, "vtm_attention_kv_folded: dtype must be VTM_F16 or VTM_BF16");
+    if (dtype == VTM_F16)
+        return launch<__half, 8, true>(q, ldq, k, ldk, vt, ldvt, out, ldo, B, h, Mq, Mqp, Mk, Mkp, scale, 1, ws, ws_bytes, q_count, s,
+                                       k_count, k_bias, ldkb);
+    return launch<vtm_bf16, 8, true>(q, ldq, k, ldk, vt, ldvt, out, ldo, B, h, Mq, Mqp, Mk, Mkp, scale, 1, ws, ws_bytes, q_count, s,
+                                     k_count, k_bias, ldkb);
 }
 
 VTM_EXPORT int vtm_attention(const void *q, int64_t ldq, const void *k, int64_t ldk, const void *vt,

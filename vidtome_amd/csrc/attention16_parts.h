@@ -1,7 +1,6 @@
 // Internal pieces shared by the two wide-tile d = 40 translation units (attention16.hip, attention16g.hip): the partial record of a
 // key-split workgroup, the device-side launch plan of query-bounded launches and the kernel that combines the records.
 #pragma once
-#include <cstdlib>
 #include "attention_common.h"
 
 namespace {
@@ -14,7 +13,7 @@ template <int D> constexpr int rec16() { return (D + 16) / 16 * 8 + 2 + 1; }
 
 // ---- device-side launch plan for QUERY-BOUNDED launches (vtm_attention_kv_bounded: compacted live queries) ----
 // How many query blocks are live is a device value (q_count), so the host cannot cut the launch into whole rounds plus a
-// key-split tail the way plan_tail16 does for a known length; rounds 4-5 split EVERY item in two instead (finer rounds).
+// key-split tail the way plan_tail does for a known length; rounds 4-5 split EVERY item in two instead (finer rounds).
 // Measured in round 6 (profiles/r06_d_attention16_ab.txt): 912 live items on 256 slots are 3.56 rounds of work and took the
 // time of 4 (4.81 ms against 4.31).  One thread now plans on the device, in front of the launch, from the counts -- a
 // GEOMETRIC tail: workgroups are dispatched in index order as slots free up, so pieces that shrink towards the end of the
@@ -134,12 +133,5 @@ __global__ __launch_bounds__(WAVES * 64) void attention16_combine_kernel(
 constexpr size_t DEVPLAN_HEADER = 256;
 static_assert(sizeof(DevPlan) <= 256, "the plan lives in the workspace header");
 inline size_t devplan_ws_bytes(int slots, size_t rec_bytes) { return DEVPLAN_HEADER + (size_t)plan_tail_wgs(slots) * rec_bytes; }
-inline bool devplan_enabled() {
-    static const bool on = [] {
-        const char *e = getenv("VTM_ATT_DEVPLAN");        // A/B hook, read once per process and translation unit
-        return e == nullptr || atoi(e) != 0;
-    }();
-    return on;
-}
 
 }  // namespace

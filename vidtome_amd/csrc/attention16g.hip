@@ -1,9 +1,11 @@
 // attention16g: shared-probability attention (utils/pnp_utils.py:57-67, 75-90) at d = 40 with the probabilities computed ONCE and
 // the matrix pipe kept busy by a one-tile SKEW (round 6).
 //
-// attention16_kernel<NQ = 1, NG> already computes one QK^T and one set of exps per source (query block, head) and NG PV
-// accumulations; per 64-key tile and wave that is 192 matrix cycles of QK^T, NG x 192 of PV and ~360 of VALU in a row --
-// 1 129 cycles at NG = 3 of which the matrix pipe works 768.  Here the tile loop is skewed by one tile: iteration t issues
+// The reference computes `sim` and `softmax` of the SOURCE sample once and reuses the probabilities for every one of the
+// `num_inputs` samples; attention_kernel's share_groups only redirects the q / k pointers and recomputes everything per sample.
+// Here one workgroup computes one QK^T and one set of exps per source (query block, head) and NG PV accumulations against the
+// NG samples' V^T tiles; per 64-key tile and wave that is 192 matrix cycles of QK^T, NG x 192 of PV and ~360 of VALU -- in a
+// row, 1 129 cycles at NG = 3 of which the matrix pipe works 768.  So the tile loop is skewed by one tile: iteration t issues
 //     S(t + 1) = K(t + 1) Q^T   and   PV of tile t - 1 for all NG samples        (matrix pipe, independent of each other)
 // beside
 //     exps / pack / maximum / swaps of tile t                                     (VALU, from the S(t) of iteration t - 1)
@@ -12,11 +14,10 @@
 // one ahead in a 3-slot ring too (tile t - 1 is read while t waits and t + 1 is written); the V^T fragments are read per
 // (sample, k-step) right before their MFMAs -- no fragment survives an iteration -- which keeps the 72 accumulator registers
 // of three samples, two score tiles and two packed P inside 256.  Arithmetic per query and tile identical to
-// attention16_kernel / attention_kernel's PV16 path.
+// attention_kernel's PV16 path.
 #include "attention16_parts.h"
 
 #include <algorithm>
-#include <cstdlib>
 #include <type_traits>
 
 namespace {
@@ -448,7 +449,7 @@ int launch16g(const Args16 &a) {
         const int slots = vtm::device_cus();       // one workgroup per CU
         const int64_t nqb_max = vtm::cdiv(a.M, QB);
         const size_t need = devplan_ws_bytes(slots, rec_bytes);
-        if (a.q_count != nullptr && a.ws != nullptr && a.ws_bytes >= need && devplan_enabled() && nqb_max * a.h * src_batch >= 2 * slots) {
+        if (a.q_count != nullptr && a.ws != nullptr && a.ws_bytes >= need && nqb_max * a.h * src_batch >= 2 * slots) {
             DevPlan *plan = reinterpret_cast<DevPlan *>(a.ws);
             float *records = reinterpret_cast<float *>(static_cast<char *>(a.ws) + DEVPLAN_HEADER);
             const int xcd_pairs = (src_batch * a.h) % 8 == 0 ? (int)(src_batch * a.h / 8) : 0;
@@ -466,7 +467,7 @@ int launch16g(const Args16 &a) {
             return vtm::launch_status("vtm_attention");
         }
     }
-    TailPlan p = plan_tail16(src_batch, a.h, a.M, a.Mk, QB, 1, rec_bytes, false);
+    TailPlan p = plan_tail(src_batch, a.h, a.M, a.Mk, QB, 1, rec_bytes, false);
     if (p.nsplit > 1 && (!a.ws || a.ws_bytes < p.ws_bytes)) {
         p.nsplit = 1;
         p.full = p.total;
@@ -493,8 +494,8 @@ namespace vtm_att {
 size_t ws_bytes16g(int ng, int64_t src_batch, int64_t h, int64_t Mq, int64_t Mk, bool bounded) {
     constexpr int WAVES = 8, NT = WAVES * 64;
     const size_t rec = (size_t)ng * rec16<40>() * NT * sizeof(float);
-    size_t n = plan_tail16(src_batch, h, Mq, Mk, (int64_t)WAVES * QW, 1, rec, false).ws_bytes;
-    if (bounded && devplan_enabled()) n = std::max(n, devplan_ws_bytes(vtm::device_cus(), rec));
+    size_t n = plan_tail(src_batch, h, Mq, Mk, (int64_t)WAVES * QW, 1, rec, false).ws_bytes;
+    if (bounded) n = std::max(n, devplan_ws_bytes(vtm::device_cus(), rec));
     return n;
 }
 
