@@ -484,6 +484,22 @@ int vtm_linear_rows(const void *x0, int64_t P0, const void *x1, int64_t P1, int 
                     const void *bias, int64_t N, void *out, int64_t ldo, int64_t out_batch_stride,
                     int transposed, vtm_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * vtm_lora_fold -- the effective weight of a LoRA-adapted projection of the block (`pipe.load_lora_weights(
+ * **gene_config.lora)`, generate.py:93-94 with `use_lora` / `lora:` of configs/default.yaml:63-69; with the PEFT
+ * backend Diffusers wraps attn1 / attn2 to_q / to_k / to_v / to_out.0, ff.net.0.proj and ff.net.2 of every
+ * BasicTransformerBlock, and its forward is `base(x) + sum_a lora_B_a(lora_A_a(x)) * scaling_a`), so that the
+ * projection kernels above run on W_eff = W + sum_a s_a B_a A_a instead of leaving the patched block:
+ *   out[o, i] = round_dtype( w[o, i] + sum_{k < r} up[o, k] * down[k, i] )
+ * w, out: (c_out, c_in) row-major in `dtype` (VTM_F16 / VTM_BF16 / VTM_F32; out may not alias up / down);
+ * up: (c_out, r) fp32 row-major = the adapters' B matrices side by side with each adapter's scale applied;
+ * down: (r, c_in) fp32 row-major = their A matrices stacked (r = the sum of the ranks).  The sum is a k-ascending
+ * fp32 fmaf chain from +0, added to w in fp32 and rounded once.  Runs once per adapter state, not per step.
+ * c_out, c_in, r > 0 (else VTM_EINVAL).
+ * ---------------------------------------------------------------------------------------------- */
+int vtm_lora_fold(const void *w, int dtype, const float *up, const float *down, int64_t c_out, int64_t c_in,
+                  int64_t r, void *out, vtm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -92,6 +92,7 @@ _SIGNATURES = {
     "vtm_geglu": ([_vp, _int, _i64, _i64, _vp, _vp], _int),
     "vtm_linear_rows": ([_vp, _i64, _vp, _i64, _int, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64,
                          _int, _vp], _int),
+    "vtm_lora_fold": ([_vp, _int, _vp, _vp, _i64, _i64, _i64, _vp, _vp], _int),
 }
 
 
@@ -806,4 +807,21 @@ def gather_panels(x0: torch.Tensor, x1: Optional[torch.Tensor], rows: Optional[t
     _check(lib().vtm_gather_panels(_ptr(x0), P0, _ptr(x1), P1, dtype_code(x0), B, C, _ptr(rows),
                                    0 if rows is None else rows.shape[1], _ptr(rows2), n, _ptr(out), n_pad, _stream()),
            "vtm_gather_panels")
+    return out
+
+
+@_on_device
+def lora_fold(w: torch.Tensor, up: torch.Tensor, down: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """W + up @ down in w's dtype (fp32 accumulation, one rounding): w (c_out, c_in), up (c_out, r) and down (r, c_in) fp32;
+    see include/vidtome_hip.h vtm_lora_fold."""
+    _req(w, "w"), _req(up, "up"), _req(down, "down")
+    c_out, c_in = w.shape
+    r = up.shape[1]
+    if up.dtype != torch.float32 or down.dtype != torch.float32 or tuple(up.shape) != (c_out, r) \
+            or tuple(down.shape) != (r, c_in) or up.device != w.device or down.device != w.device:
+        raise RuntimeError("lora_fold: up must be (c_out, r) and down (r, c_in) fp32 tensors on w's device")
+    if out is None:
+        out = torch.empty_like(w)
+    _check(lib().vtm_lora_fold(_ptr(w), dtype_code(w), _ptr(up), _ptr(down), c_out, c_in, r, _ptr(_req(out, "out")),
+                               _stream()), "vtm_lora_fold")
     return out

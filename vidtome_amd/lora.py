@@ -1,0 +1,195 @@
+"""The effective weight of a block projection: plain Linear, or LoRA-adapted and folded.
+
+The reference loads LoRA adapters as a documented option (`use_lora` / `lora:`, configs/default.yaml:63-69 ->
+`pipe.load_lora_weights(**gene_config.lora)`, generate.py:93-94).  With the PEFT backend Diffusers then wraps every
+projection of a BasicTransformerBlock -- attn1 / attn2 to_q / to_k / to_v / to_out.0, ff.net.0.proj, ff.net.2 -- in a
+LoRA layer whose forward is ``base(x) + sum_a lora_B_a(lora_A_a(dropout(x))) * scaling_a``.  For inference that is the
+Linear ``W_eff = W + sum_a s_a B_a A_a`` (bias + s_a b_B_a), folded once per adapter state by vtm_lora_fold and fed to the
+projection kernels that exist: the per-step cost is zero.
+
+`linear_params` is the ONE place the patched block reads a projection's weight and bias from.  A LoRA wrapper's
+``.weight`` is the BASE weight, and PEFT's ``merge()`` adds the adapter into it through ``.data`` (no version bump), so
+the folded tensors are keyed by a state token that covers the base and adapter tensors (pointer + version), every
+active adapter's exact scaling, ``merged`` / ``merged_adapters`` and ``disable_adapters``.  Downstream caches (stacked
+q | k weights, panel packs) key on the token too, so a scaling change, an adapter switch, disable, merge and unmerge
+all rebuild them, and a merged adapter is never counted twice.
+
+Two structures are recognised by duck typing (neither PEFT nor Diffusers is a dependency):
+* PEFT's LoRA ``Linear``: ``base_layer`` (a plain Linear), ``lora_A`` / ``lora_B`` (ModuleDicts of Linear), ``scaling``,
+  ``active_adapters``, ``merged``, ``disable_adapters``, ``use_dora``, ``lora_dropout``;
+* Diffusers' legacy ``LoRACompatibleLinear`` with a ``lora_layer`` that has ``down``, ``up``, ``network_alpha`` and
+  ``rank`` (its forward adds ``scale * up(down(x)) * network_alpha / rank``, the forward's ``scale`` being 1.0 here).
+Anything else -- DoRA, ``fan_in_fan_out``, dropout with p > 0 in training mode, adapters that are not Linears, other
+wrappers -- is not recognised and the patched block keeps the module's own forward.
+"""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import torch
+
+from . import _lib
+
+PLAIN, PEFT, LEGACY = "plain", "peft", "legacy"
+
+
+def _plain(m) -> bool:
+    """A Linear whose forward is `x W^T + b` (Diffusers' LoRA-compatible subclass with no LoRA attached included)."""
+    return (isinstance(m, torch.nn.Linear) and type(m).__name__ in ("Linear", "LoRACompatibleLinear")
+            and getattr(m, "lora_layer", None) is None)
+
+
+def _adapter_linear(m, in_features: int, out_features: int, bias_ok: bool) -> bool:
+    return (type(m) is torch.nn.Linear and m.in_features == in_features and m.out_features == out_features
+            and (bias_ok or m.bias is None))
+
+
+def _flag(v, name: str) -> bool:
+    """PEFT keeps some switches per adapter (dict) and some as one bool."""
+    return bool(v.get(name, False)) if isinstance(v, dict) else bool(v)
+
+
+def _active(m):
+    """PEFT: the active adapters that have weights on this layer, in PEFT's order."""
+    names = m.active_adapters
+    names = [names] if isinstance(names, str) else list(names)
+    return [a for a in names if a in m.lora_A]
+
+
+def _peft_ok(m) -> bool:
+    if not all(hasattr(m, a) for a in ("base_layer", "lora_A", "lora_B", "scaling", "active_adapters", "merged",
+                                       "disable_adapters", "use_dora", "lora_dropout")):
+        return False
+    base = m.base_layer
+    if not _plain(base) or getattr(m, "fan_in_fan_out", False):
+        return False
+    if not isinstance(m.lora_A, torch.nn.ModuleDict) or not isinstance(m.lora_B, torch.nn.ModuleDict):
+        return False
+    for a, A in m.lora_A.items():
+        B = m.lora_B[a] if a in m.lora_B else None
+        if type(A) is not torch.nn.Linear or A.in_features != base.in_features or A.bias is not None:
+            return False
+        if B is None or not _adapter_linear(B, A.out_features, base.out_features, bias_ok=True):
+            return False
+    if m.disable_adapters and m.merged:
+        return False            # PEFT's forward unmerges first (a side effect the module path performs)
+    for a in _active(m):
+        if _flag(m.use_dora, a) or a not in m.scaling:
+            return False
+        d = m.lora_dropout[a] if a in m.lora_dropout else torch.nn.Identity()
+        if type(d) is torch.nn.Identity:
+            continue
+        if not isinstance(d, torch.nn.Dropout) or (d.training and d.p > 0):
+            return False
+    return True
+
+
+def _legacy_ok(m) -> bool:
+    ll = m.lora_layer
+    if not all(hasattr(ll, a) for a in ("down", "up", "network_alpha", "rank")):
+        return False
+    down, up = ll.down, ll.up
+    return (type(down) is torch.nn.Linear and down.in_features == m.in_features and down.bias is None
+            and _adapter_linear(up, down.out_features, m.out_features, bias_ok=True))
+
+
+def recognise(m) -> Optional[str]:
+    """PLAIN / PEFT / LEGACY, or None when the fused path must not read this projection (the module path keeps running)."""
+    if isinstance(m, torch.nn.Linear):
+        name = type(m).__name__
+        if name not in ("Linear", "LoRACompatibleLinear"):
+            return None
+        if getattr(m, "lora_layer", None) is None:
+            return PLAIN
+        return LEGACY if name == "LoRACompatibleLinear" and _legacy_ok(m) else None
+    if hasattr(m, "base_layer") and hasattr(m, "lora_A"):
+        return PEFT if _peft_ok(m) else None
+    return None
+
+
+def base_linear(m) -> torch.nn.Linear:
+    """The Linear holding the base weight (shapes, dtype and device of the effective weight) of a recognised projection."""
+    return m.base_layer if recognise(m) == PEFT else m
+
+
+def _tkey(t: Optional[torch.Tensor]):
+    return None if t is None else (t.data_ptr(), t._version)
+
+
+def _param_key(w: torch.Tensor, b: Optional[torch.Tensor]):
+    return (w.data_ptr(), w._version, w.dtype, w.device) + ((None,) if b is None else (b.data_ptr(), b._version, b.dtype))
+
+
+def _adapters(m, kind: str):
+    """[(name, scale, A (r, c_in), B (c_out, r), B's bias or None)] of the adapters the forward adds."""
+    if kind == LEGACY:
+        ll = m.lora_layer
+        s = 1.0 if ll.network_alpha is None else float(ll.network_alpha) / float(ll.rank)
+        return [("lora_layer", s, ll.down.weight, ll.up.weight, ll.up.bias)]
+    if m.disable_adapters or m.merged:
+        return []
+    return [(a, m.scaling[a], m.lora_A[a].weight, m.lora_B[a].weight, m.lora_B[a].bias) for a in _active(m)]
+
+
+def state_token(m, kind: Optional[str] = None) -> tuple:
+    """Everything the effective weight of a LoRA layer depends on that the fold cannot see in the tensors themselves."""
+    kind = kind or recognise(m)
+    base = m.base_layer if kind == PEFT else m
+    tok = (kind, _param_key(base.weight, base.bias))
+    if kind == PEFT:
+        merged = tuple(getattr(m, "merged_adapters", ()))
+        tok += (bool(m.disable_adapters), bool(m.merged), merged)
+    elif kind == LEGACY:
+        tok += (m.lora_layer.network_alpha, m.lora_layer.rank)
+    return tok + tuple((a, float(s), _tkey(A), _tkey(B), _tkey(bB)) for a, s, A, B, bB in _adapters(m, kind))
+
+
+def _fold(m, kind: str):
+    """(weight, bias, folded?) of the adapted layer, in the base weight's dtype on its device."""
+    base = m.base_layer if kind == PEFT else m
+    w, b = base.weight.detach(), None if base.bias is None else base.bias.detach()
+    ads = _adapters(m, kind)
+    if not ads:
+        return w, b, False
+    with torch.no_grad():
+        up = torch.cat([B.detach().float() * float(s) for _, s, _, B, _ in ads], dim=1).contiguous()
+        down = torch.cat([A.detach().float() for _, _, A, _, _ in ads], dim=0).contiguous()
+        wf = _lib.lora_fold(w.contiguous(), up.to(w.device), down.to(w.device))
+        if any(bB is not None for *_, bB in ads):
+            acc = torch.zeros(w.shape[0], dtype=torch.float32, device=w.device) if b is None else b.float()
+            for _, s, _, _, bB in ads:
+                if bB is not None:
+                    acc = acc + float(s) * bB.detach().float()
+            b = acc.to(w.dtype)
+    return wf, b, True
+
+
+def linear_params(m, dtype: Optional[torch.dtype] = None, device=None
+                  ) -> Optional[Tuple[torch.Tensor, Optional[torch.Tensor], tuple]]:
+    """(weight, bias, key) of the Linear the projection computes, or None when `m` is neither a plain Linear nor a
+    recognised LoRA layer.  A plain Linear gives its own tensors, key = their (pointer, version, dtype, device).  A LoRA
+    layer gives the folded weight / bias (one copy of the projection weight in the model dtype, cached on the module under
+    its state token, which is also the key); a chunk on another HIP stream than the fold's waits for it on the device.
+    ``dtype`` / ``device``: the tensors are returned converted (a no-op when they already are; not cached)."""
+    kind = recognise(m)
+    if kind is None:
+        return None
+    if kind == PLAIN:
+        w, b = m.weight, m.bias
+        key = _param_key(w, b)
+    else:
+        key = state_token(m, kind)
+        hit = m.__dict__.get("_vtm_lora")
+        if hit is None or hit[0] != key:
+            w, b, folded = _fold(m, kind)
+            from .patch import _built_here
+            hit = (key, w, b, _built_here(w.device) if folded else None)
+            m.__dict__["_vtm_lora"] = hit
+        else:
+            from .patch import _built_before
+            _built_before(hit[3], hit[1].device)
+        w, b = hit[1], hit[2]
+    if (dtype is not None and w.dtype != dtype) or (device is not None and w.device != torch.device(device)):
+        w = w.to(device=device, dtype=dtype)
+        b = None if b is None else b.to(device=device, dtype=dtype)
+    return w, b, key

@@ -33,7 +33,7 @@ from typing import Any, Callable, Dict, Optional, Tuple, Type
 import torch
 import torch.nn.functional as F
 
-from . import _lib, merge
+from . import _lib, lora, merge
 from .utils import init_generator, isinstance_str, join_frame, split_frame
 
 # Attention over the merged sequence computes outputs only for the rows unmerge() reads (see MergePlan.q_rows);
@@ -407,17 +407,28 @@ def _built_before(mark, device) -> None:
             cur.wait_event(mark[0])
 
 
+def _linear(m: torch.nn.Module, dtype=None, device=None):
+    """(weight, bias, key) of a projection the caller's predicate accepted (lora.linear_params: its own tensors, or the
+    folded ones of a LoRA layer).  Every weight / bias read of the fused path goes through here: a direct `.weight` read of
+    a LoRA wrapper would be its BASE weight and silently drop the adapter."""
+    p = lora.linear_params(m, dtype, device)
+    if p is None:
+        raise RuntimeError(f"vidtome_amd: {type(m).__name__} is not a projection the fused path can read")
+    return p
+
+
 def _fused_weights(attn: torch.nn.Module, dtype, device):
     """[Wq; Wk] stacked once per module (one projection GEMM for q and k), cached on the module."""
     cache = attn.__dict__.get("_vtm_wcache")
-    wq = attn.to_q.weight
-    key = (wq.data_ptr(), attn.to_k.weight.data_ptr(), wq._version, attn.to_k.weight._version, dtype, device)
+    wq, bq, kq = _linear(attn.to_q)
+    wk, bk, kk = _linear(attn.to_k)
+    key = (kq, kk, dtype, device)
     if cache is None or cache[0] != key:
-        wqk = torch.cat([attn.to_q.weight, attn.to_k.weight], dim=0).to(device=device, dtype=dtype).contiguous()
+        wqk = torch.cat([wq, wk], dim=0).to(device=device, dtype=dtype).contiguous()
         bqk = None
-        if getattr(attn.to_q, "bias", None) is not None or getattr(attn.to_k, "bias", None) is not None:
-            zq = attn.to_q.bias if attn.to_q.bias is not None else torch.zeros_like(attn.to_q.weight[:, 0])
-            zk = attn.to_k.bias if attn.to_k.bias is not None else torch.zeros_like(attn.to_k.weight[:, 0])
+        if bq is not None or bk is not None:
+            zq = bq if bq is not None else torch.zeros_like(wq[:, 0])
+            zk = bk if bk is not None else torch.zeros_like(wk[:, 0])
             bqk = torch.cat([zq, zk]).to(device=device, dtype=dtype)
         cache = (key, wqk, bqk, _built_here(device))
         attn.__dict__["_vtm_wcache"] = cache
@@ -437,12 +448,11 @@ def _warn_once(key: str, msg: str) -> None:
         warnings.warn(msg, stacklevel=3)
 
 
-def _plain_linear(m) -> bool:
-    """A projection the fused path may read `.weight` / `.bias` from: a plain Linear (or Diffusers' LoRA-compatible
-    subclass with no LoRA attached).  PEFT / LoRA wrappers compute more than `x W^T + b`; reading the base weight
-    would silently drop the adapter."""
-    return (isinstance(m, torch.nn.Linear) and type(m).__name__ in ("Linear", "LoRACompatibleLinear")
-            and getattr(m, "lora_layer", None) is None)
+def _readable_linear(m) -> bool:
+    """A projection the fused path may read through `lora.linear_params`: a plain Linear (or Diffusers' LoRA-compatible
+    subclass with no LoRA attached), or a LoRA layer whose adapters fold into one Linear (vidtome_amd/lora.py).  Other
+    wrappers compute more than `x W^T + b` and keep the module path."""
+    return lora.recognise(m) is not None
 
 
 def _out_linear(attn: torch.nn.Module):
@@ -460,10 +470,10 @@ def fused_attention_ok(attn: torch.nn.Module, x: torch.Tensor, self_attn: bool =
         return False
     if not all(hasattr(attn, a) for a in ("to_q", "to_k", "to_v", "to_out", "heads")):
         return False
-    if not all(_plain_linear(m) for m in (attn.to_q, attn.to_k, attn.to_v, _out_linear(attn))):
+    if not all(_readable_linear(m) for m in (attn.to_q, attn.to_k, attn.to_v, _out_linear(attn))):
         return False
     C = x.shape[-1]
-    if attn.to_q.out_features != C or C % attn.heads or (C // attn.heads) not in _HEAD_DIMS:
+    if lora.base_linear(attn.to_q).out_features != C or C % attn.heads or (C // attn.heads) not in _HEAD_DIMS:
         return False
     if any(getattr(attn, a, None) is not None for a in ("group_norm", "spatial_norm", "norm_cross", "norm_q", "norm_k")):
         return False
@@ -499,9 +509,21 @@ def _proj_dtypes_ok(attn: torch.nn.Module, dtype) -> bool:
     read raw 16-bit words and take the dtype from the TOKENS (a mixed-dtype module -- an fp32 to_out next to fp16
     to_q / to_k / to_v, say -- would otherwise be packed and multiplied as garbage instead of leaving the fused path)."""
     for lin in (attn.to_q, attn.to_k, attn.to_v, _out_linear(attn)):
-        if lin.weight.dtype != dtype or (getattr(lin, "bias", None) is not None and lin.bias.dtype != dtype):
+        if not _linear_dtype_ok(lin, dtype):
             return False
     return True
+
+
+def _linear_dtype_ok(lin: torch.nn.Module, dtype) -> bool:
+    """The (effective) weight and bias of a projection are of `dtype` (a LoRA fold is made in its base weight's dtype; the
+    adapters themselves may be of any dtype)."""
+    base = lora.base_linear(lin)
+    return base.weight.dtype == dtype and (base.bias is None or base.bias.dtype == dtype)
+
+
+def _has_bias(lin: torch.nn.Module) -> bool:
+    """The effective Linear has a bias (a PEFT adapter's lora_B bias folds into it)."""
+    return lora.linear_params(lin)[1] is not None
 
 
 def fused_projections_ok(attn: torch.nn.Module, x: torch.Tensor) -> bool:
@@ -516,13 +538,14 @@ def panel_projections_ok(attn: torch.nn.Module, x: torch.Tensor) -> bool:
     """The panel-GEMM projections (vtm_gather_panels / vtm_layernorm_panels + vtm_linear_panels): fp16 / bf16 tokens,
     C % 64 == 0, no bias on to_v (V^T = W_v X^T is computed with the roles of the operands swapped)."""
     return (PROJ_MODE in ("auto", "panels") and x.dtype in (torch.float16, torch.bfloat16) and x.shape[-1] % 64 == 0
-            and _proj_dtypes_ok(attn, x.dtype) and getattr(attn.to_v, "bias", None) is None)
+            and _proj_dtypes_ok(attn, x.dtype) and not _has_bias(attn.to_v))
 
 
 def _panel_weight(lin: torch.nn.Module):
     """(weight as k-panels, fp32 bias or None) of a Linear, cached on the module."""
-    return _packed(lin, "rows", lambda: (_lib.to_panels(lin.weight.detach().contiguous()),
-                                        None if lin.bias is None else lin.bias.detach().float().contiguous()))
+    w, b, key = _linear(lin)
+    return _packed(lin, "rows", key, w.device, lambda: (_lib.to_panels(w.detach().contiguous()),
+                                                       None if b is None else b.detach().float().contiguous()))
 
 
 def self_attention_panels(attn: torch.nn.Module, x0: torch.Tensor, x1: Optional[torch.Tensor], rows: Optional[torch.Tensor],
@@ -594,13 +617,15 @@ def unmerged_self_attention_residual(block: torch.nn.Module, hidden_states: torc
     hs = hidden_states.contiguous()
     n = BF * N
 
+    qkv_params = [_linear(m) for m in (attn.to_q, attn.to_k, attn.to_v)]
+
     def pack_qkv():
-        w = torch.cat([attn.to_q.weight, attn.to_k.weight, attn.to_v.weight], dim=0).detach().contiguous()
-        bs = [getattr(m, "bias", None) for m in (attn.to_q, attn.to_k, attn.to_v)]
+        w = torch.cat([p[0] for p in qkv_params], dim=0).detach().contiguous()
+        bs = [p[1] for p in qkv_params]
         b = None if all(x is None for x in bs) else torch.cat(
             [torch.zeros(C, device=w.device) if x is None else x.detach().float() for x in bs]).contiguous()
         return _lib.to_panels(w), b
-    wqkv, bqkv = _packed(attn, "qkv", pack_qkv)
+    wqkv, bqkv = _packed(attn, "qkv", tuple(p[2] for p in qkv_params), qkv_params[0][0].device, pack_qkv)
     xp = _lib.layernorm_panels(hs, norm.weight, norm.bias, norm.eps)
     qkv = _lib.linear_panels(xp, n, wqkv, 3 * C, bqkv).view(BF, N, 3 * C)
     vt = _lib.transpose_cols(qkv, 2 * C, C)                              # (BF, C, N): V channel-major for the PV contraction
@@ -621,8 +646,13 @@ def self_attention_segment(block: torch.nn.Module, hidden_states: torch.Tensor, 
 
 
 def _weight(m: torch.nn.Module, dtype) -> torch.Tensor:
-    w = m.weight
+    w = _linear(m)[0]
     return w if (w.dtype == dtype and w.is_contiguous()) else w.to(dtype).contiguous()
+
+
+def _bias(m: torch.nn.Module, dtype) -> Optional[torch.Tensor]:
+    b = _linear(m)[1]
+    return None if b is None else b.to(dtype)
 
 
 def self_attention_rows(attn: torch.nn.Module, x0: torch.Tensor, x1: Optional[torch.Tensor],
@@ -644,22 +674,20 @@ def self_attention_rows(attn: torch.nn.Module, x0: torch.Tensor, x1: Optional[to
     # (q_rows under PnP sharing: the caller vouches that every sample of a group has the same rows -- align_batch)
     dt = x0.dtype
     wqk, bqk = _fused_weights(attn, dt, x0.device)
-    bv = getattr(attn.to_v, "bias", None)
+    bv = _bias(attn.to_v, dt)
     fold = None
     if plan is not None and rows is not None and share == 1 and (C // heads) in (8, 40):
         fold = plan.key_fold(dt)
     if fold is not None:
         key_sel, k_bias, k_count = fold
-        vt = _lib.linear_rows(x0, x1, rows, key_sel, M, _weight(attn.to_v, dt), None if bv is None else bv.to(dt),
-                              transposed=True)
+        vt = _lib.linear_rows(x0, x1, rows, key_sel, M, _weight(attn.to_v, dt), bv, transposed=True)
         k_op = _lib.linear_rows(x0, x1, rows, key_sel, M, wqk[C:], None if bqk is None else bqk[C:])
         Mq = M if q_rows is None else q_rows.shape[1]
         q_op = _lib.linear_rows(x0, x1, rows, q_rows, Mq, wqk[:C], None if bqk is None else bqk[:C])
         o = _lib.attention_kv(q_op, k_op, vt, heads, Mq, M, scale, q_count=q_count, k_fold=(k_count, k_bias))
         to_out = _out_linear(attn)
-        return _lib.linear_rows(o, None, None, None, Mq, _weight(to_out, dt), None if to_out.bias is None else to_out.bias.to(dt))
-    vt = _lib.linear_rows(x0, x1, rows, None, M, _weight(attn.to_v, dt), None if bv is None else bv.to(dt),
-                          transposed=True)                                                       # (B, C, Mp)
+        return _lib.linear_rows(o, None, None, None, Mq, _weight(to_out, dt), _bias(to_out, dt))
+    vt = _lib.linear_rows(x0, x1, rows, None, M, _weight(attn.to_v, dt), bv, transposed=True)     # (B, C, Mp)
     if q_rows is None:
         qk = _lib.linear_rows(x0, x1, rows, None, M, wqk, bqk)                                   # (B, Mp, 2C): q | k
         o = _lib.attention(qk[:, :, :C], qk[:, :, C:], vt, heads, M, scale, share)
@@ -670,7 +698,7 @@ def self_attention_rows(attn: torch.nn.Module, x0: torch.Tensor, x1: Optional[to
         q_op = _lib.linear_rows(x0, x1, rows, q_rows, Mq, wqk[:C], None if bqk is None else bqk[:C])
         o = _lib.attention_kv(q_op, k_op, vt, heads, Mq, M, scale, q_count=q_count, share_groups=share)
     to_out = _out_linear(attn)
-    return _lib.linear_rows(o, None, None, None, Mq, _weight(to_out, dt), None if to_out.bias is None else to_out.bias.to(dt))
+    return _lib.linear_rows(o, None, None, None, Mq, _weight(to_out, dt), _bias(to_out, dt))
 
 
 def self_attention(attn: torch.nn.Module, x: torch.Tensor, M: Optional[int] = None,
@@ -715,15 +743,15 @@ def self_attention(attn: torch.nn.Module, x: torch.Tensor, M: Optional[int] = No
         xq = _lib.gather_rows(x, None, q_rows, pad_to=8)                 # (B, Mqp, C) query tokens
         q_op = F.linear(xq, wqk[:C], None if bqk is None else bqk[:C]).to(core)
         k_op = F.linear(x, wqk[C:], None if bqk is None else bqk[C:]).to(core)
-    wv = attn.to_v.weight.to(x.dtype)
+    wv, bv, _ = _linear(attn.to_v, x.dtype)
     if B <= 4:                                                           # merged sites: few long sequences
         vt = torch.empty((B, C, Mp), dtype=x.dtype, device=x.device)     # V^T straight from the GEMM:
         for bi in range(B):                                              # W_v @ x_b^T, transposed operand
             torch.mm(wv, x[bi].t(), out=vt[bi])                          # handled by the BLAS (no copy)
     else:                                                                # un-merged sites: many short ones
         vt = torch.matmul(wv, x.transpose(1, 2))
-    if getattr(attn.to_v, "bias", None) is not None:
-        vt = vt + attn.to_v.bias.to(x.dtype)[None, :, None]
+    if bv is not None:
+        vt = vt + bv[None, :, None]
     vt = vt.to(core)
     if q_rows is None:
         o = _lib.attention(q_op, k_op, vt, heads, M, scale, share)
@@ -731,9 +759,9 @@ def self_attention(attn: torch.nn.Module, x: torch.Tensor, M: Optional[int] = No
         o = _lib.attention_kv(q_op, k_op, vt, heads, q_rows.shape[1], M, scale, q_count=q_count, share_groups=share)
         # (q_count: rows past the count are undefined; the output projection is row-wise, so they stay confined to
         # rows unmerge() never reads)
-    to_out = _out_linear(attn)
     o = o.to(x.dtype)
-    return F.linear(o, to_out.weight.to(o.dtype), None if to_out.bias is None else to_out.bias.to(o.dtype))
+    wo, bo, _ = _linear(_out_linear(attn), o.dtype)
+    return F.linear(o, wo, bo)
 
 
 def norm_cross_attention_residual(norm: torch.nn.Module, attn: torch.nn.Module, hidden_states: torch.Tensor,
@@ -754,16 +782,13 @@ def norm_cross_attention_residual(norm: torch.nn.Module, attn: torch.nn.Module, 
         enc = F.pad(enc, (0, 0, 0, Mkp - Mk))
     hs = hidden_states.contiguous()
     n = B * N
-    wq, bq = _packed(attn.to_q, "rows", lambda: (_lib.to_panels(attn.to_q.weight.detach().contiguous()),
-                                                None if attn.to_q.bias is None else attn.to_q.bias.detach().float().contiguous()))
-    to_out = _out_linear(attn)
-    wo, bo = _packed(to_out, "rows", lambda: (_lib.to_panels(to_out.weight.detach().contiguous()),
-                                              None if to_out.bias is None else to_out.bias.detach().float().contiguous()))
+    wq, bq = _panel_weight(attn.to_q)
+    wo, bo = _panel_weight(_out_linear(attn))
     xp = _lib.layernorm_panels(hs, norm.weight, norm.bias, norm.eps)
     q = _lib.linear_panels(xp, n, wq, C, bq).view(B, N, C)
     if N % 8:
         raise RuntimeError("norm_cross_attention_residual: token count must be a multiple of 8")
-    if enc.shape[2] % 64 == 0 and attn.to_k.weight.dtype == dt and attn.to_v.weight.dtype == dt:
+    if enc.shape[2] % 64 == 0 and lora.base_linear(attn.to_k).weight.dtype == dt and lora.base_linear(attn.to_v).weight.dtype == dt:
         ep = _lib.to_panels(enc.reshape(B * Mkp, enc.shape[2]))          # the (few) conditioning tokens: 77 per frame in SD
         wk, bk = _panel_weight(attn.to_k)
         wv, bv = _panel_weight(attn.to_v)
@@ -772,12 +797,17 @@ def norm_cross_attention_residual(norm: torch.nn.Module, attn: torch.nn.Module, 
     else:
         _warn_once("lib-cross-kv", f"vidtome_amd: attn2's k / v projections run as library GEMMs (conditioning width "
                                    f"{enc.shape[2]} is not a multiple of 64, or to_k / to_v are not of the tokens' dtype)")
-        lin = lambda m, t: F.linear(t, m.weight.to(t.dtype), None if m.bias is None else m.bias.to(t.dtype))
-        k = lin(attn.to_k, enc)
-        vt = lin(attn.to_v, enc).transpose(1, 2).contiguous()
+        k = _apply_linear(attn.to_k, enc)
+        vt = _apply_linear(attn.to_v, enc).transpose(1, 2).contiguous()
     o = _lib.attention_kv(q, k, vt, heads, N, Mk, scale)
     op = _lib.to_panels(o.view(n, C))
     return _lib.linear_panels(op, n, wo, C, bo, resid=hs.view(n, C)).view(B, N, C)
+
+
+def _apply_linear(m: torch.nn.Module, t: torch.Tensor) -> torch.Tensor:
+    """The projection as a library GEMM in the tokens' dtype."""
+    w, b, _ = _linear(m, t.dtype)
+    return F.linear(t, w, b)
 
 
 def fused_cross_ok(norm: torch.nn.Module, attn: torch.nn.Module, x: torch.Tensor, encoder_hidden_states,
@@ -810,12 +840,11 @@ def cross_attention(attn: torch.nn.Module, x: torch.Tensor, encoder_hidden_state
         x = F.pad(x, (0, 0, 0, Np - N))
     if Mkp != Mk:
         enc = F.pad(enc, (0, 0, 0, Mkp - Mk))
-    lin = lambda m, t: F.linear(t, m.weight.to(t.dtype), None if m.bias is None else m.bias.to(t.dtype))
-    q = lin(attn.to_q, x)
-    k = lin(attn.to_k, enc)
-    vt = lin(attn.to_v, enc).transpose(1, 2).contiguous()               # (B, C, Mkp): 77 keys, negligible
+    q = _apply_linear(attn.to_q, x)
+    k = _apply_linear(attn.to_k, enc)
+    vt = _apply_linear(attn.to_v, enc).transpose(1, 2).contiguous()     # (B, C, Mkp): 77 keys, negligible
     o = _lib.attention_kv(q, k, vt, heads, N, Mk, scale)
-    return lin(_out_linear(attn), o)[:, :N]
+    return _apply_linear(_out_linear(attn), o)[:, :N]
 
 
 # ----------------------------------------------------------------------------------------------------
@@ -828,17 +857,14 @@ def cross_attention(attn: torch.nn.Module, x: torch.Tensor, encoder_hidden_state
 FF_MODE = os.environ.get("VIDTOME_FF", "panels")
 
 
-def _packed(module: torch.nn.Module, key: str, build):
-    """Weights repacked for the panel GEMMs, cached on the module and rebuilt when the parameter changes."""
+def _packed(module: torch.nn.Module, name: str, tag, dev, build):
+    """Weights repacked for the panel GEMMs, cached on the module under `name` and rebuilt when `tag` -- the keys
+    lora.linear_params gave for the projections packed -- changes."""
     cache = module.__dict__.setdefault("_vtm_packed", {})
-    params = [p for p in module.parameters()]
-    tag = tuple((p.data_ptr(), p._version, p.dtype, p.device) for p in params)
-    hit = cache.get(key)
-    dev = params[0].device if params else None
+    hit = cache.get(name)
     if hit is None or hit[0] != tag:
-        hit = cache[key] = (tag, build(), _built_here(dev) if dev is not None else None)
-    if dev is not None:
-        _built_before(hit[2], dev)
+        hit = cache[name] = (tag, build(), _built_here(dev))
+    _built_before(hit[2], dev)
     return hit[1]
 
 
@@ -846,7 +872,7 @@ def _geglu_ff(ff: torch.nn.Module):
     """(GEGLU projection Linear, output Linear) of a Diffusers FeedForward [GEGLU, Dropout, Linear], else None."""
     net = getattr(ff, "net", None)
     if (net is not None and len(net) == 3 and net[0].__class__.__name__ == "GEGLU" and hasattr(net[0], "proj")
-            and _plain_linear(net[0].proj) and _plain_linear(net[2])
+            and _readable_linear(net[0].proj) and _readable_linear(net[2])
             and (not ff.training or getattr(net[1], "p", 0.0) == 0.0)):      # Dropout(0.0) is the identity in any mode
         return net[0].proj, net[2]
     return None
@@ -858,7 +884,7 @@ def fused_ff_ok(norm: torch.nn.Module, ff: torch.nn.Module, x: torch.Tensor) -> 
     lin = _geglu_ff(ff)
     if lin is None or type(norm) is not torch.nn.LayerNorm or len(norm.normalized_shape) != 1:
         return False
-    proj, out = lin
+    proj, out = (lora.base_linear(m) for m in lin)
     C = x.shape[-1]
     D = proj.out_features // 2
     return (norm.normalized_shape[0] == C and C % 64 == 0 and C <= 2048 and proj.in_features == C and D % 64 == 0
@@ -873,20 +899,17 @@ def norm_feed_forward_residual(norm: torch.nn.Module, ff: torch.nn.Module, hidde
     residual -> token rows.  The caller has checked ``fused_ff_ok``."""
     proj, out = _geglu_ff(ff)
     C = hidden_states.shape[-1]
-    D = proj.out_features // 2
+    pw, pb, pkey = _linear(proj)
+    D = pw.shape[0] // 2
 
     def pack_w1():
-        t = torch.arange(D // 64, device=proj.weight.device)[:, None] * 64 + torch.arange(64, device=proj.weight.device)[None, :]
+        t = torch.arange(D // 64, device=pw.device)[:, None] * 64 + torch.arange(64, device=pw.device)[None, :]
         order = torch.cat([t, t + D], dim=1).reshape(-1).to(torch.int32)       # tile t: 64 value rows, then their gate rows
-        b = None if proj.bias is None else proj.bias.detach().float()[order.long()].contiguous()
-        return _lib.to_panels(proj.weight.detach().contiguous(), order), b
+        b = None if pb is None else pb.detach().float()[order.long()].contiguous()
+        return _lib.to_panels(pw.detach().contiguous(), order), b
 
-    def pack_w2():
-        b = None if out.bias is None else out.bias.detach().float().contiguous()
-        return _lib.to_panels(out.weight.detach().contiguous()), b
-
-    w1, b1 = _packed(proj, "geglu", pack_w1)
-    w2, b2 = _packed(out, "rows", pack_w2)
+    w1, b1 = _packed(proj, "geglu", pkey, pw.device, pack_w1)
+    w2, b2 = _panel_weight(out)
     hs = hidden_states.contiguous()
     n = hs.numel() // C
     xp = _lib.layernorm_panels(hs, norm.weight, norm.bias, norm.eps)
@@ -900,10 +923,18 @@ def feed_forward(ff: torch.nn.Module, x: torch.Tensor) -> torch.Tensor:
     runs as vtm_geglu (the two Linears stay library GEMMs), otherwise the module runs unchanged."""
     net = getattr(ff, "net", None)
     if (net is not None and len(net) == 3 and net[0].__class__.__name__ == "GEGLU" and hasattr(net[0], "proj")
-            and _plain_linear(net[0].proj) and _plain_linear(net[2]) and x.is_cuda and not ff.training
-            and x.dtype in (torch.float16, torch.bfloat16, torch.float32) and net[0].proj.out_features % 16 == 0):
-        return net[2](_lib.geglu(net[0].proj(x)))
+            and _readable_linear(net[0].proj) and _readable_linear(net[2]) and x.is_cuda and not ff.training
+            and x.dtype in (torch.float16, torch.bfloat16, torch.float32)
+            and lora.base_linear(net[0].proj).out_features % 16 == 0):
+        return _linear_call(net[2], _lib.geglu(_linear_call(net[0].proj, x)))
     return ff(x)
+
+
+def _linear_call(m: torch.nn.Module, x: torch.Tensor) -> torch.Tensor:
+    """`m(x)` for a projection lora.linear_params reads: F.linear with its (effective) weight and bias, which is exactly
+    what a plain Linear's forward computes."""
+    w, b, _ = _linear(m)
+    return F.linear(x, w, b)
 
 
 # ----------------------------------------------------------------------------------------------------
@@ -1148,6 +1179,7 @@ def remove_patch(model: torch.nn.Module):
             # for SD-1.5; they are rebuilt on demand if the model is patched again
             module.__dict__.pop("_vtm_packed", None)
             module.__dict__.pop("_vtm_wcache", None)
+            module.__dict__.pop("_vtm_lora", None)             # folded LoRA weights (lora.linear_params)
             module.__dict__.pop("_vtm_match_plans", None)      # the matcher's launch planners (pinned 32-byte buffers)
     _lib.release_workspaces()            # the cached scratch buffers of the patched path (re-created on demand)
     return roots[-1]                     # the reference returns its loop variable: the last tree walked
