@@ -315,8 +315,10 @@ int vtm_unmerge_add(const void *y, int64_t M, const int32_t *inv, const void *re
  * the per-sample row count of the buffers), with row strides ldq/ldk/ldo elements (heads interleaved on the channel
  * axis = head_to_batch_dim / batch_to_head_dim without the copies); vt: (B, h*d, ldvt) = v
  * TRANSPOSED (channel-major, key-contiguous, ldvt >= M and a multiple of 8) so that the PV operand
- * is read without a transpose.  dtype VTM_F16 or VTM_BF16; fp32 accumulation; d in {40,64,80,160}
- * (any multiple of 8 up to 160).
+ * is read without a transpose.  dtype VTM_F16 or VTM_BF16 (16-bit MFMA, fp32 accumulation) or VTM_F32 (fp32 operands,
+ * products and accumulation on the f32 MFMA, csrc/attention_f32.hip: about 16x the matrix time); d in
+ * {8,16,32,40,64,80,96,128,160}.  The same dtypes for vtm_attention_kv, _bounded and _shared_bounded; the fp32 path
+ * fits the workspace the *_ws_bytes functions return and takes its split plan only when the workspace holds it.
  * share_groups > 1 = the PnP injection branch (pnp_utils.py:57-67,86-90): probabilities of sample
  * b come from q/k of sample b % (B / share_groups), v stays per sample.
  * ---------------------------------------------------------------------------------------------- */

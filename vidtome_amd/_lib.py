@@ -605,6 +605,8 @@ def attention_kv(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int,
     with ``q_count`` the caller vouches that every sample of a group has the same live rows (align_batch) -- no key folding."""
     if share_groups != 1 and k_fold is not None:
         raise RuntimeError("attention_kv: shared probabilities do not go with folded keys")
+    if k_fold is not None and q.dtype == torch.float32:
+        raise RuntimeError("attention_kv: fp32 keys are never folded (k_fold takes fp16 / bf16 operands)")
     B, Mqp, C = q.shape
     Mkp = k.shape[1]
     d = C // heads

@@ -9,6 +9,7 @@ contract (IEEE divide / sqrt, explicit fma only).
 from __future__ import annotations
 
 import concurrent.futures
+import glob
 import os
 import shutil
 import subprocess
@@ -18,7 +19,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libvidtome_hip.so")
-SOURCES = ["api.hip", "normalize.hip", "match.hip", "match_filter.hip", "sort.hip", "order.hip", "plan.hip", "gather.hip", "attention.hip", "attention16.hip", "attention16g.hip", "ddim.hip", "layernorm.hip", "geglu.hip", "linear.hip", "ff.hip", "lora.hip"]
+SOURCES = ["api.hip", "normalize.hip", "match.hip", "match_filter.hip", "sort.hip", "order.hip", "plan.hip", "gather.hip", "attention.hip", "attention16.hip", "attention16g.hip", "attention_f32.hip", "ddim.hip", "layernorm.hip", "geglu.hip", "linear.hip", "ff.hip", "lora.hip"]
 ARCH = "gfx950"
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
          "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-function",
@@ -48,7 +49,8 @@ def build(force: bool = False, verbose: bool = False, defines=(), tag: str = "")
     lib = os.path.join(libdir, "libvidtome_hip.so")
     os.makedirs(libdir, exist_ok=True)
     cc = hipcc()
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "ablate.h"), os.path.join(HERE, "..", "include", "vidtome_hip.h")]
+    # every object depends on every header (a header edit rebuilds everything that may include it)
+    headers = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", "vidtome_hip.h")]
     objs, jobs = [], []
     flags = FLAGS + ["-D" + d for d in defines]
     for src in SOURCES:

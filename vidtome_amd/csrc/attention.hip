@@ -796,6 +796,7 @@ static int attention_any(const void *q, int64_t ldq, const void *k, int64_t ldk,
     hipStream_t s = vtm::as_stream(stream);
     const Args16 a{q, ldq, k, ldk, vt, ldvt, out, ldo, dtype, B, h, Mq, Mqp, Mk, Mkp, scale, share_groups, ws, ws_bytes,
                    q_count, s, false, nullptr, nullptr, 0};
+    if (dtype == VTM_F32) return attention_f32(a, d);   // (attention_f32.hip: fp32 operands on the f32 MFMA)
     const int ng = shape16_for(d, share_groups, dtype);
     if (ng == 1) return attention16(a);
     // the value groups of one (source sample, head) share a buffer descriptor: the sample stride rides in the offset
@@ -806,7 +807,7 @@ static int attention_any(const void *q, int64_t ldq, const void *k, int64_t ldk,
     if (dtype == VTM_BF16)
         return dispatch<vtm_bf16>(d, q, ldq, k, ldk, vt, ldvt, out, ldo, B, h, Mq, Mqp, Mk, Mkp, scale, share_groups, ws,
                                   ws_bytes, q_count, s);
-    return vtm::fail(VTM_EINVAL, "vtm_attention: dtype must be VTM_F16 or VTM_BF16");
+    return vtm::fail(VTM_EINVAL, "vtm_attention: dtype must be VTM_F16, VTM_BF16 or VTM_F32");
 }
 
 VTM_EXPORT int vtm_attention_kv(const void *q, int64_t ldq, const void *k, int64_t ldk, const void *vt, int64_t ldvt,
@@ -851,6 +852,7 @@ VTM_EXPORT int vtm_attention_kv_folded(const void *q, int64_t ldq, const void *k
     VTM_REQUIRE((Mkp * ldk + d) * 2 < (1ll << 31) && (d * ldvt + Mkp) * 2 < (1ll << 31) && Mkp * 4 < (1ll << 31),
                 "vtm_attention_kv_folded: a (sample, head) slice of K or V^T must stay below 2 GiB");
     hipStream_t s = vtm::as_stream(stream);
+    if (dtype == VTM_F32) return vtm::fail(VTM_EINVAL, "vtm_attention_kv_folded: fp32 keys are never folded (dtype must be VTM_F16 or VTM_BF16)");
     if (dtype != VTM_F16 && dtype != VTM_BF16) return vtm::fail(VTM_EINVAL, "vtm_attention_kv_folded: dtype must be VTM_F16 or VTM_BF16");
     if (d == 40) {   // attention16s_kernel; d = 8: attention_kernel
         const Args16 a{q, ldq, k, ldk, vt, ldvt, out, ldo, dtype, B, h, Mq, Mqp, Mk, Mkp, scale, 1, ws, ws_bytes,

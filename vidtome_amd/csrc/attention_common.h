@@ -221,7 +221,7 @@ inline TailPlan plan_tail(int64_t B_items, int64_t h, int64_t Mq, int64_t Mk, in
 }
 
 
-// ---- hand-over attention.hip -> attention16.hip, attention16g.hip ----
+// ---- hand-over attention.hip -> attention16.hip, attention16g.hip, attention_f32.hip ----
 struct Args16 {
     const void *q; int64_t ldq; const void *k; int64_t ldk; const void *vt; int64_t ldvt; void *out; int64_t ldo;
     int dtype; int64_t B, h, M, Mp, Mk, Mkp; float scale; int share_groups; void *ws; size_t ws_bytes;
@@ -233,6 +233,8 @@ int attention16(const Args16 &a);
 // attention16g.hip: shared probabilities (ng = 2, 3 value groups), one-tile skew
 size_t ws_bytes16g(int ng, int64_t src_batch, int64_t h, int64_t Mq, int64_t Mk, bool bounded);
 int attention16g(const Args16 &a, int ng);
+// attention_f32.hip: dtype VTM_F32, every head dim (attention_f32_kernel; never folded)
+int attention_f32(const Args16 &a, int64_t d);
 
 
 }  // namespace vtm_att

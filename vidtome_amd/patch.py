@@ -702,7 +702,8 @@ def self_attention_rows(attn: torch.nn.Module, x0: torch.Tensor, x1: Optional[to
 
 
 def self_attention(attn: torch.nn.Module, x: torch.Tensor, M: Optional[int] = None,
-                   q_rows: Optional[torch.Tensor] = None, q_count: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   q_rows: Optional[torch.Tensor] = None, q_count: Optional[torch.Tensor] = None,
+                   fp32_core: bool = False) -> torch.Tensor:
     """``attn1(x)`` for self-attention without mask (patch.py:157-162), arithmetic of pnp_utils.py:47-95:
     q,k,v projections -> softmax(q k^T * scale) v per head -> to_out[0] (+ dropout(0)), on MATERIALISED tokens with
     library GEMMs (torch -> hipBLASLt) for the projections: the path of fp32 models, of channel counts the
@@ -711,9 +712,11 @@ def self_attention(attn: torch.nn.Module, x: torch.Tensor, M: Optional[int] = No
     as queries (every row stays a key / value) and the result is (B, Mq rounded up to 8, C) in q_rows order.
     The caller has checked ``fused_attention_ok(attn, x)``.
 
-    fp16 / bf16 models run everything in their dtype.  fp32 models keep the four projections in fp32 and only the
-    attention core's operands (q, k, v^T) are rounded to fp16 for the MFMA (fp32 accumulation, fp32 softmax): the
-    result is within the 1e-3 class of the fp32 reference, and a warning says so once."""
+    fp16 / bf16 models run everything in their dtype.  fp32 models keep the four projections in fp32 and by default only
+    the attention core's operands (q, k, v^T) are rounded to fp16 for the MFMA (fp32 accumulation, fp32 softmax): the
+    result is within the 1e-3 class of the fp32 reference, and a warning says so once.  With ``fp32_core`` (the block's
+    ``fp32_attention``, set by ``update_patch(model, fp32_attention=True)``) an fp32 model's core runs in fp32 on the f32
+    MFMA (csrc/attention_f32.hip), about 16x the matrix time of the fp16 core; the flag means nothing to 16-bit models."""
     B, Mp, C = x.shape
     M = Mp if M is None else M
     heads = attn.heads
@@ -731,7 +734,7 @@ def self_attention(attn: torch.nn.Module, x: torch.Tensor, M: Optional[int] = No
         _warn_once("lib-proj", f"vidtome_amd: attn1 projections of a {x.dtype} model run as library GEMMs (C = {C}: the "
                                "hand-written projection kernels take C % 32 == 0 with all four projection weights in the "
                                "tokens' dtype and no bias on to_v at C > 320)")
-    if x.dtype == torch.float32:
+    if x.dtype == torch.float32 and not fp32_core:
         core = torch.float16
         _warn_once("fp32-core", "vidtome_amd: fp32 model -- the self-attention core (QK^T, softmax, PV) runs on the "
                                 "fp16 MFMA with fp32 accumulation; projections, matching and merging stay fp32")
@@ -976,7 +979,8 @@ def patched_self_attention_segment(block: torch.nn.Module, hidden_states: torch.
                 attn_output = sa(block.attn1, plan.x_joined, plan.anchors_in, plan.gather_map, q_rows, q_count,
                                  **({"plan": plan} if by_rows else {}))
         else:
-            attn_output = self_attention(block.attn1, merged, plan.M if plan is not None else None, q_rows, q_count)
+            attn_output = self_attention(block.attn1, merged, plan.M if plan is not None else None, q_rows, q_count,
+                                         fp32_core=getattr(block, "fp32_attention", False))
         if live:
             # rows are the chunk's local merged tokens: unmerge with the local levels' map alone
             # (= the global level's unmerge, merge.py:439-460, folded into the choice of queries)
@@ -1181,6 +1185,7 @@ def remove_patch(model: torch.nn.Module):
             module.__dict__.pop("_vtm_wcache", None)
             module.__dict__.pop("_vtm_lora", None)             # folded LoRA weights (lora.linear_params)
             module.__dict__.pop("_vtm_match_plans", None)      # the matcher's launch planners (pinned 32-byte buffers)
+            module.__dict__.pop("fp32_attention", None)        # update_patch's opt-in: a later apply_patch starts without it
     _lib.release_workspaces()            # the cached scratch buffers of the patched path (re-created on demand)
     return roots[-1]                     # the reference returns its loop variable: the last tree walked
 
