@@ -2550,10 +2550,13 @@ def test_attention_shared_probabilities_with_a_query_bound(L, d, h, groups):
 
 
 def test_attention_bounded_split_all_vs_plain(L, monkeypatch):
-    """A query-bounded launch that fills at least two rounds of the chip splits EVERY work item in two along the key axis
-    (split-major order, partial records merged by attention_combine_kernel): its rows below the per-sample count must
-    match the plain launch within the tolerance of another summation order, rows of samples with a small count included;
-    with the switch off the two are bit-identical."""
+    """A query-bounded d = 40 launch that fills at least two rounds of the chip.  With the workspace attention_kv hands it
+    (vtm_attention_kv_bounded_ws_bytes) it is planned on the DEVICE (attention16_plan_kernel: whole items, then tiers split
+    along the key axis, merged by attention16_combine_kernel) -- not by the host split-all plan, which only a workspace
+    smaller than the device plan's reaches (tests/test_gpu_attention_plans.py covers it).  Its rows below the per-sample
+    count must match the plain launch within the tolerance of another summation order, rows of samples with a small count
+    included.  With the switch off the workspace is the unbounded one, too small for the split-all records, so the launch
+    falls back to the plain plan (plan_tail without the bound: here a single launch) and is bit-identical to it."""
     B, h, d, Mq, Mk = 2, 8, 40, 17408, 9000            # 68 query blocks x 16 pairs = 1 088 workgroups >= 2 x 512
     C = h * d
     g = torch.Generator(device=DEV).manual_seed(7)

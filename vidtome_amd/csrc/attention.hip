@@ -247,9 +247,12 @@ __global__ __launch_bounds__(waves_for(D) * 64, (D <= 48 ? 4 : D <= 96 ? 4 : 1))
     if (q_count != nullptr && (lin % nqb) * QB >= (int64_t)q_count[b]) return;
 
     // one-time LDS init: K pad columns = 0 (they meet Q's zero padding; garbage could be NaN), V^T pad rows
-    // = 0 except row D = 1 (denominator row) -- tile loads never touch these
+    // = 0 except row D = 1 (denominator row) -- tile loads never touch these.  FOLD: not the bias pair D + 2, D + 3, which
+    // every tile's staging writes (wave 0, write_lds) -- with no barrier in between, a late store here could overwrite the
+    // first tile's bias words with 0 and drop the copies of its keys
     for (int i = tid; i < 2 * KV * (K_STRIDE - D); i += NT) {
         const int row = i / (K_STRIDE - D), c = D + i % (K_STRIDE - D);
+        if (FOLD && (c == D + 2 || c == D + 3)) continue;
         sK[row * K_STRIDE + c] = (elem)((BIAS && c == D) ? 1.0f : 0.0f);
     }
     if constexpr (VROWS > D) {

@@ -96,9 +96,12 @@ __global__ __launch_bounds__(WAVES * 64, 2) void attention16s_kernel(
     if (q_count != nullptr && qblock0 >= (int64_t)q_count[b]) return;
 
     // one-time LDS init: K pad columns = 0 except column D = 1 (it meets the shift in the query), V^T pad rows = 0 except
-    // row D = 1 (the denominator row) -- tile loads never touch these
+    // row D = 1 (the denominator row) -- tile loads never touch these.  FOLD: not the bias pair D + 2, D + 3, which every
+    // tile's staging writes (wave 0, write_k) -- with no barrier in between, a late store here could zero the first tiles'
+    // bias words
     for (int i = tid; i < KR * KV * (K_STRIDE - D); i += NT) {
         const int row = i / (K_STRIDE - D), c = D + i % (K_STRIDE - D);
+        if (FOLD && (c == D + 2 || c == D + 3)) continue;
         sK[row * K_STRIDE + c] = (elem)(c == D ? 1.0f : 0.0f);
     }
     for (int i = tid; i < VR * (VROWS - D) * VT_STRIDE; i += NT) {
