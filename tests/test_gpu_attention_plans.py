@@ -26,8 +26,8 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 KV = 64                                               # keys per tile (attention_common.h:21)
 QW = 32                                               # queries per wave (attention_common.h:20)
-DEVPLAN_HEADER = 256                                  # attention16_parts.h:133
-PLAN_TIERS, PLAN_MAX_SPLIT = 8, 16                    # attention16_parts.h:28-29
+DEVPLAN_HEADER = 256                                  # attention_plan.h:211
+PLAN_TIERS, PLAN_MAX_SPLIT = 8, 16                    # attention_plan.h:158-159
 TOL = {torch.float16: 1e-3, torch.bfloat16: 8e-3}
 DT_CODE = {torch.float16: 1, torch.bfloat16: 2}
 KERNEL_DIMS = (8, 16, 32, 64, 80, 96, 128, 160)
@@ -91,13 +91,13 @@ class Family:
 
     def __init__(self, kind, d, ng=1):
         self.kind, self.d, self.ng = kind, d, ng
-        if kind == "k":                               # attention.hip:626-627, 647, 691
+        if kind == "k":                               # the Family of attention.hip:653-665
             self.QB, self.wg = waves_for(d) * QW, 2 if d <= 48 else 1
             self.rec = rec_floats(d) * waves_for(d) * 64 * 4
             self.xcd_min = 64
-        elif kind == "16s":                           # attention16.hip:488, 493, 498, 526
+        elif kind == "16s":                           # the Family of attention16.hip:509-518
             self.QB, self.wg, self.rec, self.xcd_min = 8 * QW * 2, 1, 2 * rec16(40) * 512 * 4, 32
-        else:                                         # attention16g.hip:431, 444, 449, 478
+        else:                                         # the Family of attention16g.hip:448-463
             self.QB, self.wg, self.rec, self.xcd_min = 8 * QW, 1, ng * rec16(40) * 512 * 4, 32
 
     def slots(self, n_cus):
@@ -105,7 +105,7 @@ class Family:
 
 
 def plan_tail(B_items, h, Mq, Mk, QB, wg, rec, bounded, n_cus):
-    """attention_common.h:189-221."""
+    """attention_plan.h:34-66."""
     nqb = cdiv(Mq, QB)
     total = nqb * h * B_items
     slots = n_cus * wg
@@ -124,11 +124,11 @@ def plan_tail(B_items, h, Mq, Mk, QB, wg, rec, bounded, n_cus):
     return p
 
 
-def devplan_ws_bytes(slots, rec):                     # attention16_parts.h:38, 135
+def devplan_ws_bytes(slots, rec):                     # attention_plan.h:168, 213
     return DEVPLAN_HEADER + (PLAN_TIERS - 1) * slots * rec
 
 
-def ws_bytes_k(D, B, h, Mq, Mk, bounded, n_cus):     # attention.hip:744-750
+def ws_bytes_k(D, B, h, Mq, Mk, bounded, n_cus):     # attention_plan.h:297-302
     F = Family("k", D)
     n = plan_tail(B, h, Mq, Mk, F.QB, F.wg, F.rec, bounded, n_cus)["ws_bytes"]
     if bounded and cdiv(Mk, KV) >= 16:
@@ -136,19 +136,19 @@ def ws_bytes_k(D, B, h, Mq, Mk, bounded, n_cus):     # attention.hip:744-750
     return n
 
 
-def ws_bytes16(B, h, Mq, Mk, bounded, n_cus):        # attention16.hip:547-553
+def ws_bytes16(B, h, Mq, Mk, bounded, n_cus):        # attention_plan.h:297-302
     F = Family("16s", 40)
     n = plan_tail(B, h, Mq, Mk, F.QB, 1, F.rec, bounded, n_cus)["ws_bytes"]
     return max(n, devplan_ws_bytes(n_cus, F.rec)) if bounded else n
 
 
-def ws_bytes16g(ng, src, h, Mq, Mk, bounded, n_cus):  # attention16g.hip:494-500
+def ws_bytes16g(ng, src, h, Mq, Mk, bounded, n_cus):  # attention_plan.h:297-302
     F = Family("16g", 40, ng)
     n = plan_tail(src, h, Mq, Mk, F.QB, 1, F.rec, False, n_cus)["ws_bytes"]
     return max(n, devplan_ws_bytes(n_cus, F.rec)) if bounded else n
 
 
-def ws_bytes_any(B, h, Mq, Mk, d, bounded, n_cus):    # attention.hip:753-772
+def ws_bytes_any(B, h, Mq, Mk, d, bounded, n_cus):    # attention.hip:677-689
     if B <= 0 or h <= 0 or Mq <= 0 or Mk <= 0:
         return 0
     if d == 40:
@@ -160,12 +160,12 @@ def ws_bytes_any(B, h, Mq, Mk, d, bounded, n_cus):    # attention.hip:753-772
     return ws_bytes_k(d, B, h, Mq, Mk, bounded, n_cus) if d in KERNEL_DIMS else 0
 
 
-def shape16_for(d, share_groups):                     # attention.hip:719-722 (16-bit dtypes)
+def shape16_for(d, share_groups):                     # attention.hip:670-673 (16-bit dtypes)
     return (share_groups if share_groups <= 3 else 0) if d == 40 else 0
 
 
 def device_plan(counts, H, QB, slots, ntiles):
-    """attention16_plan_kernel (attention16_parts.h:41-78): the 44 int32 of the DevPlan it writes."""
+    """attention16_plan_kernel (attention_plan.h:171-208): the 44 int32 of the DevPlan it writes."""
     nqb = max([1] + [cdiv(c, QB) for c in counts])
     Lit, S = nqb * H * len(counts), slots
     max_ns = max(1, min(PLAN_MAX_SPLIT, ntiles // 8))
@@ -208,9 +208,9 @@ class Selection:
 
     def __init__(self, call, d, B, h, Mq, Mk, share, ldvt, ws_bytes, counts, n_cus):
         bounded = counts is not None                  # (a query count is what makes a launch bounded)
-        if call == "folded":                          # attention.hip:857-866
+        if call == "folded":                          # attention.hip:779-780
             kind = "16s" if d == 40 else "k"
-        else:                                         # attention.hip:800-809
+        else:                                         # attention.hip:727-737
             ng = shape16_for(d, share)
             if ng == 1:
                 kind = "16s"
@@ -226,7 +226,7 @@ class Selection:
         xcd_pairs = (self.items_B * h) // 8 if (self.items_B * h) % 8 == 0 else 0
         nqb_max = cdiv(Mq, F.QB)
         self.header = None
-        # the device plan: attention.hip:655-656, attention16.hip:499-500, attention16g.hip:452
+        # the device plan: attention_plan.h:250-251
         if bounded and ws_bytes is not None and ws_bytes >= devplan_ws_bytes(slots, F.rec) and \
                 nqb_max * h * self.items_B >= 2 * slots:
             self.plan, self.combine = "device", "16" if kind != "k" else "plain"
@@ -240,7 +240,7 @@ class Selection:
                 self.split += [(item_of(item0 + i, self.nqb, xg), ns, rec0 + i * ns) for i in range(items)]
             self.ws_used = DEVPLAN_HEADER + sum(ns for _, ns, _ in self.split) * F.rec
             return
-        # the host plans: attention.hip:673-680, attention16.hip:517-523, attention16g.hip:470-474
+        # the host plans: attention_plan.h:270-277
         p = plan_tail(self.items_B, h, Mq, Mk, F.QB, F.wg, F.rec, bounded and kind != "16g", n_cus)
         if p["split_all"] and (ws_bytes is None or ws_bytes < p["ws_bytes"]):
             p = plan_tail(self.items_B, h, Mq, Mk, F.QB, F.wg, F.rec, False, n_cus)
@@ -253,9 +253,9 @@ class Selection:
             self.combine = None
         elif kind != "k":
             self.combine = "16"
-        else:                                         # attention.hip:698
+        else:                                         # attention.hip:639-641
             self.combine = "parts" if (not pv16_for(d) and rem * 4 <= n_cus) else "plain"
-        xg = xcd_pairs if p["nqb"] >= F.xcd_min else 0   # attention.hip:691, attention16.hip:526, attention16g.hip:478
+        xg = xcd_pairs if p["nqb"] >= F.xcd_min else 0   # attention_plan.h:288
         self.rec_base = 0
         self.split = [(item_of(p["full"] + i, p["nqb"], xg), p["nsplit"], i * p["nsplit"]) for i in range(rem)] \
             if p["nsplit"] > 1 else []
@@ -272,7 +272,7 @@ class Selection:
 
 
 def pieces(Mk, ns):
-    """Key ranges of the `ns` pieces of a split item over Mk keys (attention.hip:570-572, attention16.hip:336-338)."""
+    """Key ranges of the `ns` pieces of a split item over Mk keys (attention.hip:572-574, attention16.hip:339-341)."""
     ntiles = cdiv(Mk, KV)
     tps = cdiv(ntiles, ns)
     out = []

@@ -2476,7 +2476,7 @@ def test_attention_bounded_equals_unbounded_prefix(L, monkeypatch):
 @pytest.mark.parametrize("d,h", [(40, 8), (64, 5), (80, 8)])
 def test_attention_device_planned_tail_every_live_fraction(L, d, h):
     """Round 6: a query-bounded launch of two or more rounds of workgroups is planned on the device from the live counts
-    (attention16_plan_kernel: whole items, then tiers split 2 / 4 / 8 / 16 ways along the key axis; csrc/attention16_parts.h) --
+    (attention16_plan_kernel: whole items, then tiers split 2 / 4 / 8 / 16 ways along the key axis; csrc/attention_plan.h) --
     by attention16s_kernel at d = 40 and by attention_kernel at every other head dim.  Whatever the counts make of the plan
     (no tail, one tier, several, a launch that no longer fills the chip; different counts per sample), every row below its
     sample's count must equal the plain launch's row within the tolerance of another summation order.  vidtome/patch.py:157-162
@@ -2496,7 +2496,7 @@ def test_attention_device_planned_tail_every_live_fraction(L, d, h):
         for b, n in enumerate(count.tolist()):
             assert torch.isfinite(got[b, :n]).all(), (d, f0, f1, b)
             assert (got[b, :n].float() - full[b, :n].float()).abs().max() < 2e-3 * scale, (d, f0, f1, b)
-        # the plan the launch ran on sits in the first 256 bytes of the call's workspace (csrc/attention16_parts.h: DevPlan =
+        # the plan the launch ran on sits in the first 256 bytes of the call's workspace (csrc/attention_plan.h: DevPlan =
         # {nqb, ntiers, split_items, pad, 8 x {wg0, item0, items, nsplit, rec0}}): its invariants, whatever the counts
         ws = L._workspace("attention", 256, q.device)
         plan = ws[:176].view(torch.int32).cpu().tolist()

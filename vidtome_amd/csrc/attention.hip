@@ -26,10 +26,9 @@
 //   * d = 40 builds O^T from 16-row blocks (v_mfma_f32_16x16x32: 48 rows instead of 64, a quarter of the
 //     PV matrix work gone); P^T moves from the 32-query accumulator layout to the two 16-query B operands
 //     with v_permlane16_swap -- 8 swaps per tile, still no LDS round trip (PV16 below).
-#include "attention16_parts.h"   // (the device-side launch plan of query-bounded launches: DevPlan, attention16_plan_kernel)
+#include "attention_plan.h"
 
 #include <algorithm>
-#include <cstdlib>
 #include <type_traits>
 
 namespace {
@@ -46,7 +45,7 @@ __global__ __launch_bounds__(waves_for(D) * 64) void attention_combine_kernel(
     const int l31 = lane & 31, hi = lane >> 5;
     int64_t rec0 = (int64_t)blockIdx.x * nsplit;   // first partial record of this item
     int64_t pos = id0 + blockIdx.x;
-    if (dev_plan != nullptr) {        // device-planned launch (attention16_parts.h): the launch is sized for the most items a plan can split
+    if (dev_plan != nullptr) {        // device-planned launch (attention_plan.h): the launch is sized for the most items a plan can split
         if ((int)blockIdx.x >= dev_plan->split_items) return;
         nqb = dev_plan->nqb;
         xcd_groups = nqb >= 64 ? xcd_groups : 0;
@@ -207,7 +206,7 @@ __global__ __launch_bounds__(waves_for(D) * 64, (D <= 48 ? 4 : D <= 96 ? 4 : 1))
     const int l31 = lane & 31, hi = lane >> 5;
     const int l15 = lane & 15, g16 = lane >> 4;   // PV16 operand coordinates
     // (round 6) query-bounded launches: the roles come from the plan one thread made on the device from the live counts --
-    // whole items first, then tiers of items split 2, 4, 8, 16 ways (attention16_parts.h); workgroups behind the plan leave
+    // whole items first, then tiers of items split 2, 4, 8, 16 ways (attention_plan.h); workgroups behind the plan leave
     int64_t tier_item0 = nwhole, tier_wg0 = nwhole, tier_rec0 = 0;
     if (dev_plan != nullptr) {
         nqb = dev_plan->nqb;
@@ -624,96 +623,45 @@ __global__ __launch_bounds__(waves_for(D) * 64, (D <= 48 ? 4 : D <= 96 ? 4 : 1))
         write_output<T, D>(o, l_run, out, ldo, b, h, q0, M, Mp, l31, hi);
 }
 
-// attention_kernel<D> for the planners: resident workgroups per CU (launch bounds / LDS), the partial record of a key-split
-// workgroup
-constexpr int wg_per_cu_for(int D) { return D <= 48 ? 2 : 1; }
-constexpr size_t rec_bytes_for(int D) { return (size_t)rec_floats(D) * (waves_for(D) * 64) * sizeof(float); }
+// ---- attention_kernel's family ----
+constexpr size_t lds_for(int D) { return (size_t)2 * (KV * ((D + 15) / 16 * 16 + 8) + vrows_for(D) * VT_STRIDE) * 2; }
+
+template <typename T, int D, bool FOLD>
+void launch_main(const Call &c, const Launch &g) {
+    hipLaunchKernelGGL((attention_kernel<T, D, FOLD>), dim3((unsigned)g.wgs), dim3(waves_for(D) * 64), lds_for(D), c.s,
+                       (const T *)c.q, c.ldq, (const T *)c.k, c.ldk, (const T *)c.vt, c.ldvt, (T *)c.out, c.ldo, c.h, c.M, c.Mp,
+                       c.Mk, c.Mkp, g.scale_log2e, g.src_batch, g.nqb, g.whole, g.nsplit, g.partial, g.xcd_groups, c.q_count,
+                       g.split_major, c.k_count, c.k_bias, c.ldkb, plan_of(g));
+}
+
+template <typename T, int D>
+void launch_combine(const Call &c, const Launch &g) {
+    if constexpr (!pv16_for(D) && acc_floats(D) % 8 == 0) {
+        // few items of a host plan: their accumulator groups are shared out (attention_combine_parts_kernel)
+        if (g.plan == nullptr && g.split_items * 4 <= vtm::device_cus()) {
+            hipLaunchKernelGGL((attention_combine_parts_kernel<T, D>), dim3((unsigned)g.split_items, (unsigned)(acc_floats(D) / 8)),
+                               dim3(waves_for(D) * 64), 0, c.s, (const float *)g.partial, (T *)c.out, c.ldo, c.h, c.M, c.Mp,
+                               g.nqb, g.whole, g.nsplit, g.xcd_groups, c.q_count);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((attention_combine_kernel<T, D>), dim3((unsigned)g.split_items), dim3(waves_for(D) * 64), 0, c.s,
+                       (const float *)g.partial, (T *)c.out, c.ldo, c.h, c.M, c.Mp, g.nqb, g.whole, g.nsplit, g.xcd_groups,
+                       c.q_count, plan_of(g));
+}
 
 template <typename T, int D, bool FOLD = false>
-int launch(const void *q, int64_t ldq, const void *k, int64_t ldk, const void *vt, int64_t ldvt, void *out,
-           int64_t ldo, int64_t B, int64_t h, int64_t M, int64_t Mp, int64_t Mk, int64_t Mkp, float scale, int share_groups,
-           void *ws, size_t ws_bytes, const int32_t *q_count, hipStream_t s, const int32_t *k_count = nullptr,
-           const uint32_t *k_bias = nullptr, int64_t ldkb = 0) {
-    constexpr int DK = (D + 15) / 16;
-    constexpr size_t lds = (size_t)2 * (KV * (DK * 16 + 8) + vrows_for(D) * VT_STRIDE) * 2;
-    if (lds > 64 * 1024) {   // opt in to > 64 KB of dynamic LDS once per (kernel instantiation, device)
-        static std::atomic<bool> attr_set[vtm::MAX_DEVICES];   // (one per instantiation of this function template)
-        const int dev = vtm::current_device();
-        if (!attr_set[dev].load(std::memory_order_acquire)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(attention_kernel<T, D, FOLD>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess)
-                return vtm::fail(VTM_ELAUNCH, "vtm_attention: LDS attribute: %s", hipGetErrorString(e));
-            attr_set[dev].store(true, std::memory_order_release);
-        }
-    }
-    constexpr int WAVES = waves_for(D), QB = WAVES * QW;
-    const float scale_log2e = scale * 1.4426950408889634f;
-    // (round 6) a query-bounded launch is planned ON THE DEVICE from the live counts when the workspace holds the plan and
-    // the records of the largest tail a plan can have (vtm_attention_kv_bounded_ws_bytes): whole items, then tiers split
-    // 2 .. 16 ways -- rounds 4-5 split every item in two (plan_tail's `bounded`, still the plan of a smaller workspace)
-    // (launches of at least two rounds: the oversized grid and the two small launches of a plan cost 50-70 us, which a
-    // one-round launch does not get back -- profiles/r06_k_devplan_attention_kernel.txt)
-    const int slots = vtm::device_cus() * wg_per_cu_for(D);
-    if (q_count != nullptr && ws != nullptr && ws_bytes >= devplan_ws_bytes(slots, rec_bytes_for(D)) &&
-        vtm::cdiv(M, QB) * h * B >= 2 * slots) {
-        DevPlan *plan = reinterpret_cast<DevPlan *>(ws);
-        float *records = reinterpret_cast<float *>(static_cast<char *>(ws) + DEVPLAN_HEADER);
-        const int64_t nqb_max = vtm::cdiv(M, QB), total = nqb_max * h * B, tail_max = plan_tail_wgs(slots);
-        VTM_REQUIRE(total + tail_max < (1ll << 31) / 16, "vtm_attention: grid too large");
-        const int xcd_pairs = (B * h) % 8 == 0 ? (int)(B * h / 8) : 0;
-        hipLaunchKernelGGL(attention16_plan_kernel, dim3(1), dim3(64), 0, s, q_count, (int)B, (int)h, QB, slots,
-                           (int)vtm::cdiv(Mk, KV), plan);
-        hipLaunchKernelGGL((attention_kernel<T, D, FOLD>), dim3((unsigned)(total + tail_max)), dim3(WAVES * 64), lds, s,
-                           (const T *)q, ldq, (const T *)k, ldk, (const T *)vt, ldvt, (T *)out, ldo, h, M, Mp, Mk, Mkp,
-                           scale_log2e, B / share_groups, nqb_max, total, 1, records, xcd_pairs, q_count,
-                           (int64_t)0, k_count, k_bias, ldkb, (const DevPlan *)plan);
-        hipLaunchKernelGGL((attention_combine_kernel<T, D>), dim3((unsigned)plan_split_items(slots)), dim3(WAVES * 64), 0, s,
-                           (const float *)records, (T *)out, ldo, h, M, Mp, nqb_max, total, 1, xcd_pairs, q_count,
-                           (const DevPlan *)plan);
-        return vtm::launch_status("vtm_attention");
-    }
-    TailPlan p = plan_tail(B, h, M, Mk, QB, wg_per_cu_for(D), rec_bytes_for(D), q_count != nullptr);
-    if (p.split_all && (!ws || ws_bytes < p.ws_bytes))   // not enough workspace: the plain plan
-        p = plan_tail(B, h, M, Mk, QB, wg_per_cu_for(D), rec_bytes_for(D), false);
-    if (p.nsplit > 1 && (!ws || ws_bytes < p.ws_bytes)) {   // no workspace: plain single launch
-        p.nsplit = 1;
-        p.full = p.total;
-        p.split_all = false;
-    }
-    const int64_t src_batch = B / share_groups;
-    VTM_REQUIRE(p.total < (1ll << 31) / 16, "vtm_attention: grid too large");
-    // one launch: the whole workgroups first, the key-split ones of the last round behind them (they start as the
-    // slots of the last whole round free up -- no launch boundary to drain)
-    const int64_t rem = p.total - p.full;
-    // (sample, head) pairs pinned to XCDs when they divide evenly and every pair has enough query blocks to keep an
-    // XCD's share of the chip busy (see item_of); VTM_ATT_NO_XCD_MAP is an A/B build switch
-#ifdef VTM_ATT_NO_XCD_MAP
-    const int xcd_groups = 0;
-#else
-    const int xcd_groups = ((B * h) % 8 == 0 && p.nqb >= 64) ? (int)(B * h / 8) : 0;
-#endif
-    hipLaunchKernelGGL((attention_kernel<T, D, FOLD>), dim3((unsigned)(p.full + rem * p.nsplit)), dim3(WAVES * 64), lds, s,
-                       (const T *)q, ldq, (const T *)k, ldk, (const T *)vt, ldvt, (T *)out, ldo, h, M, Mp, Mk, Mkp,
-                       scale_log2e, src_batch, p.nqb, p.full, p.nsplit, (float *)ws, xcd_groups, q_count,
-                       p.split_all ? rem : (int64_t)0, k_count, k_bias, ldkb, (const DevPlan *)nullptr);
-    // (few items: their accumulator groups are shared out, attention_combine_parts_kernel)
-    bool parts = !pv16_for(D) && rem * 4 <= vtm::device_cus() && acc_floats(D) % 8 == 0;
-    static const bool no_parts = getenv("VTM_DEBUG_COMBINE_PARTS") != nullptr;   // A/B hook, read once per process
-    if (no_parts) parts = false;
-    if (p.nsplit > 1) {
-        if constexpr (!pv16_for(D)) {
-            if (parts)
-                hipLaunchKernelGGL((attention_combine_parts_kernel<T, D>), dim3((unsigned)rem, (unsigned)(acc_floats(D) / 8)),
-                                   dim3(WAVES * 64), 0, s, (const float *)ws, (T *)out, ldo, h, M, Mp, p.nqb, p.full, p.nsplit,
-                                   xcd_groups, q_count);
-        }
-        if (!parts)
-            hipLaunchKernelGGL((attention_combine_kernel<T, D>), dim3((unsigned)rem), dim3(WAVES * 64), 0, s,
-                               (const float *)ws, (T *)out, ldo, h, M, Mp, p.nqb, p.full, p.nsplit, xcd_groups, q_count,
-                               (const DevPlan *)nullptr);
-    }
-    return vtm::launch_status("vtm_attention");
+Family make_family() {
+    Family f;
+    f.qb = waves_for(D) * QW;
+    f.wg_per_cu = D <= 48 ? 2 : 1;
+    f.rec_bytes = (size_t)rec_floats(D) * (waves_for(D) * 64) * sizeof(float);
+    f.xcd_min_nqb = 64;
+    f.ws_devplan_min_tiles = 16;
+    if constexpr (lds_for(D) > 64 * 1024) f.lds_opt_in = opt_in_lds<attention_kernel<T, D, FOLD>, lds_for(D)>;
+    f.main = launch_main<T, D, FOLD>;
+    f.combine = launch_combine<T, D>;
+    return f;
 }
 
 // Which launches go to the wide-tile d = 40 kernels (round 6): self-attention to attention16s_kernel (attention16.hip, which
@@ -724,54 +672,39 @@ int shape16_for(int64_t d, int share_groups, int dtype) {
     return share_groups <= 3 ? share_groups : 0;
 }
 
-template <typename T>
-int dispatch(int64_t d, const void *q, int64_t ldq, const void *k, int64_t ldk, const void *vt, int64_t ldvt,
-             void *out, int64_t ldo, int64_t B, int64_t h, int64_t M, int64_t Mp, int64_t Mk, int64_t Mkp, float scale, int sg,
-             void *ws, size_t ws_bytes, const int32_t *q_count, hipStream_t s) {
-    switch (d) {
-        case 40: return launch<T, 40>(q, ldq, k, ldk, vt, ldvt, out, ldo, B, h, M, Mp, Mk, Mkp, scale, sg, ws, ws_bytes, q_count, s);
-        case 64: return launch<T, 64>(q, ldq, k, ldk, vt, ldvt, out, ldo, B, h, M, Mp, Mk, Mkp, scale, sg, ws, ws_bytes, q_count, s);
-        case 80: return launch<T, 80>(q, ldq, k, ldk, vt, ldvt, out, ldo, B, h, M, Mp, Mk, Mkp, scale, sg, ws, ws_bytes, q_count, s);
-        case 160: return launch<T, 160>(q, ldq, k, ldk, vt, ldvt, out, ldo, B, h, M, Mp, Mk, Mkp, scale, sg, ws, ws_bytes, q_count, s);
-        case 8: return launch<T, 8>(q, ldq, k, ldk, vt, ldvt, out, ldo, B, h, M, Mp, Mk, Mkp, scale, sg, ws, ws_bytes, q_count, s);
-        case 16: return launch<T, 16>(q, ldq, k, ldk, vt, ldvt, out, ldo, B, h, M, Mp, Mk, Mkp, scale, sg, ws, ws_bytes, q_count, s);
-        case 32: return launch<T, 32>(q, ldq, k, ldk, vt, ldvt, out, ldo, B, h, M, Mp, Mk, Mkp, scale, sg, ws, ws_bytes, q_count, s);
-        case 96: return launch<T, 96>(q, ldq, k, ldk, vt, ldvt, out, ldo, B, h, M, Mp, Mk, Mkp, scale, sg, ws, ws_bytes, q_count, s);
-        case 128: return launch<T, 128>(q, ldq, k, ldk, vt, ldvt, out, ldo, B, h, M, Mp, Mk, Mkp, scale, sg, ws, ws_bytes, q_count, s);
-    }
-    return vtm::fail(VTM_EINVAL, "vtm_attention: unsupported head dim %lld (have 8,16,32,40,64,80,96,128,160)",
-                     (long long)d);
-}
-
-// workspace of attention_kernel<D>: its host tail plan, or a device plan for a bounded launch over at least 16 key tiles
-template <int D>
-size_t ws_bytes_for(int64_t B, int64_t h, int64_t Mq, int64_t Mk, bool bounded) {
-    size_t n = plan_tail(B, h, Mq, Mk, waves_for(D) * QW, wg_per_cu_for(D), rec_bytes_for(D), bounded).ws_bytes;
-    if (bounded && vtm::cdiv(Mk, KV) >= 16)
-        n = std::max(n, devplan_ws_bytes(vtm::device_cus() * wg_per_cu_for(D), rec_bytes_for(D)));
-    return n;
-}
-
-// d = 40: the caller does not say how the launch will share its probabilities -- the largest plan any kernel could choose
+// the workspace of the largest plan a 16-bit call of this shape can take (d = 40: the caller does not say how the launch will
+// share its probabilities -- attention_kernel, attention16s_kernel or attention16g_kernel); no size depends on the element type
 size_t ws_bytes_any(int64_t B, int64_t h, int64_t Mq, int64_t Mk, int64_t d, bool bounded) {
     if (B <= 0 || h <= 0 || Mq <= 0 || Mk <= 0) return 0;
-    switch (d) {
-        case 40: {
-            size_t n = std::max(ws_bytes_for<40>(B, h, Mq, Mk, bounded), ws_bytes16(B, h, Mq, Mk, bounded));
+    return with_head_dim(d, [&](auto dim) {
+        constexpr int D = decltype(dim)::value;
+        size_t n = ws_bytes(make_family<__half, D>(), B, h, Mq, Mk, bounded);
+        if constexpr (D == 40) {
+            n = std::max(n, ws_bytes(family16s(VTM_F16, false), B, h, Mq, Mk, bounded));
             for (int ng = 2; ng <= 3; ++ng)
-                if (B % ng == 0) n = std::max(n, ws_bytes16g(ng, B / ng, h, Mq, Mk, bounded));
-            return n;
+                if (B % ng == 0) n = std::max(n, ws_bytes(family16g(VTM_F16, ng), B, h, Mq, Mk, bounded));
         }
-        case 64: return ws_bytes_for<64>(B, h, Mq, Mk, bounded);
-        case 80: return ws_bytes_for<80>(B, h, Mq, Mk, bounded);
-        case 160: return ws_bytes_for<160>(B, h, Mq, Mk, bounded);
-        case 8: return ws_bytes_for<8>(B, h, Mq, Mk, bounded);
-        case 16: return ws_bytes_for<16>(B, h, Mq, Mk, bounded);
-        case 32: return ws_bytes_for<32>(B, h, Mq, Mk, bounded);
-        case 96: return ws_bytes_for<96>(B, h, Mq, Mk, bounded);
-        case 128: return ws_bytes_for<128>(B, h, Mq, Mk, bounded);
-    }
-    return 0;
+        return n;
+    });
+}
+
+// The argument checks of every attention export; `who` names the export in the messages.  Folded keys (c.fold) also need
+// their counts and bias rows and a head dim with spare k-slots.
+int check_call(const Call &c, int64_t d, const char *who) {
+    VTM_REQUIRE(c.q && c.k && c.vt && c.out && (!c.fold || (c.k_count && c.k_bias)), "%s: null pointer", who);
+    // (a folded head dim is checked against 8 and 40 below)
+    VTM_REQUIRE(c.B > 0 && c.h > 0 && c.M > 0 && c.Mk > 0 && c.Mp >= c.M && c.Mkp >= c.Mk && (c.fold ? c.ldkb >= c.Mk : d > 0),
+                "%s: bad sizes", who);
+    VTM_REQUIRE(c.share_groups >= 1 && c.B % c.share_groups == 0, "%s: B %% share_groups != 0", who);
+    if (c.fold)
+        VTM_REQUIRE(d == 40 || d == 8, "%s: head dim %lld has no spare k-slots for the bias (d = 8, 40 do)", who, (long long)d);
+    VTM_REQUIRE(c.ldq % 8 == 0 && c.ldk % 8 == 0 && c.ldvt % 8 == 0 && c.ldo % 4 == 0 && c.ldvt >= c.Mk,
+                "%s: leading dimensions must keep 16-byte alignment (ldvt >= Mk, %% 8)", who);
+    // K / V^T tiles are addressed with 32-bit byte offsets inside one (sample, head) slice (buffer loads)
+    VTM_REQUIRE((c.Mkp * c.ldk + d) * 2 < (1ll << 31) && (d * c.ldvt + c.Mkp) * 2 < (1ll << 31) &&
+                    (!c.fold || c.Mkp * 4 < (1ll << 31)),
+                "%s: a (sample, head) slice of K or V^T must stay below 2 GiB", who);
+    return VTM_OK;
 }
 
 }  // namespace
@@ -788,29 +721,20 @@ static int attention_any(const void *q, int64_t ldq, const void *k, int64_t ldk,
                          void *out, int64_t ldo, int dtype, int64_t B, int64_t h, int64_t Mq, int64_t Mqp, int64_t Mk,
                          int64_t Mkp, int64_t d, float scale, int share_groups, void *ws, size_t ws_bytes,
                          const int32_t *q_count, vtm_stream_t stream) {
-    VTM_REQUIRE(q && k && vt && out, "vtm_attention: null pointer");
-    VTM_REQUIRE(B > 0 && h > 0 && Mq > 0 && Mk > 0 && d > 0 && Mqp >= Mq && Mkp >= Mk, "vtm_attention: bad sizes");
-    VTM_REQUIRE(share_groups >= 1 && B % share_groups == 0, "vtm_attention: B %% share_groups != 0");
-    VTM_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 8 == 0 && ldo % 4 == 0 && ldvt >= Mk,
-                "vtm_attention: leading dimensions must keep 16-byte alignment (ldvt >= Mk, %% 8)");
-    // K / V^T tiles are addressed with 32-bit byte offsets inside one (sample, head) slice (buffer loads)
-    VTM_REQUIRE((Mkp * ldk + d) * 2 < (1ll << 31) && (d * ldvt + Mkp) * 2 < (1ll << 31),
-                "vtm_attention: a (sample, head) slice of K or V^T must stay below 2 GiB");
-    hipStream_t s = vtm::as_stream(stream);
-    const Args16 a{q, ldq, k, ldk, vt, ldvt, out, ldo, dtype, B, h, Mq, Mqp, Mk, Mkp, scale, share_groups, ws, ws_bytes,
-                   q_count, s, false, nullptr, nullptr, 0};
-    if (dtype == VTM_F32) return attention_f32(a, d);   // (attention_f32.hip: fp32 operands on the f32 MFMA)
+    const Call c{q, ldq, k, ldk, vt, ldvt, out, ldo, dtype, B, h, Mq, Mqp, Mk, Mkp, scale, share_groups, ws, ws_bytes,
+                 q_count, vtm::as_stream(stream), false, nullptr, nullptr, 0};
+    if (const int e = check_call(c, d, "vtm_attention")) return e;
+    if (dtype == VTM_F32) return attention_f32(c, d);   // (attention_f32.hip: fp32 operands on the f32 MFMA)
     const int ng = shape16_for(d, share_groups, dtype);
-    if (ng == 1) return attention16(a);
+    if (ng == 1) return attention16(c);
     // the value groups of one (source sample, head) share a buffer descriptor: the sample stride rides in the offset
-    if (ng > 1 && (ng * (B / share_groups) * h * d * ldvt) * 2 < (1ll << 31)) return attention16g(a, ng);
-    if (dtype == VTM_F16)
-        return dispatch<__half>(d, q, ldq, k, ldk, vt, ldvt, out, ldo, B, h, Mq, Mqp, Mk, Mkp, scale, share_groups, ws,
-                                ws_bytes, q_count, s);
-    if (dtype == VTM_BF16)
-        return dispatch<vtm_bf16>(d, q, ldq, k, ldk, vt, ldvt, out, ldo, B, h, Mq, Mqp, Mk, Mkp, scale, share_groups, ws,
-                                  ws_bytes, q_count, s);
-    return vtm::fail(VTM_EINVAL, "vtm_attention: dtype must be VTM_F16, VTM_BF16 or VTM_F32");
+    if (ng > 1 && (ng * (B / share_groups) * h * d * ldvt) * 2 < (1ll << 31)) return attention16g(c, ng);
+    if (dtype != VTM_F16 && dtype != VTM_BF16)
+        return vtm::fail(VTM_EINVAL, "vtm_attention: dtype must be VTM_F16, VTM_BF16 or VTM_F32");
+    return with_head_dim(d, [&](auto dim) {
+        constexpr int D = decltype(dim)::value;
+        return planned_launch(c, dtype == VTM_F16 ? make_family<__half, D>() : make_family<vtm_bf16, D>());
+    });
 }
 
 VTM_EXPORT int vtm_attention_kv(const void *q, int64_t ldq, const void *k, int64_t ldk, const void *vt, int64_t ldvt,
@@ -847,26 +771,13 @@ VTM_EXPORT int vtm_attention_kv_folded(const void *q, int64_t ldq, const void *k
                                        int64_t Mk, int64_t Mkp, int64_t d, float scale, const int32_t *q_count,
                                        const int32_t *k_count, const uint32_t *k_bias, int64_t ldkb, void *ws, size_t ws_bytes,
                                        vtm_stream_t stream) {
-    VTM_REQUIRE(q && k && vt && out && k_count && k_bias, "vtm_attention_kv_folded: null pointer");
-    VTM_REQUIRE(B > 0 && h > 0 && Mq > 0 && Mk > 0 && Mqp >= Mq && Mkp >= Mk && ldkb >= Mk, "vtm_attention_kv_folded: bad sizes");
-    VTM_REQUIRE(d == 40 || d == 8, "vtm_attention_kv_folded: head dim %lld has no spare k-slots for the bias (d = 8, 40 do)", (long long)d);
-    VTM_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 8 == 0 && ldo % 4 == 0 && ldvt >= Mk,
-                "vtm_attention_kv_folded: leading dimensions must keep 16-byte alignment (ldvt >= Mk, %% 8)");
-    VTM_REQUIRE((Mkp * ldk + d) * 2 < (1ll << 31) && (d * ldvt + Mkp) * 2 < (1ll << 31) && Mkp * 4 < (1ll << 31),
-                "vtm_attention_kv_folded: a (sample, head) slice of K or V^T must stay below 2 GiB");
-    hipStream_t s = vtm::as_stream(stream);
+    const Call c{q, ldq, k, ldk, vt, ldvt, out, ldo, dtype, B, h, Mq, Mqp, Mk, Mkp, scale, 1, ws, ws_bytes,
+                 q_count, vtm::as_stream(stream), true, k_count, k_bias, ldkb};
+    if (const int e = check_call(c, d, "vtm_attention_kv_folded")) return e;
     if (dtype == VTM_F32) return vtm::fail(VTM_EINVAL, "vtm_attention_kv_folded: fp32 keys are never folded (dtype must be VTM_F16 or VTM_BF16)");
     if (dtype != VTM_F16 && dtype != VTM_BF16) return vtm::fail(VTM_EINVAL, "vtm_attention_kv_folded: dtype must be VTM_F16 or VTM_BF16");
-    if (d == 40) {   // attention16s_kernel; d = 8: attention_kernel
-        const Args16 a{q, ldq, k, ldk, vt, ldvt, out, ldo, dtype, B, h, Mq, Mqp, Mk, Mkp, scale, 1, ws, ws_bytes,
-                       q_count, s, true, k_count, k_bias, ldkb};
-        return attention16(a);
-    }
-    if (dtype == VTM_F16)
-        return launch<__half, 8, true>(q, ldq, k, ldk, vt, ldvt, out, ldo, B, h, Mq, Mqp, Mk, Mkp, scale, 1, ws, ws_bytes, q_count, s,
-                                       k_count, k_bias, ldkb);
-    return launch<vtm_bf16, 8, true>(q, ldq, k, ldk, vt, ldvt, out, ldo, B, h, Mq, Mqp, Mk, Mkp, scale, 1, ws, ws_bytes, q_count, s,
-                                     k_count, k_bias, ldkb);
+    if (d == 40) return attention16(c);   // attention16s_kernel; d = 8: attention_kernel
+    return planned_launch(c, dtype == VTM_F16 ? make_family<__half, 8, true>() : make_family<vtm_bf16, 8, true>());
 }
 
 VTM_EXPORT int vtm_attention(const void *q, int64_t ldq, const void *k, int64_t ldk, const void *vt,

@@ -486,79 +486,46 @@ __global__ __launch_bounds__(WAVES * 64, 2) void attention16s_kernel(
         write_output16<T, D>(o16[sub], out, ldo, b, h, qblock0 + (wave * NQ + sub) * QW, M, Mp, lane);
 }
 
-template <typename T, int D, bool FOLD, int WAVES>
-int launch16(const Args16 &a) {
-    constexpr int DK = (D + 15) / 16, NT = WAVES * 64, QB = WAVES * QW * 2, NV = 2;   // (two query sub-tiles per wave)
-    constexpr size_t lds = (size_t)(3 * KV * (DK * 16 + 8) + 2 * vrows_for(D) * VT_STRIDE) * 2;
-    static_assert(lds <= 64 * 1024, "dynamic LDS beyond 64 KB needs hipFuncSetAttribute");
-    const auto kernel = attention16s_kernel<T, D, FOLD, WAVES>;
-    const int64_t src_batch = a.B / a.share_groups;
-    const size_t rec_bytes = (size_t)NV * rec16<D>() * NT * sizeof(float);
-    const float scale_log2e = a.scale * 1.4426950408889634f;
-    const int64_t nqb_max = vtm::cdiv(a.M, QB);
-    const int xcd_pairs = (a.B * a.h) % 8 == 0 ? (int)(a.B * a.h / 8) : 0;
-    // query-bounded: planned on the device (attention16_plan_kernel) when the workspace holds the plan and its records
-    const int slots = vtm::device_cus();       // one workgroup per CU
-    if (a.q_count != nullptr && a.ws != nullptr && a.ws_bytes >= devplan_ws_bytes(slots, rec_bytes) &&
-        nqb_max * a.h * a.B >= 2 * slots) {      // (at least two rounds: a plan costs 50-70 us of small launches)
-        DevPlan *plan = reinterpret_cast<DevPlan *>(a.ws);
-        float *records = reinterpret_cast<float *>(static_cast<char *>(a.ws) + DEVPLAN_HEADER);
-        const int ntiles = (int)vtm::cdiv(a.Mk, KV);
-        hipLaunchKernelGGL(attention16_plan_kernel, dim3(1), dim3(64), 0, a.s, a.q_count, (int)a.B, (int)a.h, QB, slots,
-                           ntiles, plan);
-        const int64_t total = nqb_max * a.h * a.B, tail_max = plan_tail_wgs(slots);
-        VTM_REQUIRE(total + tail_max < (1ll << 31) / 16, "vtm_attention: grid too large");
-        hipLaunchKernelGGL(kernel, dim3((unsigned)(total + tail_max)), dim3(NT), lds, a.s, (const T *)a.q, a.ldq,
-                           (const T *)a.k, a.ldk, (const T *)a.vt, a.ldvt, (T *)a.out, a.ldo, a.h, a.M, a.Mp, a.Mk, a.Mkp,
-                           scale_log2e, src_batch, nqb_max, total, 1, records, xcd_pairs, a.q_count, (int64_t)0, a.k_count,
-                           a.k_bias, a.ldkb, (const DevPlan *)plan);
-        hipLaunchKernelGGL((attention16_combine_kernel<T, D, 2, 1, WAVES>), dim3((unsigned)plan_split_items(slots), (unsigned)NV),
-                           dim3(NT), 0, a.s, (const float *)records, (T *)a.out, a.ldo, a.h, a.M, a.Mp, nqb_max, total, 1,
-                           xcd_pairs, a.q_count, src_batch, (const DevPlan *)plan);
-        return vtm::launch_status("vtm_attention");
-    }
-    TailPlan p = plan_tail(a.B, a.h, a.M, a.Mk, QB, 1, rec_bytes, a.q_count != nullptr);
-    if (p.split_all && (!a.ws || a.ws_bytes < p.ws_bytes)) p = plan_tail(a.B, a.h, a.M, a.Mk, QB, 1, rec_bytes, false);
-    if (p.nsplit > 1 && (!a.ws || a.ws_bytes < p.ws_bytes)) {
-        p.nsplit = 1;
-        p.full = p.total;
-        p.split_all = false;
-    }
-    VTM_REQUIRE(p.total < (1ll << 31) / 16, "vtm_attention: grid too large");
-    const int64_t rem = p.total - p.full;
-    const int xcd_groups = p.nqb >= 32 ? xcd_pairs : 0;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)(p.full + rem * p.nsplit)), dim3(NT), lds,
-                       a.s, (const T *)a.q, a.ldq, (const T *)a.k, a.ldk, (const T *)a.vt, a.ldvt, (T *)a.out, a.ldo, a.h, a.M,
-                       a.Mp, a.Mk, a.Mkp, scale_log2e, src_batch, p.nqb, p.full, p.nsplit, (float *)a.ws, xcd_groups, a.q_count,
-                       p.split_all ? rem : (int64_t)0, a.k_count, a.k_bias, a.ldkb, (const DevPlan *)nullptr);
-    if (p.nsplit > 1)
-        hipLaunchKernelGGL((attention16_combine_kernel<T, D, 2, 1, WAVES>), dim3((unsigned)rem, (unsigned)NV), dim3(NT), 0, a.s,
-                           (const float *)a.ws, (T *)a.out, a.ldo, a.h, a.M, a.Mp, p.nqb, p.full, p.nsplit, xcd_groups,
-                           a.q_count, src_batch, (const DevPlan *)nullptr);
-    return vtm::launch_status("vtm_attention");
+// ---- attention16s_kernel's family: 8 waves, two 32-query sub-tiles per wave, one workgroup per CU ----
+constexpr int WAVES16 = 8, NT16 = WAVES16 * 64;
+constexpr size_t LDS16 = (size_t)(3 * KV * ((40 + 15) / 16 * 16 + 8) + 2 * vrows_for(40) * VT_STRIDE) * 2;
+static_assert(LDS16 <= 64 * 1024, "dynamic LDS beyond 64 KB needs an opt-in (Family::lds_opt_in)");
+
+template <typename T, bool FOLD>
+void launch_main(const Call &c, const Launch &g) {
+    hipLaunchKernelGGL((attention16s_kernel<T, 40, FOLD, WAVES16>), dim3((unsigned)g.wgs), dim3(NT16), LDS16, c.s,
+                       (const T *)c.q, c.ldq, (const T *)c.k, c.ldk, (const T *)c.vt, c.ldvt, (T *)c.out, c.ldo, c.h, c.M, c.Mp,
+                       c.Mk, c.Mkp, g.scale_log2e, g.src_batch, g.nqb, g.whole, g.nsplit, g.partial, g.xcd_groups, c.q_count,
+                       g.split_major, c.k_count, c.k_bias, c.ldkb, plan_of(g));
 }
 
 template <typename T>
-int dispatch16(const Args16 &a) {
-    return a.fold ? launch16<T, 40, true, 8>(a) : launch16<T, 40, false, 8>(a);
+void launch_combine(const Call &c, const Launch &g) {
+    hipLaunchKernelGGL((attention16_combine_kernel<T, 40, 2, 1, WAVES16>), dim3((unsigned)g.split_items, 2u), dim3(NT16), 0,
+                       c.s, (const float *)g.partial, (T *)c.out, c.ldo, c.h, c.M, c.Mp, g.nqb, g.whole, g.nsplit, g.xcd_groups,
+                       c.q_count, g.src_batch, plan_of(g));
+}
+
+template <typename T, bool FOLD>
+Family make_family() {
+    Family f;
+    f.qb = WAVES16 * QW * 2;
+    f.rec_bytes = (size_t)2 * rec16<40>() * NT16 * sizeof(float);   // (both sub-tiles)
+    f.xcd_min_nqb = 32;
+    f.main = launch_main<T, FOLD>;
+    f.combine = launch_combine<T>;
+    return f;
 }
 
 }  // namespace
 
 namespace vtm_att {
 
-size_t ws_bytes16(int64_t B, int64_t h, int64_t Mq, int64_t Mk, bool bounded) {
-    constexpr int WAVES = 8, NT = WAVES * 64;
-    const size_t rec = (size_t)2 * rec16<40>() * NT * sizeof(float);
-    size_t n = plan_tail(B, h, Mq, Mk, (int64_t)WAVES * QW * 2, 1, rec, bounded).ws_bytes;
-    if (bounded) n = std::max(n, devplan_ws_bytes(vtm::device_cus(), rec));
-    return n;
+Family family16s(int dtype, bool fold) {
+    if (dtype == VTM_F16) return fold ? make_family<__half, true>() : make_family<__half, false>();
+    return fold ? make_family<vtm_bf16, true>() : make_family<vtm_bf16, false>();
 }
 
-int attention16(const Args16 &a) {
-    if (a.dtype == VTM_F16) return dispatch16<__half>(a);
-    if (a.dtype == VTM_BF16) return dispatch16<vtm_bf16>(a);
-    return vtm::fail(VTM_EINVAL, "vtm_attention: dtype must be VTM_F16 or VTM_BF16");
-}
+int attention16(const Call &c) { return planned_launch(c, family16s(c.dtype, c.fold)); }
 
 }  // namespace vtm_att

@@ -1,7 +1,7 @@
 // Internal pieces shared by the two wide-tile d = 40 translation units (attention16.hip, attention16g.hip): the partial record of a
-// key-split workgroup, the device-side launch plan of query-bounded launches and the kernel that combines the records.
+// key-split workgroup and the kernel that combines the records.
 #pragma once
-#include "attention_common.h"
+#include "attention_plan.h"
 
 namespace {
 
@@ -10,72 +10,6 @@ using namespace vtm_att;
 // per-(query sub-tile, value group) record a key-split workgroup leaves for attention16_combine_kernel: the PV16 record of
 // attention.hip (24 accumulators at d = 40, one running max per 16-query half, one unused denominator slot)
 template <int D> constexpr int rec16() { return (D + 16) / 16 * 8 + 2 + 1; }
-
-// ---- device-side launch plan for QUERY-BOUNDED launches (vtm_attention_kv_bounded: compacted live queries) ----
-// How many query blocks are live is a device value (q_count), so the host cannot cut the launch into whole rounds plus a
-// key-split tail the way plan_tail does for a known length; rounds 4-5 split EVERY item in two instead (finer rounds).
-// Measured in round 6 (profiles/r06_d_attention16_ab.txt): 912 live items on 256 slots are 3.56 rounds of work and took the
-// time of 4 (4.81 ms against 4.31).  One thread now plans on the device, in front of the launch, from the counts -- a
-// GEOMETRIC tail: workgroups are dispatched in index order as slots free up, so pieces that shrink towards the end of the
-// grid pack like longest-first list scheduling and the idle tail is one SMALLEST piece long:
-//   L live items (the longest sample's blocks x heads x samples), S slots;
-//   tier 0: the items of the whole rounds, L - L % S of them, one workgroup each (a last round >= 0.8 full, or the only round of a
-//   launch that fills more than half of the chip, counts as whole);
-//   then, while items remain: the next tier takes S / n of them (or what is left), n = the smallest power of two >= 2 with
-//   S / n <= remaining (at most MAX_SPLIT), each split n ways along the key axis -- S pieces, one short round.
-// 912 items on 256 slots: 768 whole, 128 in halves, 16 in sixteenths = 3 + 0.5 + 1/16 rounds -- the work there is.  The
-// launch itself is sized for the host-known upper bound; workgroups the plan has no role for leave at once.
-constexpr int PLAN_TIERS = 8;
-constexpr int PLAN_MAX_SPLIT = 16;
-struct DevTier {
-    int wg0, item0, items, nsplit, rec0;   // first workgroup, first item, items, pieces per item, first partial record
-};
-struct DevPlan {
-    int nqb, ntiers, split_items, pad;     // live query blocks per (sample, head); tiers in use; items behind tier 0
-    DevTier tier[PLAN_TIERS];
-};
-// upper bounds of a plan on S slots: workgroups behind the whole items / partial records, items that are split
-constexpr int64_t plan_tail_wgs(int slots) { return (int64_t)(PLAN_TIERS - 1) * slots; }
-constexpr int64_t plan_split_items(int slots) { return slots; }
-
-__global__ void attention16_plan_kernel(const int32_t *__restrict__ q_count, int B, int H, int QB, int slots, int ntiles,
-                                        DevPlan *__restrict__ plan) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    int nqb = 1;
-    for (int b = 0; b < B; ++b) {
-        const int n = (q_count[b] + QB - 1) / QB;
-        nqb = n > nqb ? n : nqb;
-    }
-    const int L = nqb * H * B, S = slots;
-    int max_ns = ntiles / 8;                     // a piece keeps >= 8 key tiles
-    max_ns = max_ns > PLAN_MAX_SPLIT ? PLAN_MAX_SPLIT : max_ns < 1 ? 1 : max_ns;
-    DevPlan p;
-    p.nqb = nqb;
-    p.pad = 0;
-    int nt = 0, wg = 0, item = 0, rec = 0;
-    // what runs whole: the full rounds; ALSO a last round that is at least 0.8 full, or the one round of a launch that fills
-    // more than half of the chip (splitting those moves more partial records than the idle slots are worth)
-    int whole = L - L % S;
-    if (max_ns < 2 || (L % S) * 5 >= S * 4 || (L < S && L * 2 > S)) whole = L;
-    p.tier[nt++] = DevTier{0, 0, whole, 1, 0};
-    wg = item = whole;
-    while (item < L && nt < PLAN_TIERS) {
-        const int rem = L - item;
-        int n = 2;
-        while (n < max_ns && S / n > rem) n *= 2;
-        if (n > max_ns) n = max_ns;
-        int take = S / n < rem ? S / n : rem;
-        if (nt == PLAN_TIERS - 1) take = rem;    // (never with S = 256: 2, 4, 8, 16, 16 ...: the last tier takes what is left)
-        p.tier[nt++] = DevTier{wg, item, take, n, rec};
-        wg += take * n;
-        rec += take * n;
-        item += take;
-    }
-    p.ntiers = nt;
-    p.split_items = L - whole;
-    for (int i = nt; i < PLAN_TIERS; ++i) p.tier[i] = DevTier{wg, item, 0, 1, rec};
-    *plan = p;
-}
 
 template <typename T, int D, int NQ, int NG, int WAVES>
 __global__ __launch_bounds__(WAVES * 64) void attention16_combine_kernel(
@@ -128,10 +62,5 @@ __global__ __launch_bounds__(WAVES * 64) void attention16_combine_kernel(
     for (int r = 0; r < NA; ++r) o[r >> 3][(r >> 2) & 1][r & 3] = acc[r];
     write_output16<T, D>(o, out, ldo, b + g * src_batch, h, q0, M, Mp, lane);
 }
-
-// workspace of a device-planned launch: the plan (one cache line) + the records of the largest tail a plan can have
-constexpr size_t DEVPLAN_HEADER = 256;
-static_assert(sizeof(DevPlan) <= 256, "the plan lives in the workspace header");
-inline size_t devplan_ws_bytes(int slots, size_t rec_bytes) { return DEVPLAN_HEADER + (size_t)plan_tail_wgs(slots) * rec_bytes; }
 
 }  // namespace

@@ -426,88 +426,51 @@ __global__ __launch_bounds__(WAVES * 64, 2) void attention16g_kernel(
     for (int g = 0; g < NG; ++g) write_output16<T, D>(o16[g], out, ldo, b + g * src_batch, h, q0, M, Mp, lane);
 }
 
-template <typename T, int D, int NG, int WAVES>
-int launch16g(const Args16 &a) {
-    constexpr int DK = (D + 15) / 16, NT = WAVES * 64, QB = WAVES * QW, NV = NG;
-    constexpr size_t lds = (size_t)(3 * KV * (DK * 16 + 8) + 3 * NG * vrows_for(D) * VT_STRIDE) * 2;
-    if (lds > 64 * 1024) {
-        static std::atomic<bool> attr_set[vtm::MAX_DEVICES];
-        const int dev = vtm::current_device();
-        if (!attr_set[dev].load(std::memory_order_acquire)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(attention16g_kernel<T, D, NG, WAVES>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return vtm::fail(VTM_ELAUNCH, "vtm_attention: LDS attribute: %s", hipGetErrorString(e));
-            attr_set[dev].store(true, std::memory_order_release);
-        }
-    }
-    const int64_t src_batch = a.B / a.share_groups;
-    const size_t rec_bytes = (size_t)NV * rec16<D>() * NT * sizeof(float);
-    {
-        // query-bounded (vtm_attention_kv_shared_bounded): planned on the device like attention16s_kernel's bounded launches --
-        // the count is a device value, a host plan for Mq rows leaves the last round of the LIVE items mostly idle
-        // (34 816 rows, 0.78 live: 849 items on 256 slots took 4 rounds for 3.3 rounds of work)
-        const int slots = vtm::device_cus();       // one workgroup per CU
-        const int64_t nqb_max = vtm::cdiv(a.M, QB);
-        const size_t need = devplan_ws_bytes(slots, rec_bytes);
-        if (a.q_count != nullptr && a.ws != nullptr && a.ws_bytes >= need && nqb_max * a.h * src_batch >= 2 * slots) {
-            DevPlan *plan = reinterpret_cast<DevPlan *>(a.ws);
-            float *records = reinterpret_cast<float *>(static_cast<char *>(a.ws) + DEVPLAN_HEADER);
-            const int xcd_pairs = (src_batch * a.h) % 8 == 0 ? (int)(src_batch * a.h / 8) : 0;
-            const float sl2e = a.scale * 1.4426950408889634f;
-            hipLaunchKernelGGL(attention16_plan_kernel, dim3(1), dim3(64), 0, a.s, a.q_count, (int)src_batch, (int)a.h, QB, slots,
-                               (int)vtm::cdiv(a.Mk, KV), plan);
-            const int64_t total = nqb_max * a.h * src_batch, tail_max = plan_tail_wgs(slots);
-            VTM_REQUIRE(total + tail_max < (1ll << 31) / 16, "vtm_attention: grid too large");
-            hipLaunchKernelGGL((attention16g_kernel<T, D, NG, WAVES>), dim3((unsigned)(total + tail_max)), dim3(NT), lds, a.s,
-                               (const T *)a.q, a.ldq, (const T *)a.k, a.ldk, (const T *)a.vt, a.ldvt, (T *)a.out, a.ldo, a.h, a.M, a.Mp,
-                               a.Mk, a.Mkp, sl2e, src_batch, nqb_max, total, 1, records, xcd_pairs, a.q_count, (const DevPlan *)plan);
-            hipLaunchKernelGGL((attention16_combine_kernel<T, D, 1, NG, WAVES>), dim3((unsigned)plan_split_items(slots), (unsigned)NV),
-                               dim3(NT), 0, a.s, (const float *)records, (T *)a.out, a.ldo, a.h, a.M, a.Mp, nqb_max, total, 1, xcd_pairs,
-                               a.q_count, src_batch, (const DevPlan *)plan);
-            return vtm::launch_status("vtm_attention");
-        }
-    }
-    TailPlan p = plan_tail(src_batch, a.h, a.M, a.Mk, QB, 1, rec_bytes, false);
-    if (p.nsplit > 1 && (!a.ws || a.ws_bytes < p.ws_bytes)) {
-        p.nsplit = 1;
-        p.full = p.total;
-    }
-    const float scale_log2e = a.scale * 1.4426950408889634f;
-    VTM_REQUIRE(p.total < (1ll << 31) / 16, "vtm_attention: grid too large");
-    const int64_t rem = p.total - p.full;
-    const int xcd_groups = ((src_batch * a.h) % 8 == 0 && p.nqb >= 32) ? (int)(src_batch * a.h / 8) : 0;
-    hipLaunchKernelGGL((attention16g_kernel<T, D, NG, WAVES>), dim3((unsigned)(p.full + rem * p.nsplit)), dim3(NT), lds, a.s,
-                       (const T *)a.q, a.ldq, (const T *)a.k, a.ldk, (const T *)a.vt, a.ldvt, (T *)a.out, a.ldo, a.h, a.M, a.Mp,
-                       a.Mk, a.Mkp, scale_log2e, src_batch, p.nqb, p.full, p.nsplit, (float *)a.ws, xcd_groups, a.q_count,
-                       (const DevPlan *)nullptr);
-    if (p.nsplit > 1)
-        hipLaunchKernelGGL((attention16_combine_kernel<T, D, 1, NG, WAVES>), dim3((unsigned)rem, (unsigned)NV), dim3(NT), 0, a.s,
-                           (const float *)a.ws, (T *)a.out, a.ldo, a.h, a.M, a.Mp, p.nqb, p.full, p.nsplit, xcd_groups,
-                           a.q_count, src_batch, (const DevPlan *)nullptr);
-    return vtm::launch_status("vtm_attention");
+// ---- attention16g_kernel's family: 8 waves of 32 queries, one workgroup per CU, over the source samples ----
+constexpr int WAVES16G = 8, NT16G = WAVES16G * 64;
+constexpr size_t lds16g(int NG) { return (size_t)(3 * KV * ((40 + 15) / 16 * 16 + 8) + 3 * NG * vrows_for(40) * VT_STRIDE) * 2; }
+
+template <typename T, int NG>
+void launch_main(const Call &c, const Launch &g) {
+    hipLaunchKernelGGL((attention16g_kernel<T, 40, NG, WAVES16G>), dim3((unsigned)g.wgs), dim3(NT16G), lds16g(NG), c.s,
+                       (const T *)c.q, c.ldq, (const T *)c.k, c.ldk, (const T *)c.vt, c.ldvt, (T *)c.out, c.ldo, c.h, c.M, c.Mp,
+                       c.Mk, c.Mkp, g.scale_log2e, g.src_batch, g.nqb, g.whole, g.nsplit, g.partial, g.xcd_groups, c.q_count,
+                       plan_of(g));
+}
+
+template <typename T, int NG>
+void launch_combine(const Call &c, const Launch &g) {
+    hipLaunchKernelGGL((attention16_combine_kernel<T, 40, 1, NG, WAVES16G>), dim3((unsigned)g.split_items, (unsigned)NG),
+                       dim3(NT16G), 0, c.s, (const float *)g.partial, (T *)c.out, c.ldo, c.h, c.M, c.Mp, g.nqb, g.whole,
+                       g.nsplit, g.xcd_groups, c.q_count, g.src_batch, plan_of(g));
+}
+
+template <typename T, int NG>
+Family make_family() {
+    Family f;
+    f.qb = WAVES16G * QW;
+    f.rec_bytes = (size_t)NG * rec16<40>() * NT16G * sizeof(float);   // (one record per value group)
+    f.share = NG;
+    f.xcd_min_nqb = 32;
+    // no split-major order in this kernel: a query-bounded launch is planned on the device (a host plan for Mq rows left the
+    // last round of the LIVE items mostly idle -- 34 816 rows, 0.78 live: 849 items on 256 slots took 4 rounds for 3.3 rounds
+    // of work), or else takes the plain host plan
+    f.host_split_all = false;
+    if constexpr (lds16g(NG) > 64 * 1024) f.lds_opt_in = opt_in_lds<attention16g_kernel<T, 40, NG, WAVES16G>, lds16g(NG)>;
+    f.main = launch_main<T, NG>;
+    f.combine = launch_combine<T, NG>;
+    return f;
 }
 
 }  // namespace
 
 namespace vtm_att {
 
-size_t ws_bytes16g(int ng, int64_t src_batch, int64_t h, int64_t Mq, int64_t Mk, bool bounded) {
-    constexpr int WAVES = 8, NT = WAVES * 64;
-    const size_t rec = (size_t)ng * rec16<40>() * NT * sizeof(float);
-    size_t n = plan_tail(src_batch, h, Mq, Mk, (int64_t)WAVES * QW, 1, rec, false).ws_bytes;
-    if (bounded) n = std::max(n, devplan_ws_bytes(vtm::device_cus(), rec));
-    return n;
+Family family16g(int dtype, int ng) {
+    if (dtype == VTM_F16) return ng == 2 ? make_family<__half, 2>() : make_family<__half, 3>();
+    return ng == 2 ? make_family<vtm_bf16, 2>() : make_family<vtm_bf16, 3>();
 }
 
-int attention16g(const Args16 &a, int ng) {
-    if (a.dtype == VTM_F16) {
-        if (ng == 2) return launch16g<__half, 40, 2, 8>(a);
-        if (ng == 3) return launch16g<__half, 40, 3, 8>(a);
-    } else if (a.dtype == VTM_BF16) {
-        if (ng == 2) return launch16g<vtm_bf16, 40, 2, 8>(a);
-        if (ng == 3) return launch16g<vtm_bf16, 40, 3, 8>(a);
-    }
-    return vtm::fail(VTM_EINVAL, "vtm_attention: no shared-probability instantiation for %d groups", ng);
-}
+int attention16g(const Call &c, int ng) { return planned_launch(c, family16g(c.dtype, ng)); }
 
 }  // namespace vtm_att

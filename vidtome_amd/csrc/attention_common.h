@@ -1,6 +1,6 @@
 // Pieces shared by attention.hip (the general kernel) and attention16.hip / attention16g.hip (the wide-tile d = 40 kernels of
-// round 6): fragment types, tile constants, the XCD-aware work-item map, the 16-row O^T output path, the tail plan and the
-// hand-over between the translation units.  Header-only.
+// round 6): fragment types, tile constants, the XCD-aware work-item map and the 16-row O^T output path.  Header-only; the
+// launch planning is attention_plan.h's.
 #pragma once
 #include "common.h"
 
@@ -165,76 +165,5 @@ __device__ __forceinline__ void write_output16(const f32x4 (&o)[(D + 16) / 16][2
         }
     }
 }
-
-struct TailPlan {
-    int64_t nqb, total, full;   // query blocks per (sample, head), all workgroups, workgroups in whole rounds
-    int nsplit;                 // splits of each remaining work item (1 = none)
-    size_t ws_bytes;
-    bool split_all;             // every item is split (launches with a device-side query bound)
-};
-
-// Tail plan.  All workgroups of a launch take the same time, so the launch runs in "rounds" of as many workgroups
-// as the chip holds (slots); the last, partly filled round leaves most CUs idle for a whole workgroup time (cfg-2
-// mid blocks: 272 workgroups on 256 slots -> two rounds for 6 % more work than one; top blocks: 4.25 rounds).  The
-// work items of that last round are therefore split along the key axis into `nsplit` shorter workgroups that fill
-// the chip -- in the SAME launch, behind the whole ones, so they start as the slots of the last whole round free
-// up -- and merged by a combine kernel.
-// `bounded`: the launch carries a device-side query count (vtm_attention_kv_bounded: compacted live queries).  How many
-// of its workgroups do real work is not known when it is launched -- the cfg-2 top block launches 2 176 for ~1 800 live
-// ones, 3.5 rounds of 512 that cost 4 -- so the round structure cannot be planned.  It is made finer instead: EVERY
-// work item is split in two along the key axis (split-major order), the live ones then fill 7 half-length rounds
-// (profiles/r04_attention_split_all.txt); the price is one partial record per workgroup for the combine kernel.
-// B_items: samples the grid runs over; QB: query rows per workgroup; wg_per_cu: resident workgroups per CU (launch
-// bounds / LDS); rec_bytes: the partial record of one key-split workgroup.
-inline TailPlan plan_tail(int64_t B_items, int64_t h, int64_t Mq, int64_t Mk, int64_t QB, int wg_per_cu, size_t rec_bytes,
-                          bool bounded) {
-    TailPlan p;
-    p.nqb = vtm::cdiv(Mq, QB);
-    p.total = p.nqb * h * B_items;
-    const int64_t slots = (int64_t)vtm::device_cus() * wg_per_cu;
-    p.full = p.total / slots * slots;
-    const int64_t rem = p.total - p.full, ntiles = vtm::cdiv(Mk, KV);
-    p.nsplit = 1;
-    p.ws_bytes = 0;
-    p.split_all = false;
-    if (bounded && p.total >= 2 * slots && ntiles >= 64 && p.total % 8 == 0) {
-        p.full = 0;
-        p.nsplit = 2;
-        p.split_all = true;
-        p.ws_bytes = (size_t)p.total * 2 * rec_bytes;
-        return p;
-    }
-    // worth it only behind at least one whole round, for long key axes, and when the last round is at most a
-    // quarter full (a workgroup that has its CU to itself already runs about twice as fast as in a full round;
-    // measured: 128 of 512 -> -7 %, 16 of 256 -> -18 %, 192 or 256 of 512 -> no gain)
-    if (p.full > 0 && rem > 0 && rem * 4 <= slots && ntiles >= 32) {
-        int64_t ns = slots / rem;
-        if (ns > 16) ns = 16;
-        if (ns > ntiles / 8) ns = ntiles / 8;
-        if (ns >= 2) {
-            p.nsplit = (int)ns;
-            p.ws_bytes = (size_t)rem * ns * rec_bytes;
-        }
-    }
-    if (p.nsplit == 1) p.full = p.total;
-    return p;
-}
-
-
-// ---- hand-over attention.hip -> attention16.hip, attention16g.hip, attention_f32.hip ----
-struct Args16 {
-    const void *q; int64_t ldq; const void *k; int64_t ldk; const void *vt; int64_t ldvt; void *out; int64_t ldo;
-    int dtype; int64_t B, h, M, Mp, Mk, Mkp; float scale; int share_groups; void *ws; size_t ws_bytes;
-    const int32_t *q_count; hipStream_t s; bool fold; const int32_t *k_count; const uint32_t *k_bias; int64_t ldkb;
-};
-// attention16.hip: self-attention or folded keys (attention16s_kernel)
-size_t ws_bytes16(int64_t B, int64_t h, int64_t Mq, int64_t Mk, bool bounded);
-int attention16(const Args16 &a);
-// attention16g.hip: shared probabilities (ng = 2, 3 value groups), one-tile skew
-size_t ws_bytes16g(int ng, int64_t src_batch, int64_t h, int64_t Mq, int64_t Mk, bool bounded);
-int attention16g(const Args16 &a, int ng);
-// attention_f32.hip: dtype VTM_F32, every head dim (attention_f32_kernel; never folded)
-int attention_f32(const Args16 &a, int64_t d);
-
 
 }  // namespace vtm_att

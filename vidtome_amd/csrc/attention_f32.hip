@@ -19,10 +19,9 @@
 // at the same 64 FLOP / clk / SIMD; 16x16x4 has a 40-cycle dependent latency on a 32-cycle issue, so every chain of MFMAs
 // is interleaved with at least one other (2 key groups x 2 query halves for QK^T, O^T blocks x query halves for PV).
 // The fp16 / bf16 kernels are not touched by any of this.
-#include "attention16_parts.h"   // DevPlan, attention16_plan_kernel, devplan_ws_bytes (+ attention_common.h: plan_tail, item_of)
+#include "attention_plan.h"
 
 #include <algorithm>
-#include <atomic>
 #include <type_traits>
 
 namespace {
@@ -159,7 +158,7 @@ __global__ __launch_bounds__(F_NT, fwg_per_cu(D)) void attention_f32_kernel(
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l15 = lane & 15, g = lane >> 4;
     int64_t tier_item0 = nwhole, tier_wg0 = nwhole, tier_rec0 = 0;
-    if (dev_plan != nullptr) {   // query-bounded launch planned on the device (attention16_parts.h)
+    if (dev_plan != nullptr) {   // query-bounded launch planned on the device (attention_plan.h)
         nqb = dev_plan->nqb;
         xcd_groups = nqb >= 64 ? xcd_groups : 0;
         int ti = 0;
@@ -421,85 +420,47 @@ __global__ __launch_bounds__(F_NT, fwg_per_cu(D)) void attention_f32_kernel(
     }
 }
 
+// ---- attention_f32_kernel's family ----
 template <int D>
-int launch_f32(const Args16 &a) {
-    constexpr size_t lds = flds_bytes(D);
-    if (lds > 64 * 1024) {   // opt in to > 64 KB of dynamic LDS once per (instantiation, device)
-        static std::atomic<bool> attr_set[vtm::MAX_DEVICES];
-        const int dev = vtm::current_device();
-        if (!attr_set[dev].load(std::memory_order_acquire)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(attention_f32_kernel<D>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return vtm::fail(VTM_ELAUNCH, "vtm_attention (fp32): LDS attribute: %s", hipGetErrorString(e));
-            attr_set[dev].store(true, std::memory_order_release);
-        }
-    }
-    constexpr int QB = fqb_for(D);
-    const float scale_log2e = a.scale * 1.4426950408889634f;
-    const int64_t B = a.B, h = a.h, M = a.M, Mk = a.Mk;
-    const int slots = vtm::device_cus() * fwg_per_cu(D);
-    const int64_t ntiles = vtm::cdiv(Mk, KT);
-    const float *q = (const float *)a.q, *k = (const float *)a.k, *vt = (const float *)a.vt;
-    float *out = (float *)a.out;
-    // query-bounded launch of at least two rounds with a workspace that holds the plan: planned on the device (as attention.hip)
-    if (a.q_count != nullptr && a.ws != nullptr && a.ws_bytes >= devplan_ws_bytes(slots, frec_bytes(D)) &&
-        vtm::cdiv(M, QB) * h * B >= 2 * slots) {
-        DevPlan *plan = reinterpret_cast<DevPlan *>(a.ws);
-        float *records = reinterpret_cast<float *>(static_cast<char *>(a.ws) + DEVPLAN_HEADER);
-        const int64_t nqb_max = vtm::cdiv(M, QB), total = nqb_max * h * B, tail_max = plan_tail_wgs(slots);
-        VTM_REQUIRE(total + tail_max < (1ll << 31) / 16, "vtm_attention: grid too large");
-        const int xcd_pairs = (B * h) % 8 == 0 ? (int)(B * h / 8) : 0;
-        hipLaunchKernelGGL(attention16_plan_kernel, dim3(1), dim3(64), 0, a.s, a.q_count, (int)B, (int)h, QB, slots,
-                           (int)ntiles, plan);
-        hipLaunchKernelGGL(attention_f32_kernel<D>, dim3((unsigned)(total + tail_max)), dim3(F_NT), lds, a.s, q, a.ldq, k,
-                           a.ldk, vt, a.ldvt, out, a.ldo, h, M, a.Mp, Mk, a.Mkp, scale_log2e, B / a.share_groups, nqb_max,
-                           total, 1, records, xcd_pairs, a.q_count, (int64_t)0, (const DevPlan *)plan);
-        hipLaunchKernelGGL(attention_f32_combine_kernel<D>, dim3((unsigned)plan_split_items(slots)), dim3(F_NT), 0, a.s,
-                           (const float *)records, out, a.ldo, h, M, a.Mp, nqb_max, total, 1, xcd_pairs, a.q_count,
-                           (const DevPlan *)plan);
-        return vtm::launch_status("vtm_attention (fp32)");
-    }
-    // host plan (plan_tail counts 64-key tiles in its thresholds; the pieces are cut from this kernel's 32-key tiles)
-    TailPlan p = plan_tail(B, h, M, Mk, QB, fwg_per_cu(D), frec_bytes(D), a.q_count != nullptr);
-    if (p.split_all && (!a.ws || a.ws_bytes < p.ws_bytes))   // not enough workspace: the plain plan
-        p = plan_tail(B, h, M, Mk, QB, fwg_per_cu(D), frec_bytes(D), false);
-    if (p.nsplit > 1 && (!a.ws || a.ws_bytes < p.ws_bytes)) {
-        p.nsplit = 1;
-        p.full = p.total;
-        p.split_all = false;
-    }
-    VTM_REQUIRE(p.total < (1ll << 31) / 16, "vtm_attention: grid too large");
-    const int64_t rem = p.total - p.full;
-    const int xcd_groups = ((B * h) % 8 == 0 && p.nqb >= 64) ? (int)(B * h / 8) : 0;
-    hipLaunchKernelGGL(attention_f32_kernel<D>, dim3((unsigned)(p.full + rem * p.nsplit)), dim3(F_NT), lds, a.s, q, a.ldq, k,
-                       a.ldk, vt, a.ldvt, out, a.ldo, h, M, a.Mp, Mk, a.Mkp, scale_log2e, B / a.share_groups, p.nqb, p.full,
-                       p.nsplit, (float *)a.ws, xcd_groups, a.q_count, p.split_all ? rem : (int64_t)0, (const DevPlan *)nullptr);
-    if (p.nsplit > 1)
-        hipLaunchKernelGGL(attention_f32_combine_kernel<D>, dim3((unsigned)rem), dim3(F_NT), 0, a.s, (const float *)a.ws, out,
-                           a.ldo, h, M, a.Mp, p.nqb, p.full, p.nsplit, xcd_groups, a.q_count, (const DevPlan *)nullptr);
-    return vtm::launch_status("vtm_attention (fp32)");
+void launch_main(const Call &c, const Launch &g) {
+    hipLaunchKernelGGL(attention_f32_kernel<D>, dim3((unsigned)g.wgs), dim3(F_NT), flds_bytes(D), c.s, (const float *)c.q,
+                       c.ldq, (const float *)c.k, c.ldk, (const float *)c.vt, c.ldvt, (float *)c.out, c.ldo, c.h, c.M, c.Mp,
+                       c.Mk, c.Mkp, g.scale_log2e, g.src_batch, g.nqb, g.whole, g.nsplit, g.partial, g.xcd_groups, c.q_count,
+                       g.split_major, plan_of(g));
+}
+
+template <int D>
+void launch_combine(const Call &c, const Launch &g) {
+    hipLaunchKernelGGL(attention_f32_combine_kernel<D>, dim3((unsigned)g.split_items), dim3(F_NT), 0, c.s,
+                       (const float *)g.partial, (float *)c.out, c.ldo, c.h, c.M, c.Mp, g.nqb, g.whole, g.nsplit, g.xcd_groups,
+                       c.q_count, plan_of(g));
+}
+
+template <int D>
+Family make_family() {
+    Family f;
+    f.name = "vtm_attention (fp32)";
+    f.qb = fqb_for(D);
+    f.wg_per_cu = fwg_per_cu(D);
+    f.rec_bytes = frec_bytes(D);
+    // a device plan counts this kernel's 32-key tiles; the host plan (plan_tail) counts 64-key tiles in its thresholds and
+    // the pieces are cut from 32-key tiles
+    f.key_tile = KT;
+    f.xcd_min_nqb = 64;
+    if constexpr (flds_bytes(D) > 64 * 1024) f.lds_opt_in = opt_in_lds<attention_f32_kernel<D>, flds_bytes(D)>;
+    f.main = launch_main<D>;
+    f.combine = launch_combine<D>;
+    return f;
 }
 
 }  // namespace
 
 namespace vtm_att {
 
-int attention_f32(const Args16 &a, int64_t d) {
-    VTM_REQUIRE(!a.fold, "vtm_attention_kv_folded: fp32 keys are never folded (dtype must be VTM_F16 or VTM_BF16)");
-    VTM_REQUIRE((a.Mkp * a.ldk + d) * 4 < (1ll << 31) && (d * a.ldvt + a.Mkp) * 4 < (1ll << 31),
+int attention_f32(const Call &c, int64_t d) {
+    VTM_REQUIRE((c.Mkp * c.ldk + d) * 4 < (1ll << 31) && (d * c.ldvt + c.Mkp) * 4 < (1ll << 31),
                 "vtm_attention: a (sample, head) slice of fp32 K or V^T must stay below 2 GiB");
-    switch (d) {
-        case 40: return launch_f32<40>(a);
-        case 64: return launch_f32<64>(a);
-        case 80: return launch_f32<80>(a);
-        case 160: return launch_f32<160>(a);
-        case 8: return launch_f32<8>(a);
-        case 16: return launch_f32<16>(a);
-        case 32: return launch_f32<32>(a);
-        case 96: return launch_f32<96>(a);
-        case 128: return launch_f32<128>(a);
-    }
-    return vtm::fail(VTM_EINVAL, "vtm_attention: unsupported head dim %lld (have 8,16,32,40,64,80,96,128,160)", (long long)d);
+    return with_head_dim(d, [&](auto dim) { return planned_launch(c, make_family<decltype(dim)::value>()); });
 }
 
 }  // namespace vtm_att
