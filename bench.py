@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the VidToMe token-merging hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 Metric (BASELINE.json): denoising steps/sec for a 16-frame 512x512 SD-1.5 chunk, merge ratio 0.5.
 A *step* is one pass of the hot path over one chunk: the patched self-attention segment
@@ -24,6 +24,11 @@ no collective, the global level takes its anchor tokens from the previous rank's
 `allgather` = the same semantics through an RCCL all-gather per merging block; `ring` = the exact serial chain);
 value = chunk-steps per second over all ranks.
 
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: nothing else.  `--full` adds
+what takes runs of its own after the headline region: the matcher's counter pass (matching.counters), the other token
+regimes (`regimes`), two chunks in flight (`two_in_flight`), the other BASELINE configurations (`workloads`), the other
+exchange modes at N > 1 (`exchange_modes`), the real-UNet probe and the CPU baseline (`cpu_baseline`).
+
 The JSON line also carries
   roofline:     the dominant kernel (attention_kernel: flash attention over the merged tokens, fp16 MFMA), its
                 executed FLOPs / HIP-event time over the timed region vs the 2.5 PFLOP/s dense fp16 peak;
@@ -31,7 +36,7 @@ The JSON line also carries
                 time vs the same fp16 peak (the exact fp32-MFMA fallback would be bounded by 157.3 TFLOP/s);
   gather_path:  the HBM-bound kernels (LayerNorm, merge gather, unmerge + residual): algorithmic bytes / HIP-event time
                 vs 8 TB/s, next to the counter-derived (rocprofv3 FETCH_SIZE / WRITE_SIZE) rates from profiles/;
-  cpu_baseline: a plain-PyTorch CPU restatement of the same segment (oracle/torch_baseline.py: bmm + max + argsort +
+  cpu_baseline: (--full) a plain-PyTorch CPU restatement of the same segment (oracle/torch_baseline.py: bmm + max + argsort +
                 gather + SDPA, fp32) TIMED on this host's cores on one full site of every kind and summed to a step.
 """
 import argparse
@@ -96,7 +101,10 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every secondary measurement too: the matcher's counter pass, the CPU "
+                         "baseline, the other token regimes, two chunks in flight, the other workloads and exchange modes")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=90.0,
                     help="time budget of the CPU baseline: a top site whose full batch would not fit is timed on one "
                          "batch sample and doubled")
@@ -126,22 +134,22 @@ def parse():
                          "N(0,1) is what rounds 1-4 quoted; corr002 / smooth = static / smooth content; flat25 / dup load the "
                          "matcher's candidate logic")
     ap.add_argument("--regimes", default="all",
-                    help="N = 1: the other token regimes measured after the headline and reported under `regimes` "
+                    help="--full, N = 1: the other token regimes measured after the headline and reported under `regimes` "
                          "(comma-separated names, `all`, or `none`)")
     ap.add_argument("--regime-steps", type=int, default=10, help="timed passes per secondary regime")
     ap.add_argument("--workloads", default="all",
-                    help="N = 1 headline run: secondary workloads appended to the line as `workloads` (each in a child process "
-                         "of this script): all | none | comma list of cfg3,cfg5,full_block")
+                    help="--full, N = 1 headline run: secondary workloads appended to the line as `workloads` (each in a child "
+                         "process of this script): all | none | comma list of cfg3,cfg5,full_block")
     ap.add_argument("--workload-steps", type=int, default=10, help="timed passes per secondary workload")
     ap.add_argument("--no-inflight-line", dest="inflight_line", action="store_false",
-                    help="N = 1: skip the secondary `two_in_flight` region (two chunks on two HIP streams)")
+                    help="--full, N = 1: skip the secondary `two_in_flight` region (two chunks on two HIP streams)")
     ap.add_argument("--inflight", type=int, default=1,
                     help="N = 1 A/B: run the HEADLINE region with this many chunks in flight (the line then says so in "
                          "config.parallelism; the default line keeps `value` on one stream)")
     ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS),
                     help="cfg2 = the headline configuration; cfg3 / cfg5 = secondary lines (BASELINE.json configs[2] / [4])")
     ap.add_argument("--exchange-modes", default="all",
-                    help="N > 1: after the headline's exchange mode, time the other modes too and report them under "
+                    help="--full, N > 1: after the headline's exchange mode, time the other modes too and report them under "
                          "`exchange_modes` (comma-separated, `all`, or `none`); a mode that makes no progress is reported as such "
                          "and the headline line is still printed")
     ap.add_argument("--watchdog-seconds", type=float, default=120.0,
@@ -717,11 +725,11 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def run_region(regime, steps, warmup, xmode, with_box, inflight=1, dump=False):
+    def run_region(regime, steps, warmup, xmode, with_box, inflight=1, dump=False, counters=True):
         """One measured region: a fresh chunk stream of `regime`, anchors populated, `warmup` untimed and `steps` timed passes
-        between two fences (barrier + synchronize), HIP events on every `every`-th pass, one extra untimed pass for the
-        matcher's device-side counters.  Returns everything the line is built from.  With `dump`, what the last timed pass
-        returned goes to --dump-outputs."""
+        between two fences (barrier + synchronize), HIP events on every `every`-th pass, with `counters` one extra untimed
+        pass for the matcher's device-side counters.  Returns everything the line is built from.  With `dump`, what the last
+        timed pass returned goes to --dump-outputs."""
         total_passes = 1 + warmup + steps
         for b in unet.blocks:                       # a region starts like a denoising step: no anchors
             b.global_tokens = None
@@ -797,7 +805,7 @@ def main():
             if dump:                                  # sampled before the counter pass below can touch any shared buffer
                 dump_outputs(last, site_list, args.dump_outputs, rank, world)
             event_pass_ms = sum(a.elapsed_time(b) for a, b in pass_events) / max(1, len(pass_events))
-            if ex is None:                            # one untimed pass for the matcher's counters (N = 1: the chunk stream
+            if ex is None and counters:               # one untimed pass for the matcher's counters (N = 1: the chunk stream
                 mt.count = True                       # of an exchange has no spare chunk)
                 step()
                 mt.count = False
@@ -838,7 +846,7 @@ def main():
                 "executed_mfma_fraction": cnt.get("executed_mfma_fraction")}
 
     head = run_region(args.data, args.steps, args.warmup, mode, True, inflight=max(1, args.inflight) if world == 1 else 1,
-                      dump=args.dump_outputs is not None)
+                      dump=args.dump_outputs is not None, counters=args.full)
     mt, dt, box = head["mt"], head["dt"], head["box"]
     timed_passes, total_passes, event_pass_ms = head["timed_passes"], head["total_passes"], head["event_pass_ms"]
     aflops, ams, an = mt.summary("attention")
@@ -964,7 +972,7 @@ def main():
             # the fused similarity + top-1 step (second largest).  `nominal_tflops` = the reference's 2 B Ns Nd C flops per call /
             # HIP-event time of the whole vtm_match_filtered call: the fp16-MFMA filter would execute exactly those once, but
             # its partial-sum pruning skips the MFMAs of 32 x 32 blocks that can no longer matter -- `counters` carries the
-            # fraction of blocks pruned and of MFMA work really executed (device-side counters of one extra untimed pass).
+            # fraction of blocks pruned and of MFMA work really executed (--full: device-side counters of one extra untimed pass).
             # The exact fallback kernel runs on the fp32 MFMA (157.3 TFLOP/s).
             "matching": {"kernels": "prep_operand + filter_kernel + refine_kernel + exact_rows_kernel (vtm_match_filtered{,_ordered}) + vtm_position_order" if filtered
                                     else "match_kernel (vtm_match)",
@@ -973,7 +981,7 @@ def main():
                          "nominal_frac": round(mat_tf / (FP16_PEAK_TFLOPS if filtered else FP32_PEAK_TFLOPS), 4),
                          "calls": mn, "matching_ms_per_step": round(mms / timed_passes, 3),
                          "position_order_calls": on, "position_order_ms_per_step": round(oms / timed_passes, 3),
-                         # device-side counters of one extra untimed pass: pairs the exact refine pass evaluated per src row,
+                         # --full: device-side counters of one extra untimed pass: pairs the exact refine pass evaluated per src row,
                          # rows whose candidate list overflowed (exact_rows_kernel), calls recomputed as a whole, blocks pruned
                          "counters": mt.match_counters() if filtered else None},
             # q / k / v^T / out projections: GEMMs whose A rows are gathered through the composed merge map
@@ -1003,7 +1011,8 @@ def main():
         }
         # "if Diffusers + weights happen to be importable on the GPU box (probe, never assume) the same step is
         # also timed inside a real UNet; otherwise the site harness *is* the step" -- probed, reported, never assumed
-        line["real_unet_probe"] = probe_real_unet()
+        if args.full:
+            line["real_unet_probe"] = probe_real_unet()
         if args.full_block:
             def gemm(kind):
                 f, ms, n = mt.summary(kind)
@@ -1021,7 +1030,7 @@ def main():
                 "layernorm_panels": hbm("layernorm_panels")}
 
     # ---- N = 1: the other token regimes, same harness, fewer passes (SURVEY 8d names n01 and corr01) ----
-    if world == 1 and mode is None and args.regimes != "none":
+    if args.full and world == 1 and mode is None and args.regimes != "none":
         names = [n for n in ("n01", "corr01", "corr05", "corr002", "smooth", "dup", "flat25")] if args.regimes == "all" else \
             [n.strip() for n in args.regimes.split(",") if n.strip()]
         regs = {args.data: compact(head)}
@@ -1053,7 +1062,8 @@ def main():
     # await_anchors).  The dispatch gaps and the ~400 small launches of one chunk then run beside the other chunk's big kernels.
     # `value` stays the ONE-stream number (like for like with rounds 1-5); this is what a video of several chunks per denoising
     # step gets on one GPU.
-    if world == 1 and mode is None and rank == 0 and args.inflight_line and args.workload == "cfg2" and not args.local_only:
+    if args.full and world == 1 and mode is None and rank == 0 and args.inflight_line and args.workload == "cfg2" \
+            and not args.local_only:
         try:
             r2 = run_region(args.data, args.steps, args.warmup + 2, None, False, inflight=2)
             c2 = compact(r2)
@@ -1065,7 +1075,7 @@ def main():
             line["two_in_flight"] = {"error": f"{type(e).__name__}: {e}"[:300]}
 
     # ---- N = 1 headline run: the other single-GPU BASELINE configurations, driver-timed ----
-    if world == 1 and mode is None and rank == 0 and args.workloads != "none" and args.workload == "cfg2" \
+    if args.full and world == 1 and mode is None and rank == 0 and args.workloads != "none" and args.workload == "cfg2" \
             and not args.full_block and not args.local_only and FRAMES == 16:
         import subprocess
         want = ["cfg3", "cfg5", "full_block"] if args.workloads == "all" else \
@@ -1077,8 +1087,7 @@ def main():
             if w not in ("cfg3", "cfg5", "full_block"):
                 raise SystemExit(f"bench.py: unknown secondary workload {w!r}")
             cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(args.workload_steps), "--warmup", "3",
-                   "--no-cpu-baseline", "--regimes", "none", "--workloads", "none", "--no-inflight-line", "--data", args.data] + \
-                  (["--full-block"] if w == "full_block" else ["--workload", w])
+                   "--data", args.data] + (["--full-block"] if w == "full_block" else ["--workload", w])
             t0 = time.perf_counter()
             try:
                 out = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
@@ -1100,7 +1109,7 @@ def main():
                                   f"process after the headline region; `value` is NOT computed from them")
 
     # ---- N > 1: the other exchange modes (ring = the exact chain, neighbour / allgather = parallel anchors) ----
-    if world > 1 and mode is not None and args.exchange_modes != "none":
+    if args.full and world > 1 and mode is not None and args.exchange_modes != "none":
         want = ["neighbour", "ring", "allgather"] if args.exchange_modes == "all" else \
             [m.strip() for m in args.exchange_modes.split(",") if m.strip()]
         modes = {mode: {"ms_per_step": round(dt / args.steps * 1e3, 3), "steps_per_s": round(world * args.steps / dt, 3),
@@ -1124,7 +1133,7 @@ def main():
             dog.fallback = None
 
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1 and not args.full_block and args.workload == "cfg2":
+        if args.full and not args.no_cpu_baseline and world == 1 and not args.full_block and args.workload == "cfg2":
             # rank 0 at N = 1 only; the CPU leg times the segment at the headline configuration
             line["cpu_baseline"] = (cpu_baseline_torch if args.cpu_baseline == "torch" else cpu_baseline_port)(
                 args.cpu_seconds)

@@ -64,10 +64,10 @@ def test_bench_two_ranks_one_gpu_gloo(exchange):
 
 @pytest.mark.gpu
 def test_bench_two_ranks_report_every_exchange_mode():
-    """The default N > 1 line: the headline's mode (neighbour) plus the other two modes timed in the same process group --
+    """The --full N > 1 line: the headline's mode (neighbour) plus the other two modes timed in the same process group --
     what the first 8-GPU run needs for the ring-vs-neighbour comparison."""
-    d = _line(_run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], {"VIDTOME_BENCH_BACKEND": "gloo"},
-                   timeout=1200))
+    d = _line(_run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"],
+                   {"VIDTOME_BENCH_BACKEND": "gloo"}, timeout=1200))
     assert d["config"]["exchange"] == "neighbour"
     modes = d["exchange_modes"]
     assert set(modes) == {"neighbour", "ring", "allgather"}
@@ -100,7 +100,8 @@ def test_bench_two_ranks_rccl(exchange):
 
 @pytest.mark.gpu
 def test_bench_single_gpu_line_has_the_contract_fields():
-    d = _line(_run(["--steps", "5", "--warmup", "1", "--no-cpu-baseline", "--regimes", "n01,corr05", "--regime-steps", "2"]))
+    d = _line(_run(["--steps", "5", "--warmup", "1", "--no-cpu-baseline", "--regimes", "n01,corr05", "--regime-steps", "2",
+                    "--full"]))
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline"):
         assert k in d, k
@@ -120,6 +121,19 @@ def test_bench_single_gpu_line_has_the_contract_fields():
     m = d["matching"]
     assert "nominal_tflops" in m and "executed_tflops" not in m and m["counters"]["blocks_tested"] > 0
     assert d["regimes"]["n01"]["pruned_block_fraction"] < d["regimes"]["corr05"]["pruned_block_fraction"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_measures_only_the_headline():
+    """Without --full the run is the headline region and its line: no counter pass, no secondary regions, no child
+    processes, no CPU baseline."""
+    d = _line(_run(["--steps", "2", "--warmup", "1"]))
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["higher_is_better"] is True
+    assert abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-2 * d["value"]
+    assert d["roofline"]["achieved"] > 0 and d["matching"]["calls"] > 0 and d["matching"]["counters"] is None
+    for k in ("regimes", "value_worst_named", "two_in_flight", "workloads", "exchange_modes", "cpu_baseline",
+              "real_unet_probe"):
+        assert k not in d, k
 
 
 @pytest.mark.gpu

@@ -1,6 +1,6 @@
 #!/bin/bash
-# One GPU session producing everything profiles/ and DESIGN.md quote: full GPU test suite, smoke, bench (with the CPU
-# baseline leg), rocprofv3 kernel trace of the bench, PMC counters of the dominant kernels.
+# One GPU session producing everything profiles/ and DESIGN.md quote: full GPU test suite, smoke, bench --full (with the
+# CPU baseline leg), rocprofv3 kernel trace of the bench, PMC counters of the dominant kernels.
 #   gpurun --timeout 2400 -- 'bash tools/gpu_session.sh r06_final'
 TAG=${1:-session}
 R=${GRAFT_REPO_ROOT:-/root/repo}
@@ -9,7 +9,7 @@ mkdir -p $O
 cd $R
 python -m pytest tests -m gpu -q > $O/tests.log 2>&1; echo "tests rc=$?"; tail -3 $O/tests.log
 python __graft_entry__.py smoke > $O/smoke.log 2>&1; echo "smoke rc=$?"
-python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
 for rep in 2 3; do python bench.py --no-cpu-baseline --regimes none --workloads none --no-inflight-line > $O/bench_run$rep.json 2>> $O/bench.err; done
 python bench.py --no-cpu-baseline --regimes none --workloads none --no-inflight-line --full-block > $O/bench_full_block.json 2>> $O/bench.err; echo "bench full rc=$?"
 for wlk in cfg3 cfg5; do python bench.py --no-cpu-baseline --regimes none --workloads none --no-inflight-line --workload $wlk > $O/bench_$wlk.json 2>> $O/bench.err; done
