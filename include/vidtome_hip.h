@@ -480,11 +480,34 @@ int vtm_geglu(const void *x, int dtype, int64_t rows, int64_t D, void *out, vtm_
  * W: (N, K) row-major like torch.nn.Linear.weight, bias: (N) or NULL; fp16 / bf16, fp32 accumulation.
  * transposed == 0: out is (B, >= n, ldo >= N) token-major; transposed != 0: out is (B, N, ldo >= n) channel-major
  * (V^T for vtm_attention).  out_batch_stride in elements.  K % 32 == 0.  Rows >= n of out are not written.
+ * VTM_F32 is vtm_linear_f32 below with VTM_LINEAR_NONE and a VTM_F32 output (its alignment and shape rules apply).
  * ---------------------------------------------------------------------------------------------- */
 int vtm_linear_rows(const void *x0, int64_t P0, const void *x1, int64_t P1, int dtype, int64_t B, int64_t K,
                     const int32_t *rows, int64_t rows_ld, const int32_t *rows2, int64_t n, const void *W,
                     const void *bias, int64_t N, void *out, int64_t ldo, int64_t out_batch_stride,
                     int transposed, vtm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * vtm_linear_f32 -- every projection of an fp32 model's patched block in fp32, fed like vtm_linear_rows: attn1's
+ * to_q / to_k / to_v / to_out[0] through the composed merge map (vidtome/patch.py:157-162, utils/pnp_utils.py:47-95),
+ * attn2's projections (patch.py:171-185) and the GEGLU feed-forward `ff(norm3(h)) + h` (patch.py:187-199).
+ *   A rows: pool = x0 (B, P0, K) | x1 (B, P1, K), row i of sample b = pool[b, rows[b, rows2[b, i]]] exactly as
+ *   vtm_linear_rows (either map may be NULL).  W: (N, K) fp32 row-major like torch.nn.Linear.weight; bias fp32 (N) or NULL.
+ *   epilogue VTM_LINEAR_NONE:  out = x W^T + b
+ *            VTM_LINEAR_RESID: out = (x W^T + b) + resid, resid fp32 laid out like out (same ldo / out_batch_stride)
+ *            VTM_LINEAR_GEGLU: W holds 2 D rows [value; gate] (N = 2 D; bias likewise): out (n, D) = value * gelu(gate),
+ *                              exact (erf) gelu; the 2 D-wide product is never written
+ * fp32 operands and products on v_mfma_f32_32x32x2_f32: each output is a k-ascending fp32 fmaf chain from +0, then + bias,
+ * then the epilogue.  out_dtype VTM_F32, or VTM_F16 = that value rounded once at the store (q / k / V^T for the fp16
+ * attention core).  transposed == 0: out (B, >= n, ldo >= N_out) token-major; transposed != 0: out (B, N_out, ldo >= n)
+ * channel-major (V^T); N_out = N, or D for GEGLU; out_batch_stride in elements.  K % 8 == 0, N % 8 (GEGLU: 16) == 0;
+ * x0, x1 and W 16-byte aligned.  Rows >= n and columns >= N_out of out are not written.  No workspace; one launch.
+ * ---------------------------------------------------------------------------------------------- */
+enum { VTM_LINEAR_NONE = 0, VTM_LINEAR_RESID = 1, VTM_LINEAR_GEGLU = 2 };
+int vtm_linear_f32(const float *x0, int64_t P0, const float *x1, int64_t P1, int64_t B, int64_t K,
+                   const int32_t *rows, int64_t rows_ld, const int32_t *rows2, int64_t n, const float *W,
+                   const float *bias, int64_t N, int epilogue, const float *resid, void *out, int out_dtype,
+                   int64_t ldo, int64_t out_batch_stride, int transposed, vtm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * vtm_lora_fold -- the effective weight of a LoRA-adapted projection of the block (`pipe.load_lora_weights(

@@ -93,6 +93,8 @@ _SIGNATURES = {
     "vtm_linear_rows": ([_vp, _i64, _vp, _i64, _int, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64,
                          _int, _vp], _int),
     "vtm_lora_fold": ([_vp, _int, _vp, _vp, _i64, _i64, _i64, _vp, _vp], _int),
+    "vtm_linear_f32": ([_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _int, _vp, _vp, _int, _i64,
+                        _i64, _int, _vp], _int),
 }
 
 
@@ -727,6 +729,53 @@ def linear_rows(x0: torch.Tensor, x1: Optional[torch.Tensor], rows: Optional[tor
                                  0 if rows is None else rows.shape[1], _ptr(rows2), n, _ptr(weight),
                                  _ptr(bias.contiguous() if bias is not None else None), N, out.data_ptr(), out.stride(1),
                                  out.stride(0), int(transposed), _stream()), "vtm_linear_rows")
+    return out
+
+
+LINEAR_NONE, LINEAR_RESID, LINEAR_GEGLU = 0, 1, 2          # vtm_linear_f32 epilogues
+_EPILOGUES = {"none": LINEAR_NONE, "resid": LINEAR_RESID, "geglu": LINEAR_GEGLU}
+
+
+@_on_device
+def linear_f32(x0: torch.Tensor, x1: Optional[torch.Tensor], rows: Optional[torch.Tensor],
+               rows2: Optional[torch.Tensor], n: int, weight: torch.Tensor, bias: Optional[torch.Tensor],
+               epilogue: str = "none", resid: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.float32,
+               transposed: bool = False, pad_to: int = 8, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The fp32 projections (csrc/linear_f32.hip): out[b, i] = pool[b, rows[b, rows2[b, i]]] @ weight^T (+ bias) for i < n,
+    then ``epilogue`` "none", "resid" (+ ``resid``, laid out like the result) or "geglu" (weight = [value; gate] rows:
+    value * gelu(gate), D = N / 2 channels).  fp32 tokens, weight and bias; the result is fp32 or, with ``out_dtype`` fp16,
+    rounded once at the store.  Shapes and padding as linear_rows: (B, n_pad, N_out) token-major, or (B, N_out, n_pad)
+    channel-major when ``transposed`` (the padding is zero when this function allocates the result)."""
+    _req(x0, "x0"), _req(weight, "weight")
+    B, P0, K = x0.shape
+    P1 = 0 if x1 is None else _req(x1, "x1").shape[1]
+    N = weight.shape[0]
+    if x0.dtype != torch.float32 or weight.dtype != torch.float32 or weight.shape[1] != K \
+            or (x1 is not None and x1.dtype != torch.float32):
+        raise RuntimeError("linear_f32: tokens and weight must be fp32, weight (N, K)")
+    if out_dtype not in (torch.float32, torch.float16):
+        raise RuntimeError("linear_f32: out_dtype must be fp32 or fp16")
+    epi = _EPILOGUES[epilogue]
+    Nout = N // 2 if epi == LINEAR_GEGLU else N
+    if bias is not None:
+        bias = bias.detach().float().contiguous()
+    for t, name in ((rows, "rows"), (rows2, "rows2")):
+        if t is not None:
+            _req(t, name)
+    n_pad = (n + pad_to - 1) // pad_to * pad_to
+    if out is None:
+        out = torch.empty((B, Nout, n_pad) if transposed else (B, n_pad, Nout), dtype=out_dtype, device=x0.device)
+        if n_pad != n:
+            (out[:, :, n:] if transposed else out[:, n:]).zero_()
+    if out.stride(2) != 1 or out.dtype != out_dtype:
+        raise RuntimeError("linear_f32: out must be of out_dtype and contiguous along its last axis")
+    if epi == LINEAR_RESID and (resid is None or resid.dtype != torch.float32 or resid.shape[0] != B
+                                or resid.stride()[B == 1:] != out.stride()[B == 1:]):
+        raise RuntimeError("linear_f32: resid must be fp32 with the strides of the result")
+    _check(lib().vtm_linear_f32(_ptr(x0), P0, _ptr(x1), P1, B, K, _ptr(rows), 0 if rows is None else rows.shape[1],
+                                _ptr(rows2), n, _ptr(weight), _ptr(bias), N, epi, _ptr(resid), out.data_ptr(),
+                                dtype_code(out), out.stride(1), out.stride(0), int(transposed), _stream()),
+           "vtm_linear_f32")
     return out
 
 

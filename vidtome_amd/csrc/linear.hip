@@ -563,6 +563,10 @@ VTM_EXPORT int vtm_linear_rows(const void *x0, int64_t P0, const void *x1, int64
     VTM_REQUIRE(!rows || rows_ld > 0, "vtm_linear_rows: rows_ld");
     VTM_REQUIRE(ldo >= (transposed ? n : N), "vtm_linear_rows: ldo too small");
     VTM_REQUIRE(vtm::cdiv(N, 128) < 65536, "vtm_linear_rows: N too large");
+    if (dtype == VTM_F32)                                 // the fp32 GEMM (linear_f32.hip), plain epilogue, fp32 result
+        return vtm_linear_f32(static_cast<const float *>(x0), P0, static_cast<const float *>(x1), P1, B, K, rows, rows_ld,
+                              rows2, n, static_cast<const float *>(W), static_cast<const float *>(bias), N, VTM_LINEAR_NONE,
+                              nullptr, out, VTM_F32, ldo, out_batch_stride, transposed, stream);
     if (n == 0) return VTM_OK;
     hipStream_t s = vtm::as_stream(stream);
     switch (dtype) {
@@ -573,7 +577,7 @@ VTM_EXPORT int vtm_linear_rows(const void *x0, int64_t P0, const void *x1, int64
             return launch<vtm_bf16>(x0, P0, x1, P1, B, K, rows, rows_ld, rows2, n, W, bias, N, out, ldo, out_batch_stride,
                                     transposed, s);
     }
-    return vtm::fail(VTM_EINVAL, "vtm_linear_rows: dtype must be VTM_F16 or VTM_BF16");
+    return vtm::fail(VTM_EINVAL, "vtm_linear_rows: dtype must be VTM_F16, VTM_BF16 or VTM_F32");
 }
 
 namespace vtm {

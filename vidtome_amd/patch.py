@@ -701,6 +701,50 @@ def self_attention_rows(attn: torch.nn.Module, x0: torch.Tensor, x1: Optional[to
     return _lib.linear_rows(o, None, None, None, Mq, _weight(to_out, dt), _bias(to_out, dt))
 
 
+def _fp32_projections(block: torch.nn.Module) -> bool:
+    """The block's ``fp32_projections`` opt-in (``update_patch(model, fp32_projections=True)``)."""
+    return getattr(block, "fp32_projections", False) is True
+
+
+def f32_projections_ok(attn: torch.nn.Module, x: torch.Tensor) -> bool:
+    """attn1's projections as fp32 GEMMs (vtm_linear_f32): fp32 tokens with C % 8 == 0 and all four projection weights
+    (and the biases that exist) fp32.  The caller has checked ``fused_attention_ok`` and the block's opt-in."""
+    return x.is_cuda and x.dtype == torch.float32 and x.shape[-1] % 8 == 0 and _proj_dtypes_ok(attn, torch.float32)
+
+
+def self_attention_f32(attn: torch.nn.Module, x0: torch.Tensor, x1: Optional[torch.Tensor], rows: Optional[torch.Tensor],
+                       q_rows: Optional[torch.Tensor] = None, q_count: Optional[torch.Tensor] = None,
+                       fp32_core: bool = False) -> torch.Tensor:
+    """``attn1(merged)`` of an fp32 model like self_attention_rows: every projection is a vtm_linear_f32 GEMM whose A rows
+    are fetched through the composed merge map (``rows`` None = the rows of x0 as they are: the un-merged sites), q | k for
+    all M rows (or q for the ``q_rows`` positions only), V^T channel-major.  q / k / V^T are written in fp32 for the fp32
+    core (``fp32_core``, the block's ``fp32_attention``) or rounded once to fp16 at the GEMM's store for the fp16 core; the
+    output projection reads the core's output as fp32.  Keys are never folded (fp32 keys never are).
+    Returns (B, Mq rounded up to 8, C) fp32; rows >= Mq are not meaningful."""
+    B, _, C = x0.shape
+    M = x0.shape[1] if rows is None else rows.shape[1]
+    heads = attn.heads
+    scale = getattr(attn, "scale", None) or (C // heads) ** -0.5
+    share = _pnp_share_groups(attn)
+    # (q_rows under PnP sharing: the caller vouches that every sample of a group has the same rows -- align_batch)
+    f32 = torch.float32
+    core = f32 if fp32_core else torch.float16
+    wqk, bqk = _fused_weights(attn, f32, x0.device)
+    vt = _lib.linear_f32(x0, x1, rows, None, M, _weight(attn.to_v, f32), _bias(attn.to_v, f32), out_dtype=core,
+                         transposed=True)                                                      # (B, C, Mp)
+    if q_rows is None:
+        qk = _lib.linear_f32(x0, x1, rows, None, M, wqk, bqk, out_dtype=core)                   # (B, Mp, 2C): q | k
+        o = _lib.attention(qk[:, :, :C], qk[:, :, C:], vt, heads, M, scale, share)
+        Mq = M
+    else:
+        Mq = q_rows.shape[1]
+        k_op = _lib.linear_f32(x0, x1, rows, None, M, wqk[C:], None if bqk is None else bqk[C:], out_dtype=core)
+        q_op = _lib.linear_f32(x0, x1, rows, q_rows, Mq, wqk[:C], None if bqk is None else bqk[:C], out_dtype=core)
+        o = _lib.attention_kv(q_op, k_op, vt, heads, Mq, M, scale, q_count=q_count, share_groups=share)
+    to_out = _out_linear(attn)
+    return _lib.linear_f32(o.float(), None, None, None, Mq, _weight(to_out, f32), _bias(to_out, f32))
+
+
 def self_attention(attn: torch.nn.Module, x: torch.Tensor, M: Optional[int] = None,
                    q_rows: Optional[torch.Tensor] = None, q_count: Optional[torch.Tensor] = None,
                    fp32_core: bool = False) -> torch.Tensor:
@@ -823,6 +867,48 @@ def fused_cross_ok(norm: torch.nn.Module, attn: torch.nn.Module, x: torch.Tensor
             and _proj_dtypes_ok(attn, x.dtype) and fused_attention_ok(attn, x, self_attn=False))
 
 
+def _f32_layernorm_ok(norm: torch.nn.Module, x: torch.Tensor) -> bool:
+    """A plain LayerNorm over the channel axis of fp32 tokens that vtm_layernorm takes."""
+    return (type(norm) is torch.nn.LayerNorm and len(norm.normalized_shape) == 1 and norm.normalized_shape[0] == x.shape[-1]
+            and x.shape[-1] % 8 == 0 and x.shape[-1] <= 2048
+            and (norm.weight is None or norm.weight.dtype == torch.float32)
+            and (norm.bias is None or norm.bias.dtype == torch.float32))
+
+
+def f32_cross_ok(block: torch.nn.Module, norm: torch.nn.Module, attn: torch.nn.Module, x: torch.Tensor,
+                 encoder_hidden_states, attention_mask, kwargs) -> bool:
+    """attn2 of an fp32 block with the ``fp32_projections`` opt-in on the fp32 GEMMs (norm_cross_attention_f32)."""
+    return (_fp32_projections(block) and encoder_hidden_states is not None and attention_mask is None and not kwargs
+            and encoder_hidden_states.dim() == 3 and x.dim() == 3 and x.is_cuda and x.dtype == torch.float32
+            and encoder_hidden_states.shape[0] == x.shape[0] and encoder_hidden_states.shape[-1] % 8 == 0
+            and _f32_layernorm_ok(norm, x) and _proj_dtypes_ok(attn, torch.float32)
+            and fused_attention_ok(attn, x, self_attn=False))
+
+
+def norm_cross_attention_f32(norm: torch.nn.Module, attn: torch.nn.Module, hidden_states: torch.Tensor,
+                             encoder_hidden_states: torch.Tensor) -> torch.Tensor:
+    """patch.py:171-185 for an fp32 block with ``fp32_projections``: ``attn2(norm2(h), encoder_hidden_states) + h`` as
+    vtm_layernorm, the q GEMM, the k / V^T GEMMs of the conditioning tokens (padded to a multiple of 8 rows), the fp32
+    attention core (whatever ``fp32_attention`` says: the module forward it replaces is fp32, and 77 keys keep it cheap)
+    and the output GEMM with the residual add in its epilogue.  The caller has checked ``f32_cross_ok``."""
+    B, N, C = hidden_states.shape
+    heads = attn.heads
+    scale = getattr(attn, "scale", None) or (C // heads) ** -0.5
+    f32 = torch.float32
+    hs = hidden_states.contiguous()
+    enc = encoder_hidden_states.to(f32).contiguous()
+    Mk = enc.shape[1]
+    xn = _lib.layernorm(hs, norm.weight, norm.bias, norm.eps)
+    q = _lib.linear_f32(xn, None, None, None, N, _weight(attn.to_q, f32), _bias(attn.to_q, f32))          # (B, N8, C)
+    k = _lib.linear_f32(enc, None, None, None, Mk, _weight(attn.to_k, f32), _bias(attn.to_k, f32))        # (B, Mkp, C)
+    vt = _lib.linear_f32(enc, None, None, None, Mk, _weight(attn.to_v, f32), _bias(attn.to_v, f32),
+                         transposed=True)                                                                  # (B, C, Mkp)
+    o = _lib.attention_kv(q, k, vt, heads, N, Mk, scale)
+    to_out = _out_linear(attn)
+    return _lib.linear_f32(o, None, None, None, N, _weight(to_out, f32), _bias(to_out, f32), epilogue="resid", resid=hs,
+                           out=torch.empty_like(hs))
+
+
 def cross_attention(attn: torch.nn.Module, x: torch.Tensor, encoder_hidden_states: Optional[torch.Tensor],
                     attention_mask=None, **kwargs) -> torch.Tensor:
     """`self.attn2(norm_hidden_states, encoder_hidden_states=..., attention_mask=...)` (patch.py:178-183) -- the
@@ -920,6 +1006,36 @@ def norm_feed_forward_residual(norm: torch.nn.Module, ff: torch.nn.Module, hidde
     return _lib.linear_panels(hp, n, w2, C, b2, resid=hs.view(n, C)).view(hidden_states.shape)
 
 
+def f32_ff_ok(block: torch.nn.Module, norm: torch.nn.Module, ff: torch.nn.Module, x: torch.Tensor) -> bool:
+    """The feed-forward of an fp32 block with the ``fp32_projections`` opt-in on the fp32 GEMMs (norm_feed_forward_f32)."""
+    if not (_fp32_projections(block) and x.is_cuda and x.dtype == torch.float32 and _f32_layernorm_ok(norm, x)):
+        return False
+    lin = _geglu_ff(ff)
+    if lin is None:
+        return False
+    proj, out = (lora.base_linear(m) for m in lin)
+    C = x.shape[-1]
+    D = proj.out_features // 2
+    return (proj.in_features == C and proj.out_features == 2 * D and D % 8 == 0 and out.in_features == D
+            and out.out_features == C and _linear_dtype_ok(lin[0], torch.float32) and _linear_dtype_ok(lin[1], torch.float32))
+
+
+def norm_feed_forward_f32(norm: torch.nn.Module, ff: torch.nn.Module, hidden_states: torch.Tensor) -> torch.Tensor:
+    """patch.py:187-199 for an fp32 block with ``fp32_projections``: ``ff(norm3(h)) + h`` as vtm_layernorm, the GEGLU GEMM
+    with value * gelu(gate) in its epilogue (the 8C-wide projection is never written) and the output GEMM with bias and
+    residual.  The caller has checked ``f32_ff_ok``."""
+    proj, out = _geglu_ff(ff)
+    f32 = torch.float32
+    C = hidden_states.shape[-1]
+    hs = hidden_states.contiguous()
+    n = hs.numel() // C
+    xn = _lib.layernorm(hs, norm.weight, norm.bias, norm.eps).view(1, n, C)
+    h = _lib.linear_f32(xn, None, None, None, n, _weight(proj, f32), _bias(proj, f32), epilogue="geglu")   # (1, n8, D)
+    y = _lib.linear_f32(h, None, None, None, n, _weight(out, f32), _bias(out, f32), epilogue="resid", resid=hs.view(1, n, C),
+                        out=torch.empty((1, n, C), dtype=f32, device=hs.device))
+    return y.view(hidden_states.shape)
+
+
 def feed_forward(ff: torch.nn.Module, x: torch.Tensor) -> torch.Tensor:
     """`self.ff(norm_hidden_states)` (patch.py:192).  The Diffusers feed-forward of SD blocks is
     [GEGLU(proj: Linear C -> 8C), Dropout, Linear 4C -> C]; when that shape is recognised the gated activation
@@ -954,7 +1070,9 @@ def patched_self_attention_segment(block: torch.nn.Module, hidden_states: torch.
         and fused_attention_ok(block.attn1, norm_hidden_states)
     by_rows = fused and fused_projections_ok(block.attn1, norm_hidden_states)
     by_panels = fused and not by_rows and panel_projections_ok(block.attn1, norm_hidden_states)
-    m_a, u_a, merged = compute_merge(block, norm_hidden_states, block._tome_info, materialize=not (by_rows or by_panels))
+    by_f32 = fused and _fp32_projections(block) and f32_projections_ok(block.attn1, norm_hidden_states)
+    m_a, u_a, merged = compute_merge(block, norm_hidden_states, block._tome_info,
+                                     materialize=not (by_rows or by_panels or by_f32))
     plan = getattr(m_a, "plan", None)
     if not fused:
         # not the hot path (SD never masks self-attention nor makes attn1 a cross-attention; LoRA'd / custom
@@ -971,7 +1089,15 @@ def patched_self_attention_segment(block: torch.nn.Module, hidden_states: torch.
                 and (_pnp_share_groups(block.attn1) == 1 or plan.aligned))
         q_rows = plan.q_rows if live else None
         q_count = plan.q_count if live else None
-        if by_rows or by_panels:
+        if by_f32:                                                        # fp32 model with fp32_projections
+            fp32_core = getattr(block, "fp32_attention", False)
+            if plan is None:
+                attn_output = self_attention_f32(block.attn1, norm_hidden_states.contiguous(), None, None,
+                                                 fp32_core=fp32_core)
+            else:
+                attn_output = self_attention_f32(block.attn1, plan.x_joined, plan.anchors_in, plan.gather_map, q_rows,
+                                                 q_count, fp32_core=fp32_core)
+        elif by_rows or by_panels:
             sa = self_attention_rows if by_rows else self_attention_panels
             if plan is None:                                              # block does not merge: per-frame attention
                 attn_output = sa(block.attn1, norm_hidden_states.contiguous(), None, None)
@@ -1043,6 +1169,10 @@ def make_diffusers_tome_block(block_class: Type[torch.nn.Module]) -> Type[torch.
                                                                   cross_attention_kwargs):
                     hidden_states = norm_cross_attention_residual(self.norm2, self.attn2, hidden_states,
                                                                   encoder_hidden_states)
+                elif not self.use_ada_layer_norm and f32_cross_ok(self, self.norm2, self.attn2, hidden_states,
+                                                                  encoder_hidden_states, encoder_attention_mask,
+                                                                  cross_attention_kwargs):
+                    hidden_states = norm_cross_attention_f32(self.norm2, self.attn2, hidden_states, encoder_hidden_states)
                 else:
                     norm_hidden_states = (self.norm2(hidden_states, timestep) if self.use_ada_layer_norm
                                           else layer_norm(self.norm2, hidden_states))
@@ -1052,6 +1182,8 @@ def make_diffusers_tome_block(block_class: Type[torch.nn.Module]) -> Type[torch.
 
             if not self.use_ada_layer_norm_zero and fused_ff_ok(self.norm3, self.ff, hidden_states):   # patch.py:187-199
                 return norm_feed_forward_residual(self.norm3, self.ff, hidden_states)
+            if not self.use_ada_layer_norm_zero and f32_ff_ok(self, self.norm3, self.ff, hidden_states):
+                return norm_feed_forward_f32(self.norm3, self.ff, hidden_states)
             norm_hidden_states = layer_norm(self.norm3, hidden_states)
             if self.use_ada_layer_norm_zero:
                 norm_hidden_states = norm_hidden_states * (1 + scale_mlp[:, None]) + shift_mlp[:, None]
@@ -1186,6 +1318,7 @@ def remove_patch(model: torch.nn.Module):
             module.__dict__.pop("_vtm_lora", None)             # folded LoRA weights (lora.linear_params)
             module.__dict__.pop("_vtm_match_plans", None)      # the matcher's launch planners (pinned 32-byte buffers)
             module.__dict__.pop("fp32_attention", None)        # update_patch's opt-in: a later apply_patch starts without it
+            module.__dict__.pop("fp32_projections", None)      # (likewise)
     _lib.release_workspaces()            # the cached scratch buffers of the patched path (re-created on demand)
     return roots[-1]                     # the reference returns its loop variable: the last tree walked
 
