@@ -525,6 +525,28 @@ int vtm_linear_f32(const float *x0, int64_t P0, const float *x1, int64_t P1, int
 int vtm_lora_fold(const void *w, int dtype, const float *up, const float *down, int64_t c_out, int64_t c_in,
                   int64_t r, void *out, vtm_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * vtm_dora_norms / vtm_dora_fold -- the effective weight of a projection whose FIRST active adapter is DoRA (PEFT
+ * `use_dora=True`, weight-decomposed LoRA; Diffusers' PEFT backend installs it when the adapter file carries magnitude
+ * vectors).  PEFT's forward for it is base + (r - 1) (base - b) + r s_d x (B_d A_d)^T with r = m / ||W + s_d B_d A_d||
+ * per output row (m: the adapter's magnitude vector), then the plain adapters after it, i.e. the Linear
+ *   W_eff = diag(r) (W + s_d B_d A_d) + sum_{plain a} s_a B_a A_a.
+ * up / down as for vtm_lora_fold, the DoRA adapter first: up = [s_d B_d | s_a B_a ...] (c_out, r) and down =
+ * [A_d; A_a; ...] (r, c_in), fp32 row-major, the DoRA adapter's rank k_dora (0 < k_dora <= r).
+ * vtm_dora_norms: norms[o] = sqrt( sum_i (w[o, i] + sum_{k < k_dora} up[o, k] * down[k, i])^2 ), fp32 (c_out).  The inner
+ *   sums are the k-ascending fmaf chains of vtm_lora_fold, added to w in fp32; the squares are summed in a fixed order
+ *   (one workgroup per 64-row band, column tiles ascending), so two calls give the same bits.
+ * vtm_dora_fold: out[o, i] = round_dtype( (magnitude[o] / norms[o]) * (w[o, i] + sum_{k < k_dora} up[o, k] down[k, i])
+ *   + sum_{k_dora <= k < r} up[o, k] down[k, i] ), each chain from +0, each fp32 step rounded once (the division is
+ *   IEEE: a zero norm gives +-inf or NaN, as PEFT's does).  magnitude, norms: fp32 (c_out); out may not alias an input.
+ * Runs once per adapter state, not per step.  Sizes as vtm_lora_fold (else VTM_EINVAL).
+ * ---------------------------------------------------------------------------------------------- */
+int vtm_dora_norms(const void *w, int dtype, const float *up, const float *down, int64_t c_out, int64_t c_in,
+                   int64_t r, int64_t k_dora, float *norms, vtm_stream_t stream);
+int vtm_dora_fold(const void *w, int dtype, const float *up, const float *down, const float *magnitude,
+                  const float *norms, int64_t c_out, int64_t c_in, int64_t r, int64_t k_dora, void *out,
+                  vtm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -93,6 +93,8 @@ _SIGNATURES = {
     "vtm_linear_rows": ([_vp, _i64, _vp, _i64, _int, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64,
                          _int, _vp], _int),
     "vtm_lora_fold": ([_vp, _int, _vp, _vp, _i64, _i64, _i64, _vp, _vp], _int),
+    "vtm_dora_norms": ([_vp, _int, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp], _int),
+    "vtm_dora_fold": ([_vp, _int, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp], _int),
     "vtm_linear_f32": ([_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _int, _vp, _vp, _int, _i64,
                         _i64, _int, _vp], _int),
 }
@@ -875,4 +877,52 @@ def lora_fold(w: torch.Tensor, up: torch.Tensor, down: torch.Tensor, out: Option
         out = torch.empty_like(w)
     _check(lib().vtm_lora_fold(_ptr(w), dtype_code(w), _ptr(up), _ptr(down), c_out, c_in, r, _ptr(_req(out, "out")),
                                _stream()), "vtm_lora_fold")
+    return out
+
+
+def _fold_operands(what: str, w: torch.Tensor, up: torch.Tensor, down: torch.Tensor, k_dora: int) -> Tuple[int, int, int]:
+    _req(w, "w"), _req(up, "up"), _req(down, "down")
+    c_out, c_in = w.shape
+    r = up.shape[1]
+    if up.dtype != torch.float32 or down.dtype != torch.float32 or tuple(up.shape) != (c_out, r) \
+            or tuple(down.shape) != (r, c_in) or up.device != w.device or down.device != w.device:
+        raise RuntimeError(f"{what}: up must be (c_out, r) and down (r, c_in) fp32 tensors on w's device")
+    if not 0 < k_dora <= r:
+        raise RuntimeError(f"{what}: k_dora {k_dora} not in [1, r = {r}]")
+    return c_out, c_in, r
+
+
+@_on_device
+def dora_norms(w: torch.Tensor, up: torch.Tensor, down: torch.Tensor, k_dora: int,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32 (c_out,) row norms of W + up[:, :k_dora] @ down[:k_dora] (operands as for lora_fold); see
+    include/vidtome_hip.h vtm_dora_norms."""
+    c_out, c_in, r = _fold_operands("dora_norms", w, up, down, k_dora)
+    if out is None:
+        out = torch.empty(c_out, dtype=torch.float32, device=w.device)
+    if out.dtype != torch.float32 or tuple(out.shape) != (c_out,) or out.device != w.device:
+        raise RuntimeError("dora_norms: out must be an fp32 (c_out,) tensor on w's device")
+    _check(lib().vtm_dora_norms(_ptr(w), dtype_code(w), _ptr(up), _ptr(down), c_out, c_in, r, k_dora, _ptr(_req(out, "out")),
+                                _stream()), "vtm_dora_norms")
+    return out
+
+
+@_on_device
+def dora_fold(w: torch.Tensor, up: torch.Tensor, down: torch.Tensor, magnitude: torch.Tensor, k_dora: int,
+              norms: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(magnitude / norms) (W + up[:, :k_dora] @ down[:k_dora]) + up[:, k_dora:] @ down[k_dora:] in w's dtype, row-scaled,
+    for a layer whose first adapter is DoRA: the DoRA adapter's columns / rows first in up / down (operands as for
+    lora_fold), magnitude fp32 (c_out,); `norms` = dora_norms(w, up, down, k_dora) unless given.  See
+    include/vidtome_hip.h vtm_dora_fold."""
+    c_out, c_in, r = _fold_operands("dora_fold", w, up, down, k_dora)
+    if norms is None:
+        norms = dora_norms(w, up, down, k_dora)
+    for name, t in (("magnitude", magnitude), ("norms", norms)):
+        if t.dtype != torch.float32 or tuple(t.shape) != (c_out,) or t.device != w.device:
+            raise RuntimeError(f"dora_fold: {name} must be an fp32 (c_out,) tensor on w's device")
+    if out is None:
+        out = torch.empty_like(w)
+    _check(lib().vtm_dora_fold(_ptr(w), dtype_code(w), _ptr(up), _ptr(down), _ptr(_req(magnitude, "magnitude")),
+                               _ptr(_req(norms, "norms")), c_out, c_in, r, k_dora, _ptr(_req(out, "out")), _stream()),
+           "vtm_dora_fold")
     return out

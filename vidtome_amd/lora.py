@@ -19,8 +19,20 @@ Two structures are recognised by duck typing (neither PEFT nor Diffusers is a de
   ``active_adapters``, ``merged``, ``disable_adapters``, ``use_dora``, ``lora_dropout``;
 * Diffusers' legacy ``LoRACompatibleLinear`` with a ``lora_layer`` that has ``down``, ``up``, ``network_alpha`` and
   ``rank`` (its forward adds ``scale * up(down(x)) * network_alpha / rank``, the forward's ``scale`` being 1.0 here).
-Anything else -- DoRA, ``fan_in_fan_out``, dropout with p > 0 in training mode, adapters that are not Linears, other
-wrappers -- is not recognised and the patched block keeps the module's own forward.
+DoRA (PEFT ``use_dora=True``, weight-decomposed LoRA) is recognised in its one unambiguous form: exactly one active DoRA
+adapter ``d``, FIRST in PEFT's order, with a magnitude vector ``m`` of shape (c_out,) in ``lora_magnitude_vector[d]`` (a
+tensor, or a module whose ``.weight`` it is) and no ``lora_B`` bias.  PEFT then computes
+``base + (r - 1) (base - b) + r s_d x (B_d A_d)^T`` with ``r = m / ||W + s_d B_d A_d||`` per output row and the running
+result ``base``, so the layer is the Linear ``diag(r) (W + s_d B_d A_d) + sum_{plain a after d} s_a B_a A_a`` (bias
+``b + sum_a s_a b_B_a``), folded by vtm_dora_norms + vtm_dora_fold (a zero norm divides as IEEE does, like PEFT).  A merged
+DoRA adapter is already in the base weight (PEFT's ``merge()`` writes ``r (W + s_d B_d A_d)`` into ``.data``) and is read like
+any merged adapter.  The state token adds the magnitude's (pointer, version).  The extra memory is the LoRA fold's: one
+folded copy per adapted projection.
+
+Anything else -- DoRA after another adapter or on more than one adapter (which running result PEFT scales there has
+changed between releases), DoRA without a magnitude vector or with a ``lora_B`` bias, ``fan_in_fan_out``, dropout with
+p > 0 in training mode, adapters that are not Linears, other wrappers -- is not recognised and the patched block keeps the
+module's own forward.
 """
 from __future__ import annotations
 
@@ -56,6 +68,32 @@ def _active(m):
     return [a for a in names if a in m.lora_A]
 
 
+def _magnitude(m, a: str) -> Optional[torch.Tensor]:
+    """PEFT: DoRA adapter `a`'s magnitude vector (c_out,) -- a tensor / Parameter (older PEFT) or the ``.weight`` of a
+    DoraLinearLayer -- or None when it is missing or not of that form."""
+    mv = getattr(m, "lora_magnitude_vector", None)
+    try:
+        v = mv[a] if mv is not None and a in mv else None
+    except TypeError:
+        return None
+    if v is not None and not isinstance(v, torch.Tensor):
+        if getattr(v, "fan_in_fan_out", False):
+            return None
+        v = getattr(v, "weight", None)
+    if not isinstance(v, torch.Tensor) or not v.is_floating_point() or tuple(v.shape) != (m.base_layer.out_features,):
+        return None
+    return v
+
+
+def _dora_ok(m, active) -> bool:
+    """The DoRA adapters among `active` (if any) are one adapter, first, with a magnitude vector and no lora_B bias."""
+    dora = [a for a in active if _flag(m.use_dora, a)]
+    if not dora:
+        return True
+    d = dora[0]
+    return len(dora) == 1 and d == active[0] and _magnitude(m, d) is not None and m.lora_B[d].bias is None
+
+
 def _peft_ok(m) -> bool:
     if not all(hasattr(m, a) for a in ("base_layer", "lora_A", "lora_B", "scaling", "active_adapters", "merged",
                                        "disable_adapters", "use_dora", "lora_dropout")):
@@ -73,8 +111,11 @@ def _peft_ok(m) -> bool:
             return False
     if m.disable_adapters and m.merged:
         return False            # PEFT's forward unmerges first (a side effect the module path performs)
-    for a in _active(m):
-        if _flag(m.use_dora, a) or a not in m.scaling:
+    active = _active(m)
+    if not m.merged and not _dora_ok(m, active):
+        return False            # a merged DoRA adapter is in the base weight: PEFT's forward is then the base layer
+    for a in active:
+        if a not in m.scaling:
             return False
         d = m.lora_dropout[a] if a in m.lora_dropout else torch.nn.Identity()
         if type(d) is torch.nn.Identity:
@@ -121,14 +162,16 @@ def _param_key(w: torch.Tensor, b: Optional[torch.Tensor]):
 
 
 def _adapters(m, kind: str):
-    """[(name, scale, A (r, c_in), B (c_out, r), B's bias or None)] of the adapters the forward adds."""
+    """[(name, scale, A (r, c_in), B (c_out, r), B's bias or None, DoRA magnitude or None)] of the adapters the forward
+    adds; a DoRA adapter is always the first (recognise)."""
     if kind == LEGACY:
         ll = m.lora_layer
         s = 1.0 if ll.network_alpha is None else float(ll.network_alpha) / float(ll.rank)
-        return [("lora_layer", s, ll.down.weight, ll.up.weight, ll.up.bias)]
+        return [("lora_layer", s, ll.down.weight, ll.up.weight, ll.up.bias, None)]
     if m.disable_adapters or m.merged:
         return []
-    return [(a, m.scaling[a], m.lora_A[a].weight, m.lora_B[a].weight, m.lora_B[a].bias) for a in _active(m)]
+    return [(a, m.scaling[a], m.lora_A[a].weight, m.lora_B[a].weight, m.lora_B[a].bias,
+             _magnitude(m, a) if _flag(m.use_dora, a) else None) for a in _active(m)]
 
 
 def state_token(m, kind: Optional[str] = None) -> tuple:
@@ -141,7 +184,8 @@ def state_token(m, kind: Optional[str] = None) -> tuple:
         tok += (bool(m.disable_adapters), bool(m.merged), merged)
     elif kind == LEGACY:
         tok += (m.lora_layer.network_alpha, m.lora_layer.rank)
-    return tok + tuple((a, float(s), _tkey(A), _tkey(B), _tkey(bB)) for a, s, A, B, bB in _adapters(m, kind))
+    return tok + tuple((a, float(s), _tkey(A), _tkey(B), _tkey(bB)) + (() if mag is None else ("dora", _tkey(mag)))
+                       for a, s, A, B, bB, mag in _adapters(m, kind))
 
 
 def _fold(m, kind: str):
@@ -152,12 +196,17 @@ def _fold(m, kind: str):
     if not ads:
         return w, b, False
     with torch.no_grad():
-        up = torch.cat([B.detach().float() * float(s) for _, s, _, B, _ in ads], dim=1).contiguous()
-        down = torch.cat([A.detach().float() for _, _, A, _, _ in ads], dim=0).contiguous()
-        wf = _lib.lora_fold(w.contiguous(), up.to(w.device), down.to(w.device))
-        if any(bB is not None for *_, bB in ads):
+        up = torch.cat([B.detach().float() * float(s) for _, s, _, B, _, _ in ads], dim=1).contiguous()
+        down = torch.cat([A.detach().float() for _, _, A, _, _, _ in ads], dim=0).contiguous()
+        mag = ads[0][5]
+        if mag is None:
+            wf = _lib.lora_fold(w.contiguous(), up.to(w.device), down.to(w.device))
+        else:                   # DoRA first: its rank is the first k columns of up / rows of down
+            wf = _lib.dora_fold(w.contiguous(), up.to(w.device), down.to(w.device),
+                                mag.detach().float().to(w.device).contiguous(), ads[0][2].shape[0])
+        if any(bB is not None for *_, bB, _ in ads):
             acc = torch.zeros(w.shape[0], dtype=torch.float32, device=w.device) if b is None else b.float()
-            for _, s, _, _, bB in ads:
+            for _, s, _, _, bB, _ in ads:
                 if bB is not None:
                     acc = acc + float(s) * bB.detach().float()
             b = acc.to(w.dtype)
