@@ -342,6 +342,22 @@ int vtm_attention_kv(const void *q, int64_t ldq, const void *k, int64_t ldk, con
                      int64_t Mk, int64_t Mkp, int64_t d, float scale, int share_groups, void *ws, size_t ws_bytes,
                      vtm_stream_t stream);
 
+/* vtm_attention_kv_sets -- cross-attention over SEVERAL key sets, one softmax per set: what an image-prompt adapter
+ * (IP-Adapter's "decoupled cross-attention") turns the `self.attn2(...)` call of vidtome/patch.py:178-183 into.  Per head
+ *     out[b, i] = sum_{s < n_sets} w_s * softmax_{j in set s}(q[b, i] . k[b, j] * scale) v[b, j]
+ * q, out, k, vt exactly as for vtm_attention_kv (heads interleaved on the channel axis, vt channel-major).  All sets live in
+ * ONE k buffer (B, Mkp, .) and ONE vt buffer (B, h*d, ldvt); set s is the key range [set_start[s], set_start[s] + set_len[s])
+ * inside [0, Mkp) and [0, ldvt).  set_start[s] must be a multiple of 8 (V^T is fetched in 16-byte pieces of 8 keys),
+ * set_len[s] >= 1; keys outside every set (padding between sets) are never read as keys.  n_sets (1 .. 8), set_start,
+ * set_len and set_weight are HOST values (arrays of n_sets entries, read before the call returns); the weights may be
+ * negative or above 1.  Every set keeps a running max, a denominator and fp32 accumulators of its own; the weighted sum
+ * is formed in fp32 and rounded to the output type once.  scale > 0.  dtype VTM_F16 or VTM_BF16 (VTM_F32: VTM_EINVAL); d as
+ * for vtm_attention.  One launch, no workspace: the key axis is a few hundred keys, the launch streams q and out. */
+int vtm_attention_kv_sets(const void *q, int64_t ldq, const void *k, int64_t ldk, const void *vt, int64_t ldvt,
+                          void *out, int64_t ldo, int dtype, int64_t B, int64_t h, int64_t Mq, int64_t Mqp,
+                          int64_t Mkp, int64_t d, float scale, int n_sets, const int64_t *set_start,
+                          const int64_t *set_len, const float *set_weight, vtm_stream_t stream);
+
 /* vtm_attention_kv with a DEVICE-side query bound: sample b only has q_count[b] <= Mq meaningful query rows (the
  * compacted live queries of vtm_compact_queries); query blocks that start at or beyond the count exit at once, rows
  * beyond it are not meaningful.  The launch is sized for the host-known bound Mq -- no host round trip. */

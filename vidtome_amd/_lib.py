@@ -68,6 +68,8 @@ _SIGNATURES = {
     "vtm_attention_ws_bytes": ([_i64, _i64, _i64, _i64, _i64], ctypes.c_size_t),
     "vtm_attention_kv": ([_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                           _f32, _int, _vp, ctypes.c_size_t, _vp], _int),
+    "vtm_attention_kv_sets": ([_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _f32,
+                               _int, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_f32), _vp], _int),
     "vtm_attention_kv_bounded": ([_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                   _f32, _vp, _vp, ctypes.c_size_t, _vp], _int),
     "vtm_attention_kv_shared_bounded": ([_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
@@ -652,6 +654,74 @@ def attention_kv(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int,
     _check(lib().vtm_attention_kv(q.data_ptr(), q.stride(1), k.data_ptr(), k.stride(1), vt.data_ptr(), vt.stride(1),
                                   out.data_ptr(), C, dtype_code(q), B, heads, Mq, Mqp, Mk, Mkp, d, float(scale),
                                   int(share_groups), _ptr(ws), nb, _stream()), "vtm_attention_kv")
+    return out
+
+
+MAX_KEY_SETS = 8
+
+
+@_on_device
+def attention_kv_range(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, Mq: int, start: int, Mk: int,
+                       scale: float) -> torch.Tensor:
+    """attention_kv over the key range [start, start + Mk) of k (B, Mkp, C) / vt (B, C, ldvt), start a multiple of 8: the
+    same vtm_attention_kv launch on the buffers where they are (pointers moved to the range, the buffers' own strides).
+    start == 0 IS attention_kv(q, k, vt, heads, Mq, Mk, scale)."""
+    start, Mk = int(start), int(Mk)
+    B, Mqp, C = q.shape
+    Mkp = k.shape[1]
+    if start % 8 or start < 0 or Mk < 1 or start + Mk > Mkp or start + Mk > vt.shape[2]:
+        raise RuntimeError("attention_kv_range: the range must start on a multiple of 8 and lie inside k and vt")
+    if start == 0:
+        return attention_kv(q, k, vt, heads, Mq, Mk, scale)
+    d = C // heads
+    if q.stride(2) != 1 or k.stride(2) != 1 or vt.stride(2) != 1:
+        raise RuntimeError("attention operands must be contiguous along their last axis")
+    if q.stride(0) != Mqp * q.stride(1) or k.stride(0) != Mkp * k.stride(1) or vt.stride(0) != C * vt.stride(1):
+        raise RuntimeError("attention operands must have dense batch strides")
+    out = torch.zeros((B, Mqp, C), dtype=q.dtype, device=q.device) if Mqp != Mq else \
+        torch.empty((B, Mqp, C), dtype=q.dtype, device=q.device)
+    ws, nb = _attention_ws(B, heads, Mq, Mk, d, q.device)
+    es = k.element_size()
+    # (sample b's keys start at k + (b * Mkp + start) * ldk: the row count Mkp stays the sample stride)
+    _check(lib().vtm_attention_kv(q.data_ptr(), q.stride(1), k.data_ptr() + start * k.stride(1) * es, k.stride(1),
+                                  vt.data_ptr() + start * es, vt.stride(1), out.data_ptr(), C, dtype_code(q), B, heads, Mq, Mqp,
+                                  Mk, Mkp, d, float(scale), 1, _ptr(ws), nb, _stream()), "vtm_attention_kv")
+    return out
+
+
+@_on_device
+def attention_kv_sets(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, Mq: int, sets, scale: float
+                      ) -> torch.Tensor:
+    """Cross-attention over several key sets, one softmax per set (vtm_attention_kv_sets): q (B, Mqp, C), k (B, Mkp, C)
+    views contiguous along the last axis, vt (B, C, ldvt) = v transposed, as for attention_kv.  ``sets`` is a sequence of
+    (start, length, weight): set s is the key range [start, start + length) of k / vt, start a multiple of 8; the result
+    is sum_s weight_s * softmax(q K_s^T * scale) V_s, (B, Mqp, C).  fp16 / bf16 operands only.  One set of weight 1 IS the
+    plain core and goes to attention_kv (the same launch and bits as a block without the extra sets)."""
+    sets = [(int(s), int(n), float(w)) for s, n, w in sets]
+    if not 1 <= len(sets) <= MAX_KEY_SETS:
+        raise RuntimeError(f"attention_kv_sets: 1 .. {MAX_KEY_SETS} key sets, got {len(sets)}")
+    if q.dtype not in (torch.float16, torch.bfloat16) or k.dtype != q.dtype or vt.dtype != q.dtype:
+        raise RuntimeError("attention_kv_sets: q, k and vt must share one of fp16 / bf16 (fp32 models keep the module path)")
+    B, Mqp, C = q.shape
+    Mkp = k.shape[1]
+    d = C // heads
+    if q.stride(2) != 1 or k.stride(2) != 1 or vt.stride(2) != 1:
+        raise RuntimeError("attention operands must be contiguous along their last axis")
+    if q.stride(0) != Mqp * q.stride(1) or k.stride(0) != Mkp * k.stride(1) or vt.stride(0) != C * vt.stride(1):
+        raise RuntimeError("attention operands must have dense batch strides")
+    if k.shape[0] != B or vt.shape[0] != B or k.shape[2] != C or vt.shape[1] != C:
+        raise RuntimeError("attention_kv_sets: k must be (B, Mkp, C) and vt (B, C, ldvt)")
+    if len(sets) == 1 and sets[0][2] == 1.0:
+        return attention_kv_range(q, k, vt, heads, Mq, sets[0][0], sets[0][1], scale)
+    out = torch.zeros((B, Mqp, C), dtype=q.dtype, device=q.device) if Mqp != Mq else \
+        torch.empty((B, Mqp, C), dtype=q.dtype, device=q.device)
+    n = len(sets)
+    starts = (_i64 * n)(*[s for s, _, _ in sets])
+    lens = (_i64 * n)(*[m for _, m, _ in sets])
+    weights = (_f32 * n)(*[w for _, _, w in sets])
+    _check(lib().vtm_attention_kv_sets(q.data_ptr(), q.stride(1), k.data_ptr(), k.stride(1), vt.data_ptr(), vt.stride(1),
+                                       out.data_ptr(), C, dtype_code(q), B, heads, Mq, Mqp, Mkp, d, float(scale), n, starts,
+                                       lens, weights, _stream()), "vtm_attention_kv_sets")
     return out
 
 

@@ -1,6 +1,6 @@
-// How an attention launch is planned and issued, once for the four kernel families (attention_kernel in attention.hip,
+// How an attention launch is planned and issued, once for the five kernel families (attention_kernel in attention.hip,
 // attention16s_kernel in attention16.hip, attention16g_kernel in attention16g.hip, attention_f32_kernel in
-// attention_f32.hip): the host tail plan, the device plan of query-bounded launches, the family descriptor, the launch
+// attention_f32.hip, attention_sets_kernel in attention_sets.hip): the host tail plan, the device plan of query-bounded launches, the family descriptor, the launch
 // driver, the workspace size and the head-dim dispatch.  Header-only; host code apart from attention16_plan_kernel.
 #pragma once
 #include "attention_common.h"
@@ -70,6 +70,15 @@ struct Call {
     const void *q; int64_t ldq; const void *k; int64_t ldk; const void *vt; int64_t ldvt; void *out; int64_t ldo;
     int dtype; int64_t B, h, M, Mp, Mk, Mkp; float scale; int share_groups; void *ws; size_t ws_bytes;
     const int32_t *q_count; hipStream_t s; bool fold; const int32_t *k_count; const uint32_t *k_bias; int64_t ldkb;
+    const struct KeySets *sets = nullptr;   // vtm_attention_kv_sets only: the key ranges, each with a softmax of its own
+};
+
+// ---- the key sets of one vtm_attention_kv_sets call (attention_sets.hip): set s = keys [start[s], start[s] + len[s]) ----
+constexpr int MAX_KEY_SETS = 8;
+struct KeySets {
+    int n;
+    int start[MAX_KEY_SETS], len[MAX_KEY_SETS];
+    float w[MAX_KEY_SETS];
 };
 
 // ---- what planned_launch computed, for a family's launch thunks ----

@@ -1,0 +1,338 @@
+// vtm_attention_kv_sets: cross-attention over SEVERAL key sets, one softmax per set, the sets added with weights:
+//     out[b, i, head] = sum_s w_s * softmax_{j in set s}(q[b, i, head] . k[b, j, head] * scale) v[b, j, head]
+// This is the "decoupled cross-attention" an image-prompt adapter adds to attn2 (vidtome/patch.py:178-183 is the call it
+// stands beside): set 0 = the text tokens, one more set per loaded adapter, all with the same q.  Composed from
+// vtm_attention_kv it costs 1 + n launches that each read all of q and write all of out, plus the adds; here a workgroup
+// keeps its query fragments, walks the sets and writes out once.
+//
+// Structure (the building blocks of attention.hip, without what a few hundred keys do not need -- no key split, no
+// workspace, no spare-slot tricks):
+//   * workgroup = waves of 32 query rows; the K / V^T tiles of 64 keys are staged through LDS and shared by the waves, the
+//     next tile's global loads in flight in registers while the current one is computed; a tile never crosses a set;
+//   * S^T = K Q^T on v_mfma_f32_32x32x16 (one query per lane), online softmax in registers, base 2, deferred rescale; P
+//     is rounded to the operand type for the PV contraction (bf16: as a hi + lo pair, two MFMAs) and the DENOMINATOR is
+//     summed from the same rounded P;
+//   * every tile is loaded through the masked path (keys outside [start_s, start_s + len_s) are never fetched as keys and
+//     are zeroed as values): the key axis is 2 - 10 tiles long, bounds logic is not what this kernel waits for;
+//   * per set: running max, denominator and fp32 accumulators of its own; at the end of the set they are folded into a
+//     second fp32 accumulator as w_s / l_s; that sum is rounded to the output type once.
+#include "attention_plan.h"
+
+#include <cmath>
+
+namespace {
+
+// Two accumulator sets (the running set's and the weighted sum) double the register budget of attention_kernel: 8 waves
+// (2 per SIMD, 256 VGPRs) up to d = 96, 4 waves above.
+constexpr int sets_waves(int D) { return D <= 96 ? 8 : 4; }
+// resident workgroups per CU (the launch bounds' waves per SIMD follow from it): d = 40 and 64 need 168 VGPRs and spill at 128
+constexpr int sets_wg_per_cu(int D) { return D <= 32 ? 2 : 1; }
+
+template <typename T, int D>
+__global__ __launch_bounds__(sets_waves(D) * 64, sets_wg_per_cu(D) * sets_waves(D) / 4) void attention_sets_kernel(
+    const T *__restrict__ q, int64_t ldq, const T *__restrict__ k, int64_t ldk, const T *__restrict__ vt, int64_t ldvt,
+    T *__restrict__ out, int64_t ldo, int64_t H, int64_t M, int64_t Mp, int64_t Mkp, float scale_log2e, int64_t nqb,
+    int xcd_groups, KeySets sets) {
+    using F = Frag<T>;
+    using vec = typename F::vec;
+    using elem = typename F::elem;
+    constexpr int WAVES = sets_waves(D), NT = WAVES * 64, QB = WAVES * QW;
+    constexpr bool SPLIT_P = std::is_same_v<T, vtm_bf16>;   // P as hi + lo parts (see tile)
+    constexpr int DK = (D + 15) / 16;      // k-steps of the QK^T contraction
+    constexpr int DV = (D + 31) / 32;      // 32-row blocks of O^T
+    constexpr int VROWS = DV * 32;
+    constexpr int K_STRIDE = DK * 16 + 8;  // elements; conflict-free b128 reads (see attention.hip)
+    constexpr int DCH = D / 8;             // 16-byte chunks per K row
+    constexpr int K_CHUNKS = KV * DCH, V_CHUNKS = D * (KV / 8);
+    constexpr int K_PER_T = (K_CHUNKS + NT - 1) / NT, V_PER_T = (V_CHUNKS + NT - 1) / NT;
+
+    __shared__ __attribute__((aligned(16))) elem sK[KV * K_STRIDE];
+    __shared__ __attribute__((aligned(16))) elem sV[VROWS * VT_STRIDE];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int l31 = lane & 31, hi = lane >> 5;
+    const int64_t lin = item_of((int64_t)blockIdx.x, nqb, xcd_groups);
+    const int64_t b = lin / (nqb * H), h = (lin / nqb) % H;
+    const int64_t q0 = (lin % nqb) * QB + wave * QW;
+    const int64_t C = H * D;
+
+    // one-time LDS init: the K pad columns meet Q's zero padding and the V^T pad rows feed O^T rows nobody stores, but
+    // garbage there could be NaN; tile stores never touch them
+    for (int i = tid; i < KV * (K_STRIDE - D); i += NT)
+        sK[(i / (K_STRIDE - D)) * K_STRIDE + D + i % (K_STRIDE - D)] = (elem)0.0f;
+    for (int i = tid; i < (VROWS - D) * VT_STRIDE; i += NT) sV[D * VT_STRIDE + i] = (elem)0.0f;
+
+    // Q fragments (B operand of S^T = K Q^T): lane (query l31, half hi) holds d = 16 ks + 8 hi + 0..7
+    vec qf[DK];
+    {
+        const int64_t qi = q0 + l31;
+        const T *qp = q + (b * Mp + (qi < M ? qi : 0)) * ldq + h * D;
+#pragma unroll
+        for (int ks = 0; ks < DK; ++ks) {
+            const int d0 = ks * 16 + hi * 8;
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (d0 < D && qi < M) v = *reinterpret_cast<const uint4 *>(qp + d0);
+            qf[ks] = *reinterpret_cast<vec *>(&v);
+        }
+    }
+
+    // staging addresses, as in attention_kernel: chunk c = tid + NT i; K: (row c / DCH, 16-byte piece c % DCH); V^T:
+    // (channel row c / 8, key piece c % 8), stored as [k0-3 | k8-11 | k4-7 | k12-15] inside every 16-key group
+    uint32_t kgo[K_PER_T], vgo[V_PER_T];
+    int koff[K_PER_T], voff[V_PER_T], krow[K_PER_T], vkey[V_PER_T];
+    bool kok[K_PER_T], vok[V_PER_T];
+#pragma unroll
+    for (int i = 0; i < K_PER_T; ++i) {
+        const int c = tid + i * NT;
+        kok[i] = c < K_CHUNKS;
+        krow[i] = c / DCH;
+        kgo[i] = kok[i] ? (uint32_t)(krow[i] * (int)ldk + (c % DCH) * 8) * 2u : 0u;
+        koff[i] = krow[i] * K_STRIDE + (c % DCH) * 8;
+    }
+#pragma unroll
+    for (int i = 0; i < V_PER_T; ++i) {
+        const int c = tid + i * NT;
+        vok[i] = c < V_CHUNKS;
+        vkey[i] = (c % (KV / 8)) * 8;
+        vgo[i] = vok[i] ? (uint32_t)((c / (KV / 8)) * (int)ldvt + vkey[i]) * 2u : 0u;
+        voff[i] = (c / (KV / 8)) * VT_STRIDE + (vkey[i] & ~15) + ((vkey[i] >> 3) & 1) * 4;
+    }
+    // (the descriptors carry no real bound: every fetch is guarded by the set's end below)
+    const auto rsrc_k = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(k + b * Mkp * ldk + h * D), 0, 0x7fffffff, 0x00020000);
+    const auto rsrc_v = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(vt + (b * C + h * D) * ldvt), 0, 0x7fffffff, 0x00020000);
+    auto fetch = [](const auto &rsrc, uint32_t voff_, uint32_t soff_) {
+        return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff_, soff_, 0));
+    };
+
+    uint4 rk[K_PER_T], rv[V_PER_T];
+    auto issue = [&](int key0, int end) {   // the tile of keys [key0, key0 + 64): rows / keys >= end read as zero
+        const uint32_t so_k = (uint32_t)key0 * (uint32_t)ldk * 2u, so_v = (uint32_t)key0 * 2u;
+#pragma unroll
+        for (int i = 0; i < K_PER_T; ++i) {
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (kok[i] && key0 + krow[i] < end) v = fetch(rsrc_k, kgo[i], so_k);
+            rk[i] = v;
+        }
+#pragma unroll
+        for (int i = 0; i < V_PER_T; ++i) {
+            uint4 v = make_uint4(0, 0, 0, 0);
+            const int key = key0 + vkey[i];
+            if (vok[i] && key < end) {   // key % 8 == 0 and ldvt % 8 == 0, ldvt >= end: the 16-byte piece is inside the row
+                v = fetch(rsrc_v, vgo[i], so_v);
+                mask_keys(v, end - key);   // p is 0 there, but 0 * garbage may be NaN
+            }
+            rv[i] = v;
+        }
+    };
+    auto write_lds = [&]() {
+#pragma unroll
+        for (int i = 0; i < K_PER_T; ++i)
+            if (kok[i]) *reinterpret_cast<uint4 *>(sK + koff[i]) = rk[i];
+#pragma unroll
+        for (int i = 0; i < V_PER_T; ++i)
+            if (vok[i]) {
+                uint2 *dst = reinterpret_cast<uint2 *>(sV + voff[i]);
+                dst[0] = make_uint2(rv[i].x, rv[i].y);
+                dst[2] = make_uint2(rv[i].z, rv[i].w);
+            }
+    };
+
+    // o: the running set's unnormalised O^T; total: the weighted sum over the finished sets.  Both in the 32-row layout:
+    // [dv][r] = row 32 dv + (r & 3) + 8 (r >> 2) + 4 hi of query l31
+    f32x16 o[DV], total[DV];
+#pragma unroll
+    for (int dv = 0; dv < DV; ++dv)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            o[dv][r] = 0.0f;
+            total[dv][r] = 0.0f;
+        }
+    float m_run = -INFINITY;   // running max of the set, scaled (log2) units
+    float l_run = 0.0f;        // this lane's share of the set's denominator
+
+    auto tile = [&](int lim) {   // lim = keys of the tile that belong to the set (>= 64: all)
+        f32x16 s[2];
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) s[kb][r] = 0.0f;
+            const elem *kp = sK + (kb * 32 + l31) * K_STRIDE + hi * 8;
+#pragma unroll
+            for (int ks = 0; ks < DK; ++ks) s[kb] = F::mfma(*reinterpret_cast<const vec *>(kp + ks * 16), qf[ks], s[kb]);
+        }
+        if (lim < KV) {   // lane (l31, hi) holds keys 32 kb + (r & 3) + 8 (r >> 2) + 4 hi
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    if (kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi >= lim) s[kb][r] = -INFINITY;
+        }
+        // online softmax, base 2, deferred rescale (scale > 0: the maximum commutes with it).  The first tile of a set
+        // has at least one key and m_run = -inf, so it always installs its own maximum.
+        float mt = fmaxf(s[0][0], s[1][0]);
+#pragma unroll
+        for (int r = 1; r < 16; ++r) mt = fmaxf(fmaxf(mt, s[0][r]), s[1][r]);
+        mt = fmaxf(mt, __shfl_xor(mt, 32, 64)) * scale_log2e;
+        if (!__all(mt <= m_run + DEFER_THR)) {
+            const float m_new = fmaxf(m_run, mt);
+            const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);   // first tile: exp2(-inf) = 0
+            m_run = m_new;
+            l_run *= alpha;
+#pragma unroll
+            for (int dv = 0; dv < DV; ++dv)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) o[dv][r] *= alpha;
+        }
+        // per 16-key step: p of keys 16 st + (e & 3) + 8 (e >> 2) + 4 hi, packed to the operand type, then O^T += V^T P^T with
+        // k-slot (hi, e) <-> key 16 st + 8 (e >> 2) + 4 hi + (e & 3).  bf16 keeps 8 bits of P: there P goes in as hi + lo (two
+        // MFMAs on the same V^T fragment, the matrix pipe is idle anyway), so that its rounding stays below the operands' own;
+        // the denominator is summed from what the numerator sees.
+#pragma unroll
+        for (int st = 0; st < 4; ++st) {
+            float p[8], plo[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+                p[e] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[st >> 1][8 * (st & 1) + e], scale_log2e, -m_run));
+            vec ph, pl;
+            F::pack8(ph, p);
+            if constexpr (SPLIT_P) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) plo[e] = p[e] - (float)ph[e];
+                F::pack8(pl, plo);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) l_run += (float)ph[e] + (float)pl[e];
+            } else {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) l_run += (float)ph[e];
+            }
+#pragma unroll
+            for (int dv = 0; dv < DV; ++dv) {
+                const vec vf = *reinterpret_cast<const vec *>(sV + (dv * 32 + l31) * VT_STRIDE + 8 * hi + st * 16);
+                o[dv] = F::mfma(vf, ph, o[dv]);
+                if constexpr (SPLIT_P) o[dv] = F::mfma(vf, pl, o[dv]);
+            }
+        }
+    };
+    auto finish_set = [&](float w) {   // total += w * o / l; the next set starts from nothing
+        const float f = w / (l_run + __shfl_xor(l_run, 32, 64));
+#pragma unroll
+        for (int dv = 0; dv < DV; ++dv)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                total[dv][r] = __builtin_fmaf(o[dv][r], f, total[dv][r]);
+                o[dv][r] = 0.0f;
+            }
+        m_run = -INFINITY;
+        l_run = 0.0f;
+    };
+
+    // the tiles of all sets, one after the other; (cs, ct) is the tile in LDS, (ns, nt) the one in flight
+    int cs = 0, ct = 0;
+    issue(sets.start[0], sets.start[0] + sets.len[0]);
+    write_lds();
+    __syncthreads();
+    for (;;) {
+        const int len = sets.len[cs];
+        int ns = cs, nt = ct + 1;
+        if (nt * KV >= len) {
+            ns = cs + 1;
+            nt = 0;
+        }
+        const bool more = ns < sets.n;
+        if (more) issue(sets.start[ns] + nt * KV, sets.start[ns] + sets.len[ns]);
+        tile(len - ct * KV);
+        if (ns != cs) finish_set(sets.w[cs]);
+        if (!more) break;
+        __syncthreads();   // every wave has read the tile
+        write_lds();
+        __syncthreads();
+        cs = ns;
+        ct = nt;
+    }
+
+    const int64_t qi = q0 + l31;
+    if (qi < M) {
+        T *op = out + (b * Mp + qi) * ldo + h * D;
+#pragma unroll
+        for (int dv = 0; dv < DV; ++dv)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int d0 = dv * 32 + 8 * g + 4 * hi;
+                if (d0 < D) {   // D % 8 == 0 and d0 % 4 == 0 -> the 4 channels are all valid
+                    elem w4[4];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) w4[e] = (elem)total[dv][g * 4 + e];
+                    *reinterpret_cast<uint2 *>(op + d0) = *reinterpret_cast<uint2 *>(w4);
+                }
+            }
+    }
+}
+
+template <typename T, int D>
+void launch_sets(const Call &c, const Launch &g) {
+    hipLaunchKernelGGL((attention_sets_kernel<T, D>), dim3((unsigned)g.wgs), dim3(sets_waves(D) * 64), 0, c.s, (const T *)c.q,
+                       c.ldq, (const T *)c.k, c.ldk, (const T *)c.vt, c.ldvt, (T *)c.out, c.ldo, c.h, c.M, c.Mp, c.Mkp,
+                       g.scale_log2e, g.nqb, g.xcd_groups, *c.sets);
+}
+
+// The family: one workgroup per (query block, head, sample), never key-split (no partial record, no combine kernel) -- the
+// planner sizes the grid and pins the (sample, head) pairs to XCDs like every other family's.
+template <typename T, int D>
+Family sets_family() {
+    Family f;
+    f.name = "vtm_attention_kv_sets";
+    f.qb = sets_waves(D) * QW;
+    f.wg_per_cu = sets_wg_per_cu(D);
+    f.rec_bytes = 0;
+    f.xcd_min_nqb = 64;
+    f.host_split_all = false;
+    f.main = launch_sets<T, D>;
+    return f;
+}
+
+}  // namespace
+
+VTM_EXPORT int vtm_attention_kv_sets(const void *q, int64_t ldq, const void *k, int64_t ldk, const void *vt, int64_t ldvt,
+                                     void *out, int64_t ldo, int dtype, int64_t B, int64_t h, int64_t Mq, int64_t Mqp,
+                                     int64_t Mkp, int64_t d, float scale, int n_sets, const int64_t *set_start,
+                                     const int64_t *set_len, const float *set_weight, vtm_stream_t stream) {
+    const char *who = "vtm_attention_kv_sets";
+    VTM_REQUIRE(q && k && vt && out && set_start && set_len && set_weight, "%s: null pointer", who);
+    VTM_REQUIRE(n_sets >= 1 && n_sets <= MAX_KEY_SETS, "%s: n_sets must be 1 .. %d, got %d", who, MAX_KEY_SETS, n_sets);
+    VTM_REQUIRE(B > 0 && h > 0 && Mq > 0 && Mqp >= Mq && Mkp > 0 && d > 0, "%s: bad sizes", who);
+    VTM_REQUIRE(scale > 0.0f && std::isfinite(scale), "%s: scale must be positive and finite", who);
+    if (dtype == VTM_F32)
+        return vtm::fail(VTM_EINVAL, "%s: fp32 operands are not taken (dtype must be VTM_F16 or VTM_BF16)", who);
+    if (dtype != VTM_F16 && dtype != VTM_BF16) return vtm::fail(VTM_EINVAL, "%s: dtype must be VTM_F16 or VTM_BF16", who);
+    VTM_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 8 == 0 && ldo % 4 == 0,
+                "%s: leading dimensions must keep 16-byte alignment", who);
+    // K / V^T tiles are addressed with 32-bit byte offsets inside one (sample, head) slice (buffer loads)
+    VTM_REQUIRE((Mkp * ldk + d) * 2 < (1ll << 31) && (d * ldvt + Mkp) * 2 < (1ll << 31),
+                "%s: a (sample, head) slice of K or V^T must stay below 2 GiB", who);
+    KeySets sets;
+    sets.n = n_sets;
+    int64_t keys = 0;
+    for (int s = 0; s < MAX_KEY_SETS; ++s) {
+        sets.start[s] = sets.len[s] = 0;
+        sets.w[s] = 0.0f;
+        if (s >= n_sets) continue;
+        // V^T is fetched in 16-byte pieces of 8 keys: a set starts on one
+        VTM_REQUIRE(set_start[s] >= 0 && set_start[s] % 8 == 0, "%s: start of set %d (%lld) must be a multiple of 8", who, s,
+                    (long long)set_start[s]);
+        VTM_REQUIRE(set_len[s] >= 1 && set_start[s] + set_len[s] <= Mkp && set_start[s] + set_len[s] <= ldvt,
+                    "%s: set %d = keys [%lld, %lld) does not lie inside Mkp = %lld, ldvt = %lld", who, s,
+                    (long long)set_start[s], (long long)(set_start[s] + set_len[s]), (long long)Mkp, (long long)ldvt);
+        VTM_REQUIRE(std::isfinite(set_weight[s]), "%s: weight of set %d is not finite", who, s);
+        sets.start[s] = (int)set_start[s];
+        sets.len[s] = (int)set_len[s];
+        sets.w[s] = set_weight[s];
+        keys += set_len[s];
+    }
+    Call c{q, ldq, k, ldk, vt, ldvt, out, ldo, dtype, B, h, Mq, Mqp, keys, Mkp, scale, 1, nullptr, 0,
+           nullptr, vtm::as_stream(stream), false, nullptr, nullptr, 0};
+    c.sets = &sets;
+    return with_head_dim(d, [&](auto dim) {
+        constexpr int D = decltype(dim)::value;
+        return planned_launch(c, dtype == VTM_F16 ? sets_family<__half, D>() : sets_family<vtm_bf16, D>());
+    });
+}

@@ -33,7 +33,7 @@ from typing import Any, Callable, Dict, Optional, Tuple, Type
 import torch
 import torch.nn.functional as F
 
-from . import _lib, lora, merge
+from . import _lib, ip_adapter, lora, merge
 from .utils import init_generator, isinstance_str, join_frame, split_frame
 
 # Attention over the merged sequence computes outputs only for the rows unmerge() reads (see MergePlan.q_rows);
@@ -460,7 +460,8 @@ def _out_linear(attn: torch.nn.Module):
     return to_out[0] if isinstance(to_out, (torch.nn.ModuleList, torch.nn.Sequential, list, tuple)) else to_out  # pnp_utils.py:41-45
 
 
-def fused_attention_ok(attn: torch.nn.Module, x: torch.Tensor, self_attn: bool = True) -> bool:
+def fused_attention_ok(attn: torch.nn.Module, x: torch.Tensor, self_attn: bool = True,
+                       processors=_PLAIN_PROCESSORS) -> bool:
     """True when `attn(x)` is exactly `to_out[0](softmax(to_q(x) to_k(.)^T * scale) to_v(.))` -- the arithmetic of
     utils/pnp_utils.py:47-95 -- so that the fused path (projection GEMMs + vtm_attention) computes what the module
     would.  Anything else (LoRA / PEFT projections, custom processors or a replaced forward, group / cross norms,
@@ -480,8 +481,8 @@ def fused_attention_ok(attn: torch.nn.Module, x: torch.Tensor, self_attn: bool =
     if getattr(attn, "rescale_output_factor", 1.0) != 1.0 or getattr(attn, "residual_connection", False):
         return False
     proc = getattr(attn, "processor", None)
-    if proc is not None and type(proc).__name__ not in _PLAIN_PROCESSORS:
-        return False
+    if proc is not None and type(proc).__name__ not in processors:
+        return False                              # (``processors``: the IP-Adapter path names its own, ip_cross_call)
     if "forward" in attn.__dict__ and not (self_attn and _pnp_num_inputs(attn) is not None):
         return False                              # replaced forward: only the PnP closure is understood
     to_out = attn.to_out
@@ -811,22 +812,60 @@ def self_attention(attn: torch.nn.Module, x: torch.Tensor, M: Optional[int] = No
     return F.linear(o, wo, bo)
 
 
+def _cross_kv(to_k: torch.nn.Module, to_v: torch.nn.Module, enc: torch.Tensor, C: int, panels: bool = True):
+    """k (B, Mkp, C) and v^T (B, C, Mkp) of conditioning tokens ``enc`` (B, Mkp, D) in the tokens' dtype, Mkp % 8 == 0: panel
+    GEMMs when the width allows (``panels``: the FF_MODE == "panels" path), else library GEMMs."""
+    B, Mkp, D = enc.shape
+    dt = enc.dtype
+    if panels and D % 64 == 0 and lora.base_linear(to_k).weight.dtype == dt and lora.base_linear(to_v).weight.dtype == dt:
+        ep = _lib.to_panels(enc.reshape(B * Mkp, D))                     # the (few) conditioning tokens: 77 per frame in SD
+        wk, bk = _panel_weight(to_k)
+        wv, bv = _panel_weight(to_v)
+        k = _lib.linear_panels(ep, B * Mkp, wk, C, bk).view(B, Mkp, C)
+        vt = _lib.linear_panels(ep, B * Mkp, wv, C, bv).view(B, Mkp, C).transpose(1, 2).contiguous()   # (B, C, Mkp)
+    else:
+        if panels:
+            _warn_once("lib-cross-kv", f"vidtome_amd: attn2's k / v projections run as library GEMMs (conditioning width "
+                                       f"{D} is not a multiple of 64, or to_k / to_v are not of the tokens' dtype)")
+        k = _apply_linear(to_k, enc)
+        vt = _apply_linear(to_v, enc).transpose(1, 2).contiguous()
+    return k, vt
+
+
+def _pad_keys(enc: torch.Tensor, dt) -> torch.Tensor:
+    """Conditioning tokens in the tokens' dtype, zero rows appended up to a multiple of 8."""
+    enc = enc.to(dt)
+    pad = -enc.shape[1] % 8
+    return F.pad(enc, (0, 0, 0, pad)) if pad else enc
+
+
+def _ip_key_sets(attn: torch.nn.Module, ip: "ip_adapter.Call", dt, C: int, panels: bool):
+    """The operands of the IP-Adapter core: text k / v^T as for the plain block, every adapter whose scale is not 0
+    projected the same way with to_k_ip[a] / to_v_ip[a] into its slice of ONE k (B, Mkp, C) and ONE v^T (B, C, Mkp) buffer
+    -> (k, vt, [(start, length, weight)]).  With no adapter taking part k / vt ARE the plain block's tensors."""
+    sets, active, _ = ip_adapter.key_sets(ip.text.shape[1], [im.shape[1] for im in ip.images], ip.scales)
+    k, vt = _cross_kv(attn.to_k, attn.to_v, _pad_keys(ip.text, dt), C, panels)
+    if active:
+        parts = [(k, vt)] + [_cross_kv(ip.k_proj[a], ip.v_proj[a], _pad_keys(ip.images[a], dt), C, panels) for a in active]
+        k = torch.cat([p[0] for p in parts], dim=1)
+        vt = torch.cat([p[1] for p in parts], dim=2)
+    return k, vt, sets
+
+
 def norm_cross_attention_residual(norm: torch.nn.Module, attn: torch.nn.Module, hidden_states: torch.Tensor,
-                                  encoder_hidden_states: torch.Tensor) -> torch.Tensor:
+                                  encoder_hidden_states: torch.Tensor, ip: Optional["ip_adapter.Call"] = None
+                                  ) -> torch.Tensor:
     """patch.py:171-185 for the plain case: ``attn2(norm2(hidden_states), encoder_hidden_states) + hidden_states`` with the
     query projection as a panel GEMM fed by the LayerNorm (vtm_layernorm_panels -> vtm_linear_panels: the normalised
     tokens are only ever read by to_q, so they are written once, as panels), k / v^T of the (few) conditioning tokens by the
     library, the attention core on vtm_attention_kv and the output projection + bias + residual as a panel GEMM too.
-    The caller has checked ``fused_cross_ok``."""
+    The caller has checked ``fused_cross_ok``.
+    With ``ip`` (an IP-Adapter call, ``ip_cross_call``; ``encoder_hidden_states`` is then not read) the core is ONE
+    vtm_attention_kv_sets launch over the text keys and every adapter's image keys (``_ip_key_sets``)."""
     B, N, C = hidden_states.shape
     heads = attn.heads
     scale = getattr(attn, "scale", None) or (C // heads) ** -0.5
     dt = hidden_states.dtype
-    enc = encoder_hidden_states.to(dt)
-    Mk = enc.shape[1]
-    Mkp = (Mk + 7) // 8 * 8
-    if Mkp != Mk:
-        enc = F.pad(enc, (0, 0, 0, Mkp - Mk))
     hs = hidden_states.contiguous()
     n = B * N
     wq, bq = _panel_weight(attn.to_q)
@@ -835,18 +874,13 @@ def norm_cross_attention_residual(norm: torch.nn.Module, attn: torch.nn.Module, 
     q = _lib.linear_panels(xp, n, wq, C, bq).view(B, N, C)
     if N % 8:
         raise RuntimeError("norm_cross_attention_residual: token count must be a multiple of 8")
-    if enc.shape[2] % 64 == 0 and lora.base_linear(attn.to_k).weight.dtype == dt and lora.base_linear(attn.to_v).weight.dtype == dt:
-        ep = _lib.to_panels(enc.reshape(B * Mkp, enc.shape[2]))          # the (few) conditioning tokens: 77 per frame in SD
-        wk, bk = _panel_weight(attn.to_k)
-        wv, bv = _panel_weight(attn.to_v)
-        k = _lib.linear_panels(ep, B * Mkp, wk, C, bk).view(B, Mkp, C)
-        vt = _lib.linear_panels(ep, B * Mkp, wv, C, bv).view(B, Mkp, C).transpose(1, 2).contiguous()   # (B, C, Mkp)
+    if ip is None:
+        Mk = encoder_hidden_states.shape[1]
+        k, vt = _cross_kv(attn.to_k, attn.to_v, _pad_keys(encoder_hidden_states, dt), C)
+        o = _lib.attention_kv(q, k, vt, heads, N, Mk, scale)
     else:
-        _warn_once("lib-cross-kv", f"vidtome_amd: attn2's k / v projections run as library GEMMs (conditioning width "
-                                   f"{enc.shape[2]} is not a multiple of 64, or to_k / to_v are not of the tokens' dtype)")
-        k = _apply_linear(attn.to_k, enc)
-        vt = _apply_linear(attn.to_v, enc).transpose(1, 2).contiguous()
-    o = _lib.attention_kv(q, k, vt, heads, N, Mk, scale)
+        k, vt, sets = _ip_key_sets(attn, ip, dt, C, True)
+        o = _lib.attention_kv_sets(q, k, vt, heads, N, sets, scale)
     op = _lib.to_panels(o.view(n, C))
     return _lib.linear_panels(op, n, wo, C, bo, resid=hs.view(n, C)).view(B, N, C)
 
@@ -858,13 +892,30 @@ def _apply_linear(m: torch.nn.Module, t: torch.Tensor) -> torch.Tensor:
 
 
 def fused_cross_ok(norm: torch.nn.Module, attn: torch.nn.Module, x: torch.Tensor, encoder_hidden_states,
-                   attention_mask, kwargs) -> bool:
-    return (FF_MODE == "panels" and encoder_hidden_states is not None and attention_mask is None and not kwargs
+                   attention_mask, kwargs, processors=_PLAIN_PROCESSORS) -> bool:
+    # (an IP-Adapter block hands a TUPLE as encoder_hidden_states: not a tensor, not this path -- see ip_cross_call)
+    return (FF_MODE == "panels" and isinstance(encoder_hidden_states, torch.Tensor) and attention_mask is None and not kwargs
             and encoder_hidden_states.dim() == 3 and x.dim() == 3 and x.is_cuda and x.dtype in (torch.float16, torch.bfloat16)
             and type(norm) is torch.nn.LayerNorm and len(norm.normalized_shape) == 1
             and norm.normalized_shape[0] == x.shape[-1] and x.shape[-1] % 64 == 0 and x.shape[1] % 8 == 0
             and (norm.weight is None or norm.weight.dtype == x.dtype) and (norm.bias is None or norm.bias.dtype == x.dtype)
-            and _proj_dtypes_ok(attn, x.dtype) and fused_attention_ok(attn, x, self_attn=False))
+            and _proj_dtypes_ok(attn, x.dtype) and fused_attention_ok(attn, x, self_attn=False, processors=processors))
+
+
+def ip_cross_call(attn: torch.nn.Module, x: torch.Tensor, encoder_hidden_states, attention_mask, kwargs,
+                  norm: Optional[torch.nn.Module] = None) -> Optional["ip_adapter.Call"]:
+    """The IP-Adapter call of attn2 when the fused path may take it, else None (the module path): the processor and the
+    call are what `ip_adapter.recognise` understands, and the module is everything ``fused_attention_ok`` asks of attn2
+    apart from the processor's name.  With ``norm`` (norm2): for the panel path of ``norm_cross_attention_residual`` --
+    what ``fused_cross_ok`` asks, on the text tokens; without: for ``cross_attention``'s library GEMMs around the core."""
+    if not ip_adapter.is_ip_processor(attn):
+        return None
+    ip = ip_adapter.recognise(attn, x, encoder_hidden_states, attention_mask, kwargs)
+    if ip is None:
+        return None
+    if norm is not None:
+        return ip if fused_cross_ok(norm, attn, x, ip.text, None, None, ip_adapter.PROCESSORS) else None
+    return ip if fused_attention_ok(attn, x, self_attn=False, processors=ip_adapter.PROCESSORS) else None
 
 
 def _f32_layernorm_ok(norm: torch.nn.Module, x: torch.Tensor) -> bool:
@@ -878,8 +929,8 @@ def _f32_layernorm_ok(norm: torch.nn.Module, x: torch.Tensor) -> bool:
 def f32_cross_ok(block: torch.nn.Module, norm: torch.nn.Module, attn: torch.nn.Module, x: torch.Tensor,
                  encoder_hidden_states, attention_mask, kwargs) -> bool:
     """attn2 of an fp32 block with the ``fp32_projections`` opt-in on the fp32 GEMMs (norm_cross_attention_f32)."""
-    return (_fp32_projections(block) and encoder_hidden_states is not None and attention_mask is None and not kwargs
-            and encoder_hidden_states.dim() == 3 and x.dim() == 3 and x.is_cuda and x.dtype == torch.float32
+    return (_fp32_projections(block) and isinstance(encoder_hidden_states, torch.Tensor) and attention_mask is None
+            and not kwargs and encoder_hidden_states.dim() == 3 and x.dim() == 3 and x.is_cuda and x.dtype == torch.float32
             and encoder_hidden_states.shape[0] == x.shape[0] and encoder_hidden_states.shape[-1] % 8 == 0
             and _f32_layernorm_ok(norm, x) and _proj_dtypes_ok(attn, torch.float32)
             and fused_attention_ok(attn, x, self_attn=False))
@@ -913,12 +964,21 @@ def cross_attention(attn: torch.nn.Module, x: torch.Tensor, encoder_hidden_state
                     attention_mask=None, **kwargs) -> torch.Tensor:
     """`self.attn2(norm_hidden_states, encoder_hidden_states=..., attention_mask=...)` (patch.py:178-183) -- the
     un-merged tokens attending to the conditioning (77 text tokens in SD).  The plain case (projection Linears, no
-    mask, no processor kwargs) runs on vtm_attention_kv; everything else is the module's own forward."""
-    plain = (encoder_hidden_states is not None and attention_mask is None and not kwargs
+    mask, no processor kwargs) runs on vtm_attention_kv, a recognised IP-Adapter call (``ip_cross_call``) on
+    vtm_attention_kv_sets, with library GEMMs around the core; everything else is the module's own forward."""
+    plain = (isinstance(encoder_hidden_states, torch.Tensor) and attention_mask is None and not kwargs
              and encoder_hidden_states.dim() == 3 and x.dtype in (torch.float16, torch.bfloat16)
              and fused_attention_ok(attn, x, self_attn=False))
     if not plain:
-        return attn(x, encoder_hidden_states=encoder_hidden_states, attention_mask=attention_mask, **kwargs)
+        ip = ip_cross_call(attn, x, encoder_hidden_states, attention_mask, kwargs)
+        if ip is None:
+            return attn(x, encoder_hidden_states=encoder_hidden_states, attention_mask=attention_mask, **kwargs)
+        B, N, C = x.shape
+        scale = getattr(attn, "scale", None) or (C // attn.heads) ** -0.5
+        xq = F.pad(x, (0, 0, 0, -N % 8)) if N % 8 else x
+        k, vt, sets = _ip_key_sets(attn, ip, x.dtype, C, False)
+        o = _lib.attention_kv_sets(_apply_linear(attn.to_q, xq), k, vt, attn.heads, N, sets, scale)
+        return _apply_linear(_out_linear(attn), o)[:, :N]
     B, N, C = x.shape
     enc = encoder_hidden_states.to(x.dtype)
     Mk = enc.shape[1]
@@ -1164,9 +1224,14 @@ def make_diffusers_tome_block(block_class: Type[torch.nn.Module]) -> Type[torch.
 
             cross_attention_kwargs = cross_attention_kwargs if cross_attention_kwargs is not None else {}
             if self.attn2 is not None:                                             # patch.py:171-185
-                if not self.use_ada_layer_norm and fused_cross_ok(self.norm2, self.attn2, hidden_states,
-                                                                  encoder_hidden_states, encoder_attention_mask,
-                                                                  cross_attention_kwargs):
+                ip = None if self.use_ada_layer_norm else ip_cross_call(
+                    self.attn2, hidden_states, encoder_hidden_states, encoder_attention_mask, cross_attention_kwargs,
+                    self.norm2)
+                if ip is not None:                                                 # IP-Adapter: text + image key sets
+                    hidden_states = norm_cross_attention_residual(self.norm2, self.attn2, hidden_states, None, ip)
+                elif not self.use_ada_layer_norm and fused_cross_ok(self.norm2, self.attn2, hidden_states,
+                                                                    encoder_hidden_states, encoder_attention_mask,
+                                                                    cross_attention_kwargs):
                     hidden_states = norm_cross_attention_residual(self.norm2, self.attn2, hidden_states,
                                                                   encoder_hidden_states)
                 elif not self.use_ada_layer_norm and f32_cross_ok(self, self.norm2, self.attn2, hidden_states,
@@ -1316,6 +1381,8 @@ def remove_patch(model: torch.nn.Module):
             module.__dict__.pop("_vtm_packed", None)
             module.__dict__.pop("_vtm_wcache", None)
             module.__dict__.pop("_vtm_lora", None)             # folded LoRA weights (lora.linear_params)
+            if hasattr(module, "processor"):                   # ... and the same on an IP-Adapter processor's projections
+                ip_adapter.drop_caches(module)
             module.__dict__.pop("_vtm_match_plans", None)      # the matcher's launch planners (pinned 32-byte buffers)
             module.__dict__.pop("fp32_attention", None)        # update_patch's opt-in: a later apply_patch starts without it
             module.__dict__.pop("fp32_projections", None)      # (likewise)
