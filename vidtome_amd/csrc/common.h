@@ -36,6 +36,19 @@ template <> __device__ __forceinline__ float to_f32<float>(float v) { return v; 
 template <> __device__ __forceinline__ float to_f32<__half>(__half v) { return __half2float(v); }
 template <> __device__ __forceinline__ float to_f32<vtm_bf16>(vtm_bf16 v) { return __bfloat162float(v); }
 
+// Calls fn(T{}) with a value-initialised element of the model dtype (float, __half, vtm_bf16): the body takes its `auto`
+// parameter's type as T and writes a kernel's argument list ONCE for the three instantiations.  For any other dtype the
+// call fails (VTM_EINVAL, "<what>: unsupported dtype").  (attention_plan.h's with_head_dim is the same idea for head dims.)
+template <typename Fn>
+int with_dtype(int dtype, const char *what, Fn &&fn) {
+    switch (dtype) {
+        case VTM_F32: return fn(float{});
+        case VTM_F16: return fn(__half{});
+        case VTM_BF16: return fn(vtm_bf16{});
+    }
+    return fail(VTM_EINVAL, "%s: unsupported dtype %d", what, dtype);
+}
+
 // compute units of the CURRENT device (256 on MI355X; 8 XCDs of 32), cached per device ordinal: a process may
 // drive several devices (one stream each), and a planner called for device 1 must not see device 0's answer
 constexpr int MAX_DEVICES = 64;

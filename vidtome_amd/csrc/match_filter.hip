@@ -28,8 +28,7 @@
 // flood the filter with candidate pushes either.
 #include "common.h"
 #include "ablate.h"
-
-#include <cstdlib>
+#include "match_plan.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -38,11 +37,10 @@ namespace {
 
 // (The ABL_* macros in filter_kernel are the ablation switches of ablate.h: in the shipped build each expands to the code
 // it wraps and nothing else.)
-constexpr int FBD = 128;      // dst rows per tile (MFMA A operand, LDS)
-constexpr int FBS = 256;      // src rows per workgroup (B operand, registers), 64 per wave
-constexpr int FBK = 64;       // channels per pipeline step = 4 MFMA k-steps = 8 panels
+// (the tile constants FBD / FBS / FBK / CAP / XS / XD / XK, the workspace layout and the launch plan: match_plan.h)
+using namespace vtm_match_plan;
+static_assert(MODE_SCOUT_RANGE == VTM_MATCH_SCOUT_RANGE, "match_plan.h restates the public mode value");
 constexpr int THREADS = 256;
-constexpr int CAP = 64;       // candidate slots per src row
 // Survivors (candidates inside the window of the row's FINAL approximate maximum) go to the per-pair refine pass however
 // many a row has (<= CAP): the anchor tokens of a global level hold exact copies of matched rows (patch.py:80), so a
 // src row whose best dst row exists m times has m tied survivors -- m ~ 10 after one local-is-src pass -- and the exact
@@ -50,13 +48,8 @@ constexpr int CAP = 64;       // candidate slots per src row
 // (every list full), so its reservation cannot fail.
 constexpr float SCALE = 1024.0f;
 constexpr float INV_S2 = 1.0f / (1024.0f * 1024.0f);
-// Which products the filter accumulates (the refine pass is exact whatever the filter does; fewer products = less
-// MFMA work and operand traffic, wider window = more candidates for the refine pass):
-//   SRC_LO && DST_LO : 3 products  hi*hi + hi*lo + lo*hi
-//   DST_LO only      : 2 products  (hi_dst + lo_dst) * hi_src
-//   neither          : 1 product   hi_dst * hi_src                                  <- shipped
-// Error budget per score for unit vectors (sum |a_k b_k| <= 1), C <= 1280, fp16 unit roundoff u = 2^-11
-// (|lo| <= u |1024 xhat| element-wise):
+// Error budget of the filter's products (SRC_LO / DST_LO: match_plan.h) per score for unit vectors (sum |a_k b_k| <= 1),
+// C <= 1280, fp16 unit roundoff u = 2^-11 (|lo| <= u |1024 xhat| element-wise):
 //   each dropped lo operand                <= u * sum |a_k b_k|               = 4.9e-4   (both: 2u + u^2 = 9.8e-4)
 //   hi/lo representation tails             <= 3 * 2^-22                       = 7e-7
 //   reciprocal-multiply operands (1 product) <= 2 * 2.4e-7                      = 5e-7
@@ -64,12 +57,6 @@ constexpr float INV_S2 = 1.0f / (1024.0f * 1024.0f);
 //   the canonical fp32 chain itself        <= C * 2^-24                       = 7.6e-5
 // EPS = 3.25e-4 (3 products) / 7.5e-4 (2) / 1.2e-3 (1); observed filter errors are ~1e-6 / ~1e-5 / ~2e-5.
 // Measured on the cfg-2 shapes: the wider window adds < 10 % surviving pairs (the refine pass is ~3 % of the call).
-#ifndef VTM_FILTER_PRODUCTS
-#define VTM_FILTER_PRODUCTS 1   // build-time choice (1, 2 or 3); the shipped library uses 1
-#endif
-constexpr bool SRC_LO = VTM_FILTER_PRODUCTS >= 3;
-constexpr bool DST_LO = VTM_FILTER_PRODUCTS >= 2;
-static_assert(DST_LO || !SRC_LO, "the src lo half is only used together with the dst lo half");
 constexpr float WINDOW = SRC_LO ? 6.5e-4f : DST_LO ? 1.5e-3f : 2.4e-3f;   // 2 * EPS
 constexpr int MAX_C = 1280;                              // the budget above is derived for C <= 1280
 
@@ -179,10 +166,6 @@ struct SplitArgs {   // one operand: gathered rows, their norms (out), the panel
 #ifndef VTM_PREP_PIECES
 #define VTM_PREP_PIECES 10      // (A/B build switches; 4 odd multiples keep the LDS rows conflict-free: 2, 6, 10, 14 ...)
 #endif
-#ifndef VTM_PREP_WAVES
-#define VTM_PREP_WAVES 4
-#endif
-constexpr int PREP_WAVES = VTM_PREP_WAVES;
 constexpr int PREP_PIECES = VTM_PREP_PIECES;           // 16-byte pieces (8 channels) of a row per chunk
 constexpr int PREP_STRIDE = PREP_PIECES * 16 + 16;     // bytes per LDS row: 44 words = 4 x odd -> conflict-free b128
 
@@ -980,10 +963,6 @@ __global__ __launch_bounds__(256) void seed_kernel(const T *__restrict__ x0, int
 //   2 (4 C + 32) 2^-24 -- and ran the canonical chain only on the pairs within that window of the row's best was written
 //   twice, exact both times, and SLOWER both times: top global level, 16 pairs per row, 1.51 vs 1.35 ms per call; it adds a
 //   pass over the same rows, and the chain pass is not limited by its instruction count.  profiles/r05_d_refine_ab.txt.)
-#ifndef VTM_RROWS
-#define VTM_RROWS 64        // (A/B build switch: 256 = rounds 1-4)
-#endif
-constexpr int RROWS = VTM_RROWS;   // rows per refine workgroup (256 threads)
 static_assert(RROWS == 32 || RROWS == 64 || RROWS == 128 || RROWS == 256, "refine rows per workgroup");
 template <typename T>
 __global__ __launch_bounds__(256) void refine_kernel(const T *__restrict__ x0, int64_t P0, const T *__restrict__ x1,
@@ -1155,12 +1134,6 @@ __global__ __launch_bounds__(256) void refine_kernel(const T *__restrict__ x0, i
 // dst operand is normalised once per 128 listed rows (the scalar row pass this replaces normalised it once per ROW).
 // Work items = (list, XS-row tile of the list, sample [aligned: every sample's dst set], dst split); the counts live on
 // the device, so a fixed grid strides over the items and leaves at once when there are none.
-#ifndef VTM_XS
-#define VTM_XS 128          // (A/B build switch: 256 = 64 src rows per wave, one workgroup per CU: profiles/r04_escape_tile.txt)
-#endif
-constexpr int XS = VTM_XS;   // listed src rows per workgroup: 32 (or two 32-row MFMA blocks) per wave
-constexpr int XD = 128;   // dst rows per tile
-constexpr int XK = 32;    // channels per step
 constexpr int XPD = XD + 1, XPS = XS + 1;   // rows per LDS panel (+1: the 4 pieces of a row land in different bank groups)
 constexpr int XSB = XS / 128;                // 32-row src blocks per wave
 constexpr int XSU = XS / 64;                 // src rows a thread stages per step
@@ -1449,71 +1422,38 @@ __global__ __launch_bounds__(256, XS == 128 ? 2 : 1) void exact_rows_kernel(
     }
 }
 
-inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
+// The arrays of one call, carved out of the caller's workspace by Layout.
+struct Workspace {
+    float *na, *nb;                       // canonical norms
+    uint4 *ah, *al, *bh, *bl;             // fp16 panels (hi / lo) of the src / dst operand
+    unsigned int *amax, *seedlb, *tilemap;
+    int *cnt, *flags, *ovf_rows, *ovf_cnt;
+    uint2 *cand, *pairs;
+    // rest norms of the filter's cut (per src row / per dst tile; the per-tile values are written for every call:
+    // refine_kernel reads the "row without a usable norm" mark from them) and of the shallow scout's cut
+    float *rest_a, *rest_bt, *rest_a2, *rest_bt2;
+    int64_t zero_words;                   // prep_operand clears amax .. cand: amax, cnt, seedlb, tilemap, flags, ovf_cnt
 
-struct Layout {
-    size_t na, nb, ah, al, bh, bl, amax, cnt, seedlb, tilemap, cand, flags, ovf_cnt, ovf, pairs, rest_a, rest_bt, rest_a2, rest_bt2, total;
-    int64_t Ns_pad, Nd_pad, C64;
+    Workspace(void *ws, const Layout &L) : zero_words((int64_t)((L.cand - L.amax) / 4)) {
+        auto at = [ws](auto *&p, size_t off) { p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(static_cast<char *>(ws) + off); };
+        at(na, L.na), at(nb, L.nb), at(ah, L.ah), at(al, L.al), at(bh, L.bh), at(bl, L.bl), at(amax, L.amax), at(seedlb, L.seedlb);
+        at(tilemap, L.tilemap), at(cnt, L.cnt), at(flags, L.flags), at(ovf_rows, L.ovf), at(ovf_cnt, L.ovf_cnt), at(cand, L.cand);
+        at(pairs, L.pairs), at(rest_a, L.rest_a), at(rest_bt, L.rest_bt), at(rest_a2, L.rest_a2), at(rest_bt2, L.rest_bt2);
+    }
 };
 
-Layout make_layout(int64_t B, int64_t C, int64_t Ns, int64_t Nd, int align) {
-    Layout L;
-    L.Ns_pad = vtm::cdiv(Ns, FBS) * FBS;
-    L.Nd_pad = vtm::cdiv(Nd, FBS) * FBS;
-    L.C64 = vtm::cdiv(C, 64) * 64;
-    const int64_t rows_out = align ? Ns : B * Ns;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o += align_up(bytes); return at; };
-    L.na = take((size_t)B * Ns * 4);
-    L.nb = take((size_t)B * Nd * 4);
-    L.ah = take((size_t)B * L.C64 * L.Ns_pad * 2);
-    L.al = take(SRC_LO ? (size_t)B * L.C64 * L.Ns_pad * 2 : 0);
-    L.bh = take((size_t)B * L.C64 * L.Nd_pad * 2);
-    L.bl = take(DST_LO ? (size_t)B * L.C64 * L.Nd_pad * 2 : 0);
-    L.amax = take((size_t)rows_out * 4);      // amax, cnt and flags are contiguous: cleared together
-    L.cnt = take((size_t)rows_out * 4);
-    L.seedlb = take((size_t)rows_out * 4);    // certified lower bounds of the rows' exact maxima (seed_kernel -> exact_rows_kernel)
-    // the scout's map of live (src tile, dst tile) pairs: one bit per dst tile (inside the cleared range)
-    L.tilemap = take((size_t)B * (L.Ns_pad / FBS) * ((L.Nd_pad / FBD + 31) / 32) * 4);
-    L.flags = take(256);
-    L.ovf_cnt = take((size_t)B * 4);          // per-sample overflow-list lengths (inside the cleared range)
-    L.cand = take((size_t)rows_out * CAP * 8);
-    L.ovf = take((size_t)rows_out * 4);
-    L.pairs = take((size_t)rows_out * CAP * 8);
-    L.rest_a = take((size_t)B * L.Ns_pad * 4);
-    L.rest_bt = take((size_t)B * (L.Nd_pad / FBD) * 4);
-    L.rest_a2 = take((size_t)B * L.Ns_pad * 4);              // ... for the shallow scout's cut
-    L.rest_bt2 = take((size_t)B * (L.Nd_pad / FBD) * 4);
-    L.total = o;
-    return L;
+// Where exact_rows_kernel may publish the call's counters itself: `flags_out` when it is memory a kernel can store to
+// (device, or host memory the runtime has pinned / registered -- then its device alias); nullptr for pageable host memory
+// (the counters are copied behind the call instead) and when no counters are wanted.
+int32_t *kernel_writable(int32_t *flags_out) {
+    if (!flags_out) return nullptr;
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, flags_out) == hipSuccess &&
+        (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeHost || attr.type == hipMemoryTypeManaged))
+        return attr.type == hipMemoryTypeHost && attr.devicePointer ? (int32_t *)attr.devicePointer : flags_out;
+    (void)hipGetLastError();          // (an unregistered pointer is an "error" of the query, not of the call)
+    return nullptr;
 }
-
-// Tuning / A-B hooks of the host side, read from the environment ONCE per process (they were getenv calls on
-// every matcher call).  Every one of them is result-preserving: they move launch shapes and pruning depths, never what
-// `best` holds.  (A hook that changes results belongs behind a VTM_EXP_* build switch of ablate.h, where it sets a bit of
-// VTM_ABLATIONS and the Python binding refuses to load the library.)
-struct DebugEnv {
-    int kp5, kp, nsplit;              // -1 = unset
-    bool seed_dry, nsplit_r4, no_xprune;
-};
-const DebugEnv &debug_env() {
-    static const DebugEnv e = [] {
-        auto num = [](const char *name) {
-            const char *v = getenv(name);
-            return v ? atoi(v) : -1;
-        };
-        DebugEnv d;
-        d.kp5 = num("VTM_DEBUG_KP5");
-        d.kp = num("VTM_DEBUG_KP");
-        d.nsplit = num("VTM_DEBUG_NSPLIT");
-        d.seed_dry = getenv("VTM_DEBUG_SEED_DRY") != nullptr;
-        d.nsplit_r4 = getenv("VTM_DEBUG_NSPLIT_R4") != nullptr;
-        d.no_xprune = getenv("VTM_DEBUG_NOXPRUNE") != nullptr;
-        return d;
-    }();
-    return e;
-}
-
 }  // namespace
 
 VTM_EXPORT size_t vtm_match_filtered_ws_bytes(int64_t B, int64_t C, int64_t Ns, int64_t Nd, int align) {
@@ -1521,11 +1461,13 @@ VTM_EXPORT size_t vtm_match_filtered_ws_bytes(int64_t B, int64_t C, int64_t Ns, 
     return make_layout(B, C, Ns, Nd, align).total;
 }
 
+// validate -> plan (match_plan.h: pure host arithmetic, pinned by tests/test_match_plan_host.py) -> launch from the plan
 static int match_filtered_impl(const void *x0, int64_t P0, const void *x1, int64_t P1, int dtype, int64_t B,
                                int64_t C, const int32_t *a_rows, int64_t Ns, const int32_t *b_rows, int64_t Nd,
                                int align, void *ws, size_t ws_bytes, uint64_t *best, int32_t *flags_out,
                                int64_t seed_L, int64_t seed_N, const int32_t *seed_pos1, const int32_t *seed_table,
                                int mode, const int32_t *src_order, const int32_t *dst_order, vtm_stream_t stream) {
+    const char *what = "vtm_match_filtered";
     VTM_REQUIRE(x0 && a_rows && b_rows && ws && best, "vtm_match_filtered: null pointer");
     const int scout_steps = (mode >> 8) & 0xff;      // VTM_MATCH_SCOUT_STEPS(k): the scout tests after k pipeline steps
     mode &= 0xff;
@@ -1539,231 +1481,75 @@ static int match_filtered_impl(const void *x0, int64_t P0, const void *x1, int64
     const Layout L = make_layout(B, C, Ns, Nd, align);
     if (ws_bytes < L.total)
         return vtm::fail(VTM_EWORKSPACE, "vtm_match_filtered: workspace %zu < %zu bytes", ws_bytes, L.total);
-    hipStream_t s = vtm::as_stream(stream);
-    char *w = static_cast<char *>(ws);
-    float *na = (float *)(w + L.na), *nb = (float *)(w + L.nb);
-    uint4 *ah = (uint4 *)(w + L.ah), *al = (uint4 *)(w + L.al), *bh = (uint4 *)(w + L.bh), *bl = (uint4 *)(w + L.bl);
-    unsigned int *amax = (unsigned int *)(w + L.amax);
-    int *cnt = (int *)(w + L.cnt), *flags = (int *)(w + L.flags);
-    uint2 *cand = (uint2 *)(w + L.cand);
-    int *ovf_rows = (int *)(w + L.ovf), *ovf_cnt = (int *)(w + L.ovf_cnt);
-    uint2 *pairs = (uint2 *)(w + L.pairs);
     const int64_t rows_out = align ? Ns : B * Ns;
     VTM_REQUIRE(rows_out * CAP < (1ll << 31), "vtm_match_filtered: too many rows for the 32-bit candidate index");
-
     VTM_REQUIRE(dtype == VTM_F32 || dtype == VTM_F16 || dtype == VTM_BF16, "vtm_match_filtered: bad dtype");
-    // partial-sum pruning: check after KP of the KT channel steps; off for short rows and for the 2- / 3-product
-    // builds (their lo products are not covered by the hi rest norms)
-    const int KT = (int)(L.C64 / FBK);
-    int KP = (VTM_FILTER_PRODUCTS == 1 && KT >= 4) ? (2 * KT + 2) / 5 : 0;   // 40 % depth (profiles/r04_kp_sweep.txt)
+
     const DebugEnv &dbg = debug_env();   // tuning / A-B hooks, read ONCE per process (all of them leave the results unchanged)
-    if (VTM_FILTER_PRODUCTS == 1 && KT == 5 && dbg.kp5 >= 0 && dbg.kp5 < KT) KP = dbg.kp5;   // the C = 320 levels alone (KT = 5)
-    if (VTM_FILTER_PRODUCTS == 1 && dbg.kp >= 0 && dbg.kp < KT) KP = dbg.kp;                 // 0 = off, else the step after which blocks are tested
-    const bool prune = KP > 0 && KP < KT;
-    // (the per-tile values are written for every call: refine_kernel reads the "row without a usable norm" mark from them)
-    float *rest_a = (float *)(w + L.rest_a), *rest_bt = (float *)(w + L.rest_bt);
-    const int64_t cut = prune ? (int64_t)KP * FBK : L.C64;
-    // the scout of the scout + range plan may test EARLIER than the filter proper (its own rest norms): a low-noise clip's
-    // dead tiles are dead after one step already, and the scout's cost is its steps
-    const int KPS = (prune && mode == VTM_MATCH_SCOUT_RANGE && scout_steps > 0 && scout_steps < KP) ? scout_steps : KP;
-    float *rest_a2 = (float *)(w + L.rest_a2), *rest_bt2 = (float *)(w + L.rest_bt2);
-    const int64_t cut2 = KPS < KP ? (int64_t)KPS * FBK : cut;
-    {
-        // one launch: canonical norms + fp16 panels of both operands; it also clears amax / cnt / flags (contiguous)
-        // and zero-fills `best`
-        const SplitArgs A0{a_rows, Ns, na, ah, SRC_LO ? al : nullptr, L.Ns_pad, rest_a, nullptr, KPS < KP ? rest_a2 : nullptr, nullptr};
-        const SplitArgs A1{b_rows, Nd, nb, bh, DST_LO ? bl : nullptr, L.Nd_pad, nullptr, rest_bt, nullptr, KPS < KP ? rest_bt2 : nullptr};
-        const int64_t total = B * (L.Ns_pad + L.Nd_pad);
-        unsigned long long *bp0 = reinterpret_cast<unsigned long long *>(best);
-        uint32_t *zp = reinterpret_cast<uint32_t *>(w + L.amax);
-        const int64_t zw = (int64_t)((L.cand - L.amax) / 4);
-        const dim3 grid((unsigned)vtm::cdiv(total, 64 * PREP_WAVES)), block(64 * PREP_WAVES);
-        switch (dtype) {
-            case VTM_F32:
-                hipLaunchKernelGGL(prep_operand<float>, grid, block, 0, s, (const float *)x0, P0, (const float *)x1, P1,
-                                   B, C, A0, A1, L.C64, zp, zw, bp0, rows_out, cut, cut2);
-                break;
-            case VTM_F16:
-                hipLaunchKernelGGL(prep_operand<__half>, grid, block, 0, s, (const __half *)x0, P0, (const __half *)x1,
-                                   P1, B, C, A0, A1, L.C64, zp, zw, bp0, rows_out, cut, cut2);
-                break;
-            default:
-                hipLaunchKernelGGL(prep_operand<vtm_bf16>, grid, block, 0, s, (const vtm_bf16 *)x0, P0,
-                                   (const vtm_bf16 *)x1, P1, B, C, A0, A1, L.C64, zp, zw, bp0, rows_out, cut, cut2);
-        }
+    const FilterPlan P = plan_filter(L, B, C, Ns, Nd, align, mode, scout_steps, seed_N, src_order != nullptr, vtm::device_cus(), dbg);
+    const Workspace W(ws, L);
+    hipStream_t s = vtm::as_stream(stream);
+    unsigned long long *bp = reinterpret_cast<unsigned long long *>(best);
+    const dim3 block(256);
+    const bool shallow = P.KPS < P.KP;   // the scout tests earlier than the filter proper, against rest norms of its own
+
+    // one launch: canonical norms + fp16 panels of both operands; it also clears amax / cnt / flags (contiguous)
+    // and zero-fills `best`
+    vtm::with_dtype(dtype, what, [&](auto t) {
+        using T = decltype(t);
+        const SplitArgs A0{a_rows, Ns, W.na, W.ah, SRC_LO ? W.al : nullptr, L.Ns_pad, W.rest_a, nullptr, shallow ? W.rest_a2 : nullptr, nullptr};
+        const SplitArgs A1{b_rows, Nd, W.nb, W.bh, DST_LO ? W.bl : nullptr, L.Nd_pad, nullptr, W.rest_bt, nullptr, shallow ? W.rest_bt2 : nullptr};
+        hipLaunchKernelGGL(prep_operand<T>, dim3(P.prep_grid), dim3(64 * PREP_WAVES), 0, s, (const T *)x0, P0, (const T *)x1, P1,
+                           B, C, A0, A1, L.C64, W.amax, W.zero_words, bp, rows_out, P.cut, P.cut2);
+        return VTM_OK;
+    });
+    if (P.seed_grid)   // starting maxima from same-position guesses (a kernel boundary behind prep_operand: norms, cleared amax)
+        vtm::with_dtype(dtype, what, [&](auto t) {
+            using T = decltype(t);
+            const int dry = dbg.seed_dry;   // A/B hook: the seeds are computed and thrown away
+            const float lb_margin = (4.0f * (float)C + 32.0f) * 0x1p-24f + 1e-6f;   // see seed_kernel
+            hipLaunchKernelGGL(seed_kernel<T>, dim3(P.seed_grid), block, 0, s, (const T *)x0, P0, (const T *)x1, P1, B, C, a_rows,
+                               Ns, b_rows, Nd, (const float *)W.na, (const float *)W.nb, align, seed_L, seed_N, seed_pos1, seed_table,
+                               W.amax, dry, W.seedlb, lb_margin);
+            return VTM_OK;
+        });
+
+    // the filter: one launch over the plan's dst splits, or (scout + range plan, see filter_kernel) a scout that marks the
+    // live (src tile, dst tile) pairs and a second launch, one split per dst frame / span, over the marked tiles only
+    auto filter = [&](auto kernel, int64_t grid, int nsplit, int tps, const float *rest_a, const float *rest_bt, int kp,
+                      unsigned int *tilemap) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(THREADS), 0, s, W.ah, W.al, W.bh, W.bl, Ns, Nd, L.Ns_pad, L.Nd_pad,
+                           L.C64, align, P.ns_tiles, P.nd_tiles, nsplit, tps, P.total_src_tiles, P.patch_tiles, W.amax, W.cnt, W.cand,
+                           (int)rows_out, W.flags, rest_a, rest_bt, kp, flags_out != nullptr ? 1 : 0, tilemap, P.map_words);
+    };
+    if (P.range_plan) {
+        filter(filter_kernel<true>, P.grid, P.nsplit, P.tiles_per_split, shallow ? W.rest_a2 : W.rest_a,
+               shallow ? W.rest_bt2 : W.rest_bt, P.KPS, W.tilemap);
+        filter(filter_kernel<false>, P.grid_r, P.nsplit_r, P.tps_r, W.rest_a, W.rest_bt, P.KP, W.tilemap);
+    } else {
+        filter(filter_kernel<false>, P.grid, P.nsplit, P.tiles_per_split, P.prune ? W.rest_a : nullptr,
+               P.prune ? W.rest_bt : nullptr, P.prune ? P.KP : 0x7fffffff, nullptr);
     }
 
-    if (seed_N > 0) {   // starting maxima from same-position guesses (a kernel boundary behind prep_operand: norms, cleared amax)
-        const int dry = dbg.seed_dry;   // A/B hook: the seeds are computed and thrown away
-        unsigned int *seedlb = (unsigned int *)(w + L.seedlb);
-        const float lb_margin = (4.0f * (float)C + 32.0f) * 0x1p-24f + 1e-6f;   // see seed_kernel
-        const dim3 grid((unsigned)vtm::cdiv(B * Ns * 8, 256)), block(256);
-        switch (dtype) {
-            case VTM_F32:
-                hipLaunchKernelGGL(seed_kernel<float>, grid, block, 0, s, (const float *)x0, P0, (const float *)x1, P1, B, C, a_rows,
-                                   Ns, b_rows, Nd, (const float *)na, (const float *)nb, align, seed_L, seed_N, seed_pos1, seed_table, amax, dry, seedlb, lb_margin);
-                break;
-            case VTM_F16:
-                hipLaunchKernelGGL(seed_kernel<__half>, grid, block, 0, s, (const __half *)x0, P0, (const __half *)x1, P1, B, C,
-                                   a_rows, Ns, b_rows, Nd, (const float *)na, (const float *)nb, align, seed_L, seed_N, seed_pos1, seed_table, amax, dry, seedlb, lb_margin);
-                break;
-            default:
-                hipLaunchKernelGGL(seed_kernel<vtm_bf16>, grid, block, 0, s, (const vtm_bf16 *)x0, P0, (const vtm_bf16 *)x1, P1, B,
-                                   C, a_rows, Ns, b_rows, Nd, (const float *)na, (const float *)nb, align, seed_L, seed_N, seed_pos1, seed_table, amax, dry, seedlb, lb_margin);
-        }
-    }
-    {
-        const int ns_tiles = (int)(L.Ns_pad / FBS), nd_tiles = (int)(L.Nd_pad / FBD);
-        const int total_src_tiles = (int)(B * ns_tiles);
-        // patch size: at most 16 src tiles while their (hi) operands fit comfortably in one L2 (16 x 256 rows x C x
-        // 2 B <= 3 MiB), else 8 -- and balanced: patch g runs on XCD g % 8, so the tiles are cut into equal patches
-        // whose number per XCD is the same for all XCDs (17 patches of 16 tiles would keep one XCD busy for three
-        // patches while the other seven idle after two)
-        const int max_patch = (int64_t)16 * FBS * L.C64 * 2 <= (3 << 20) ? 16 : 8;
-        const int tiles_per_xcd = (int)vtm::cdiv(total_src_tiles, 8);
-        const int patches_per_xcd = (int)vtm::cdiv(tiles_per_xcd, max_patch);
-        const int patch_tiles = (int)vtm::cdiv(tiles_per_xcd, patches_per_xcd);
-        const int ngroups = (int)vtm::cdiv(total_src_tiles, patch_tiles);
-        // workgroups one XCD has to run (2 per CU at a time) for a split count
-        auto wgs_per_xcd = [&](int ns) {
-            const int tps = (int)vtm::cdiv(nd_tiles, ns);
-            return patches_per_xcd * patch_tiles * (int)vtm::cdiv(nd_tiles, tps);
-        };
-        int nsplit;
-        if (dbg.nsplit_r4) {
-            // rounds 1-4: enough workgroups to fill the chip, >= 4 dst tiles each, at most 8 (every split contributes >= 1
-            // candidate per row), 8 whenever the dst axis is long enough, 7 or 6 when that saves a round (A/B hook)
-            int64_t want = vtm::cdiv(1536, (int64_t)ns_tiles * B);
-            nsplit = (int)(want < 1 ? 1 : want);
-            if (nd_tiles >= 32) nsplit = 8;
-            if (nsplit > nd_tiles / 4) nsplit = nd_tiles / 4 > 0 ? nd_tiles / 4 : 1;
-            if (nsplit > 8) nsplit = 8;
-            if (nsplit == 8) {
-                const int slots = vtm::device_cus() / 8 * 2;
-                for (int ns = 7; ns >= 6; --ns)
-                    if (wgs_per_xcd(8) > slots && wgs_per_xcd(ns) <= slots) {
-                        nsplit = ns;
-                        break;
-                    }
-            }
-        } else {
-            // Round 5: the split count that minimises  rounds x (tiles per split + 1.5) + 0.25 splits  -- an XCD runs its
-            // workgroups in rounds of its CUs x 2, a
-            // workgroup costs its dst tiles plus ~1.5 tiles of prologue / flush, and every split adds candidates to the rows'
-            // lists.  Reproduces the best of tools/sweep_nsplit.py's 2..14 sweep on all six cfg-2 shapes
-            // (profiles/r05_h_sweeps.txt): level 2 takes 5 splits instead of 8 (768 workgroups = 1.5 rounds -> 480 = one round:
-            // -6 %), the mid levels 5 / 14 instead of 8 (-7 % / -10 %), the top global level 7.
-            const int slots = vtm::device_cus() / 8 * 2;
-            double best_cost = 1e30;
-            nsplit = 1;
-            for (int ns = 1; ns <= 16 && ns <= nd_tiles; ++ns) {
-                const int tps = (int)vtm::cdiv(nd_tiles, ns);
-                if ((int)vtm::cdiv(nd_tiles, tps) != ns) continue;          // same workgroups as a smaller count
-                if (tps < 4 && ns > 1) continue;                            // >= 4 dst tiles per split (rounds 1-4's rule: every split
-                                                                            // starts its rows' running maxima and lists anew)
-                const int wgs = wgs_per_xcd(ns);
-                // (a single round must leave a few slots free: 63 workgroups on 64 slots measured as two rounds)
-                const double rounds = (wgs <= slots && wgs > slots - slots / 16) ? 2.0 : (double)vtm::cdiv(wgs, slots);
-                const double cost = rounds * (tps + 1.5) + 0.25 * ns;
-                if (cost < best_cost - 1e-9) {
-                    best_cost = cost;
-                    nsplit = ns;
-                }
-            }
-        }
-        if (dbg.nsplit >= 1 && dbg.nsplit <= 16 && dbg.nsplit <= nd_tiles) nsplit = dbg.nsplit;   // tuning hook (tools/sweep_nsplit.py)
-        const int tiles_per_split = (int)vtm::cdiv(nd_tiles, nsplit);
-        nsplit = (int)vtm::cdiv(nd_tiles, tiles_per_split);
-        const int64_t grid = (int64_t)8 * vtm::cdiv(ngroups, 8) * patch_tiles * nsplit;
-        const int64_t c_run = L.C64;   // (rounds 4-5 had a timing hook here that cut the channel loop short -- WRONG results from a
-                                       // shipped library by an environment variable: removed in round 6)
-        // scout + range plan (see filter_kernel): needs the pruning test, the seeds (without a starting maximum nothing is
-        // dead) and dst frames of whole tiles -- one split per dst frame, so that a span is the live tiles of ONE frame
-        const int map_words = (nd_tiles + 31) / 32;
-        unsigned int *tilemap = (unsigned int *)(w + L.tilemap);
-        // (position-ordered call: the whole dst axis is ONE position-major run; the splits stay the one-launch plan's -- a src
-        // tile's span then lies in one or two of them and the other workgroups leave at once, while a level whose spans are long
-        // keeps its parallelism: with a single split corr05's top global level took 2.9 ms instead of 1.3)
-        const bool ordered = src_order != nullptr;
-        const bool range_plan = mode == VTM_MATCH_SCOUT_RANGE && prune && c_run == L.C64 &&
-                                (ordered ? seed_N > 0 && nd_tiles >= 2 : seed_N >= 2 * FBD && seed_N % FBD == 0);
-        if (range_plan) {
-            hipLaunchKernelGGL(filter_kernel<true>, dim3((unsigned)grid), dim3(THREADS), 0, s, ah, al, bh, bl, Ns, Nd, L.Ns_pad,
-                               L.Nd_pad, L.C64, align, ns_tiles, nd_tiles, nsplit, tiles_per_split, total_src_tiles, patch_tiles,
-                               amax, cnt, cand, (int)rows_out, flags, (const float *)(KPS < KP ? rest_a2 : rest_a),
-                               (const float *)(KPS < KP ? rest_bt2 : rest_bt), KPS, flags_out != nullptr ? 1 : 0, tilemap, map_words);
-            const int tps_r = ordered ? tiles_per_split : (int)(seed_N / FBD);
-            const int nsplit_r = (int)vtm::cdiv(nd_tiles, tps_r);
-            const int64_t grid_r = (int64_t)8 * vtm::cdiv(ngroups, 8) * patch_tiles * nsplit_r;
-            hipLaunchKernelGGL(filter_kernel<false>, dim3((unsigned)grid_r), dim3(THREADS), 0, s, ah, al, bh, bl, Ns, Nd,
-                               L.Ns_pad, L.Nd_pad, L.C64, align, ns_tiles, nd_tiles, nsplit_r, tps_r, total_src_tiles, patch_tiles,
-                               amax, cnt, cand, (int)rows_out, flags, (const float *)rest_a, (const float *)rest_bt, KP,
-                               flags_out != nullptr ? 1 : 0, tilemap, map_words);
-        } else {
-            hipLaunchKernelGGL(filter_kernel<false>, dim3((unsigned)grid), dim3(THREADS), 0, s, ah, al, bh, bl, Ns, Nd, L.Ns_pad,
-                               L.Nd_pad, c_run, align, ns_tiles, nd_tiles, nsplit, tiles_per_split, total_src_tiles, patch_tiles,
-                               amax, cnt, cand, (int)rows_out, flags, prune ? (const float *)rest_a : nullptr,
-                               prune ? (const float *)rest_bt : nullptr, prune ? KP : 0x7fffffff, flags_out != nullptr ? 1 : 0,
-                               (unsigned int *)nullptr, map_words);
-        }
-    }
-    bool flags_direct = false;
-    {
-        const dim3 grid((unsigned)vtm::cdiv(rows_out, RROWS)), block(256);
-        unsigned long long *bp = reinterpret_cast<unsigned long long *>(best);
-        const int64_t n_tile_rest = B * (L.Nd_pad / FBD);
-#define VTM_REFINE_ARGS a_rows, Ns, b_rows, Nd, na, nb, align, flags, rows_out, amax, cnt, cand, ovf_cnt, ovf_rows, pairs, \
-                        (const float *)rest_bt, n_tile_rest, bp, src_order, dst_order
-        // the escape: a fixed grid strides over the (device-side) lists of overflowed rows -- normally empty, then the
-        // workgroups leave at once; dst splits of >= 8 tiles so that a short list still spreads over the chip
-        const int xd_tiles = (int)vtm::cdiv(Nd, XD);
-        int xsplit = xd_tiles / 8;
-        xsplit = xsplit < 1 ? 1 : xsplit > 16 ? 16 : xsplit;
-        const int xtps = (int)vtm::cdiv(xd_tiles, xsplit);
-        xsplit = (int)vtm::cdiv(xd_tiles, xtps);
-        const dim3 xgrid((unsigned)((XS == 128 ? 2 : 1) * vtm::device_cus()));
-        // exact_rows_kernel's tile pruning: the rest norms prep_operand wrote for the filter's cut, in 32-channel steps
-        const int KX = dbg.no_xprune ? 0 : (int)(cut / XK);
-        // where the counters go: written by exact_rows_kernel itself when the destination is memory a kernel can store to
-        // (device, or host memory the runtime has pinned / registered), copied behind the call otherwise (pageable host memory)
-        int32_t *flags_pub = nullptr;
-        if (flags_out) {
-            hipPointerAttribute_t attr;
-            if (hipPointerGetAttributes(&attr, flags_out) == hipSuccess &&
-                (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeHost || attr.type == hipMemoryTypeManaged))
-                flags_pub = attr.type == hipMemoryTypeHost && attr.devicePointer ? (int32_t *)attr.devicePointer : flags_out;
-            else
-                (void)hipGetLastError();          // (an unregistered pointer is an "error" of the query, not of the call)
-        }
-        flags_direct = flags_pub != nullptr;
-#define VTM_XPRUNE_ARGS (const float *)rest_a, (const float *)rest_bt, KX, L.Ns_pad, L.Nd_pad / FBD, (const unsigned int *)(w + L.seedlb), \
-                        flags + 6, src_order, dst_order, flags_pub
-        switch (dtype) {
-            case VTM_F32:
-                hipLaunchKernelGGL(refine_kernel<float>, grid, block, 0, s, (const float *)x0, P0, (const float *)x1, P1,
-                                   B, C, VTM_REFINE_ARGS);
-                hipLaunchKernelGGL((src_order ? exact_rows_kernel<float, true> : exact_rows_kernel<float, false>), xgrid, block, 0, s, (const float *)x0, P0, (const float *)x1, P1,
-                                   B, C, a_rows, Ns, b_rows, Nd, na, nb, align, flags, ovf_cnt, ovf_rows, bp, xsplit, xtps, VTM_XPRUNE_ARGS);
-                break;
-            case VTM_F16:
-                hipLaunchKernelGGL(refine_kernel<__half>, grid, block, 0, s, (const __half *)x0, P0, (const __half *)x1,
-                                   P1, B, C, VTM_REFINE_ARGS);
-                hipLaunchKernelGGL((src_order ? exact_rows_kernel<__half, true> : exact_rows_kernel<__half, false>), xgrid, block, 0, s, (const __half *)x0, P0, (const __half *)x1,
-                                   P1, B, C, a_rows, Ns, b_rows, Nd, na, nb, align, flags, ovf_cnt, ovf_rows, bp, xsplit, xtps, VTM_XPRUNE_ARGS);
-                break;
-            default:
-                hipLaunchKernelGGL(refine_kernel<vtm_bf16>, grid, block, 0, s, (const vtm_bf16 *)x0, P0,
-                                   (const vtm_bf16 *)x1, P1, B, C, VTM_REFINE_ARGS);
-                hipLaunchKernelGGL((src_order ? exact_rows_kernel<vtm_bf16, true> : exact_rows_kernel<vtm_bf16, false>), xgrid, block, 0, s, (const vtm_bf16 *)x0, P0,
-                                   (const vtm_bf16 *)x1, P1, B, C, a_rows, Ns, b_rows, Nd, na, nb, align, flags, ovf_cnt,
-                                   ovf_rows, bp, xsplit, xtps, VTM_XPRUNE_ARGS);
-        }
-    }
-    if (int rc = vtm::launch_status("vtm_match_filtered")) return rc;
+    // the exact fp32 chain on the survivors, then the escape: a fixed grid strides over the (device-side) lists of overflowed
+    // rows -- normally empty, then the workgroups leave at once.  It also publishes the counters (kernel_writable).
+    int32_t *flags_pub = kernel_writable(flags_out);
+    vtm::with_dtype(dtype, what, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(refine_kernel<T>, dim3(P.refine_grid), block, 0, s, (const T *)x0, P0, (const T *)x1, P1, B, C, a_rows, Ns,
+                           b_rows, Nd, W.na, W.nb, align, W.flags, rows_out, W.amax, W.cnt, W.cand, W.ovf_cnt, W.ovf_rows, W.pairs,
+                           (const float *)W.rest_bt, B * (L.Nd_pad / FBD), bp, src_order, dst_order);
+        hipLaunchKernelGGL((src_order ? exact_rows_kernel<T, true> : exact_rows_kernel<T, false>), dim3(P.xgrid), block, 0, s,
+                           (const T *)x0, P0, (const T *)x1, P1, B, C, a_rows, Ns, b_rows, Nd, W.na, W.nb, align, W.flags, W.ovf_cnt,
+                           W.ovf_rows, bp, P.xsplit, P.xtps, (const float *)W.rest_a, (const float *)W.rest_bt, P.KX, L.Ns_pad,
+                           L.Nd_pad / FBD, (const unsigned int *)W.seedlb, W.flags + 6, src_order, dst_order, flags_pub);
+        return VTM_OK;
+    });
+    if (int rc = vtm::launch_status(what)) return rc;
 
-    if (flags_out && !flags_direct) {
+    if (flags_out && !flags_pub) {
         // (pageable host memory: the copy direction is taken from the pointers)
-        const hipError_t e = hipMemcpyAsync(flags_out, flags, 8 * sizeof(int), hipMemcpyDefault, s);
+        const hipError_t e = hipMemcpyAsync(flags_out, W.flags, 8 * sizeof(int), hipMemcpyDefault, s);
         if (e != hipSuccess) return vtm::fail(VTM_ELAUNCH, "vtm_match_filtered: copy: %s", hipGetErrorString(e));
     }
     return VTM_OK;

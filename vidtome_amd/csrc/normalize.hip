@@ -117,10 +117,7 @@ VTM_EXPORT int vtm_normalize_gather(const void *x0, int64_t P0, const void *x1, 
     VTM_REQUIRE(n_pad >= n && n_pad % VTM_MATCH_ROW_PAD == 0, "vtm_normalize_gather: bad n_pad");
     VTM_REQUIRE(C_pad >= C && C_pad % VTM_MATCH_K_PAD == 0, "vtm_normalize_gather: bad C_pad");
     hipStream_t s = vtm::as_stream(stream);
-    switch (dtype) {
-        case VTM_F32: return run<float>(x0, P0, x1, P1, B, C, rows, n, norms, out, n_pad, C_pad, s);
-        case VTM_F16: return run<__half>(x0, P0, x1, P1, B, C, rows, n, norms, out, n_pad, C_pad, s);
-        case VTM_BF16: return run<vtm_bf16>(x0, P0, x1, P1, B, C, rows, n, norms, out, n_pad, C_pad, s);
-    }
-    return vtm::fail(VTM_EINVAL, "vtm_normalize_gather: unsupported dtype %d", dtype);
+    return vtm::with_dtype(dtype, "vtm_normalize_gather", [&](auto t) {
+        return run<decltype(t)>(x0, P0, x1, P1, B, C, rows, n, norms, out, n_pad, C_pad, s);
+    });
 }
