@@ -1965,7 +1965,10 @@ def test_geglu_vs_torch_fp32(L, dtype):
                                             (2, 4096, 1000, 640, 640, 3000),
                                             # K = 320: the weight-stationary kernel -- several blocks per wave, ragged last block,
                                             # more than one 160-channel half per sample
-                                            (2, 60000, 3000, 320, 320, 40013), (1, 2000, 0, 320, 640, 1500)])
+                                            (2, 60000, 3000, 320, 320, 40013), (1, 2000, 0, 320, 640, 1500),
+                                            # K % 320 == 0 with N % 160 != 0: the tiled kernel's 160-channel chunks with 128-wide
+                                            # output tiles (ragged in N and in n)
+                                            (2, 300, 100, 320, 192, 91), (2, 300, 100, 640, 96, 257)])
 def test_linear_rows_vs_torch_fp32(L, dtype, B, P0, P1, K, N, n):
     """vtm_linear_rows = Linear(gather(pool, rows)): both output layouts, one- and two-level maps, bias, ragged tiles."""
     g = torch.Generator().manual_seed(K + n)

@@ -54,7 +54,10 @@ template <> struct Mma<vtm_bf16> {
 
 // 0.5 g (1 + erf(g / sqrt 2)) with erfc(|x|) = t (a1 + t (a2 + t (a3 + t (a4 + t a5)))) e^{-x^2}, t = 1 / (1 + p |x|)
 // (Abramowitz & Stegun 7.1.26, |error| <= 1.5e-7 absolute): no cancellation on the negative side, where the exact value
-// is erfc itself; far below the rounding of the 16-bit result (torch's GELU here is the erf form: `approximate="none"`).
+// is erfc itself (torch's GELU here is the erf form: `approximate="none"`).  Measured over every 16-bit gate against the
+// float64 chain (tests/test_gpu_dispatch_variants.py): within 1 ulp of the correctly rounded result for every
+// fp16 gate and for every bf16 gate g >= -6; below that the polynomial's relative error shows in bf16, which still resolves
+// |gelu(g)| < 6e-9: up to 33 ulps (106 gates).
 __device__ __forceinline__ float gelu_erf(float g) {
     const float x = __builtin_fabsf(g) * 0.70710678118654752440f;
     const float t = __builtin_amdgcn_rcpf(__builtin_fmaf(0.3275911f, x, 1.0f));
