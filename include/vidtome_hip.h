@@ -290,8 +290,10 @@ int vtm_gather_rows(const void *x0, int64_t P0, const void *x1, int64_t P1, int 
  * compute_merge, part of the closure protocol):
  *     dst = dst.scatter_reduce(-2, dst_idx.expand(n, r, c), gather(src, src_idx), reduce=mode, include_self=True)
  * with torch's CPU arithmetic -- the sources of a destination row are folded into it one by one in index order, in fp32;
- * a 16-bit tensor is rounded once at the end; "mean" divides the rounded sum by (1 + number of sources) and rounds again;
- * amax / amin propagate NaN.  x is (B, N, C); src_rows (B, r) / dst_rows (B, Nd) are the rows of x of the merged src tokens
+ * a 16-bit tensor is rounded once at the end; "mean" divides the rounded sum by (1 + number of sources) ROUNDED TO THE
+ * TENSOR'S DTYPE (torch holds the count in that dtype: exact up to 2048 in fp16 and 256 in bf16, beyond that the nearest
+ * representable count, so 2049 members of an fp16 row divide by 2048) and rounds again; amax / amin propagate NaN and keep
+ * the accumulator on a tie (of +0 and -0 the one that came first stays).  x is (B, N, C); src_rows (B, r) / dst_rows (B, Nd) are the rows of x of the merged src tokens
  * (in src_idx order) and of the dst tokens; seg_dst (B, r) lists the destinations of the r pairs in ASCENDING order and
  * seg_order (B, r) the pair each entry is (a STABLE sort by destination, e.g. vtm_sort_desc on keys whose high word is
  * 0xffffffff - dst_idx).  Writes out[b, out_row0 + j, :] for j < Nd; out is (B, out_ld, C) -- the merged sequence

@@ -30,3 +30,59 @@ def forked_generator_from_state(rng_state):
     """vidtome/utils.py:22-23: torch.Generator('cpu').set_state(torch.get_rng_state())."""
     import torch
     return torch.Generator(device="cpu").set_state(torch.from_numpy(np.asarray(rng_state)))
+
+
+# ---- the merge closures' reduce modes: torch's CPU scatter_reduce as the reference (test_gpu_merge_modes.py on the GPU,
+# test_oracle_merge_modes.py on the CPU) ----
+REDUCE_MODES = ("sum", "prod", "mean", "amax", "amin")
+# members of a destination row (itself + its sources) around the largest count that the dtype still represents exactly
+# (fp16: 2048, bf16: 256): "mean" divides by the count rounded to the tensors' dtype
+MEMBER_COUNTS = {"fp16": (1, 2, 5, 2047, 2048, 2049, 2050, 2051, 2501, 4099),
+                 "bf16": (1, 2, 5, 255, 256, 257, 258, 259, 301, 2501),
+                 "fp32": (1, 2, 5, 2501)}
+
+
+def scatter_reduce_reference(x, src_rows, dst_rows, dst_idx, mode):
+    """merge.py:127-131 in plain torch on the CPU: the dst rows ``x[b, dst_rows]`` with the src rows ``x[b, src_rows]``
+    folded in, ``dst.scatter_reduce(-2, dst_idx.expand(.., C), src, reduce=mode, include_self=True)`` -> (B, Nd, C)."""
+    import torch
+    assert x.device.type == "cpu"
+    C = x.shape[-1]
+    bi = torch.arange(x.shape[0])[:, None]
+    dst, src = x[bi, dst_rows.long()], x[bi, src_rows.long()]
+    return dst.scatter_reduce(-2, dst_idx.long()[..., None].expand(-1, -1, C), src, reduce=mode, include_self=True)
+
+
+def same_bits(got, want):
+    """Elementwise: equal bit patterns, a NaN equal to a NaN whatever its payload."""
+    import torch
+    assert got.shape == want.shape and got.dtype == want.dtype
+    ints = torch.int32 if got.dtype == torch.float32 else torch.int16
+    return (got.view(ints) == want.view(ints)) | (got.isnan() & want.isnan())
+
+
+def interleaved_destinations(counts, seed):
+    """(1, r) int32 destinations in which row j has counts[j] members, i.e. counts[j] - 1 sources, the pairs of different
+    rows shuffled into one another (not laid out row by row: only a stable sort keeps a row's sources in index order)."""
+    import torch
+    per_row = torch.tensor(counts) - 1
+    d = torch.repeat_interleave(torch.arange(len(counts)), per_row)
+    d = d[torch.randperm(d.numel(), generator=torch.Generator().manual_seed(seed))]
+    assert torch.equal(torch.bincount(d, minlength=len(counts)), per_row)
+    for j in (per_row > 1).nonzero().flatten().tolist():
+        at = (d == j).nonzero().flatten()
+        assert int(at[-1] - at[0]) >= at.numel(), f"the sources of row {j} came out as one run"
+    return d.to(torch.int32)[None]
+
+
+def reduce_tokens(shape, dtype, seed, mode):
+    """Tokens for a reduce-mode case, float32 values rounded to ``dtype``, random signs.  "prod": magnitudes 2 ** U(-0.32,
+    0.32), so that a product over thousands of sources is a random walk of the exponent that stays finite and nonzero in
+    fp32 (its deviation over 4098 factors: 2 ** +-12).  Otherwise 10 ** U(-2, 2): sums over mixed magnitudes round at every
+    step, so they depend on the order and on the accumulator's precision."""
+    import torch
+    g = torch.Generator().manual_seed(seed)
+    span = 0.32 if mode == "prod" else 2.0
+    mag = torch.pow(2.0 if mode == "prod" else 10.0, (torch.rand(shape, generator=g) * 2 - 1) * span)
+    sign = torch.randint(0, 2, shape, generator=g) * 2 - 1
+    return (mag * sign).to(dtype)

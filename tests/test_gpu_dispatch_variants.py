@@ -13,9 +13,9 @@ C == 1280 && rows <  32768 -> layernorm_kernel<T,3,2,..>        layernorm.hip:22
 2 rows C sizeof(T) > STREAM_BYTES, C = 320 (rows kernel, NT)   layernorm.hip:218,234  test_layernorm_streaming[rows_kernel-fp16]
 2 rows C sizeof(T) > STREAM_BYTES, C = 512 (wave per row, NT)  layernorm.hip:218,254  test_layernorm_streaming[wave_per_row-fp32|bf16]
 gamma / beta null or not (four epilogues, both kernels)        layernorm.hip:129,206  test_layernorm_affine_combinations
-blocks > 256 * 16 -> second grid-stride pass of the row moves  gather.hip:150-154      test_gather_rows_grid_stride, test_unmerge_add_grid_stride
-2 total 16 > STREAM_BYTES -> gather_rows_kernel<true>           gather.hip:203         test_gather_rows_streaming
-y + (1 | 2) rows > STREAM_BYTES -> unmerge_add_kernel<T,true>   gather.hip:222         test_unmerge_add_streaming
+blocks > 256 * 16 -> second grid-stride pass of the row moves  gather.hip:154-158      test_gather_rows_grid_stride, test_unmerge_add_grid_stride
+2 total 16 > STREAM_BYTES -> gather_rows_kernel<true>           gather.hip:207         test_gather_rows_streaming
+y + (1 | 2) rows > STREAM_BYTES -> unmerge_add_kernel<T,true>   gather.hip:226         test_unmerge_add_streaming
 resid == nullptr (pure unmerge gather)                         gather.hip:81          test_unmerge_add_grid_stride[..-gather_only]
 cdiv(n, 256) > 4096 -> second pass of cfg_ddim_kernel           ddim.hip:57            test_cfg_ddim_beyond_one_grid_pass
 cdiv(total, 256) > 65536 -> second pass of geglu_kernel         geglu.hip:46           test_geglu_grid_stride
@@ -40,7 +40,7 @@ STREAM_BYTES = 256 << 20             # common.h:76
 LN_ROWS_KERNEL_ALWAYS = (320, 640)   # layernorm.hip:224
 LN_LPR32_MIN_ROWS = 32768            # layernorm.hip:224 (C == 1280 only)
 BLOCK = 256                          # threads per block of the row moves, cfg_ddim and geglu
-MOVE_GRID_CAP = 256 * 16             # gather.hip:152
+MOVE_GRID_CAP = 256 * 16             # gather.hip:156
 DDIM_GRID_CAP = 4096                 # ddim.hip:57
 GEGLU_GRID_CAP = 65536               # geglu.hip:46
 _PINS = {

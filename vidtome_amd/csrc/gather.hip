@@ -89,8 +89,10 @@ __global__ __launch_bounds__(256) void unmerge_add_kernel(const char *__restrict
 // ---- the reference's other merge modes (merge.py:127-131: dst.scatter_reduce(-2, dst_idx, src, reduce=mode,
 // include_self=True)); never reached from compute_merge, kept for the closure protocol ----
 // torch's CPU kernel folds the sources of a destination row into it ONE BY ONE IN INDEX ORDER, in fp32 whatever the tensor
-// dtype; a 16-bit tensor is rounded once at the end, "mean" then divides by (1 + number of sources) and rounds again; amax /
-// amin propagate NaN (probed bit for bit, tests/golden/make_golden_modes.py).  The pairs arrive sorted by destination
+// dtype; a 16-bit tensor is rounded once at the end, "mean" then divides by (1 + number of sources) ROUNDED TO THE TENSOR'S
+// DTYPE (exact up to 2048 in fp16 and 256 in bf16; 2049 members divide by 2048) and rounds again; amax / amin propagate NaN
+// and keep the accumulator on a tie, so the first of two differently signed zeros stays (probed bit for bit,
+// tests/golden/make_golden_modes.py and tests/test_gpu_merge_modes.py).  The pairs arrive sorted by destination
 // (stable, so index order survives inside a destination's segment: vtm_sort_desc on the host side): a thread owns 8
 // channels of one dst row, finds its segment by bisection and walks it.
 enum { RED_SUM = 0, RED_PROD = 1, RED_MEAN = 2, RED_AMAX = 3, RED_AMIN = 4 };
@@ -129,18 +131,20 @@ __global__ __launch_bounds__(256) void merge_reduce_kernel(const T *__restrict__
             const float v = vtm::to_f32(s[e]);
             switch (mode) {
                 case RED_PROD: acc[e] = acc[e] * v; break;
-                case RED_AMAX: acc[e] = (v != v || acc[e] != acc[e]) ? NAN : fmaxf(acc[e], v); break;
-                case RED_AMIN: acc[e] = (v != v || acc[e] != acc[e]) ? NAN : fminf(acc[e], v); break;
+                // (not fmaxf / fminf: they order -0 below +0, torch keeps the accumulator's zero)
+                case RED_AMAX: acc[e] = (v != v || acc[e] != acc[e]) ? NAN : (v > acc[e] ? v : acc[e]); break;
+                case RED_AMIN: acc[e] = (v != v || acc[e] != acc[e]) ? NAN : (v < acc[e] ? v : acc[e]); break;
                 default: acc[e] = acc[e] + v;
             }
         }
         count += 1.0f;
     }
     T *o = out + (b * out_ld + out_row0 + j) * C + c * 8;
+    const float divisor = vtm::to_f32(round_to<T>(count));   // torch holds the count in the tensor's dtype
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         T v = round_to<T>(acc[e]);
-        if (mode == RED_MEAN) v = round_to<T>(vtm::to_f32(v) / count);
+        if (mode == RED_MEAN) v = round_to<T>(vtm::to_f32(v) / divisor);
         o[e] = v;
     }
 }
