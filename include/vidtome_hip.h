@@ -498,6 +498,11 @@ int vtm_geglu(const void *x, int dtype, int64_t rows, int64_t D, void *out, vtm_
  * W: (N, K) row-major like torch.nn.Linear.weight, bias: (N) or NULL; fp16 / bf16, fp32 accumulation.
  * transposed == 0: out is (B, >= n, ldo >= N) token-major; transposed != 0: out is (B, N, ldo >= n) channel-major
  * (V^T for vtm_attention).  out_batch_stride in elements.  K % 32 == 0.  Rows >= n of out are not written.
+ * Alignment of out: any ldo >= the row length, any out_batch_stride and any element-aligned base are accepted, and
+ * nothing outside the valid (n, N) elements is written.  Vector stores are used where they are aligned, single elements
+ * otherwise: 16-byte stores when ldo % 8 == 0 and the sample's base (out + b * out_batch_stride) is 16-byte aligned; for
+ * K % 320 != 0, 8-byte stores when ldo % 4 == 0 and that base is 8-byte aligned.  The K = 320 kernel with resident weights
+ * needs ldo % 8 == 0, out_batch_stride % 8 == 0 and a 16-byte aligned out; other layouts take the tiled kernel.
  * VTM_F32 is vtm_linear_f32 below with VTM_LINEAR_NONE and a VTM_F32 output (its alignment and shape rules apply).
  * ---------------------------------------------------------------------------------------------- */
 int vtm_linear_rows(const void *x0, int64_t P0, const void *x1, int64_t P1, int dtype, int64_t B, int64_t K,

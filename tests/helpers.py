@@ -86,3 +86,40 @@ def reduce_tokens(shape, dtype, seed, mode):
     mag = torch.pow(2.0 if mode == "prod" else 10.0, (torch.rand(shape, generator=g) * 2 - 1) * span)
     sign = torch.randint(0, 2, shape, generator=g) * 2 - 1
     return (mag * sign).to(dtype)
+
+
+# ---- the 16-bit projection GEMMs (test_gpu_gemm16.py) ----
+SENTINEL16 = 0x7FA5          # a NaN pattern in fp16 and in bf16 that no arithmetic of the kernels produces
+EXACT_INT_MAX = {"fp16": 2048, "bf16": 256}    # every integer up to here is a value of the format
+
+
+def int_uniform(shape, lo, hi, dtype, gen, device="cuda"):
+    """Integers uniform in [lo, hi] held in ``dtype`` (exact: the callers keep |lo|, |hi| inside the format's integers)."""
+    import torch
+    return torch.randint(lo, hi + 1, shape, generator=gen, device=device).to(dtype)
+
+
+def sentinel_filled(shape, dtype, device="cuda"):
+    """A tensor of ``dtype`` (16 bits) whose every element holds the SENTINEL16 bit pattern."""
+    import torch
+    return torch.full(shape, SENTINEL16, dtype=torch.int16, device=device).view(dtype)
+
+
+def is_sentinel(t):
+    import torch
+    return t.view(torch.int16) == SENTINEL16
+
+
+def ulp16(m, dtype):
+    """Spacing of ``dtype`` (fp16 / bf16) at the magnitudes ``m`` (float64, >= 0): 2 ** (max(floor(log2 m), emin) - p + 1),
+    the subnormal spacing below 2 ** emin.  frexp, not log2: exact at the powers of two."""
+    import torch
+    mant, emin = (10, -14) if dtype == torch.float16 else (7, -126)
+    _, e = torch.frexp(m)                                   # m = f * 2 ** e, f in [0.5, 1)
+    e = (e.to(torch.int64) - 1).clamp_min(emin) - mant
+    return torch.ldexp(torch.ones_like(m), e)
+
+
+def rounding_bound(ref, slack, dtype):
+    """|RN_dtype(x) - ref| for any x within ``slack`` of ``ref`` (float64): slack + half a spacing at |ref| + slack."""
+    return 0.5 * ulp16(ref.abs() + slack, dtype) + slack

@@ -266,7 +266,9 @@ __global__ __launch_bounds__(NT, 2) void linear_rows_kernel(
             }
         }
     } else {
-        // small-K instantiation (its weight ring is too small to hold the tile): direct 8-byte stores
+        // small-K instantiation (its weight ring is too small to hold the tile): direct 8-byte stores where the sample's
+        // base, the row stride and the element index keep them aligned, single elements otherwise
+        const bool vec4_ok = ((ldo & 3) == 0) && ((reinterpret_cast<uintptr_t>(ob) & 7) == 0);
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             const int64_t ch0 = n0 + 32 * j;
@@ -282,7 +284,7 @@ __global__ __launch_bounds__(NT, 2) void linear_rows_kernel(
 #pragma unroll
                         for (int e = 0; e < 4; ++e) w4[e] = M::cvt(acc[j][4 * g + e] + bv);
                         T *dst = ob + ch * ldo + tok;
-                        if (tok + 3 < n && ((ldo | tok) & 3) == 0) {
+                        if (tok + 3 < n && (tok & 3) == 0 && vec4_ok) {
                             *reinterpret_cast<uint2 *>(dst) = *reinterpret_cast<const uint2 *>(w4);
                         } else {
 #pragma unroll
@@ -300,7 +302,7 @@ __global__ __launch_bounds__(NT, 2) void linear_rows_kernel(
                             w4[e] = M::cvt(acc[j][4 * g + e] + bv);
                         }
                         T *dst = ob + tok * ldo + ch;
-                        if (ch + 3 < N && ((ldo | ch) & 3) == 0) {
+                        if (ch + 3 < N && (ch & 3) == 0 && vec4_ok) {
                             *reinterpret_cast<uint2 *>(dst) = *reinterpret_cast<const uint2 *>(w4);
                         } else {
 #pragma unroll
