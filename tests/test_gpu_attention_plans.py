@@ -26,8 +26,8 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 KV = 64                                               # keys per tile (attention_common.h:21)
 QW = 32                                               # queries per wave (attention_common.h:20)
-DEVPLAN_HEADER = 256                                  # attention_plan.h:211
-PLAN_TIERS, PLAN_MAX_SPLIT = 8, 16                    # attention_plan.h:158-159
+DEVPLAN_HEADER = 256                                  # attention_plan.h:326
+PLAN_TIERS, PLAN_MAX_SPLIT = 8, 16                    # attention_plan.h:169-170
 TOL = {torch.float16: 1e-3, torch.bfloat16: 8e-3}
 DT_CODE = {torch.float16: 1, torch.bfloat16: 2}
 KERNEL_DIMS = (8, 16, 32, 64, 80, 96, 128, 160)
@@ -91,13 +91,13 @@ class Family:
 
     def __init__(self, kind, d, ng=1):
         self.kind, self.d, self.ng = kind, d, ng
-        if kind == "k":                               # the Family of attention.hip:653-665
+        if kind == "k":                               # the Family of attention.hip:612-624
             self.QB, self.wg = waves_for(d) * QW, 2 if d <= 48 else 1
             self.rec = rec_floats(d) * waves_for(d) * 64 * 4
             self.xcd_min = 64
-        elif kind == "16s":                           # the Family of attention16.hip:509-518
+        elif kind == "16s":                           # the Family of attention16.hip:487-496
             self.QB, self.wg, self.rec, self.xcd_min = 8 * QW * 2, 1, 2 * rec16(40) * 512 * 4, 32
-        else:                                         # the Family of attention16g.hip:448-463
+        else:                                         # the Family of attention16g.hip:424-439
             self.QB, self.wg, self.rec, self.xcd_min = 8 * QW, 1, ng * rec16(40) * 512 * 4, 32
 
     def slots(self, n_cus):
@@ -105,7 +105,7 @@ class Family:
 
 
 def plan_tail(B_items, h, Mq, Mk, QB, wg, rec, bounded, n_cus):
-    """attention_plan.h:34-66."""
+    """attention_plan.h:36-68."""
     nqb = cdiv(Mq, QB)
     total = nqb * h * B_items
     slots = n_cus * wg
@@ -124,11 +124,11 @@ def plan_tail(B_items, h, Mq, Mk, QB, wg, rec, bounded, n_cus):
     return p
 
 
-def devplan_ws_bytes(slots, rec):                     # attention_plan.h:168, 213
+def devplan_ws_bytes(slots, rec):                     # attention_plan.h:283, 328
     return DEVPLAN_HEADER + (PLAN_TIERS - 1) * slots * rec
 
 
-def ws_bytes_k(D, B, h, Mq, Mk, bounded, n_cus):     # attention_plan.h:297-302
+def ws_bytes_k(D, B, h, Mq, Mk, bounded, n_cus):     # attention_plan.h:415-420
     F = Family("k", D)
     n = plan_tail(B, h, Mq, Mk, F.QB, F.wg, F.rec, bounded, n_cus)["ws_bytes"]
     if bounded and cdiv(Mk, KV) >= 16:
@@ -136,19 +136,19 @@ def ws_bytes_k(D, B, h, Mq, Mk, bounded, n_cus):     # attention_plan.h:297-302
     return n
 
 
-def ws_bytes16(B, h, Mq, Mk, bounded, n_cus):        # attention_plan.h:297-302
+def ws_bytes16(B, h, Mq, Mk, bounded, n_cus):        # attention_plan.h:415-420
     F = Family("16s", 40)
     n = plan_tail(B, h, Mq, Mk, F.QB, 1, F.rec, bounded, n_cus)["ws_bytes"]
     return max(n, devplan_ws_bytes(n_cus, F.rec)) if bounded else n
 
 
-def ws_bytes16g(ng, src, h, Mq, Mk, bounded, n_cus):  # attention_plan.h:297-302
+def ws_bytes16g(ng, src, h, Mq, Mk, bounded, n_cus):  # attention_plan.h:415-420
     F = Family("16g", 40, ng)
     n = plan_tail(src, h, Mq, Mk, F.QB, 1, F.rec, False, n_cus)["ws_bytes"]
     return max(n, devplan_ws_bytes(n_cus, F.rec)) if bounded else n
 
 
-def ws_bytes_any(B, h, Mq, Mk, d, bounded, n_cus):    # attention.hip:677-689
+def ws_bytes_any(B, h, Mq, Mk, d, bounded, n_cus):    # attention.hip:636-648
     if B <= 0 or h <= 0 or Mq <= 0 or Mk <= 0:
         return 0
     if d == 40:
@@ -160,12 +160,12 @@ def ws_bytes_any(B, h, Mq, Mk, d, bounded, n_cus):    # attention.hip:677-689
     return ws_bytes_k(d, B, h, Mq, Mk, bounded, n_cus) if d in KERNEL_DIMS else 0
 
 
-def shape16_for(d, share_groups):                     # attention.hip:670-673 (16-bit dtypes)
+def shape16_for(d, share_groups):                     # attention.hip:629-632 (16-bit dtypes)
     return (share_groups if share_groups <= 3 else 0) if d == 40 else 0
 
 
 def device_plan(counts, H, QB, slots, ntiles):
-    """attention16_plan_kernel (attention_plan.h:171-208): the 44 int32 of the DevPlan it writes."""
+    """attention16_plan_kernel (attention_plan.h:286-323): the 44 int32 of the DevPlan it writes."""
     nqb = max([1] + [cdiv(c, QB) for c in counts])
     Lit, S = nqb * H * len(counts), slots
     max_ns = max(1, min(PLAN_MAX_SPLIT, ntiles // 8))
@@ -208,9 +208,9 @@ class Selection:
 
     def __init__(self, call, d, B, h, Mq, Mk, share, ldvt, ws_bytes, counts, n_cus):
         bounded = counts is not None                  # (a query count is what makes a launch bounded)
-        if call == "folded":                          # attention.hip:779-780
+        if call == "folded":                          # attention.hip:738-739
             kind = "16s" if d == 40 else "k"
-        else:                                         # attention.hip:727-737
+        else:                                         # attention.hip:686-696
             ng = shape16_for(d, share)
             if ng == 1:
                 kind = "16s"
@@ -226,7 +226,7 @@ class Selection:
         xcd_pairs = (self.items_B * h) // 8 if (self.items_B * h) % 8 == 0 else 0
         nqb_max = cdiv(Mq, F.QB)
         self.header = None
-        # the device plan: attention_plan.h:250-251
+        # the device plan: attention_plan.h:368-369
         if bounded and ws_bytes is not None and ws_bytes >= devplan_ws_bytes(slots, F.rec) and \
                 nqb_max * h * self.items_B >= 2 * slots:
             self.plan, self.combine = "device", "16" if kind != "k" else "plain"
@@ -240,7 +240,7 @@ class Selection:
                 self.split += [(item_of(item0 + i, self.nqb, xg), ns, rec0 + i * ns) for i in range(items)]
             self.ws_used = DEVPLAN_HEADER + sum(ns for _, ns, _ in self.split) * F.rec
             return
-        # the host plans: attention_plan.h:270-277
+        # the host plans: attention_plan.h:388-395
         p = plan_tail(self.items_B, h, Mq, Mk, F.QB, F.wg, F.rec, bounded and kind != "16g", n_cus)
         if p["split_all"] and (ws_bytes is None or ws_bytes < p["ws_bytes"]):
             p = plan_tail(self.items_B, h, Mq, Mk, F.QB, F.wg, F.rec, False, n_cus)
@@ -253,9 +253,9 @@ class Selection:
             self.combine = None
         elif kind != "k":
             self.combine = "16"
-        else:                                         # attention.hip:639-641
+        else:                                         # attention.hip:600-602
             self.combine = "parts" if (not pv16_for(d) and rem * 4 <= n_cus) else "plain"
-        xg = xcd_pairs if p["nqb"] >= F.xcd_min else 0   # attention_plan.h:288
+        xg = xcd_pairs if p["nqb"] >= F.xcd_min else 0   # attention_plan.h:406
         self.rec_base = 0
         self.split = [(item_of(p["full"] + i, p["nqb"], xg), p["nsplit"], i * p["nsplit"]) for i in range(rem)] \
             if p["nsplit"] > 1 else []
@@ -272,7 +272,7 @@ class Selection:
 
 
 def pieces(Mk, ns):
-    """Key ranges of the `ns` pieces of a split item over Mk keys (attention.hip:572-574, attention16.hip:339-341)."""
+    """Key ranges of the `ns` pieces of a split item over Mk keys (attention.hip:534-536, attention16.hip:320-322)."""
     ntiles = cdiv(Mk, KV)
     tps = cdiv(ntiles, ns)
     out = []
@@ -584,6 +584,58 @@ def test_attention16g_plans(L, oracle, ng, src, plan, dtype):
 def test_attention_kernel_shared_plans(L, oracle, d, ng, plan, dtype):
     """attention_kernel's shared-probability path: d = 64 over 3 groups, and d = 40 over 4 (beyond attention16g)."""
     _plan_case(L, oracle, "k", dtype, d, plan, ng=ng)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# device plans on both sides of a family's XCD threshold
+# ---------------------------------------------------------------------------------------------------------------------
+XCD_SIDES = ("below_split", "below", "at", "above")
+
+
+def _xcd_threshold_case(L, oracle, kind, dtype, d, B, side):
+    """A device-planned launch whose (sample, head) pairs divide over the 8 XCDs, with the live query blocks per pair
+    (the longest sample's, DevPlan.nqb) just below and at the family's xcd_min_nqb: the main kernel and the combine kernel
+    each decide from that device value whether the items are pinned to XCDs (item_of), and a combine kernel that decided
+    otherwise would merge other items' records.  The smallest shape that takes the device plan: B h = 8 pairs per round of
+    slots, Mq = threshold x QB rows, 16 key tiles (a tier may split in two, 8 tiles per piece).
+    "below" / "at": threshold - 1 / threshold live blocks, as close as the threshold can be straddled.  With B h a multiple
+    of 8 these two plans have no split tier on a 256-CU device (threshold x B h is a whole number of rounds, one block less
+    a last round more than 0.8 full), so the combine kernel has no item there; "above" (threshold + 1 blocks, Mq one block
+    longer) and "below_split" (the largest count below the threshold whose plan has a split tier) are the nearest counts
+    on either side at which main and combine kernel have to agree on the placement."""
+    n_cus, h, Mk = cus(), 8, 1000
+    F = Family(kind, d)
+    S, thr = F.slots(n_cus), F.xcd_min
+    assert (B * h) % 8 == 0
+    plan_of = lambda n: device_plan([77] * (B - 1) + [n * F.QB], h, F.QB, S, cdiv(Mk, KV))
+    if side == "below_split":
+        live = next((n for n in range(thr - 1, 0, -1) if plan_of(n)[1] >= 2), None)
+        assert live is not None, "no count below the threshold gives this device a split tier"
+    else:
+        live = thr + {"below": -1, "at": 0, "above": 1}[side]
+    Mq = max(thr, live) * F.QB
+    counts = [77] * (B - 1) + [(live - 1) * F.QB + F.QB // 3]
+    assert cdiv(Mq, F.QB) * h * B >= 2 * S, "the shape does not take the device plan"
+    sel = run_case(L, oracle, "bounded", dtype, d, B, h, Mq, Mk, (kind, "device", "16" if kind != "k" else "plain"),
+                   counts=counts, seed=zlib.crc32(f"xcd/{kind}/{side}".encode()) % 1000)
+    assert sel.nqb == live and (live >= thr) == (side in ("at", "above")), (sel.nqb, live, thr)
+    if side in ("below_split", "above"):
+        assert sel.header[1] >= 2 and sel.split, sel.header
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=DT_IDS)
+@pytest.mark.parametrize("side", XCD_SIDES)
+def test_attention_kernel_plans_around_the_xcd_threshold(L, oracle, side, dtype):
+    """attention_kernel<T, 64>: one sample of 8 heads, 63 / 64 (and 57 / 65) live blocks of 512 rows."""
+    _xcd_threshold_case(L, oracle, "k", dtype, 64, 1, side)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=DT_IDS)
+@pytest.mark.parametrize("side", XCD_SIDES)
+def test_attention16s_plans_around_the_xcd_threshold(L, oracle, side, dtype):
+    """attention16s_kernel<T, 40>: 31 / 32 (and 28 / 33) live blocks of 512 rows.  Two samples of 8 heads: at 32 blocks
+    one sample's 256 items are a single round of the 256 slots, which takes no device plan."""
+    _xcd_threshold_case(L, oracle, "16s", dtype, 40, 2, side)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -543,6 +543,20 @@ def _attention_ws(B: int, heads: int, Mq: int, Mk: int, d: int, device):
     return _workspace("attention", nb, device), nb
 
 
+def _attention_out(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, Mq: int, Mkp: int, alloc: bool = True):
+    """The operand checks every attention wrapper makes -- q (B, Mqp, C), k (B, Mkp, C), vt (B, C, ldvt) contiguous along
+    the last axis, dense batch strides -- and its (B, Mqp, C) result: zeroed when there are pad rows behind Mq (no kernel
+    writes them), else uninitialised."""
+    B, Mqp, C = q.shape
+    if q.stride(2) != 1 or k.stride(2) != 1 or vt.stride(2) != 1:
+        raise RuntimeError("attention operands must be contiguous along their last axis")
+    if q.stride(0) != Mqp * q.stride(1) or k.stride(0) != Mkp * k.stride(1) or vt.stride(0) != C * vt.stride(1):
+        raise RuntimeError("attention operands must have dense batch strides")
+    if not alloc:
+        return None
+    return (torch.zeros if Mqp != Mq else torch.empty)((B, Mqp, C), dtype=q.dtype, device=q.device)
+
+
 @_on_device
 def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, M: int, scale: float,
               share_groups: int = 1) -> torch.Tensor:
@@ -550,12 +564,7 @@ def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, M:
     Returns out (B, Mp, C) (rows >= M untouched/zero)."""
     B, Mp, C = q.shape
     d = C // heads
-    if q.stride(2) != 1 or k.stride(2) != 1 or vt.stride(2) != 1:
-        raise RuntimeError("attention operands must be contiguous along their last axis")
-    if q.stride(0) != Mp * q.stride(1) or k.stride(0) != Mp * k.stride(1) or vt.stride(0) != C * vt.stride(1):
-        raise RuntimeError("attention operands must have dense batch strides")
-    out = torch.zeros((B, Mp, C), dtype=q.dtype, device=q.device) if Mp != M else \
-        torch.empty((B, Mp, C), dtype=q.dtype, device=q.device)
+    out = _attention_out(q, k, vt, M, Mp)
     ws, nb = _attention_ws(B, heads, M, M, d, q.device)
     _check(lib().vtm_attention(q.data_ptr(), q.stride(1), k.data_ptr(), k.stride(1), vt.data_ptr(), vt.stride(1),
                                out.data_ptr(), C, dtype_code(q), B, heads, M, Mp, d, float(scale),
@@ -616,12 +625,7 @@ def attention_kv(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int,
     B, Mqp, C = q.shape
     Mkp = k.shape[1]
     d = C // heads
-    if q.stride(2) != 1 or k.stride(2) != 1 or vt.stride(2) != 1:
-        raise RuntimeError("attention operands must be contiguous along their last axis")
-    if q.stride(0) != Mqp * q.stride(1) or k.stride(0) != Mkp * k.stride(1) or vt.stride(0) != C * vt.stride(1):
-        raise RuntimeError("attention operands must have dense batch strides")
-    out = torch.zeros((B, Mqp, C), dtype=q.dtype, device=q.device) if Mqp != Mq else \
-        torch.empty((B, Mqp, C), dtype=q.dtype, device=q.device)
+    out = _attention_out(q, k, vt, Mq, Mkp)
     ws, nb = _attention_ws(B, heads, Mq, Mk, d, q.device) if use_workspace else (None, 0)
     if q_count is not None and (q_count.dtype != torch.int32 or q_count.numel() != B or not q_count.is_cuda):
         raise RuntimeError("attention_kv: q_count must be a (B,) int32 device tensor")
@@ -674,12 +678,7 @@ def attention_kv_range(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads
     if start == 0:
         return attention_kv(q, k, vt, heads, Mq, Mk, scale)
     d = C // heads
-    if q.stride(2) != 1 or k.stride(2) != 1 or vt.stride(2) != 1:
-        raise RuntimeError("attention operands must be contiguous along their last axis")
-    if q.stride(0) != Mqp * q.stride(1) or k.stride(0) != Mkp * k.stride(1) or vt.stride(0) != C * vt.stride(1):
-        raise RuntimeError("attention operands must have dense batch strides")
-    out = torch.zeros((B, Mqp, C), dtype=q.dtype, device=q.device) if Mqp != Mq else \
-        torch.empty((B, Mqp, C), dtype=q.dtype, device=q.device)
+    out = _attention_out(q, k, vt, Mq, Mkp)
     ws, nb = _attention_ws(B, heads, Mq, Mk, d, q.device)
     es = k.element_size()
     # (sample b's keys start at k + (b * Mkp + start) * ldk: the row count Mkp stays the sample stride)
@@ -705,16 +704,12 @@ def attention_kv_sets(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads:
     B, Mqp, C = q.shape
     Mkp = k.shape[1]
     d = C // heads
-    if q.stride(2) != 1 or k.stride(2) != 1 or vt.stride(2) != 1:
-        raise RuntimeError("attention operands must be contiguous along their last axis")
-    if q.stride(0) != Mqp * q.stride(1) or k.stride(0) != Mkp * k.stride(1) or vt.stride(0) != C * vt.stride(1):
-        raise RuntimeError("attention operands must have dense batch strides")
+    _attention_out(q, k, vt, Mq, Mkp, alloc=False)
     if k.shape[0] != B or vt.shape[0] != B or k.shape[2] != C or vt.shape[1] != C:
         raise RuntimeError("attention_kv_sets: k must be (B, Mkp, C) and vt (B, C, ldvt)")
     if len(sets) == 1 and sets[0][2] == 1.0:
         return attention_kv_range(q, k, vt, heads, Mq, sets[0][0], sets[0][1], scale)
-    out = torch.zeros((B, Mqp, C), dtype=q.dtype, device=q.device) if Mqp != Mq else \
-        torch.empty((B, Mqp, C), dtype=q.dtype, device=q.device)
+    out = _attention_out(q, k, vt, Mq, Mkp)
     n = len(sets)
     starts = (_i64 * n)(*[s for s, _, _ in sets])
     lens = (_i64 * n)(*[m for _, m, _ in sets])

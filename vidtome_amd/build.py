@@ -80,7 +80,7 @@ def build(force: bool = False, verbose: bool = False, defines=(), tag: str = "")
 def kernel_resources(obj: str) -> dict:
     """Register / scratch budget of every gfx950 kernel in one of the built objects (`lib/<source>.o`), from the code
     object's metadata: {demangled-ish name: {vgpr_count, sgpr_count, vgpr_spill_count, sgpr_spill_count,
-    private_segment_fixed_size}}.  tests/test_host.py pins the hot kernels with it (the filter's hand-counted memory
+    private_segment_fixed_size, group_segment_fixed_size}}.  tests/test_host.py pins the hot kernels with it (the filter's hand-counted memory
     pipeline must not spill; the attention kernel must keep 4 waves per SIMD)."""
     import re
     import tempfile
@@ -97,13 +97,17 @@ def kernel_resources(obj: str) -> dict:
                 raise RuntimeError(" ".join(cmd) + "\n" + p.stdout)
         notes = subprocess.run([os.path.join(llvm, "llvm-readelf"), "--notes", dev], stdout=subprocess.PIPE, text=True,
                                check=True).stdout
-    out, cur = {}, None
+    out, cur, lds = {}, None, {}
     for line in notes.splitlines():
-        m = re.match(r"\s*\.(name|vgpr_count|sgpr_count|vgpr_spill_count|sgpr_spill_count|private_segment_fixed_size):\s+(\S+)", line)
+        m = re.match(r"\s*\.(name|vgpr_count|sgpr_count|vgpr_spill_count|sgpr_spill_count|private_segment_fixed_size|group_segment_fixed_size):\s+(\S+)", line)
         if not m:
             continue
-        if m.group(1) == "name":
+        if m.group(1) == "group_segment_fixed_size":   # (the keys are sorted: the static LDS size precedes its kernel's name)
+            lds = {m.group(1): int(m.group(2))}
+        elif m.group(1) == "name":
             cur = out.setdefault(m.group(2), {})
+            cur.update(lds)
+            lds = {}
         elif cur is not None:
             cur[m.group(1)] = int(m.group(2))
     return {k: v for k, v in out.items() if "vgpr_count" in v}

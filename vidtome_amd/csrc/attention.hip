@@ -33,40 +33,32 @@
 
 namespace {
 
+// ---- the constants of attention_kernel's family, for its kernels and for make_family ----
+constexpr int XCD_MIN_NQB = 64;                                                  // Family::xcd_min_nqb
+constexpr int qb_for(int D) { return waves_for(D) * QW; }                        // query rows per workgroup
+constexpr int64_t rec_size(int D) { return (int64_t)rec_floats(D) * (waves_for(D) * 64); }   // floats of a partial record
+
 // merges the `nsplit` partial states of a query block (same thread <-> register mapping as attention_kernel)
 template <typename T, int D>
 __global__ __launch_bounds__(waves_for(D) * 64) void attention_combine_kernel(
-    const float *__restrict__ partial, T *__restrict__ out, int64_t ldo, int64_t H, int64_t M, int64_t Mp, int64_t nqb,
-    int64_t id0, int nsplit, int xcd_groups, const int32_t *__restrict__ q_count, const DevPlan *__restrict__ dev_plan) {
-    constexpr int WAVES = waves_for(D), NT = WAVES * 64, QB = WAVES * QW, DV = (D + 31) / 32;
+    T *__restrict__ out, int64_t ldo, int64_t H, int64_t M, int64_t Mp, PlanArgs plan) {
+    constexpr int WAVES = waves_for(D), NT = WAVES * 64, DV = (D + 31) / 32;
     constexpr bool PV16 = pv16_for(D);
-    constexpr int NA = acc_floats(D), NM = max_floats(D), REC = rec_floats(D);
+    constexpr int NA = acc_floats(D), NM = max_floats(D);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, hi = lane >> 5;
-    int64_t rec0 = (int64_t)blockIdx.x * nsplit;   // first partial record of this item
-    int64_t pos = id0 + blockIdx.x;
-    if (dev_plan != nullptr) {        // device-planned launch (attention_plan.h): the launch is sized for the most items a plan can split
-        if ((int)blockIdx.x >= dev_plan->split_items) return;
-        nqb = dev_plan->nqb;
-        xcd_groups = nqb >= 64 ? xcd_groups : 0;
-        pos = dev_plan->tier[0].items + blockIdx.x;
-        int ti = 1;
-        while (ti + 1 < dev_plan->ntiers && pos >= dev_plan->tier[ti + 1].item0) ++ti;
-        const DevTier tr = dev_plan->tier[ti];
-        nsplit = tr.nsplit;
-        rec0 = tr.rec0 + (pos - tr.item0) * tr.nsplit;
-    }
-    const int64_t lin = item_of(pos, nqb, xcd_groups);
-    const int64_t b = lin / (nqb * H), h = (lin / nqb) % H;
-    const int64_t q0 = (lin % nqb) * QB + wave * QW;
-    if (q_count != nullptr && (lin % nqb) * QB >= (int64_t)q_count[b]) return;   // its partial records were never written
+    const WorkItem w = decode_combine_item<qb_for(D), XCD_MIN_NQB>(plan, H, blockIdx.x);
+    if (w.leave) return;
+    const int64_t b = w.b, h = w.h, q0 = w.q0 + wave * QW;
+    const int nsplit = w.nsplit;
+    const float *partial = plan.partial_base + w.rec * rec_size(D);
     float acc[NA], m[NM], l = 0.0f;
 #pragma unroll
     for (int r = 0; r < NA; ++r) acc[r] = 0.0f;
 #pragma unroll
     for (int j = 0; j < NM; ++j) m[j] = -INFINITY;
     for (int sp = 0; sp < nsplit; ++sp) {
-        const float *pp = partial + (rec0 + sp) * REC * NT + tid;
+        const float *pp = partial + sp * rec_size(D) + tid;
         float fa[NM], fb[NM];
 #pragma unroll
         for (int j = 0; j < NM; ++j) {
@@ -103,23 +95,22 @@ __global__ __launch_bounds__(waves_for(D) * 64) void attention_combine_kernel(
 // for arithmetic on an earlier record; the register group is addressed at run time, the 8 accumulators are static.
 template <typename T, int D>
 __global__ __launch_bounds__(waves_for(D) * 64) void attention_combine_parts_kernel(
-    const float *__restrict__ partial, T *__restrict__ out, int64_t ldo, int64_t H, int64_t M, int64_t Mp, int64_t nqb,
-    int64_t id0, int nsplit, int xcd_groups, const int32_t *__restrict__ q_count) {
+    T *__restrict__ out, int64_t ldo, int64_t H, int64_t M, int64_t Mp, PlanArgs plan) {
     using elem = typename Frag<T>::elem;
     static_assert(!pv16_for(D), "32-row O^T layout");
-    constexpr int WAVES = waves_for(D), NT = WAVES * 64, QB = WAVES * QW;
+    constexpr int WAVES = waves_for(D), NT = WAVES * 64;
     constexpr int NA = acc_floats(D), REC = rec_floats(D);
     constexpr bool SPARE = (D % 32) != 0;
     constexpr int LREG_ALL = SPARE ? (D / 32) * 16 + ((D % 32) & 3) + 4 * ((D % 32) >> 3) : 0;
     constexpr int LHI = ((D % 32) >> 2) & 1;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, hi = lane >> 5;
-    const int64_t lin = item_of(id0 + blockIdx.x, nqb, xcd_groups);
-    const int64_t b = lin / (nqb * H), h = (lin / nqb) % H;
-    const int64_t q0 = (lin % nqb) * QB + wave * QW;
-    if (q_count != nullptr && (lin % nqb) * QB >= (int64_t)q_count[b]) return;
+    const WorkItem w = decode_combine_item<qb_for(D), XCD_MIN_NQB>(plan, H, blockIdx.x);   // (host plans only)
+    if (w.leave) return;
+    const int64_t b = w.b, h = w.h, q0 = w.q0 + wave * QW;
+    const int nsplit = w.nsplit;
     const int r0 = (int)blockIdx.y * 8;
-    const float *p0 = partial + (int64_t)blockIdx.x * nsplit * REC * NT + tid;
+    const float *p0 = plan.partial_base + w.rec * rec_size(D) + tid;
     float m = -INFINITY;
 #pragma unroll 4
     for (int sp = 0; sp < nsplit; ++sp) m = fmaxf(m, p0[((int64_t)sp * REC + NA) * NT]);
@@ -158,21 +149,18 @@ template <typename T, int D, bool FOLD>
 __global__ __launch_bounds__(waves_for(D) * 64, (D <= 48 ? 4 : D <= 96 ? 4 : 1)) void attention_kernel(
     const T *__restrict__ q, int64_t ldq, const T *__restrict__ k, int64_t ldk,
     const T *__restrict__ vt, int64_t ldvt, T *__restrict__ out, int64_t ldo, int64_t H,
-    int64_t M, int64_t Mp, int64_t Mk_arg, int64_t Mkp, float scale_log2e, int64_t src_batch, int64_t nqb, int64_t nwhole,
-    int nsplit_tail, float *__restrict__ partial_base, int xcd_groups, const int32_t *__restrict__ q_count,
-    int64_t split_major_items, const int32_t *__restrict__ k_count, const uint32_t *__restrict__ k_bias, int64_t ldkb,
-    const DevPlan *__restrict__ dev_plan) {
+    int64_t M, int64_t Mp, int64_t Mk_arg, int64_t Mkp, float scale_log2e, int64_t src_batch,
+    const int32_t *__restrict__ k_count, const uint32_t *__restrict__ k_bias, int64_t ldkb, PlanArgs plan) {
     // M / Mp: queries per sample and their row stride; Mk / Mkp: keys per sample and the row stride of k
     // (self-attention passes the same values; cross-attention, patch.py:178-183, has Mk = 77).
-    // Work decomposition: work item = (query block, head, sample), query blocks fastest.  Workgroups [0, nwhole) take
-    // one item each and all its key tiles; the workgroups behind them share the remaining items `nsplit_tail` ways
-    // along the key axis: each covers the key tiles of one split and leaves its
-    // unnormalised accumulators, running max and denominator in `partial` for attention_combine_kernel (used for
-    // the query blocks that do not fill a whole round of the chip, see launch()).
+    // Work decomposition: work item = (query block, head, sample), query blocks fastest (decode_work_item).  A workgroup
+    // that covers the key tiles of one split of its item leaves its unnormalised accumulators, running max and
+    // denominator in `partial` for attention_combine_kernel (used for the query blocks that do not fill a whole round of
+    // the chip, see planned_launch).
     using F = Frag<T>;
     using vec = typename F::vec;
     using elem = typename F::elem;
-    constexpr int WAVES = waves_for(D), NT = WAVES * 64, QB = WAVES * QW;
+    constexpr int WAVES = waves_for(D), NT = WAVES * 64;
     constexpr int DK = (D + 15) / 16;      // k-steps of the QK^T contraction
     constexpr int DV = (D + 31) / 32;      // 32-row blocks of O^T
     constexpr bool PV16 = pv16_for(D);     // ... or 16-row blocks (see pv16_for)
@@ -205,45 +193,19 @@ __global__ __launch_bounds__(waves_for(D) * 64, (D <= 48 ? 4 : D <= 96 ? 4 : 1))
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, hi = lane >> 5;
     const int l15 = lane & 15, g16 = lane >> 4;   // PV16 operand coordinates
-    // (round 6) query-bounded launches: the roles come from the plan one thread made on the device from the live counts --
-    // whole items first, then tiers of items split 2, 4, 8, 16 ways (attention_plan.h); workgroups behind the plan leave
-    int64_t tier_item0 = nwhole, tier_wg0 = nwhole, tier_rec0 = 0;
-    if (dev_plan != nullptr) {
-        nqb = dev_plan->nqb;
-        xcd_groups = nqb >= 64 ? xcd_groups : 0;
-        int ti = 0;
-        while (ti + 1 < dev_plan->ntiers && (int)blockIdx.x >= dev_plan->tier[ti + 1].wg0) ++ti;
-        const DevTier tr = dev_plan->tier[ti];
-        if ((int64_t)blockIdx.x >= (int64_t)tr.wg0 + (int64_t)tr.items * tr.nsplit) return;
-        nwhole = dev_plan->tier[0].items;
-        nsplit_tail = tr.nsplit;
-        split_major_items = tr.items;       // (inside a tier: all first pieces, then all second pieces ...)
-        tier_item0 = tr.item0;
-        tier_wg0 = tr.wg0;
-        tier_rec0 = tr.rec0;
-    }
-    const bool tail_wg = (int64_t)blockIdx.x >= nwhole;
-    const int64_t tail_id = (int64_t)blockIdx.x - tier_wg0;      // (host plan: one tier behind the whole items)
-    const int nsplit = tail_wg ? nsplit_tail : 1;
-    // split-minor (a partly filled last round: the splits of an item sit next to each other) or split-MAJOR (launches
-    // with a device-side query bound split EVERY item, see launch(): all first halves, then all second halves, so that
-    // workgroup p and its item still share p % 8 = the XCD the item's (sample, head) pair is pinned to)
-    const int64_t tail_item = split_major_items ? tail_id % split_major_items : tail_id / nsplit;
-    const int split = !tail_wg ? 0 : split_major_items ? (int)(tail_id / split_major_items) : (int)(tail_id % nsplit);
-    const int64_t lin = item_of(tail_wg ? tier_item0 + tail_item : (int64_t)blockIdx.x, nqb, xcd_groups);
-    float *partial = tail_wg ? partial_base + (tier_rec0 + tail_item * nsplit + split) * rec_floats(D) * (waves_for(D) * 64) : nullptr;
-    const int64_t b = lin / (nqb * H), h = (lin / nqb) % H;
+    const WorkItem w = decode_work_item<qb_for(D), XCD_MIN_NQB>(plan, H, blockIdx.x);
+    if (w.leave) return;
+    const int nsplit = w.nsplit, split = w.split;
+    float *partial = w.rec >= 0 ? plan.partial_base + w.rec * rec_size(D) : nullptr;
+    const int64_t b = w.b, h = w.h;
     const int64_t bq = b % src_batch;  // PnP injection: q/k of the source sample (pnp_utils.py:57-67)
-    const int64_t q0 = (lin % nqb) * QB + wave * QW;
+    const int64_t q0 = w.q0 + wave * QW;
     const int64_t C = H * D;
     int64_t Mk = Mk_arg;
     if constexpr (FOLD) {
         const int64_t kc = k_count[b];
         Mk = kc < Mk_arg ? (kc > 0 ? kc : 1) : Mk_arg;
     }
-    // device-side query bound (compacted live queries, vtm_compact_queries): the launch is sized for the host-known
-    // upper bound M; a query block that starts at or beyond its sample's count has nothing anybody reads
-    if (q_count != nullptr && (lin % nqb) * QB >= (int64_t)q_count[b]) return;
 
     // one-time LDS init: K pad columns = 0 (they meet Q's zero padding; garbage could be NaN), V^T pad rows
     // = 0 except row D = 1 (denominator row) -- tile loads never touch these.  FOLD: not the bias pair D + 2, D + 3, which
@@ -630,8 +592,7 @@ template <typename T, int D, bool FOLD>
 void launch_main(const Call &c, const Launch &g) {
     hipLaunchKernelGGL((attention_kernel<T, D, FOLD>), dim3((unsigned)g.wgs), dim3(waves_for(D) * 64), lds_for(D), c.s,
                        (const T *)c.q, c.ldq, (const T *)c.k, c.ldk, (const T *)c.vt, c.ldvt, (T *)c.out, c.ldo, c.h, c.M, c.Mp,
-                       c.Mk, c.Mkp, g.scale_log2e, g.src_batch, g.nqb, g.whole, g.nsplit, g.partial, g.xcd_groups, c.q_count,
-                       g.split_major, c.k_count, c.k_bias, c.ldkb, plan_of(g));
+                       c.Mk, c.Mkp, g.scale_log2e, g.src_batch, c.k_count, c.k_bias, c.ldkb, plan_args(c, g));
 }
 
 template <typename T, int D>
@@ -640,23 +601,21 @@ void launch_combine(const Call &c, const Launch &g) {
         // few items of a host plan: their accumulator groups are shared out (attention_combine_parts_kernel)
         if (g.plan == nullptr && g.split_items * 4 <= vtm::device_cus()) {
             hipLaunchKernelGGL((attention_combine_parts_kernel<T, D>), dim3((unsigned)g.split_items, (unsigned)(acc_floats(D) / 8)),
-                               dim3(waves_for(D) * 64), 0, c.s, (const float *)g.partial, (T *)c.out, c.ldo, c.h, c.M, c.Mp,
-                               g.nqb, g.whole, g.nsplit, g.xcd_groups, c.q_count);
+                               dim3(waves_for(D) * 64), 0, c.s, (T *)c.out, c.ldo, c.h, c.M, c.Mp, plan_args(c, g));
             return;
         }
     }
     hipLaunchKernelGGL((attention_combine_kernel<T, D>), dim3((unsigned)g.split_items), dim3(waves_for(D) * 64), 0, c.s,
-                       (const float *)g.partial, (T *)c.out, c.ldo, c.h, c.M, c.Mp, g.nqb, g.whole, g.nsplit, g.xcd_groups,
-                       c.q_count, plan_of(g));
+                       (T *)c.out, c.ldo, c.h, c.M, c.Mp, plan_args(c, g));
 }
 
 template <typename T, int D, bool FOLD = false>
 Family make_family() {
     Family f;
-    f.qb = waves_for(D) * QW;
+    f.qb = qb_for(D);
     f.wg_per_cu = D <= 48 ? 2 : 1;
-    f.rec_bytes = (size_t)rec_floats(D) * (waves_for(D) * 64) * sizeof(float);
-    f.xcd_min_nqb = 64;
+    f.rec_bytes = (size_t)rec_size(D) * sizeof(float);
+    f.xcd_min_nqb = XCD_MIN_NQB;
     f.ws_devplan_min_tiles = 16;
     if constexpr (lds_for(D) > 64 * 1024) f.lds_opt_in = opt_in_lds<attention_kernel<T, D, FOLD>, lds_for(D)>;
     f.main = launch_main<T, D, FOLD>;

@@ -20,6 +20,8 @@
 
 namespace {
 
+constexpr int QSUB16S = 2, QB16S = qb16(QSUB16S);     // query sub-tiles per wave, query rows per workgroup
+
 // ---- the skewed pipeline (tools/ubench/attn_tile_model.hip `tile_model2`: 620 cycles per 32-query tile-wave against 703 for
 // the plain order -- profiles/r06_c_ubench_skewed_pipeline.txt) ----
 // With two sub-tiles A, B per wave EVERY matrix phase gets independent VALU work of the same wave into its basic block:
@@ -30,37 +32,22 @@ namespace {
 // V^T stays double-buffered), the V^T fragments of tile t kept in registers across the barrier for B's deferred PV, one
 // barrier per tile.  The rare exact redo of a sub-tile (first tile / scores that outgrew the shift) re-reads its K
 // fragments from the ring.  Arithmetic per query and tile identical to attention_kernel's PV16 path.
-template <typename T, int D, bool FOLD, int WAVES>
-__global__ __launch_bounds__(WAVES * 64, 2) void attention16s_kernel(
+template <typename T, int D, bool FOLD>
+__global__ __launch_bounds__(NT16, 2) void attention16s_kernel(
     const T *__restrict__ q, int64_t ldq, const T *__restrict__ k, int64_t ldk,
     const T *__restrict__ vt, int64_t ldvt, T *__restrict__ out, int64_t ldo, int64_t H,
-    int64_t M, int64_t Mp, int64_t Mk_arg, int64_t Mkp, float scale_log2e, int64_t src_batch, int64_t nqb, int64_t nwhole,
-    int nsplit_tail, float *__restrict__ partial_base, int xcd_groups, const int32_t *__restrict__ q_count,
-    int64_t split_major_items, const int32_t *__restrict__ k_count, const uint32_t *__restrict__ k_bias, int64_t ldkb,
-    const DevPlan *__restrict__ dev_plan) {
+    int64_t M, int64_t Mp, int64_t Mk_arg, int64_t Mkp, float scale_log2e, int64_t src_batch,
+    const int32_t *__restrict__ k_count, const uint32_t *__restrict__ k_bias, int64_t ldkb, PlanArgs plan) {
     // Arguments as attention_kernel's.  Work item = (query block of QB = 512 rows, head, sample).
     using F = Frag<T>;
     using vec = typename F::vec;
     using elem = typename F::elem;
     static_assert(pv16_for(D) && (D % 16) != 0, "the 16-row O^T path: a head dim with a spare k-slot and a spare O^T row");
     static_assert(!FOLD || (D % 8 == 0 && D % 16 == 8), "key folding needs the spare k-slots of a d % 16 == 8 head");
-    constexpr int NQ = 2, KR = 3, VR = 2;
-    int64_t tier_item0 = nwhole, tier_wg0 = nwhole, tier_rec0 = 0;
-    if (dev_plan != nullptr) {        // query-bounded launch: the roles come from attention16_plan_kernel (wave-uniform loads)
-        nqb = dev_plan->nqb;
-        xcd_groups = nqb >= 32 ? xcd_groups : 0;
-        int ti = 0;
-        while (ti + 1 < dev_plan->ntiers && (int)blockIdx.x >= dev_plan->tier[ti + 1].wg0) ++ti;
-        const DevTier tr = dev_plan->tier[ti];
-        if ((int64_t)blockIdx.x >= (int64_t)tr.wg0 + (int64_t)tr.items * tr.nsplit) return;   // behind the last tier
-        nwhole = dev_plan->tier[0].items;
-        nsplit_tail = tr.nsplit;
-        split_major_items = tr.items;       // (inside a tier: all first pieces, then all second pieces ...)
-        tier_item0 = tr.item0;
-        tier_wg0 = tr.wg0;
-        tier_rec0 = tr.rec0;
-    }
-    constexpr int NT = WAVES * 64, QB = WAVES * QW * NQ, NV = NQ;
+    constexpr int NQ = QSUB16S, KR = 3, VR = 2;
+    constexpr int NT = NT16;
+    const WorkItem w = decode_work_item<QB16S, XCD_MIN_NQB16>(plan, H, blockIdx.x);   // (wave-uniform loads)
+    if (w.leave) return;
     constexpr int DK = (D + 15) / 16, DV16 = (D + 16) / 16, VROWS = vrows_for(D);
     constexpr int BIAS_HI = (D % 16) / 8, BIAS_E = D % 8;
     constexpr int K_STRIDE = DK * 16 + 8;
@@ -77,23 +64,17 @@ __global__ __launch_bounds__(WAVES * 64, 2) void attention16s_kernel(
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, hi = lane >> 5;
     const int l15 = lane & 15, g16 = lane >> 4;
-    const bool tail_wg = (int64_t)blockIdx.x >= nwhole;
-    const int64_t tail_id = (int64_t)blockIdx.x - tier_wg0;      // (host plan: one tier behind the whole items)
-    const int nsplit = tail_wg ? nsplit_tail : 1;
-    const int64_t tail_item = split_major_items ? tail_id % split_major_items : tail_id / nsplit;
-    const int split = !tail_wg ? 0 : split_major_items ? (int)(tail_id / split_major_items) : (int)(tail_id % nsplit);
-    const int64_t lin = item_of(tail_wg ? tier_item0 + tail_item : (int64_t)blockIdx.x, nqb, xcd_groups);
-    float *partial = tail_wg ? partial_base + (tier_rec0 + tail_item * nsplit + split) * NV * REC * NT : nullptr;
-    const int64_t b = lin / (nqb * H), h = (lin / nqb) % H;
+    const int nsplit = w.nsplit, split = w.split;
+    float *partial = w.rec >= 0 ? plan.partial_base + w.rec * rec16_size<D>(NQ) : nullptr;
+    const int64_t b = w.b, h = w.h;
     const int64_t bq = b % src_batch;
-    const int64_t qblock0 = (lin % nqb) * QB;
+    const int64_t qblock0 = w.q0;
     const int64_t C = H * D;
     int64_t Mk = Mk_arg;
     if constexpr (FOLD) {
         const int64_t kc = k_count[b];
         Mk = kc < Mk_arg ? (kc > 0 ? kc : 1) : Mk_arg;
     }
-    if (q_count != nullptr && qblock0 >= (int64_t)q_count[b]) return;
 
     // one-time LDS init: K pad columns = 0 except column D = 1 (it meets the shift in the query), V^T pad rows = 0 except
     // row D = 1 (the denominator row) -- tile loads never touch these.  FOLD: not the bias pair D + 2, D + 3, which every
@@ -487,31 +468,28 @@ __global__ __launch_bounds__(WAVES * 64, 2) void attention16s_kernel(
 }
 
 // ---- attention16s_kernel's family: 8 waves, two 32-query sub-tiles per wave, one workgroup per CU ----
-constexpr int WAVES16 = 8, NT16 = WAVES16 * 64;
 constexpr size_t LDS16 = (size_t)(3 * KV * ((40 + 15) / 16 * 16 + 8) + 2 * vrows_for(40) * VT_STRIDE) * 2;
 static_assert(LDS16 <= 64 * 1024, "dynamic LDS beyond 64 KB needs an opt-in (Family::lds_opt_in)");
 
 template <typename T, bool FOLD>
 void launch_main(const Call &c, const Launch &g) {
-    hipLaunchKernelGGL((attention16s_kernel<T, 40, FOLD, WAVES16>), dim3((unsigned)g.wgs), dim3(NT16), LDS16, c.s,
+    hipLaunchKernelGGL((attention16s_kernel<T, 40, FOLD>), dim3((unsigned)g.wgs), dim3(NT16), LDS16, c.s,
                        (const T *)c.q, c.ldq, (const T *)c.k, c.ldk, (const T *)c.vt, c.ldvt, (T *)c.out, c.ldo, c.h, c.M, c.Mp,
-                       c.Mk, c.Mkp, g.scale_log2e, g.src_batch, g.nqb, g.whole, g.nsplit, g.partial, g.xcd_groups, c.q_count,
-                       g.split_major, c.k_count, c.k_bias, c.ldkb, plan_of(g));
+                       c.Mk, c.Mkp, g.scale_log2e, g.src_batch, c.k_count, c.k_bias, c.ldkb, plan_args(c, g));
 }
 
 template <typename T>
 void launch_combine(const Call &c, const Launch &g) {
-    hipLaunchKernelGGL((attention16_combine_kernel<T, 40, 2, 1, WAVES16>), dim3((unsigned)g.split_items, 2u), dim3(NT16), 0,
-                       c.s, (const float *)g.partial, (T *)c.out, c.ldo, c.h, c.M, c.Mp, g.nqb, g.whole, g.nsplit, g.xcd_groups,
-                       c.q_count, g.src_batch, plan_of(g));
+    hipLaunchKernelGGL((attention16_combine_kernel<T, 40, QSUB16S, 1>), dim3((unsigned)g.split_items, (unsigned)QSUB16S),
+                       dim3(NT16), 0, c.s, (T *)c.out, c.ldo, c.h, c.M, c.Mp, g.src_batch, plan_args(c, g));
 }
 
 template <typename T, bool FOLD>
 Family make_family() {
     Family f;
-    f.qb = WAVES16 * QW * 2;
-    f.rec_bytes = (size_t)2 * rec16<40>() * NT16 * sizeof(float);   // (both sub-tiles)
-    f.xcd_min_nqb = 32;
+    f.qb = QB16S;
+    f.rec_bytes = (size_t)rec16_size<40>(QSUB16S) * sizeof(float);   // (both sub-tiles)
+    f.xcd_min_nqb = XCD_MIN_NQB16;
     f.main = launch_main<T, FOLD>;
     f.combine = launch_combine<T>;
     return f;

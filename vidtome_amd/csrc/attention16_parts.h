@@ -10,38 +10,31 @@ using namespace vtm_att;
 // per-(query sub-tile, value group) record a key-split workgroup leaves for attention16_combine_kernel: the PV16 record of
 // attention.hip (24 accumulators at d = 40, one running max per 16-query half, one unused denominator slot)
 template <int D> constexpr int rec16() { return (D + 16) / 16 * 8 + 2 + 1; }
+// the constants both wide-tile families share, for their kernels and their Family: workgroups of 8 waves, the XCD threshold
+// (Family::xcd_min_nqb), the query rows of a workgroup (NQ sub-tiles of 32 rows per wave), the floats of its partial records
+// (NV of them: query sub-tiles x value groups)
+constexpr int WAVES16 = 8, NT16 = WAVES16 * 64;
+constexpr int XCD_MIN_NQB16 = 32;
+constexpr int qb16(int NQ) { return WAVES16 * QW * NQ; }
+template <int D> constexpr int64_t rec16_size(int NV) { return (int64_t)NV * rec16<D>() * NT16; }
 
-template <typename T, int D, int NQ, int NG, int WAVES>
-__global__ __launch_bounds__(WAVES * 64) void attention16_combine_kernel(
-    const float *__restrict__ partial, T *__restrict__ out, int64_t ldo, int64_t H, int64_t M, int64_t Mp, int64_t nqb,
-    int64_t id0, int nsplit, int xcd_groups, const int32_t *__restrict__ q_count, int64_t src_batch,
-    const DevPlan *__restrict__ dev_plan) {
-    constexpr int NT = WAVES * 64, QB = WAVES * QW * NQ, NV = NQ * NG;
+template <typename T, int D, int NQ, int NG>
+__global__ __launch_bounds__(NT16) void attention16_combine_kernel(
+    T *__restrict__ out, int64_t ldo, int64_t H, int64_t M, int64_t Mp, int64_t src_batch, PlanArgs plan) {
+    constexpr int NT = NT16, NV = NQ * NG;
     constexpr int NA = (D + 16) / 16 * 8, REC = rec16<D>();
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int v = blockIdx.y, sub = v / NG, g = v % NG;
-    int64_t rec0 = (int64_t)blockIdx.x * nsplit;   // first partial record of this item
-    int64_t pos = id0 + blockIdx.x;
-    if (dev_plan != nullptr) {        // (the launch is sized for the most items a plan can split)
-        if ((int)blockIdx.x >= dev_plan->split_items) return;
-        nqb = dev_plan->nqb;
-        xcd_groups = nqb >= 32 ? xcd_groups : 0;
-        pos = dev_plan->tier[0].items + blockIdx.x;
-        int ti = 1;
-        while (ti + 1 < dev_plan->ntiers && pos >= dev_plan->tier[ti + 1].item0) ++ti;
-        const DevTier tr = dev_plan->tier[ti];
-        nsplit = tr.nsplit;
-        rec0 = tr.rec0 + (pos - tr.item0) * tr.nsplit;
-    }
-    const int64_t lin = item_of(pos, nqb, xcd_groups);
-    const int64_t b = lin / (nqb * H), h = (lin / nqb) % H;
-    const int64_t q0 = (lin % nqb) * QB + (wave * NQ + sub) * QW;
-    if (q_count != nullptr && (lin % nqb) * QB >= (int64_t)q_count[b]) return;   // its partial records were never written
+    const WorkItem w = decode_combine_item<qb16(NQ), XCD_MIN_NQB16>(plan, H, blockIdx.x);
+    if (w.leave) return;
+    const int64_t b = w.b, h = w.h, q0 = w.q0 + (wave * NQ + sub) * QW;
+    const int nsplit = w.nsplit;
+    const float *partial = plan.partial_base + w.rec * rec16_size<D>(NV);
     float acc[NA], m[2] = {-INFINITY, -INFINITY};
 #pragma unroll
     for (int r = 0; r < NA; ++r) acc[r] = 0.0f;
     for (int sp = 0; sp < nsplit; ++sp) {
-        const float *pp = partial + ((rec0 + sp) * NV + v) * REC * NT + tid;
+        const float *pp = partial + ((int64_t)sp * NV + v) * REC * NT + tid;
         float fa[2], fb[2];
 #pragma unroll
         for (int j = 0; j < 2; ++j) {

@@ -22,19 +22,19 @@
 
 namespace {
 
-template <typename T, int D, int NG, int WAVES>
-__global__ __launch_bounds__(WAVES * 64, 2) void attention16g_kernel(
+constexpr int QB16G = qb16(1);   // query rows per workgroup: one 32-row tile per wave
+
+template <typename T, int D, int NG>
+__global__ __launch_bounds__(NT16, 2) void attention16g_kernel(
     const T *__restrict__ q, int64_t ldq, const T *__restrict__ k, int64_t ldk,
     const T *__restrict__ vt, int64_t ldvt, T *__restrict__ out, int64_t ldo, int64_t H,
-    int64_t M, int64_t Mp, int64_t Mk, int64_t Mkp, float scale_log2e, int64_t src_batch, int64_t nqb, int64_t nwhole,
-    int nsplit_tail, float *__restrict__ partial_base, int xcd_groups, const int32_t *__restrict__ q_count,
-    const DevPlan *__restrict__ dev_plan) {
+    int64_t M, int64_t Mp, int64_t Mk, int64_t Mkp, float scale_log2e, int64_t src_batch, PlanArgs plan) {
     using F = Frag<T>;
     using vec = typename F::vec;
     using elem = typename F::elem;
     static_assert(pv16_for(D) && (D % 16) != 0, "the 16-row O^T path: a head dim with a spare k-slot and a spare O^T row");
     constexpr int KR = 3, VR = 3;
-    constexpr int NT = WAVES * 64, QB = WAVES * QW, NV = NG;
+    constexpr int NT = NT16;
     constexpr int DK = (D + 15) / 16, DV16 = (D + 16) / 16, VROWS = vrows_for(D);
     constexpr int BIAS_HI = (D % 16) / 8, BIAS_E = D % 8;
     constexpr int K_STRIDE = DK * 16 + 8;
@@ -51,36 +51,15 @@ __global__ __launch_bounds__(WAVES * 64, 2) void attention16g_kernel(
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, hi = lane >> 5;
     const int l15 = lane & 15, g16 = lane >> 4;
-    // query-bounded launch planned on the device (attention16_plan_kernel, see attention16s_kernel): the roles of the workgroups
-    // behind the whole items come from the plan's tiers (wave-uniform loads); inside a tier all first pieces, then all second ...
-    int64_t tier_item0 = nwhole, tier_wg0 = nwhole, tier_rec0 = 0, split_major_items = 0;
-    if (dev_plan != nullptr) {
-        nqb = dev_plan->nqb;
-        xcd_groups = nqb >= 32 ? xcd_groups : 0;
-        int ti = 0;
-        while (ti + 1 < dev_plan->ntiers && (int)blockIdx.x >= dev_plan->tier[ti + 1].wg0) ++ti;
-        const DevTier tr = dev_plan->tier[ti];
-        if ((int64_t)blockIdx.x >= (int64_t)tr.wg0 + (int64_t)tr.items * tr.nsplit) return;   // behind the last tier
-        nwhole = dev_plan->tier[0].items;
-        nsplit_tail = tr.nsplit;
-        split_major_items = tr.items;
-        tier_item0 = tr.item0;
-        tier_wg0 = tr.wg0;
-        tier_rec0 = tr.rec0;
-    }
-    const bool tail_wg = (int64_t)blockIdx.x >= nwhole;
-    const int64_t tail_id = (int64_t)blockIdx.x - tier_wg0;      // (host plan: one tier behind the whole items)
-    const int nsplit = tail_wg ? nsplit_tail : 1;
-    const int64_t tail_item = split_major_items ? tail_id % split_major_items : tail_id / nsplit;
-    const int split = !tail_wg ? 0 : split_major_items ? (int)(tail_id / split_major_items) : (int)(tail_id % nsplit);
-    const int64_t lin = item_of(tail_wg ? tier_item0 + tail_item : (int64_t)blockIdx.x, nqb, xcd_groups);
-    float *partial = tail_wg ? partial_base + (tier_rec0 + tail_item * nsplit + split) * NV * REC * NT : nullptr;
-    const int64_t b = lin / (nqb * H), h = (lin / nqb) % H;   // b: a SOURCE sample; the groups are the samples b + g * src_batch
-    const int64_t q0 = (lin % nqb) * QB + wave * QW;
+    // The grid runs over the SOURCE samples: so do q_count and the decode's b (compacted live queries are the same rows in
+    // every sample of a group).  A block beyond the source sample's count leaves at once, its key-split pieces too.
+    const WorkItem w = decode_work_item<QB16G, XCD_MIN_NQB16>(plan, H, blockIdx.x);
+    if (w.leave) return;
+    const int nsplit = w.nsplit, split = w.split;
+    float *partial = w.rec >= 0 ? plan.partial_base + w.rec * rec16_size<D>(NG) : nullptr;
+    const int64_t b = w.b, h = w.h;   // b: a SOURCE sample; the groups are the samples b + g * src_batch
+    const int64_t q0 = w.q0 + wave * QW;
     const int64_t C = H * D;
-    // a device-side query bound (compacted live queries, the same rows in every sample of the group): blocks beyond the source
-    // sample's count leave at once, the key-split pieces of such a block too (the combine kernel skips their records)
-    if (q_count != nullptr && (lin % nqb) * QB >= (int64_t)q_count[b]) return;
 
     for (int i = tid; i < KR * KV * (K_STRIDE - D); i += NT) {
         const int row = i / (K_STRIDE - D), c = D + i % (K_STRIDE - D);
@@ -427,36 +406,33 @@ __global__ __launch_bounds__(WAVES * 64, 2) void attention16g_kernel(
 }
 
 // ---- attention16g_kernel's family: 8 waves of 32 queries, one workgroup per CU, over the source samples ----
-constexpr int WAVES16G = 8, NT16G = WAVES16G * 64;
 constexpr size_t lds16g(int NG) { return (size_t)(3 * KV * ((40 + 15) / 16 * 16 + 8) + 3 * NG * vrows_for(40) * VT_STRIDE) * 2; }
 
 template <typename T, int NG>
 void launch_main(const Call &c, const Launch &g) {
-    hipLaunchKernelGGL((attention16g_kernel<T, 40, NG, WAVES16G>), dim3((unsigned)g.wgs), dim3(NT16G), lds16g(NG), c.s,
+    hipLaunchKernelGGL((attention16g_kernel<T, 40, NG>), dim3((unsigned)g.wgs), dim3(NT16), lds16g(NG), c.s,
                        (const T *)c.q, c.ldq, (const T *)c.k, c.ldk, (const T *)c.vt, c.ldvt, (T *)c.out, c.ldo, c.h, c.M, c.Mp,
-                       c.Mk, c.Mkp, g.scale_log2e, g.src_batch, g.nqb, g.whole, g.nsplit, g.partial, g.xcd_groups, c.q_count,
-                       plan_of(g));
+                       c.Mk, c.Mkp, g.scale_log2e, g.src_batch, plan_args(c, g));
 }
 
 template <typename T, int NG>
 void launch_combine(const Call &c, const Launch &g) {
-    hipLaunchKernelGGL((attention16_combine_kernel<T, 40, 1, NG, WAVES16G>), dim3((unsigned)g.split_items, (unsigned)NG),
-                       dim3(NT16G), 0, c.s, (const float *)g.partial, (T *)c.out, c.ldo, c.h, c.M, c.Mp, g.nqb, g.whole,
-                       g.nsplit, g.xcd_groups, c.q_count, g.src_batch, plan_of(g));
+    hipLaunchKernelGGL((attention16_combine_kernel<T, 40, 1, NG>), dim3((unsigned)g.split_items, (unsigned)NG), dim3(NT16), 0,
+                       c.s, (T *)c.out, c.ldo, c.h, c.M, c.Mp, g.src_batch, plan_args(c, g));
 }
 
 template <typename T, int NG>
 Family make_family() {
     Family f;
-    f.qb = WAVES16G * QW;
-    f.rec_bytes = (size_t)NG * rec16<40>() * NT16G * sizeof(float);   // (one record per value group)
+    f.qb = QB16G;
+    f.rec_bytes = (size_t)rec16_size<40>(NG) * sizeof(float);   // (one record per value group)
     f.share = NG;
-    f.xcd_min_nqb = 32;
+    f.xcd_min_nqb = XCD_MIN_NQB16;
     // no split-major order in this kernel: a query-bounded launch is planned on the device (a host plan for Mq rows left the
     // last round of the LIVE items mostly idle -- 34 816 rows, 0.78 live: 849 items on 256 slots took 4 rounds for 3.3 rounds
     // of work), or else takes the plain host plan
     f.host_split_all = false;
-    if constexpr (lds16g(NG) > 64 * 1024) f.lds_opt_in = opt_in_lds<attention16g_kernel<T, 40, NG, WAVES16G>, lds16g(NG)>;
+    if constexpr (lds16g(NG) > 64 * 1024) f.lds_opt_in = opt_in_lds<attention16g_kernel<T, 40, NG>, lds16g(NG)>;
     f.main = launch_main<T, NG>;
     f.combine = launch_combine<T, NG>;
     return f;

@@ -33,6 +33,7 @@ constexpr int FVT_STRIDE = KT + 4;     // floats per V^T row in LDS (36 = 4 x od
 // widest heads (d = 160: 2 x (40 + 40) registers for Q and O^T alone)
 constexpr int nqh_for(int D) { return D >= 128 ? 1 : 2; }
 constexpr int fqb_for(int D) { return F_WAVES * 16 * nqh_for(D); }           // queries per workgroup
+constexpr int F_XCD_MIN_NQB = 64;                                             // Family::xcd_min_nqb
 constexpr int fwg_per_cu(int D) { return D <= 128 ? 2 : 1; }    // resident workgroups per CU (LDS: d = 160 takes 88 KB)
 constexpr int dv16_for(int D) { return (D + 15) / 16; }                       // 16-row blocks of O^T
 constexpr int fk_stride(int D) { return D + 4; }                              // floats per K row in LDS (4 x odd words)
@@ -40,7 +41,7 @@ constexpr int fk_stride(int D) { return D + 4; }                              //
 // running max of half 0 / half 1, denominator of half 0 / half 1 (they are the same in the four groups of a query)
 constexpr int facc_floats(int D) { return dv16_for(D) * 4 * nqh_for(D); }
 constexpr int frec_floats(int D) { return facc_floats(D) + 1; }
-constexpr size_t frec_bytes(int D) { return (size_t)frec_floats(D) * F_NT * sizeof(float); }
+constexpr int64_t frec_size(int D) { return (int64_t)frec_floats(D) * F_NT; }   // floats of a workgroup's partial record
 constexpr size_t flds_bytes(int D) { return (size_t)2 * (KT * fk_stride(D) + dv16_for(D) * 16 * FVT_STRIDE) * sizeof(float); }
 
 __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
@@ -77,27 +78,14 @@ __device__ __forceinline__ void store_row(const f32x4 (&o)[dv16_for(D)], float i
 // merges the `nsplit` partial records of a query block (same thread <-> register mapping as attention_f32_kernel)
 template <int D>
 __global__ __launch_bounds__(F_NT) void attention_f32_combine_kernel(
-    const float *__restrict__ partial, float *__restrict__ out, int64_t ldo, int64_t H, int64_t M, int64_t Mp, int64_t nqb,
-    int64_t id0, int nsplit, int xcd_groups, const int32_t *__restrict__ q_count, const DevPlan *__restrict__ dev_plan) {
-    constexpr int NQH = nqh_for(D), QB = fqb_for(D), DV = dv16_for(D), NA = facc_floats(D), REC = frec_floats(D);
+    float *__restrict__ out, int64_t ldo, int64_t H, int64_t M, int64_t Mp, PlanArgs plan) {
+    constexpr int NQH = nqh_for(D), DV = dv16_for(D), NA = facc_floats(D);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, g = lane >> 4;
-    int64_t rec0 = (int64_t)blockIdx.x * nsplit;
-    int64_t pos = id0 + blockIdx.x;
-    if (dev_plan != nullptr) {        // device-planned launch: sized for the most items a plan can split
-        if ((int)blockIdx.x >= dev_plan->split_items) return;
-        nqb = dev_plan->nqb;
-        xcd_groups = nqb >= 64 ? xcd_groups : 0;
-        pos = dev_plan->tier[0].items + blockIdx.x;
-        int ti = 1;
-        while (ti + 1 < dev_plan->ntiers && pos >= dev_plan->tier[ti + 1].item0) ++ti;
-        const DevTier tr = dev_plan->tier[ti];
-        nsplit = tr.nsplit;
-        rec0 = tr.rec0 + (pos - tr.item0) * tr.nsplit;
-    }
-    const int64_t lin = item_of(pos, nqb, xcd_groups);
-    const int64_t b = lin / (nqb * H), h = (lin / nqb) % H;
-    const int64_t q0 = (lin % nqb) * QB + wave * 16 * NQH;
-    if (q_count != nullptr && (lin % nqb) * QB >= (int64_t)q_count[b]) return;   // its partial records were never written
+    const WorkItem w = decode_combine_item<fqb_for(D), F_XCD_MIN_NQB>(plan, H, blockIdx.x);
+    if (w.leave) return;
+    const int64_t b = w.b, h = w.h, q0 = w.q0 + wave * 16 * NQH;
+    const int nsplit = w.nsplit;
+    const float *partial = plan.partial_base + w.rec * frec_size(D);
     f32x4 o[DV][NQH];
     float m[NQH], l[NQH];
 #pragma unroll
@@ -108,7 +96,7 @@ __global__ __launch_bounds__(F_NT) void attention_f32_combine_kernel(
         for (int dv = 0; dv < DV; ++dv) o[dv][qh] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     for (int sp = 0; sp < nsplit; ++sp) {
-        const float *pp = partial + (rec0 + sp) * REC * F_NT + tid;
+        const float *pp = partial + sp * frec_size(D) + tid;
         const float ml = pp[NA * F_NT];
 #pragma unroll
         for (int qh = 0; qh < NQH; ++qh) {
@@ -139,12 +127,10 @@ template <int D>
 __global__ __launch_bounds__(F_NT, fwg_per_cu(D)) void attention_f32_kernel(
     const float *__restrict__ q, int64_t ldq, const float *__restrict__ k, int64_t ldk, const float *__restrict__ vt,
     int64_t ldvt, float *__restrict__ out, int64_t ldo, int64_t H, int64_t M, int64_t Mp, int64_t Mk, int64_t Mkp,
-    float scale_log2e, int64_t src_batch, int64_t nqb, int64_t nwhole, int nsplit_tail, float *__restrict__ partial_base,
-    int xcd_groups, const int32_t *__restrict__ q_count, int64_t split_major_items, const DevPlan *__restrict__ dev_plan) {
-    // Work decomposition as attention_kernel: work item = (query block, head, sample), query blocks fastest; workgroups
-    // [0, nwhole) take one item and all its key tiles, the ones behind them a key range of a split item and leave a
+    float scale_log2e, int64_t src_batch, PlanArgs plan) {
+    // Work decomposition as attention_kernel (decode_work_item); a workgroup that takes a key range of a split item leaves a
     // partial record for attention_f32_combine_kernel.
-    constexpr int NQH = nqh_for(D), QB = fqb_for(D), DV = dv16_for(D), DS = D / 4;
+    constexpr int NQH = nqh_for(D), DV = dv16_for(D), DS = D / 4;
     constexpr int KS = fk_stride(D);
     constexpr int CHUNKS = KT * D / 4;                     // 16-byte pieces of a K tile = of a V^T tile
     constexpr int PER_T = (CHUNKS + F_NT - 1) / F_NT;
@@ -157,33 +143,14 @@ __global__ __launch_bounds__(F_NT, fwg_per_cu(D)) void attention_f32_kernel(
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l15 = lane & 15, g = lane >> 4;
-    int64_t tier_item0 = nwhole, tier_wg0 = nwhole, tier_rec0 = 0;
-    if (dev_plan != nullptr) {   // query-bounded launch planned on the device (attention_plan.h)
-        nqb = dev_plan->nqb;
-        xcd_groups = nqb >= 64 ? xcd_groups : 0;
-        int ti = 0;
-        while (ti + 1 < dev_plan->ntiers && (int)blockIdx.x >= dev_plan->tier[ti + 1].wg0) ++ti;
-        const DevTier tr = dev_plan->tier[ti];
-        if ((int64_t)blockIdx.x >= (int64_t)tr.wg0 + (int64_t)tr.items * tr.nsplit) return;
-        nwhole = dev_plan->tier[0].items;
-        nsplit_tail = tr.nsplit;
-        split_major_items = tr.items;
-        tier_item0 = tr.item0;
-        tier_wg0 = tr.wg0;
-        tier_rec0 = tr.rec0;
-    }
-    const bool tail_wg = (int64_t)blockIdx.x >= nwhole;
-    const int64_t tail_id = (int64_t)blockIdx.x - tier_wg0;
-    const int nsplit = tail_wg ? nsplit_tail : 1;
-    const int64_t tail_item = split_major_items ? tail_id % split_major_items : tail_id / nsplit;
-    const int split = !tail_wg ? 0 : split_major_items ? (int)(tail_id / split_major_items) : (int)(tail_id % nsplit);
-    const int64_t lin = item_of(tail_wg ? tier_item0 + tail_item : (int64_t)blockIdx.x, nqb, xcd_groups);
-    float *partial = tail_wg ? partial_base + (tier_rec0 + tail_item * nsplit + split) * frec_floats(D) * F_NT : nullptr;
-    const int64_t b = lin / (nqb * H), h = (lin / nqb) % H;
+    const WorkItem w = decode_work_item<fqb_for(D), F_XCD_MIN_NQB>(plan, H, blockIdx.x);
+    if (w.leave) return;
+    const int nsplit = w.nsplit, split = w.split;
+    float *partial = w.rec >= 0 ? plan.partial_base + w.rec * frec_size(D) : nullptr;
+    const int64_t b = w.b, h = w.h;
     const int64_t bq = b % src_batch;  // PnP injection: q / k of the source sample (pnp_utils.py:57-67)
-    const int64_t q0 = (lin % nqb) * QB + wave * 16 * NQH;
+    const int64_t q0 = w.q0 + wave * 16 * NQH;
     const int64_t C = H * D;
-    if (q_count != nullptr && (lin % nqb) * QB >= (int64_t)q_count[b]) return;
 
     // V^T rows D .. 16 DV - 1 (d % 16 == 8) meet O^T rows nobody stores: zero them once (tile loads never touch them)
     if constexpr (DV * 16 > D) {
@@ -425,15 +392,13 @@ template <int D>
 void launch_main(const Call &c, const Launch &g) {
     hipLaunchKernelGGL(attention_f32_kernel<D>, dim3((unsigned)g.wgs), dim3(F_NT), flds_bytes(D), c.s, (const float *)c.q,
                        c.ldq, (const float *)c.k, c.ldk, (const float *)c.vt, c.ldvt, (float *)c.out, c.ldo, c.h, c.M, c.Mp,
-                       c.Mk, c.Mkp, g.scale_log2e, g.src_batch, g.nqb, g.whole, g.nsplit, g.partial, g.xcd_groups, c.q_count,
-                       g.split_major, plan_of(g));
+                       c.Mk, c.Mkp, g.scale_log2e, g.src_batch, plan_args(c, g));
 }
 
 template <int D>
 void launch_combine(const Call &c, const Launch &g) {
     hipLaunchKernelGGL(attention_f32_combine_kernel<D>, dim3((unsigned)g.split_items), dim3(F_NT), 0, c.s,
-                       (const float *)g.partial, (float *)c.out, c.ldo, c.h, c.M, c.Mp, g.nqb, g.whole, g.nsplit, g.xcd_groups,
-                       c.q_count, plan_of(g));
+                       (float *)c.out, c.ldo, c.h, c.M, c.Mp, plan_args(c, g));
 }
 
 template <int D>
@@ -442,11 +407,11 @@ Family make_family() {
     f.name = "vtm_attention (fp32)";
     f.qb = fqb_for(D);
     f.wg_per_cu = fwg_per_cu(D);
-    f.rec_bytes = frec_bytes(D);
+    f.rec_bytes = (size_t)frec_size(D) * sizeof(float);
     // a device plan counts this kernel's 32-key tiles; the host plan (plan_tail) counts 64-key tiles in its thresholds and
     // the pieces are cut from 32-key tiles
     f.key_tile = KT;
-    f.xcd_min_nqb = 64;
+    f.xcd_min_nqb = F_XCD_MIN_NQB;
     if constexpr (flds_bytes(D) > 64 * 1024) f.lds_opt_in = opt_in_lds<attention_f32_kernel<D>, flds_bytes(D)>;
     f.main = launch_main<D>;
     f.combine = launch_combine<D>;

@@ -1,7 +1,9 @@
 // How an attention launch is planned and issued, once for the five kernel families (attention_kernel in attention.hip,
 // attention16s_kernel in attention16.hip, attention16g_kernel in attention16g.hip, attention_f32_kernel in
 // attention_f32.hip, attention_sets_kernel in attention_sets.hip): the host tail plan, the device plan of query-bounded launches, the family descriptor, the launch
-// driver, the workspace size and the head-dim dispatch.  Header-only; host code apart from attention16_plan_kernel.
+// driver, the workspace size and the head-dim dispatch -- and the device side of the same plan: how a workgroup of a main or
+// combine kernel finds its work item (decode_work_item, decode_combine_item).  Header-only; host code apart from those and
+// attention16_plan_kernel.
 #pragma once
 #include "attention_common.h"
 
@@ -173,6 +175,110 @@ struct DevPlan {
     int nqb, ntiers, split_items, pad;     // live query blocks per (sample, head); tiers in use; items behind tier 0
     DevTier tier[PLAN_TIERS];
 };
+
+// ---- the planning arguments of a launch: ONE by-value argument of every main and combine kernel (plan_args below) ----
+struct PlanArgs {
+    int64_t nqb, nwhole;         // query blocks per (sample, head); the items in front of the split ones, one workgroup each
+    int64_t split_major_items;   // host plan: the items split in split-major order (plan_tail's split_all), else 0
+    float *partial_base;         // partial records of the key-split workgroups
+    const int32_t *q_count;      // device-side query bound of every sample the grid runs over, or nullptr
+    const DevPlan *dev_plan;     // a device-planned launch: nqb and the roles come from it (the host values are upper bounds)
+    int nsplit_tail, xcd_groups; // host plan: pieces per split item; see item_of
+};
+
+// what one workgroup does, decoded from its index and the PlanArgs (all of it wave-uniform)
+struct WorkItem {
+    int64_t b, h, q0;   // sample of the grid, head, first query row of the item's query block
+    int64_t rec;        // main kernel: the partial record this key-split workgroup leaves (-1: a whole item, it writes the
+                        // output); combine kernel: the first record of the item.  In records: the caller knows their size
+    int nsplit, split;  // pieces of the item along the key axis, and which one this workgroup is
+    bool leave;         // no role in the plan, or a query block at or beyond q_count[b]: return at once
+};
+
+// work item `lin` (query blocks fastest, then heads, then samples) -> its coordinates and the q_count exit
+template <int QB>
+__device__ __forceinline__ WorkItem item_coords(int64_t lin, int64_t nqb, int64_t H, const int32_t *q_count = nullptr) {
+    WorkItem w{};
+    w.b = lin / (nqb * H);
+    w.h = (lin / nqb) % H;
+    w.q0 = (lin % nqb) * QB;
+    w.rec = -1;
+    w.nsplit = 1;
+    // device-side query bound (compacted live queries, vtm_compact_queries): the launch is sized for the host-known upper
+    // bound; a query block that starts at or beyond its sample's count has nothing anybody reads (and leaves no record)
+    w.leave = q_count != nullptr && w.q0 >= (int64_t)q_count[w.b];
+    return w;
+}
+
+// Main kernels: workgroup `wg` of the grid.  Workgroups [0, nwhole) take one item each and all its key tiles; the ones
+// behind them share the remaining items nsplit ways along the key axis, split-minor (a partly filled last round: the
+// pieces of an item sit next to each other) or split-MAJOR (all first pieces, then all second pieces ..., so that workgroup
+// p and its item still share p % 8 = the XCD the item's (sample, head) pair is pinned to: a host plan that splits EVERY
+// item, and every tier of a device plan).  A device plan (one thread made it from the live counts: whole items, then tiers
+// split 2, 4, 8, 16 ways) overrides the host's upper bounds; workgroups behind its last tier leave.
+// QB: query rows per workgroup; XCD_MIN_NQB: the family's Family::xcd_min_nqb, which a device plan checks here.
+template <int QB, int XCD_MIN_NQB>
+__device__ __forceinline__ WorkItem decode_work_item(const PlanArgs &p, int64_t H, int64_t wg) {
+    int64_t nqb = p.nqb, nwhole = p.nwhole, split_major_items = p.split_major_items;
+    int nsplit_tail = p.nsplit_tail, xcd_groups = p.xcd_groups;
+    int64_t tier_item0 = nwhole, tier_wg0 = nwhole, tier_rec0 = 0;   // (host plan: one tier behind the whole items)
+    if (p.dev_plan != nullptr) {
+        nqb = p.dev_plan->nqb;
+        xcd_groups = nqb >= XCD_MIN_NQB ? xcd_groups : 0;
+        int ti = 0;
+        while (ti + 1 < p.dev_plan->ntiers && (int)wg >= p.dev_plan->tier[ti + 1].wg0) ++ti;
+        const DevTier tr = p.dev_plan->tier[ti];
+        if (wg >= (int64_t)tr.wg0 + (int64_t)tr.items * tr.nsplit) {   // behind the last tier
+            WorkItem w{};
+            w.leave = true;
+            return w;
+        }
+        nwhole = p.dev_plan->tier[0].items;
+        nsplit_tail = tr.nsplit;
+        split_major_items = tr.items;
+        tier_item0 = tr.item0;
+        tier_wg0 = tr.wg0;
+        tier_rec0 = tr.rec0;
+    }
+    const bool tail_wg = wg >= nwhole;
+    const int64_t tail_id = wg - tier_wg0;
+    const int nsplit = tail_wg ? nsplit_tail : 1;
+    const int64_t tail_item = split_major_items ? tail_id % split_major_items : tail_id / nsplit;
+    const int split = !tail_wg ? 0 : split_major_items ? (int)(tail_id / split_major_items) : (int)(tail_id % nsplit);
+    WorkItem w = item_coords<QB>(item_of(tail_wg ? tier_item0 + tail_item : wg, nqb, xcd_groups), nqb, H, p.q_count);
+    w.rec = tail_wg ? tier_rec0 + tail_item * nsplit + split : -1;
+    w.nsplit = nsplit;
+    w.split = split;
+    return w;
+}
+
+// Combine kernels: split item `idx` of the launch (a device-planned launch is sized for the most items a plan can split).
+// It must see the items exactly as decode_work_item does -- same QB, same XCD_MIN_NQB -- or it merges other items' records.
+template <int QB, int XCD_MIN_NQB>
+__device__ __forceinline__ WorkItem decode_combine_item(const PlanArgs &p, int64_t H, int64_t idx) {
+    int64_t nqb = p.nqb, pos = p.nwhole + idx, rec0 = idx * p.nsplit_tail;
+    int nsplit = p.nsplit_tail, xcd_groups = p.xcd_groups;
+    if (p.dev_plan != nullptr) {
+        if ((int)idx >= p.dev_plan->split_items) {
+            WorkItem w{};
+            w.leave = true;
+            return w;
+        }
+        nqb = p.dev_plan->nqb;
+        xcd_groups = nqb >= XCD_MIN_NQB ? xcd_groups : 0;
+        pos = p.dev_plan->tier[0].items + idx;
+        int ti = 1;
+        while (ti + 1 < p.dev_plan->ntiers && pos >= p.dev_plan->tier[ti + 1].item0) ++ti;
+        const DevTier tr = p.dev_plan->tier[ti];
+        nsplit = tr.nsplit;
+        rec0 = tr.rec0 + (pos - tr.item0) * tr.nsplit;
+    }
+    WorkItem w = item_coords<QB>(item_of(pos, nqb, xcd_groups), nqb, H, p.q_count);   // (dead block: its records were never written)
+    w.rec = rec0;
+    w.nsplit = nsplit;
+    return w;
+}
+
 // upper bounds of a plan on S slots: workgroups behind the whole items / partial records, items that are split
 constexpr int64_t plan_tail_wgs(int slots) { return (int64_t)(PLAN_TIERS - 1) * slots; }
 constexpr int64_t plan_split_items(int slots) { return slots; }
@@ -221,7 +327,10 @@ constexpr size_t DEVPLAN_HEADER = 256;
 static_assert(sizeof(DevPlan) <= 256, "the plan lives in the workspace header");
 inline size_t devplan_ws_bytes(int slots, size_t rec_bytes) { return DEVPLAN_HEADER + (size_t)plan_tail_wgs(slots) * rec_bytes; }
 
-inline const DevPlan *plan_of(const Launch &g) { return static_cast<const DevPlan *>(g.plan); }
+// the PlanArgs of a planned launch, for a family's launch thunks
+inline PlanArgs plan_args(const Call &c, const Launch &g) {
+    return {g.nqb, g.whole, g.split_major, g.partial, c.q_count, static_cast<const DevPlan *>(g.plan), g.nsplit, g.xcd_groups};
+}
 
 // once per (kernel, device): lets Kernel use LDS bytes of dynamic LDS, beyond the default 64 KB (a Family's lds_opt_in)
 template <auto Kernel, size_t LDS>

@@ -27,6 +27,7 @@ namespace {
 constexpr int sets_waves(int D) { return D <= 96 ? 8 : 4; }
 // resident workgroups per CU (the launch bounds' waves per SIMD follow from it): d = 40 and 64 need 168 VGPRs and spill at 128
 constexpr int sets_wg_per_cu(int D) { return D <= 32 ? 2 : 1; }
+constexpr int sets_qb(int D) { return sets_waves(D) * QW; }   // query rows per workgroup
 
 template <typename T, int D>
 __global__ __launch_bounds__(sets_waves(D) * 64, sets_wg_per_cu(D) * sets_waves(D) / 4) void attention_sets_kernel(
@@ -36,7 +37,7 @@ __global__ __launch_bounds__(sets_waves(D) * 64, sets_wg_per_cu(D) * sets_waves(
     using F = Frag<T>;
     using vec = typename F::vec;
     using elem = typename F::elem;
-    constexpr int WAVES = sets_waves(D), NT = WAVES * 64, QB = WAVES * QW;
+    constexpr int WAVES = sets_waves(D), NT = WAVES * 64;
     constexpr bool SPLIT_P = std::is_same_v<T, vtm_bf16>;   // P as hi + lo parts (see tile)
     constexpr int DK = (D + 15) / 16;      // k-steps of the QK^T contraction
     constexpr int DV = (D + 31) / 32;      // 32-row blocks of O^T
@@ -51,9 +52,8 @@ __global__ __launch_bounds__(sets_waves(D) * 64, sets_wg_per_cu(D) * sets_waves(
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, hi = lane >> 5;
-    const int64_t lin = item_of((int64_t)blockIdx.x, nqb, xcd_groups);
-    const int64_t b = lin / (nqb * H), h = (lin / nqb) % H;
-    const int64_t q0 = (lin % nqb) * QB + wave * QW;
+    const WorkItem w = item_coords<sets_qb(D)>(item_of((int64_t)blockIdx.x, nqb, xcd_groups), nqb, H);   // (never key-split)
+    const int64_t b = w.b, h = w.h, q0 = w.q0 + wave * QW;
     const int64_t C = H * D;
 
     // one-time LDS init: the K pad columns meet Q's zero padding and the V^T pad rows feed O^T rows nobody stores, but
@@ -281,7 +281,7 @@ template <typename T, int D>
 Family sets_family() {
     Family f;
     f.name = "vtm_attention_kv_sets";
-    f.qb = sets_waves(D) * QW;
+    f.qb = sets_qb(D);
     f.wg_per_cu = sets_wg_per_cu(D);
     f.rec_bytes = 0;
     f.xcd_min_nqb = 64;
