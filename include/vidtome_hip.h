@@ -360,6 +360,25 @@ int vtm_attention_kv_sets(const void *q, int64_t ldq, const void *k, int64_t ldk
                           int64_t Mkp, int64_t d, float scale, int n_sets, const int64_t *set_start,
                           const int64_t *set_len, const float *set_weight, vtm_stream_t stream);
 
+/* vtm_attention_kv_sets_masked -- the same sum with a weight PER QUERY on chosen sets: what Diffusers' IP-Adapter region
+ * masks (`cross_attention_kwargs={"ip_adapter_masks": [...]}`, one image prompt per region of the frame) turn the
+ * `self.attn2(...)` call of vidtome/patch.py:178-183 into.  Per head
+ *     out[b, i] = sum_{s < n_sets} w_s * m_s[b, i] * softmax_{j in set s}(q[b, i] . k[b, j] * scale) v[b, j]
+ *     m_s[b, i] = set_mask[s] < 0 ? 1 : mask[b * mask_batch_stride + set_mask[s] * ld_mask + i]
+ * All arguments of vtm_attention_kv_sets, then: set_mask, n_sets HOST ints, each -1 (the set is not masked) or a row of the
+ * table, 0 <= row < n_sets (a table has at most one row per set; sets may share a row); mask, a DEVICE pointer to fp32
+ * weights, rows of ld_mask >= Mq elements (may be NULL when no set is masked); mask_batch_stride, in elements: 0 when one
+ * table serves every sample (what Diffusers gives), else at least (largest row + 1) * ld_mask.  The weights are shared by the
+ * heads and may be fractional, negative or above 1 (a bicubic downsample overshoots).  Set s is folded into the fp32 sum with
+ * the factor (w_s * m_s) / l_s: a weight of 1 gives the bits of the unmasked call, and with every set_mask[s] == -1 the call
+ * IS vtm_attention_kv_sets (the same kernel).  The masked term is weighted in fp32 and the sum rounded once, where the
+ * processor rounds every term, multiplies and adds in the model's dtype.  Rows >= Mq of out are not written. */
+int vtm_attention_kv_sets_masked(const void *q, int64_t ldq, const void *k, int64_t ldk, const void *vt, int64_t ldvt,
+                                 void *out, int64_t ldo, int dtype, int64_t B, int64_t h, int64_t Mq, int64_t Mqp,
+                                 int64_t Mkp, int64_t d, float scale, int n_sets, const int64_t *set_start,
+                                 const int64_t *set_len, const float *set_weight, const int *set_mask, const float *mask,
+                                 int64_t ld_mask, int64_t mask_batch_stride, vtm_stream_t stream);
+
 /* vtm_attention_kv with a DEVICE-side query bound: sample b only has q_count[b] <= Mq meaningful query rows (the
  * compacted live queries of vtm_compact_queries); query blocks that start at or beyond the count exit at once, rows
  * beyond it are not meaningful.  The launch is sized for the host-known bound Mq -- no host round trip. */

@@ -70,6 +70,9 @@ _SIGNATURES = {
                           _f32, _int, _vp, ctypes.c_size_t, _vp], _int),
     "vtm_attention_kv_sets": ([_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _f32,
                                _int, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_f32), _vp], _int),
+    "vtm_attention_kv_sets_masked": ([_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _f32,
+                                      _int, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_f32),
+                                      ctypes.POINTER(_int), _vp, _i64, _i64, _vp], _int),
     "vtm_attention_kv_bounded": ([_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                   _f32, _vp, _vp, ctypes.c_size_t, _vp], _int),
     "vtm_attention_kv_shared_bounded": ([_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
@@ -717,6 +720,48 @@ def attention_kv_sets(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads:
     _check(lib().vtm_attention_kv_sets(q.data_ptr(), q.stride(1), k.data_ptr(), k.stride(1), vt.data_ptr(), vt.stride(1),
                                        out.data_ptr(), C, dtype_code(q), B, heads, Mq, Mqp, Mkp, d, float(scale), n, starts,
                                        lens, weights, _stream()), "vtm_attention_kv_sets")
+    return out
+
+
+@_on_device
+def attention_kv_sets_masked(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, Mq: int, sets, scale: float,
+                             set_mask, mask: Optional[torch.Tensor]) -> torch.Tensor:
+    """attention_kv_sets with a weight per query on chosen sets (vtm_attention_kv_sets_masked): ``set_mask[s]`` is -1 (set s
+    is weighted by its scalar alone) or a row of ``mask``, fp32 on q's device, (R, ld) -- one table for every sample, what
+    Diffusers' ``ip_adapter_masks`` give -- or (B, R, ld) with a table per sample; ld >= Mq, the weights are shared by the
+    heads.  The result is sum_s weight_s * mask[set_mask[s]][query] * softmax(q K_s^T * scale) V_s, the masked term weighted
+    in fp32.  With every ``set_mask[s] == -1`` this IS attention_kv_sets(q, k, vt, heads, Mq, sets, scale)."""
+    sets = [(int(s), int(n), float(w)) for s, n, w in sets]
+    rows = [int(r) for r in set_mask]
+    if len(rows) != len(sets):
+        raise RuntimeError(f"attention_kv_sets_masked: {len(sets)} sets but {len(rows)} mask rows")
+    if all(r == -1 for r in rows):
+        return attention_kv_sets(q, k, vt, heads, Mq, sets, scale)
+    if not 1 <= len(sets) <= MAX_KEY_SETS:
+        raise RuntimeError(f"attention_kv_sets_masked: 1 .. {MAX_KEY_SETS} key sets, got {len(sets)}")
+    if q.dtype not in (torch.float16, torch.bfloat16) or k.dtype != q.dtype or vt.dtype != q.dtype:
+        raise RuntimeError("attention_kv_sets_masked: q, k and vt must share one of fp16 / bf16")
+    B, Mqp, C = q.shape
+    Mkp = k.shape[1]
+    d = C // heads
+    if k.shape[0] != B or vt.shape[0] != B or k.shape[2] != C or vt.shape[1] != C:
+        raise RuntimeError("attention_kv_sets_masked: k must be (B, Mkp, C) and vt (B, C, ldvt)")
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.float32 or mask.device != q.device \
+            or mask.dim() not in (2, 3) or not mask.is_contiguous() or mask.shape[-1] < Mq \
+            or (mask.dim() == 3 and mask.shape[0] != B):
+        raise RuntimeError("attention_kv_sets_masked: mask must be contiguous fp32 on q's device, (R, >= Mq) or (B, R, >= Mq)")
+    R, ld = mask.shape[-2], mask.shape[-1]
+    if not all(-1 <= r < R for r in rows):
+        raise RuntimeError(f"attention_kv_sets_masked: mask rows {rows} do not lie in the table of {R} rows")
+    out = _attention_out(q, k, vt, Mq, Mkp)
+    n = len(sets)
+    starts = (_i64 * n)(*[s for s, _, _ in sets])
+    lens = (_i64 * n)(*[m for _, m, _ in sets])
+    weights = (_f32 * n)(*[w for _, _, w in sets])
+    _check(lib().vtm_attention_kv_sets_masked(q.data_ptr(), q.stride(1), k.data_ptr(), k.stride(1), vt.data_ptr(),
+                                              vt.stride(1), out.data_ptr(), C, dtype_code(q), B, heads, Mq, Mqp, Mkp, d,
+                                              float(scale), n, starts, lens, weights, (_int * n)(*rows), mask.data_ptr(), ld,
+                                              R * ld if mask.dim() == 3 else 0, _stream()), "vtm_attention_kv_sets_masked")
     return out
 
 

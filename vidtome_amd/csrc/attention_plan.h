@@ -73,6 +73,7 @@ struct Call {
     int dtype; int64_t B, h, M, Mp, Mk, Mkp; float scale; int share_groups; void *ws; size_t ws_bytes;
     const int32_t *q_count; hipStream_t s; bool fold; const int32_t *k_count; const uint32_t *k_bias; int64_t ldkb;
     const struct KeySets *sets = nullptr;   // vtm_attention_kv_sets only: the key ranges, each with a softmax of its own
+    const struct SetMasks *set_masks = nullptr;   // vtm_attention_kv_sets_masked only: the per-query weights of the sets
 };
 
 // ---- the key sets of one vtm_attention_kv_sets call (attention_sets.hip): set s = keys [start[s], start[s] + len[s]) ----
@@ -81,6 +82,13 @@ struct KeySets {
     int n;
     int start[MAX_KEY_SETS], len[MAX_KEY_SETS];
     float w[MAX_KEY_SETS];
+};
+// ---- the per-query weights of a vtm_attention_kv_sets_masked call: set s is weighted by w[s] * table[b * batch_stride +
+// row[s] * ld + query] (row[s] = -1: by w[s] alone); one table for all heads ----
+struct SetMasks {
+    const float *table;
+    int64_t ld, batch_stride;
+    int row[MAX_KEY_SETS];
 };
 
 // ---- what planned_launch computed, for a family's launch thunks ----

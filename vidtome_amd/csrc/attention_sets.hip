@@ -4,6 +4,8 @@
 // stands beside): set 0 = the text tokens, one more set per loaded adapter, all with the same q.  Composed from
 // vtm_attention_kv it costs 1 + n launches that each read all of q and write all of out, plus the adds; here a workgroup
 // keeps its query fragments, walks the sets and writes out once.
+// vtm_attention_kv_sets_masked is the same kernel with a weight per QUERY on chosen sets, w_s * mask_s[b, i]: Diffusers'
+// IP-Adapter region masks (one image prompt per region of the frame; every masked image is a set of its own).
 //
 // Structure (the building blocks of attention.hip, without what a few hundred keys do not need -- no key split, no
 // workspace, no spare-slot tricks):
@@ -29,11 +31,18 @@ constexpr int sets_waves(int D) { return D <= 96 ? 8 : 4; }
 constexpr int sets_wg_per_cu(int D) { return D <= 32 ? 2 : 1; }
 constexpr int sets_qb(int D) { return sets_waves(D) * QW; }   // query rows per workgroup
 
-template <typename T, int D>
+// With one trailing SetMasks argument (MASKED) set s is weighted per query, w_s * mask_s[query]: the kernel of
+// vtm_attention_kv_sets_masked.  Without it the kernel is instruction for instruction what it was before the flag.
+__device__ __forceinline__ const SetMasks *masks_of() { return nullptr; }
+__device__ __forceinline__ const SetMasks *masks_of(const SetMasks &m) { return &m; }
+
+template <typename T, int D, typename... Masks>
 __global__ __launch_bounds__(sets_waves(D) * 64, sets_wg_per_cu(D) * sets_waves(D) / 4) void attention_sets_kernel(
     const T *__restrict__ q, int64_t ldq, const T *__restrict__ k, int64_t ldk, const T *__restrict__ vt, int64_t ldvt,
     T *__restrict__ out, int64_t ldo, int64_t H, int64_t M, int64_t Mp, int64_t Mkp, float scale_log2e, int64_t nqb,
-    int xcd_groups, KeySets sets) {
+    int xcd_groups, KeySets sets, Masks... masks_arg) {
+    static_assert(sizeof...(Masks) <= 1, "at most one SetMasks");
+    constexpr bool MASKED = sizeof...(Masks) == 1;
     using F = Frag<T>;
     using vec = typename F::vec;
     using elem = typename F::elem;
@@ -213,8 +222,25 @@ __global__ __launch_bounds__(sets_waves(D) * 64, sets_wg_per_cu(D) * sets_waves(
             }
         }
     };
+    // MASKED: the weight of this lane's query in the set being computed (mw) and in the set whose first tile is in flight
+    // (mw_next) -- one plain global load per set and lane, issued with that first tile and read when the set is finished,
+    // at least a whole tile later.  A set without a row, and a query >= M (which stores nothing), weigh 1.
+    float mw = 1.0f, mw_next = 1.0f;
+    auto issue_weight = [&](int s) {
+        if constexpr (MASKED) {
+            const SetMasks &masks = *masks_of(masks_arg...);
+            const int row = masks.row[s];
+            mw_next = 1.0f;
+            if (row >= 0 && q0 + l31 < M)
+                mw_next = masks.table[b * masks.batch_stride + (int64_t)row * masks.ld + q0 + l31];
+        }
+    };
     auto finish_set = [&](float w) {   // total += w * o / l; the next set starts from nothing
-        const float f = w / (l_run + __shfl_xor(l_run, 32, 64));
+        float f;
+        if constexpr (MASKED)
+            f = (w * mw) / (l_run + __shfl_xor(l_run, 32, 64));   // (this association: a weight of 1 gives the unmasked bits)
+        else
+            f = w / (l_run + __shfl_xor(l_run, 32, 64));
 #pragma unroll
         for (int dv = 0; dv < DV; ++dv)
 #pragma unroll
@@ -229,6 +255,10 @@ __global__ __launch_bounds__(sets_waves(D) * 64, sets_wg_per_cu(D) * sets_waves(
     // the tiles of all sets, one after the other; (cs, ct) is the tile in LDS, (ns, nt) the one in flight
     int cs = 0, ct = 0;
     issue(sets.start[0], sets.start[0] + sets.len[0]);
+    if constexpr (MASKED) {
+        issue_weight(0);
+        mw = mw_next;
+    }
     write_lds();
     __syncthreads();
     for (;;) {
@@ -240,8 +270,13 @@ __global__ __launch_bounds__(sets_waves(D) * 64, sets_wg_per_cu(D) * sets_waves(
         }
         const bool more = ns < sets.n;
         if (more) issue(sets.start[ns] + nt * KV, sets.start[ns] + sets.len[ns]);
+        if constexpr (MASKED)
+            if (more && ns != cs) issue_weight(ns);
         tile(len - ct * KV);
-        if (ns != cs) finish_set(sets.w[cs]);
+        if (ns != cs) {
+            finish_set(sets.w[cs]);
+            if constexpr (MASKED) mw = mw_next;
+        }
         if (!more) break;
         __syncthreads();   // every wave has read the tile
         write_lds();
@@ -275,28 +310,33 @@ void launch_sets(const Call &c, const Launch &g) {
                        g.scale_log2e, g.nqb, g.xcd_groups, *c.sets);
 }
 
+template <typename T, int D>
+void launch_sets_masked(const Call &c, const Launch &g) {
+    hipLaunchKernelGGL((attention_sets_kernel<T, D, SetMasks>), dim3((unsigned)g.wgs), dim3(sets_waves(D) * 64), 0, c.s,
+                       (const T *)c.q, c.ldq, (const T *)c.k, c.ldk, (const T *)c.vt, c.ldvt, (T *)c.out, c.ldo, c.h, c.M, c.Mp,
+                       c.Mkp, g.scale_log2e, g.nqb, g.xcd_groups, *c.sets, *c.set_masks);
+}
+
 // The family: one workgroup per (query block, head, sample), never key-split (no partial record, no combine kernel) -- the
 // planner sizes the grid and pins the (sample, head) pairs to XCDs like every other family's.
 template <typename T, int D>
-Family sets_family() {
+Family sets_family(bool masked = false) {
     Family f;
-    f.name = "vtm_attention_kv_sets";
+    f.name = masked ? "vtm_attention_kv_sets_masked" : "vtm_attention_kv_sets";
     f.qb = sets_qb(D);
     f.wg_per_cu = sets_wg_per_cu(D);
     f.rec_bytes = 0;
     f.xcd_min_nqb = 64;
     f.host_split_all = false;
-    f.main = launch_sets<T, D>;
+    f.main = masked ? launch_sets_masked<T, D> : launch_sets<T, D>;
     return f;
 }
 
-}  // namespace
-
-VTM_EXPORT int vtm_attention_kv_sets(const void *q, int64_t ldq, const void *k, int64_t ldk, const void *vt, int64_t ldvt,
-                                     void *out, int64_t ldo, int dtype, int64_t B, int64_t h, int64_t Mq, int64_t Mqp,
-                                     int64_t Mkp, int64_t d, float scale, int n_sets, const int64_t *set_start,
-                                     const int64_t *set_len, const float *set_weight, vtm_stream_t stream) {
-    const char *who = "vtm_attention_kv_sets";
+// The checks and the launch of both exports; `masks` = nullptr: vtm_attention_kv_sets.
+int sets_launch(const char *who, const void *q, int64_t ldq, const void *k, int64_t ldk, const void *vt, int64_t ldvt, void *out,
+                int64_t ldo, int dtype, int64_t B, int64_t h, int64_t Mq, int64_t Mqp, int64_t Mkp, int64_t d, float scale,
+                int n_sets, const int64_t *set_start, const int64_t *set_len, const float *set_weight, const SetMasks *masks,
+                vtm_stream_t stream) {
     VTM_REQUIRE(q && k && vt && out && set_start && set_len && set_weight, "%s: null pointer", who);
     VTM_REQUIRE(n_sets >= 1 && n_sets <= MAX_KEY_SETS, "%s: n_sets must be 1 .. %d, got %d", who, MAX_KEY_SETS, n_sets);
     VTM_REQUIRE(B > 0 && h > 0 && Mq > 0 && Mqp >= Mq && Mkp > 0 && d > 0, "%s: bad sizes", who);
@@ -331,8 +371,54 @@ VTM_EXPORT int vtm_attention_kv_sets(const void *q, int64_t ldq, const void *k, 
     Call c{q, ldq, k, ldk, vt, ldvt, out, ldo, dtype, B, h, Mq, Mqp, keys, Mkp, scale, 1, nullptr, 0,
            nullptr, vtm::as_stream(stream), false, nullptr, nullptr, 0};
     c.sets = &sets;
+    c.set_masks = masks;
+    const bool masked = masks != nullptr;
     return with_head_dim(d, [&](auto dim) {
         constexpr int D = decltype(dim)::value;
-        return planned_launch(c, dtype == VTM_F16 ? sets_family<__half, D>() : sets_family<vtm_bf16, D>());
+        return planned_launch(c, dtype == VTM_F16 ? sets_family<__half, D>(masked) : sets_family<vtm_bf16, D>(masked));
     });
+}
+
+}  // namespace
+
+VTM_EXPORT int vtm_attention_kv_sets(const void *q, int64_t ldq, const void *k, int64_t ldk, const void *vt, int64_t ldvt,
+                                     void *out, int64_t ldo, int dtype, int64_t B, int64_t h, int64_t Mq, int64_t Mqp,
+                                     int64_t Mkp, int64_t d, float scale, int n_sets, const int64_t *set_start,
+                                     const int64_t *set_len, const float *set_weight, vtm_stream_t stream) {
+    return sets_launch("vtm_attention_kv_sets", q, ldq, k, ldk, vt, ldvt, out, ldo, dtype, B, h, Mq, Mqp, Mkp, d, scale, n_sets,
+                       set_start, set_len, set_weight, nullptr, stream);
+}
+
+VTM_EXPORT int vtm_attention_kv_sets_masked(const void *q, int64_t ldq, const void *k, int64_t ldk, const void *vt,
+                                            int64_t ldvt, void *out, int64_t ldo, int dtype, int64_t B, int64_t h, int64_t Mq,
+                                            int64_t Mqp, int64_t Mkp, int64_t d, float scale, int n_sets,
+                                            const int64_t *set_start, const int64_t *set_len, const float *set_weight,
+                                            const int *set_mask, const float *mask, int64_t ld_mask, int64_t mask_batch_stride,
+                                            vtm_stream_t stream) {
+    const char *who = "vtm_attention_kv_sets_masked";
+    VTM_REQUIRE(set_mask, "%s: null pointer", who);
+    VTM_REQUIRE(n_sets >= 1 && n_sets <= MAX_KEY_SETS, "%s: n_sets must be 1 .. %d, got %d", who, MAX_KEY_SETS, n_sets);
+    SetMasks masks{mask, ld_mask, mask_batch_stride, {}};
+    int rows = 0;   // rows of the table the call names
+    for (int s = 0; s < MAX_KEY_SETS; ++s) {
+        masks.row[s] = -1;
+        if (s >= n_sets) continue;
+        // (a table has at most one row per set: that is the range of a row index)
+        VTM_REQUIRE(set_mask[s] >= -1 && set_mask[s] < n_sets, "%s: mask row of set %d is %d (-1 = none, or a row 0 .. %d)", who,
+                    s, set_mask[s], n_sets - 1);
+        masks.row[s] = set_mask[s];
+        rows = std::max(rows, set_mask[s] + 1);
+    }
+    if (rows == 0)   // no set is masked: the unmasked kernel, the table is not looked at
+        return sets_launch(who, q, ldq, k, ldk, vt, ldvt, out, ldo, dtype, B, h, Mq, Mqp, Mkp, d, scale, n_sets, set_start,
+                           set_len, set_weight, nullptr, stream);
+    VTM_REQUIRE(mask, "%s: a set is masked but the table is null", who);
+    VTM_REQUIRE(ld_mask >= Mq, "%s: ld_mask = %lld is shorter than a row of Mq = %lld weights", who, (long long)ld_mask,
+                (long long)Mq);
+    // one table for every sample (stride 0), or per-sample tables that do not overlap: that is also what bounds a row index
+    VTM_REQUIRE(mask_batch_stride == 0 || mask_batch_stride >= (int64_t)rows * ld_mask,
+                "%s: mask_batch_stride = %lld must be 0 or at least rows * ld_mask = %lld", who, (long long)mask_batch_stride,
+                (long long)((int64_t)rows * ld_mask));
+    return sets_launch(who, q, ldq, k, ldk, vt, ldvt, out, ldo, dtype, B, h, Mq, Mqp, Mkp, d, scale, n_sets, set_start, set_len,
+                       set_weight, &masks, stream);
 }

@@ -17,12 +17,25 @@ forward, never a guess.  It accepts a processor when
   without bias, ``out_features == C``, weights of the tokens' dtype; ``num_tokens`` is a sequence of n positive ints and
   ``scale`` a sequence of n plain numbers (a per-layer list of scales is not understood);
 * the call is the plain one: no attention mask, ``cross_attention_kwargs`` empty or holding only ``ip_adapter_masks`` that
-  is None or all None;
+  is None, all None, or region masks in the published form (below);
 * ``encoder_hidden_states`` is the tuple ``(text, images)`` -- text (B, T, D), images a list / tuple of n tensors, each
   (B, T_a, D) or (B, m, T_a, D) (m images: m * T_a keys, like the processor's ``view(B, -1, ...)``) -- or the legacy single
   tensor with the image tokens appended, split at ``shape[1] - num_tokens[0]`` (then n must be 1).
 Neither Diffusers nor an adapter checkpoint is a dependency: the contract is duck-typed against the published processor
 (tests/ip_adapter_standin.py restates it); a release whose processor differs is not recognised and keeps the module path.
+
+Region masks (``cross_attention_kwargs={"ip_adapter_masks": [...]}``, one entry per adapter): an entry is None -- the adapter
+acts everywhere, one set of ``m * T_a`` keys as above -- or a tensor (1, m_a, H, W) for an adapter whose image tensor is 4-D
+with ``m_a`` images.  The processor then gives every image a softmax of its own and weighs it per query,
+
+    out += s_a * softmax(q K_{a,i}^T * scale) V_{a,i} * downsample(mask[:, i], B, N, C)
+
+which is one key set per image with a row of per-query weights: vtm_attention_kv_sets_masked.  The downsample (bicubic, to
+the site's token grid) is NOT restated here: it is ``IPAdapterMaskProcessor.downsample`` of the module that defines the
+processor class, called as ``downsample(mask[:, i], 1, N, 1)``, and its (N,) row is kept in fp32.  A mask in another form (the
+3-D tensors of custom processors), a masked adapter with a 3-D image tensor, more than 8 sets in all, a module without that
+name or a result of another shape keep the module path.  The one arithmetic difference: the masked term is weighted in fp32
+and the sum is rounded once, where the processor rounds the mask and every term to the model's dtype and adds there.
 
 ``scale`` is read at every call (``pipe.set_ip_adapter_scale`` takes effect on the next forward).  An adapter whose
 scale is 0 is left out, as the processor skips it -- a NaN in its unused image tokens never reaches the output -- and with
@@ -31,6 +44,7 @@ every scale 0 the block issues exactly the launches of a block without an adapte
 from __future__ import annotations
 
 import numbers
+import sys
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
@@ -39,6 +53,7 @@ from . import lora
 
 PROCESSORS = ("IPAdapterAttnProcessor", "IPAdapterAttnProcessor2_0", "IPAdapterXFormersAttnProcessor")
 MAX_ADAPTERS = 7             # vtm_attention_kv_sets takes 8 sets: the text and 7 adapters
+MAX_KEY_SETS = 8             # ... and with region masks every image of a masked adapter is a set of its own
 SET_ALIGN = 8                # a set starts on a multiple of 8 keys (V^T is fetched in 16-byte pieces)
 
 
@@ -49,6 +64,8 @@ class Call(NamedTuple):
     k_proj: List[torch.nn.Module]        # to_k_ip
     v_proj: List[torch.nn.Module]        # to_v_ip
     scales: List[float]
+    masks: Optional[List[Optional[torch.Tensor]]] = None   # region masks: per adapter None, or (m_a, N) fp32 query weights
+                                                           # -- one row, and one key set, per image of the adapter
 
 
 def is_ip_processor(attn) -> bool:
@@ -88,10 +105,42 @@ def masks_absent(kwargs) -> bool:
     return masks is None or (isinstance(masks, (list, tuple)) and all(m is None for m in masks))
 
 
+def _region_masks(kwargs, n: int):
+    """``ip_adapter_masks`` when ``cross_attention_kwargs`` holds nothing else and it is a list / tuple of n entries, each
+    None or a 4-D floating-point tensor (1, m, H, W); else None."""
+    if not kwargs or set(kwargs) != {"ip_adapter_masks"}:
+        return None
+    masks = kwargs["ip_adapter_masks"]
+    if not isinstance(masks, (list, tuple)) or len(masks) != n:
+        return None
+    for m in masks:
+        if m is not None and not (isinstance(m, torch.Tensor) and m.dim() == 4 and m.shape[0] == 1 and m.shape[1] >= 1
+                                  and m.shape[2] >= 1 and m.shape[3] >= 1 and m.is_floating_point()):
+            return None
+    return list(masks)
+
+
+def _mask_rows(proc, mask: torch.Tensor, N: int, device) -> Optional[torch.Tensor]:
+    """(m, N) fp32 per-query weights of a (1, m, H, W) region mask at a site of N tokens, by the processor's own
+    ``IPAdapterMaskProcessor.downsample`` -- found in the module that defines the processor class, where Diffusers'
+    attention_processor imports it -- or None when that cannot be resolved or gives something else than (1, N, 1)."""
+    mod = sys.modules.get(type(proc).__module__)
+    downsample = getattr(getattr(mod, "IPAdapterMaskProcessor", None), "downsample", None)
+    if not callable(downsample):
+        return None
+    rows = []
+    for i in range(mask.shape[1]):
+        row = downsample(mask[:, i], 1, N, 1)
+        if not isinstance(row, torch.Tensor) or tuple(row.shape) != (1, N, 1) or not row.is_floating_point():
+            return None
+        rows.append(row.reshape(N).to(device=device, dtype=torch.float32))
+    return torch.stack(rows)
+
+
 def recognise(attn, x: torch.Tensor, encoder_hidden_states, attention_mask=None, kwargs=None) -> Optional[Call]:
     """The parts of a plain IP-Adapter call of ``attn`` on tokens ``x`` (B, N, C), or None (the module path).  What
     `patch.fused_attention_ok` asks of the module itself is the caller's to check."""
-    if not is_ip_processor(attn) or attention_mask is not None or not masks_absent(kwargs):
+    if not is_ip_processor(attn) or attention_mask is not None:
         return None
     if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.dtype not in (torch.float16, torch.bfloat16):
         return None
@@ -108,6 +157,11 @@ def recognise(attn, x: torch.Tensor, encoder_hidden_states, attention_mask=None,
         return None
     if not isinstance(scale, (list, tuple)) or len(scale) != n or not all(_plain_number(s) for s in scale):
         return None
+    region = None
+    if not masks_absent(kwargs):
+        region = _region_masks(kwargs, n)
+        if region is None:
+            return None
     B, _, C = x.shape
     if not all(_projection_ok(m, C, x.dtype) for m in list(k_ip) + list(v_ip)):
         return None
@@ -129,18 +183,35 @@ def recognise(attn, x: torch.Tensor, encoder_hidden_states, attention_mask=None,
     if not isinstance(text, torch.Tensor) or text.dim() != 3 or text.shape[0] != B or text.shape[1] < 1 \
             or not text.is_floating_point() or text.device != x.device:
         return None
-    flat = []
+    flat, n_sets = [], 1
     for a, im in enumerate(images):
         if not isinstance(im, torch.Tensor) or im.dim() not in (3, 4) or im.shape[0] != B or not im.is_floating_point() \
                 or im.device != x.device:
             return None
+        if region is not None and region[a] is not None:     # a masked adapter: one image, one mask channel, one key set
+            if im.dim() != 4 or im.shape[1] != region[a].shape[1]:
+                return None
+            n_sets += im.shape[1] if float(scale[a]) != 0.0 else 0
+        else:
+            n_sets += 1 if float(scale[a]) != 0.0 else 0
         if im.dim() == 4:
             im = im.reshape(B, im.shape[1] * im.shape[2], im.shape[3])
         if im.shape[1] < 1 or im.shape[2] != lora.base_linear(k_ip[a]).in_features \
                 or im.shape[2] != lora.base_linear(v_ip[a]).in_features:
             return None
         flat.append(im)
-    return Call(text, flat, list(k_ip), list(v_ip), [float(s) for s in scale])
+    scales = [float(s) for s in scale]
+    if region is None:
+        return Call(text, flat, list(k_ip), list(v_ip), scales)
+    if n_sets > MAX_KEY_SETS:
+        return None
+    rows = []
+    for a, m in enumerate(region):
+        # (an adapter of scale 0 takes no part: the processor never downsamples its mask either)
+        rows.append(None if m is None or scales[a] == 0.0 else _mask_rows(proc, m, x.shape[1], x.device))
+        if m is not None and scales[a] != 0.0 and rows[-1] is None:
+            return None
+    return Call(text, flat, list(k_ip), list(v_ip), scales, rows)
 
 
 def key_sets(text_len: int, image_lens: Sequence[int], scales: Sequence[float]
@@ -158,6 +229,29 @@ def key_sets(text_len: int, image_lens: Sequence[int], scales: Sequence[float]
         active.append(a)
         end = _round_up(end + n)
     return sets, active, end
+
+
+def masked_key_sets(text_len: int, image_lens: Sequence[int], scales: Sequence[float], images: Sequence[int]
+                    ) -> Tuple[List[Tuple[int, int, float]], List[int], int, List[int]]:
+    """`key_sets` for a call with region masks: ``images[a]`` is 0 for an adapter without a mask -- one set of
+    ``image_lens[a]`` keys, as in `key_sets` -- or m_a, the images of a masked adapter, whose ``image_lens[a] = m_a * T_a`` keys
+    become m_a sets of T_a keys, each on the next multiple of 8 keys and each weighted by the adapter's scale.  The fourth
+    result names every set's row of the weight table: -1, or 0, 1, ... over the masked sets in order (the rows of the active
+    adapters' ``Call.masks``, concatenated)."""
+    sets, rows = [(0, int(text_len), 1.0)], [-1]
+    active = []
+    end, row = _round_up(text_len), 0
+    for a, (n, s, m) in enumerate(zip(image_lens, scales, images)):
+        if float(s) == 0.0:
+            continue
+        active.append(a)
+        parts = max(int(m), 1)
+        for _ in range(parts):
+            sets.append((end, int(n) // parts, float(s)))
+            rows.append(row if m else -1)
+            row += 1 if m else 0
+            end = _round_up(end + int(n) // parts)
+    return sets, active, end, rows
 
 
 def _round_up(n: int) -> int:

@@ -640,10 +640,18 @@ def self_attention_segment(block: torch.nn.Module, hidden_states: torch.Tensor, 
                            attention_mask=None, cross_attention_kwargs=None) -> torch.Tensor:
     """patch.py:146-169 for the plain-LayerNorm block: norm1 -> compute_merge -> attn1 -> unmerge -> + residual."""
     if (encoder_hidden_states is None or not block.only_cross_attention) and attention_mask is None \
-            and not cross_attention_kwargs and unmerged_self_attention_ok(block, hidden_states):
+            and not _attn1_kwargs(cross_attention_kwargs) and unmerged_self_attention_ok(block, hidden_states):
         return unmerged_self_attention_residual(block, hidden_states)
     return patched_self_attention_segment(block, hidden_states, layer_norm(block.norm1, hidden_states),
                                           encoder_hidden_states, attention_mask, cross_attention_kwargs, None)
+
+
+def _attn1_kwargs(cross_attention_kwargs) -> dict:
+    """What of ``cross_attention_kwargs`` a plain processor on attn1 gets to see.  ``ip_adapter_masks`` is read by the
+    IP-Adapter processors on attn2 alone: Diffusers' ``Attention.forward`` drops, without a word, the arguments a processor's
+    ``__call__`` does not take, and the plain processors ``fused_attention_ok`` accepts do not take it -- so region masks
+    do not send attn1 to its module forward.  (Whenever the module IS called it gets the kwargs untouched.)"""
+    return {k: v for k, v in (cross_attention_kwargs or {}).items() if k != "ip_adapter_masks"}
 
 
 def _weight(m: torch.nn.Module, dtype) -> torch.Tensor:
@@ -842,14 +850,44 @@ def _pad_keys(enc: torch.Tensor, dt) -> torch.Tensor:
 def _ip_key_sets(attn: torch.nn.Module, ip: "ip_adapter.Call", dt, C: int, panels: bool):
     """The operands of the IP-Adapter core: text k / v^T as for the plain block, every adapter whose scale is not 0
     projected the same way with to_k_ip[a] / to_v_ip[a] into its slice of ONE k (B, Mkp, C) and ONE v^T (B, C, Mkp) buffer
-    -> (k, vt, [(start, length, weight)]).  With no adapter taking part k / vt ARE the plain block's tensors."""
-    sets, active, _ = ip_adapter.key_sets(ip.text.shape[1], [im.shape[1] for im in ip.images], ip.scales)
+    -> (k, vt, [(start, length, weight)], mask rows, mask table).  With no adapter taking part k / vt ARE the plain block's
+    tensors.  Region masks (``ip.masks``): all m_a * T_a image tokens of a masked adapter are projected in one GEMM like any
+    other adapter's, then every image's T_a rows go to a set of their own on a multiple of 8 keys; the mask rows name each
+    set's row (-1: none) of the (R, N) fp32 table of per-query weights.  Without a masked set taking part both are None."""
+    lens = [im.shape[1] for im in ip.images]
+    masks = ip.masks if ip.masks is not None else [None] * len(lens)
+    images = [0 if m is None else m.shape[0] for m in masks]
+    if any(images):
+        sets, active, _, rows = ip_adapter.masked_key_sets(ip.text.shape[1], lens, ip.scales, images)
+    else:
+        (sets, active, _), rows = ip_adapter.key_sets(ip.text.shape[1], lens, ip.scales), []
     k, vt = _cross_kv(attn.to_k, attn.to_v, _pad_keys(ip.text, dt), C, panels)
     if active:
-        parts = [(k, vt)] + [_cross_kv(ip.k_proj[a], ip.v_proj[a], _pad_keys(ip.images[a], dt), C, panels) for a in active]
+        parts = [(k, vt)]
+        for a in active:
+            ka, vta = _cross_kv(ip.k_proj[a], ip.v_proj[a], _pad_keys(ip.images[a], dt), C, panels)
+            t = lens[a] // max(images[a], 1)
+            if images[a] > 1 and t % 8:                                 # every image's keys onto a multiple of 8
+                pad = -t % 8
+                ka = torch.cat([F.pad(ka[:, i * t:(i + 1) * t], (0, 0, 0, pad)) for i in range(images[a])], dim=1)
+                vta = torch.cat([F.pad(vta[:, :, i * t:(i + 1) * t], (0, pad)) for i in range(images[a])], dim=2)
+            parts.append((ka, vta))
         k = torch.cat([p[0] for p in parts], dim=1)
         vt = torch.cat([p[1] for p in parts], dim=2)
-    return k, vt, sets
+    if not any(r >= 0 for r in rows):
+        return k, vt, sets, None, None
+    table = torch.cat([masks[a] for a in active if masks[a] is not None]).contiguous()
+    return k, vt, sets, rows, table
+
+
+def _ip_core(attn: torch.nn.Module, ip: "ip_adapter.Call", q: torch.Tensor, N: int, scale: float, panels: bool) -> torch.Tensor:
+    """The decoupled cross-attention of an IP-Adapter call on query tokens q (B, Np, C), N <= Np of them meaningful: ONE
+    launch over the text keys and every adapter's image keys -- vtm_attention_kv_sets, or vtm_attention_kv_sets_masked when
+    the call carries region masks."""
+    k, vt, sets, rows, table = _ip_key_sets(attn, ip, q.dtype, q.shape[-1], panels)
+    if table is None:
+        return _lib.attention_kv_sets(q, k, vt, attn.heads, N, sets, scale)
+    return _lib.attention_kv_sets_masked(q, k, vt, attn.heads, N, sets, scale, rows, table)
 
 
 def norm_cross_attention_residual(norm: torch.nn.Module, attn: torch.nn.Module, hidden_states: torch.Tensor,
@@ -861,7 +899,8 @@ def norm_cross_attention_residual(norm: torch.nn.Module, attn: torch.nn.Module, 
     library, the attention core on vtm_attention_kv and the output projection + bias + residual as a panel GEMM too.
     The caller has checked ``fused_cross_ok``.
     With ``ip`` (an IP-Adapter call, ``ip_cross_call``; ``encoder_hidden_states`` is then not read) the core is ONE
-    vtm_attention_kv_sets launch over the text keys and every adapter's image keys (``_ip_key_sets``)."""
+    vtm_attention_kv_sets launch over the text keys and every adapter's image keys, or with region masks ONE
+    vtm_attention_kv_sets_masked launch (``_ip_core``)."""
     B, N, C = hidden_states.shape
     heads = attn.heads
     scale = getattr(attn, "scale", None) or (C // heads) ** -0.5
@@ -879,8 +918,7 @@ def norm_cross_attention_residual(norm: torch.nn.Module, attn: torch.nn.Module, 
         k, vt = _cross_kv(attn.to_k, attn.to_v, _pad_keys(encoder_hidden_states, dt), C)
         o = _lib.attention_kv(q, k, vt, heads, N, Mk, scale)
     else:
-        k, vt, sets = _ip_key_sets(attn, ip, dt, C, True)
-        o = _lib.attention_kv_sets(q, k, vt, heads, N, sets, scale)
+        o = _ip_core(attn, ip, q, N, scale, True)
     op = _lib.to_panels(o.view(n, C))
     return _lib.linear_panels(op, n, wo, C, bo, resid=hs.view(n, C)).view(B, N, C)
 
@@ -965,7 +1003,8 @@ def cross_attention(attn: torch.nn.Module, x: torch.Tensor, encoder_hidden_state
     """`self.attn2(norm_hidden_states, encoder_hidden_states=..., attention_mask=...)` (patch.py:178-183) -- the
     un-merged tokens attending to the conditioning (77 text tokens in SD).  The plain case (projection Linears, no
     mask, no processor kwargs) runs on vtm_attention_kv, a recognised IP-Adapter call (``ip_cross_call``) on
-    vtm_attention_kv_sets, with library GEMMs around the core; everything else is the module's own forward."""
+    vtm_attention_kv_sets (with region masks: vtm_attention_kv_sets_masked), with library GEMMs around the core; everything
+    else is the module's own forward."""
     plain = (isinstance(encoder_hidden_states, torch.Tensor) and attention_mask is None and not kwargs
              and encoder_hidden_states.dim() == 3 and x.dtype in (torch.float16, torch.bfloat16)
              and fused_attention_ok(attn, x, self_attn=False))
@@ -976,8 +1015,7 @@ def cross_attention(attn: torch.nn.Module, x: torch.Tensor, encoder_hidden_state
         B, N, C = x.shape
         scale = getattr(attn, "scale", None) or (C // attn.heads) ** -0.5
         xq = F.pad(x, (0, 0, 0, -N % 8)) if N % 8 else x
-        k, vt, sets = _ip_key_sets(attn, ip, x.dtype, C, False)
-        o = _lib.attention_kv_sets(_apply_linear(attn.to_q, xq), k, vt, attn.heads, N, sets, scale)
+        o = _ip_core(attn, ip, _apply_linear(attn.to_q, xq), N, scale, False)
         return _apply_linear(_out_linear(attn), o)[:, :N]
     B, N, C = x.shape
     enc = encoder_hidden_states.to(x.dtype)
@@ -1126,7 +1164,7 @@ def patched_self_attention_segment(block: torch.nn.Module, hidden_states: torch.
     """patch.py:148-169: compute_merge -> attn1(merged) -> unmerge -> + residual."""
     cross_attention_kwargs = cross_attention_kwargs if cross_attention_kwargs is not None else {}
     custom = encoder_hidden_states is not None and block.only_cross_attention
-    fused = not (custom or attention_mask is not None or cross_attention_kwargs) \
+    fused = not (custom or attention_mask is not None or _attn1_kwargs(cross_attention_kwargs)) \
         and fused_attention_ok(block.attn1, norm_hidden_states)
     by_rows = fused and fused_projections_ok(block.attn1, norm_hidden_states)
     by_panels = fused and not by_rows and panel_projections_ok(block.attn1, norm_hidden_states)
