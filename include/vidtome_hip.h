@@ -379,6 +379,23 @@ int vtm_attention_kv_sets_masked(const void *q, int64_t ldq, const void *k, int6
                                  const int64_t *set_len, const float *set_weight, const int *set_mask, const float *mask,
                                  int64_t ld_mask, int64_t mask_batch_stride, vtm_stream_t stream);
 
+/* vtm_attention_kv_bias -- the cross-attention core with one additive fp32 term PER KEY on the scores: what an
+ * `encoder_attention_mask` turns the `self.attn2(...)` call of vidtome/patch.py:178-183 into (Diffusers' UNet hands the
+ * (B, K) mask of a padded prompt on as an additive (B, 1, K) row of 0 / -10000).  Per head
+ *     out[b, i] = softmax_j(q[b, i] . k[b, j] * scale + bias[b * bias_batch_stride + j]) v[b, j],   j < Mk
+ * q, k, vt, out exactly as for vtm_attention_kv (heads interleaved on the channel axis, vt channel-major, ldvt >= Mk), and
+ * Mkp % 8 == 0.  bias: a DEVICE pointer to fp32, one value per key, shared by all heads and all queries of a sample; rows of
+ * ld_bias >= Mk elements; bias_batch_stride, in elements: 0 when one row serves every sample, else at least ld_bias.  A bias
+ * value is finite or -inf; a key whose bias is -inf gets probability exactly 0, whatever (finite) values its k and v rows
+ * hold.  A sample whose keys are ALL -inf gives NaN, as torch's scaled_dot_product_attention does.  The bias is added to the
+ * scaled scores in fp32 before the running maximum is taken.  scale > 0.  dtype VTM_F16 or VTM_BF16 (VTM_F32: VTM_EINVAL);
+ * d as for vtm_attention.  One launch, no workspace, no key split: the key axis is a few hundred keys, the launch streams q
+ * and out.  Rows >= Mq of out are not written.  On a bad argument nothing is launched and out is untouched. */
+int vtm_attention_kv_bias(const void *q, int64_t ldq, const void *k, int64_t ldk, const void *vt, int64_t ldvt,
+                          void *out, int64_t ldo, int dtype, int64_t B, int64_t h, int64_t Mq, int64_t Mqp,
+                          int64_t Mk, int64_t Mkp, int64_t d, float scale, const float *bias, int64_t ld_bias,
+                          int64_t bias_batch_stride, vtm_stream_t stream);
+
 /* vtm_attention_kv with a DEVICE-side query bound: sample b only has q_count[b] <= Mq meaningful query rows (the
  * compacted live queries of vtm_compact_queries); query blocks that start at or beyond the count exit at once, rows
  * beyond it are not meaningful.  The launch is sized for the host-known bound Mq -- no host round trip. */

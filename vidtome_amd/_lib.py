@@ -73,6 +73,8 @@ _SIGNATURES = {
     "vtm_attention_kv_sets_masked": ([_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _f32,
                                       _int, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_f32),
                                       ctypes.POINTER(_int), _vp, _i64, _i64, _vp], _int),
+    "vtm_attention_kv_bias": ([_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
+                               _f32, _vp, _i64, _i64, _vp], _int),
     "vtm_attention_kv_bounded": ([_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                   _f32, _vp, _vp, ctypes.c_size_t, _vp], _int),
     "vtm_attention_kv_shared_bounded": ([_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
@@ -762,6 +764,35 @@ def attention_kv_sets_masked(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor,
                                               vt.stride(1), out.data_ptr(), C, dtype_code(q), B, heads, Mq, Mqp, Mkp, d,
                                               float(scale), n, starts, lens, weights, (_int * n)(*rows), mask.data_ptr(), ld,
                                               R * ld if mask.dim() == 3 else 0, _stream()), "vtm_attention_kv_sets_masked")
+    return out
+
+
+@_on_device
+def attention_kv_bias(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, Mq: int, Mk: int, scale: float,
+                      bias: torch.Tensor) -> torch.Tensor:
+    """attention_kv with one additive fp32 term per key on the scores (vtm_attention_kv_bias): q (B, Mqp, C), k (B, Mkp, C)
+    views contiguous along the last axis, vt (B, C, ldvt >= Mk) = v transposed, Mkp a multiple of 8, as for attention_kv.
+    ``bias`` is fp32 on q's device, (B, Mk') with a row per sample or (1, Mk') with one row for all, Mk' >= Mk, contiguous
+    along the last axis; the values are shared by the heads and the queries and are finite or -inf (-inf: probability exactly
+    0).  The result is softmax(q K^T * scale + bias) V, (B, Mqp, C).  fp16 / bf16 operands only."""
+    if q.dtype not in (torch.float16, torch.bfloat16) or k.dtype != q.dtype or vt.dtype != q.dtype:
+        raise RuntimeError("attention_kv_bias: q, k and vt must share one of fp16 / bf16 (fp32 models keep the module path)")
+    B, Mqp, C = q.shape
+    Mkp = k.shape[1]
+    d = C // heads
+    Mk = int(Mk)
+    if k.shape[0] != B or vt.shape[0] != B or k.shape[2] != C or vt.shape[1] != C:
+        raise RuntimeError("attention_kv_bias: k must be (B, Mkp, C) and vt (B, C, ldvt)")
+    if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or bias.device != q.device or bias.dim() != 2 \
+            or bias.shape[0] not in (1, B) or bias.shape[1] < Mk or bias.stride(1) != 1 \
+            or (bias.shape[0] == B and B > 1 and 0 < bias.stride(0) < bias.shape[1]):   # (stride 0: an expanded row)
+        raise RuntimeError("attention_kv_bias: bias must be fp32 on q's device, (B, >= Mk) or (1, >= Mk), contiguous along "
+                           "its last axis")
+    out = _attention_out(q, k, vt, Mq, Mkp)
+    batch_stride = bias.stride(0) if bias.shape[0] == B and B > 1 else 0
+    _check(lib().vtm_attention_kv_bias(q.data_ptr(), q.stride(1), k.data_ptr(), k.stride(1), vt.data_ptr(), vt.stride(1),
+                                       out.data_ptr(), C, dtype_code(q), B, heads, Mq, Mqp, Mk, Mkp, d, float(scale),
+                                       bias.data_ptr(), bias.shape[1], batch_stride, _stream()), "vtm_attention_kv_bias")
     return out
 
 

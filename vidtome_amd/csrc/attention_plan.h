@@ -74,6 +74,7 @@ struct Call {
     const int32_t *q_count; hipStream_t s; bool fold; const int32_t *k_count; const uint32_t *k_bias; int64_t ldkb;
     const struct KeySets *sets = nullptr;   // vtm_attention_kv_sets only: the key ranges, each with a softmax of its own
     const struct SetMasks *set_masks = nullptr;   // vtm_attention_kv_sets_masked only: the per-query weights of the sets
+    const struct KeyBias *key_bias = nullptr;     // vtm_attention_kv_bias only: the per-key score bias (attention_bias.hip)
 };
 
 // ---- the key sets of one vtm_attention_kv_sets call (attention_sets.hip): set s = keys [start[s], start[s] + len[s]) ----

@@ -890,9 +890,27 @@ def _ip_core(attn: torch.nn.Module, ip: "ip_adapter.Call", q: torch.Tensor, N: i
     return _lib.attention_kv_sets_masked(q, k, vt, attn.heads, N, sets, scale, rows, table)
 
 
+def _key_bias_ok(attention_mask, B: int, Mk: int, device=None) -> bool:
+    """The mask form ``key_bias`` takes: Diffusers' UNet turns an ``encoder_attention_mask`` (B, K) into the additive
+    (B, 1, K) bias ``(1 - mask) * -10000`` in the sample's dtype -- one value per key, for every head and every query."""
+    return (isinstance(attention_mask, torch.Tensor) and attention_mask.is_floating_point() and attention_mask.dim() == 3
+            and attention_mask.shape[1] == 1 and attention_mask.shape[0] in (1, B) and attention_mask.shape[2] == Mk
+            and (device is None or attention_mask.device == device))
+
+
+def key_bias(attention_mask, B: int, Mk: int, device=None) -> Optional[torch.Tensor]:
+    """The per-key score bias of a masked attn2 call for vtm_attention_kv_bias: fp32 rows (B or 1, Mk) from an additive
+    floating-point ``attention_mask`` of shape (B or 1, 1, Mk) on ``device`` (the tokens'; None: not asked), else None --
+    the module path.  Bool / integer masks, 2-D masks, per-query masks (B, N, K) and a key count that is not the
+    conditioning's are the module's own business.  One dtype conversion, nothing is read back to the host."""
+    if not _key_bias_ok(attention_mask, B, Mk, device):
+        return None
+    return attention_mask[:, 0].to(torch.float32).contiguous()
+
+
 def norm_cross_attention_residual(norm: torch.nn.Module, attn: torch.nn.Module, hidden_states: torch.Tensor,
-                                  encoder_hidden_states: torch.Tensor, ip: Optional["ip_adapter.Call"] = None
-                                  ) -> torch.Tensor:
+                                  encoder_hidden_states: torch.Tensor, ip: Optional["ip_adapter.Call"] = None,
+                                  attention_mask=None) -> torch.Tensor:
     """patch.py:171-185 for the plain case: ``attn2(norm2(hidden_states), encoder_hidden_states) + hidden_states`` with the
     query projection as a panel GEMM fed by the LayerNorm (vtm_layernorm_panels -> vtm_linear_panels: the normalised
     tokens are only ever read by to_q, so they are written once, as panels), k / v^T of the (few) conditioning tokens by the
@@ -900,7 +918,9 @@ def norm_cross_attention_residual(norm: torch.nn.Module, attn: torch.nn.Module, 
     The caller has checked ``fused_cross_ok``.
     With ``ip`` (an IP-Adapter call, ``ip_cross_call``; ``encoder_hidden_states`` is then not read) the core is ONE
     vtm_attention_kv_sets launch over the text keys and every adapter's image keys, or with region masks ONE
-    vtm_attention_kv_sets_masked launch (``_ip_core``)."""
+    vtm_attention_kv_sets_masked launch (``_ip_core``).
+    With ``attention_mask`` (the plain case only; ``fused_cross_ok`` has accepted its form, ``key_bias``) the core is
+    vtm_attention_kv_bias; everything around it is the same."""
     B, N, C = hidden_states.shape
     heads = attn.heads
     scale = getattr(attn, "scale", None) or (C // heads) ** -0.5
@@ -916,7 +936,10 @@ def norm_cross_attention_residual(norm: torch.nn.Module, attn: torch.nn.Module, 
     if ip is None:
         Mk = encoder_hidden_states.shape[1]
         k, vt = _cross_kv(attn.to_k, attn.to_v, _pad_keys(encoder_hidden_states, dt), C)
-        o = _lib.attention_kv(q, k, vt, heads, N, Mk, scale)
+        if attention_mask is None:
+            o = _lib.attention_kv(q, k, vt, heads, N, Mk, scale)
+        else:
+            o = _lib.attention_kv_bias(q, k, vt, heads, N, Mk, scale, key_bias(attention_mask, B, Mk, hs.device))
     else:
         o = _ip_core(attn, ip, q, N, scale, True)
     op = _lib.to_panels(o.view(n, C))
@@ -932,8 +955,10 @@ def _apply_linear(m: torch.nn.Module, t: torch.Tensor) -> torch.Tensor:
 def fused_cross_ok(norm: torch.nn.Module, attn: torch.nn.Module, x: torch.Tensor, encoder_hidden_states,
                    attention_mask, kwargs, processors=_PLAIN_PROCESSORS) -> bool:
     # (an IP-Adapter block hands a TUPLE as encoder_hidden_states: not a tensor, not this path -- see ip_cross_call)
-    return (FF_MODE == "panels" and isinstance(encoder_hidden_states, torch.Tensor) and attention_mask is None and not kwargs
+    # An attention_mask of the per-key form (``key_bias``) goes along: the core is then vtm_attention_kv_bias.
+    return (FF_MODE == "panels" and isinstance(encoder_hidden_states, torch.Tensor) and not kwargs
             and encoder_hidden_states.dim() == 3 and x.dim() == 3 and x.is_cuda and x.dtype in (torch.float16, torch.bfloat16)
+            and (attention_mask is None or _key_bias_ok(attention_mask, x.shape[0], encoder_hidden_states.shape[1], x.device))
             and type(norm) is torch.nn.LayerNorm and len(norm.normalized_shape) == 1
             and norm.normalized_shape[0] == x.shape[-1] and x.shape[-1] % 64 == 0 and x.shape[1] % 8 == 0
             and (norm.weight is None or norm.weight.dtype == x.dtype) and (norm.bias is None or norm.bias.dtype == x.dtype)
@@ -1002,12 +1027,13 @@ def cross_attention(attn: torch.nn.Module, x: torch.Tensor, encoder_hidden_state
                     attention_mask=None, **kwargs) -> torch.Tensor:
     """`self.attn2(norm_hidden_states, encoder_hidden_states=..., attention_mask=...)` (patch.py:178-183) -- the
     un-merged tokens attending to the conditioning (77 text tokens in SD).  The plain case (projection Linears, no
-    mask, no processor kwargs) runs on vtm_attention_kv, a recognised IP-Adapter call (``ip_cross_call``) on
-    vtm_attention_kv_sets (with region masks: vtm_attention_kv_sets_masked), with library GEMMs around the core; everything
-    else is the module's own forward."""
-    plain = (isinstance(encoder_hidden_states, torch.Tensor) and attention_mask is None and not kwargs
+    mask, no processor kwargs) runs on vtm_attention_kv, the plain case with a per-key additive mask (``key_bias``) on
+    vtm_attention_kv_bias, a recognised IP-Adapter call (``ip_cross_call``) on vtm_attention_kv_sets (with region masks:
+    vtm_attention_kv_sets_masked), with library GEMMs around the core; everything else is the module's own forward."""
+    plain = (isinstance(encoder_hidden_states, torch.Tensor) and not kwargs
              and encoder_hidden_states.dim() == 3 and x.dtype in (torch.float16, torch.bfloat16)
-             and fused_attention_ok(attn, x, self_attn=False))
+             and fused_attention_ok(attn, x, self_attn=False)
+             and (attention_mask is None or _key_bias_ok(attention_mask, x.shape[0], encoder_hidden_states.shape[1], x.device)))
     if not plain:
         ip = ip_cross_call(attn, x, encoder_hidden_states, attention_mask, kwargs)
         if ip is None:
@@ -1030,7 +1056,10 @@ def cross_attention(attn: torch.nn.Module, x: torch.Tensor, encoder_hidden_state
     q = _apply_linear(attn.to_q, x)
     k = _apply_linear(attn.to_k, enc)
     vt = _apply_linear(attn.to_v, enc).transpose(1, 2).contiguous()     # (B, C, Mkp): 77 keys, negligible
-    o = _lib.attention_kv(q, k, vt, heads, N, Mk, scale)
+    if attention_mask is None:
+        o = _lib.attention_kv(q, k, vt, heads, N, Mk, scale)
+    else:
+        o = _lib.attention_kv_bias(q, k, vt, heads, N, Mk, scale, key_bias(attention_mask, B, Mk, x.device))
     return _apply_linear(_out_linear(attn), o)[:, :N]
 
 
@@ -1271,7 +1300,8 @@ def make_diffusers_tome_block(block_class: Type[torch.nn.Module]) -> Type[torch.
                                                                     encoder_hidden_states, encoder_attention_mask,
                                                                     cross_attention_kwargs):
                     hidden_states = norm_cross_attention_residual(self.norm2, self.attn2, hidden_states,
-                                                                  encoder_hidden_states)
+                                                                  encoder_hidden_states,
+                                                                  attention_mask=encoder_attention_mask)
                 elif not self.use_ada_layer_norm and f32_cross_ok(self, self.norm2, self.attn2, hidden_states,
                                                                   encoder_hidden_states, encoder_attention_mask,
                                                                   cross_attention_kwargs):
@@ -1279,8 +1309,13 @@ def make_diffusers_tome_block(block_class: Type[torch.nn.Module]) -> Type[torch.
                 else:
                     norm_hidden_states = (self.norm2(hidden_states, timestep) if self.use_ada_layer_norm
                                           else layer_norm(self.norm2, hidden_states))
-                    attn_output = cross_attention(self.attn2, norm_hidden_states, encoder_hidden_states,
-                                                  encoder_attention_mask, **cross_attention_kwargs)
+                    if self.use_ada_layer_norm and encoder_attention_mask is not None:
+                        # AdaLayerNorm blocks keep the module's own forward for a masked call, whatever the mask's form
+                        attn_output = self.attn2(norm_hidden_states, encoder_hidden_states=encoder_hidden_states,
+                                                 attention_mask=encoder_attention_mask, **cross_attention_kwargs)
+                    else:
+                        attn_output = cross_attention(self.attn2, norm_hidden_states, encoder_hidden_states,
+                                                      encoder_attention_mask, **cross_attention_kwargs)
                     hidden_states = attn_output + hidden_states
 
             if not self.use_ada_layer_norm_zero and fused_ff_ok(self.norm3, self.ff, hidden_states):   # patch.py:187-199
