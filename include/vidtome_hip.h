@@ -344,6 +344,12 @@ int vtm_attention_kv(const void *q, int64_t ldq, const void *k, int64_t ldk, con
                      int64_t Mk, int64_t Mkp, int64_t d, float scale, int share_groups, void *ws, size_t ws_bytes,
                      vtm_stream_t stream);
 
+/* Row counts of every attention entry: rows are addressed as (b * Mp + i) * ld, so only the LEADING DIMENSIONS must keep the
+ * 16-byte alignment (ldq, ldk, ldvt multiples of 8, ldo of 4); Mp / Mqp / Mkp may be any count >= M / Mq / Mk, the sequence
+ * length itself included (dense (B, M, .) buffers: a frame of 405 or 1590 tokens needs no padded copy; vtm_attention_kv_bias
+ * alone asks Mkp % 8 == 0).  Key rows >= Mk are never read; of vt only ldvt >= Mk rounded up to 8 is asked and the columns
+ * >= Mk may hold anything (they are masked before the PV product). */
+
 /* vtm_attention_kv_sets -- cross-attention over SEVERAL key sets, one softmax per set: what an image-prompt adapter
  * (IP-Adapter's "decoupled cross-attention") turns the `self.attn2(...)` call of vidtome/patch.py:178-183 into.  Per head
  *     out[b, i] = sum_{s < n_sets} w_s * softmax_{j in set s}(q[b, i] . k[b, j] * scale) v[b, j]

@@ -599,7 +599,9 @@ def unmerged_site(block: torch.nn.Module, x: torch.Tensor) -> bool:
 
 def unmerged_self_attention_ok(block: torch.nn.Module, x: torch.Tensor) -> bool:
     norm, attn = block.norm1, block.attn1
-    return (x.is_cuda and x.dim() == 3 and x.shape[1] % 8 == 0 and type(norm) is torch.nn.LayerNorm and len(norm.normalized_shape) == 1
+    # (any token count: q and k are row ranges of the dense (BF, N, 3C) projection -- the cores address a row as
+    # (sample * N + row) * ld with ld % 8 == 0 -- and only V^T needs a padded row, which vtm_transpose_cols writes)
+    return (x.is_cuda and x.dim() == 3 and type(norm) is torch.nn.LayerNorm and len(norm.normalized_shape) == 1
             and norm.normalized_shape[0] == x.shape[-1] and (norm.weight is None or norm.weight.dtype == x.dtype)
             and (norm.bias is None or norm.bias.dtype == x.dtype) and fused_attention_ok(attn, x)
             and panel_projections_ok(attn, x) and not fused_projections_ok(attn, x) and _pnp_share_groups(attn) == 1
@@ -629,7 +631,8 @@ def unmerged_self_attention_residual(block: torch.nn.Module, hidden_states: torc
     wqkv, bqkv = _packed(attn, "qkv", tuple(p[2] for p in qkv_params), qkv_params[0][0].device, pack_qkv)
     xp = _lib.layernorm_panels(hs, norm.weight, norm.bias, norm.eps)
     qkv = _lib.linear_panels(xp, n, wqkv, 3 * C, bqkv).view(BF, N, 3 * C)
-    vt = _lib.transpose_cols(qkv, 2 * C, C)                              # (BF, C, N): V channel-major for the PV contraction
+    # (BF, C, N rounded up to 8): V channel-major for the PV contraction, the key columns past N written as zeros
+    vt = _lib.transpose_cols(qkv, 2 * C, C)
     o = _lib.attention(qkv[:, :, :C], qkv[:, :, C:2 * C], vt, heads, N, scale, 1)
     wo, bo = _panel_weight(_out_linear(attn))
     op = _lib.to_panels(o.view(n, C))
@@ -930,9 +933,7 @@ def norm_cross_attention_residual(norm: torch.nn.Module, attn: torch.nn.Module, 
     wq, bq = _panel_weight(attn.to_q)
     wo, bo = _panel_weight(_out_linear(attn))
     xp = _lib.layernorm_panels(hs, norm.weight, norm.bias, norm.eps)
-    q = _lib.linear_panels(xp, n, wq, C, bq).view(B, N, C)
-    if N % 8:
-        raise RuntimeError("norm_cross_attention_residual: token count must be a multiple of 8")
+    q = _lib.linear_panels(xp, n, wq, C, bq).view(B, N, C)             # any N: the core's query row stride is N itself
     if ip is None:
         Mk = encoder_hidden_states.shape[1]
         k, vt = _cross_kv(attn.to_k, attn.to_v, _pad_keys(encoder_hidden_states, dt), C)
@@ -960,7 +961,7 @@ def fused_cross_ok(norm: torch.nn.Module, attn: torch.nn.Module, x: torch.Tensor
             and encoder_hidden_states.dim() == 3 and x.dim() == 3 and x.is_cuda and x.dtype in (torch.float16, torch.bfloat16)
             and (attention_mask is None or _key_bias_ok(attention_mask, x.shape[0], encoder_hidden_states.shape[1], x.device))
             and type(norm) is torch.nn.LayerNorm and len(norm.normalized_shape) == 1
-            and norm.normalized_shape[0] == x.shape[-1] and x.shape[-1] % 64 == 0 and x.shape[1] % 8 == 0
+            and norm.normalized_shape[0] == x.shape[-1] and x.shape[-1] % 64 == 0
             and (norm.weight is None or norm.weight.dtype == x.dtype) and (norm.bias is None or norm.bias.dtype == x.dtype)
             and _proj_dtypes_ok(attn, x.dtype) and fused_attention_ok(attn, x, self_attn=False, processors=processors))
 
@@ -977,6 +978,10 @@ def ip_cross_call(attn: torch.nn.Module, x: torch.Tensor, encoder_hidden_states,
     if ip is None:
         return None
     if norm is not None:
+        # the panel path of an IP-Adapter call still asks N % 8 == 0, as tests/test_ip_adapter_host.py
+        # (test_panel_path_asks_what_fused_cross_ok_asks) pins: other token counts take cross_attention's library GEMMs
+        if x.dim() != 3 or x.shape[1] % 8:
+            return None
         return ip if fused_cross_ok(norm, attn, x, ip.text, None, None, ip_adapter.PROCESSORS) else None
     return ip if fused_attention_ok(attn, x, self_attn=False, processors=ip_adapter.PROCESSORS) else None
 
