@@ -612,6 +612,33 @@ int vtm_dora_fold(const void *w, int dtype, const float *up, const float *down, 
                   const float *norms, int64_t c_out, int64_t c_in, int64_t r, int64_t k_dora, void *out,
                   vtm_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * vtm_loha_delta / vtm_lokr_delta / vtm_delta_fold -- the effective weight of a projection wrapped in a LyCORIS layer
+ * (PEFT `LoHaConfig` / `LoKrConfig`).  Beyond the reference: it loads adapters through `pipe.load_lora_weights(
+ * **gene_config.lora)` (generate.py:93-94), and these are the remaining adapter family Stable Diffusion users load on
+ * the same ten projections.  At inference either layer is one Linear,
+ *   LoHa: W_eff = W + sum_a s_a (W1a_a W1b_a) * (W2a_a W2b_a)   (* elementwise)
+ *   LoKr: W_eff = W + sum_a s_a kron(W1_a, W2_a),
+ * built as an fp32 delta (c_out, c_in) row-major, one adapter per call in PEFT's adapter order (accumulate = 0 writes
+ * delta, 1 adds to what it holds with one fp32 addition), then folded into W.  All operands fp32 row-major; the host
+ * multiplies s_a into one factor (w1a / w1) in fp32.
+ * vtm_loha_delta: delta[o, i] (+)= (sum_{k < r} w1a[o, k] w1b[k, i]) * (sum_{k < r} w2a[o, k] w2b[k, i]); w1a, w2a:
+ *   (c_out, r), w1b, w2b: (r, c_in).  Each sum is the k-ascending fp32 fmaf chain from +0 of vtm_lora_fold; then one fp32
+ *   product.
+ * vtm_lokr_delta: delta[i1 * a2 + i2, j1 * b2 + j2] (+)= w1[i1, j1] * w2[i2, j2], one fp32 product; w1: (a1, b1), w2:
+ *   (a2, b2), a1 * a2 = c_out and b1 * b2 = c_in (else VTM_EINVAL).  A low-rank factor is multiplied out first by
+ *   vtm_lora_fold on a zero fp32 base.
+ * vtm_delta_fold: out[o, i] = round_dtype( fp32(w[o, i]) + delta[o, i] ); w, out: (c_out, c_in) in `dtype` (VTM_F16 /
+ *   VTM_BF16 / VTM_F32), out may alias w.
+ * Run once per adapter state, not per step; two calls give the same bits.  Sizes > 0 (else VTM_EINVAL).
+ * ---------------------------------------------------------------------------------------------- */
+int vtm_loha_delta(const float *w1a, const float *w1b, const float *w2a, const float *w2b, int64_t c_out, int64_t c_in,
+                   int64_t r, int accumulate, float *delta, vtm_stream_t stream);
+int vtm_lokr_delta(const float *w1, const float *w2, int64_t a1, int64_t b1, int64_t a2, int64_t b2, int64_t c_out,
+                   int64_t c_in, int accumulate, float *delta, vtm_stream_t stream);
+int vtm_delta_fold(const void *w, int dtype, const float *delta, int64_t c_out, int64_t c_in, void *out,
+                   vtm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

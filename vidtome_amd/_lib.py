@@ -102,6 +102,9 @@ _SIGNATURES = {
     "vtm_lora_fold": ([_vp, _int, _vp, _vp, _i64, _i64, _i64, _vp, _vp], _int),
     "vtm_dora_norms": ([_vp, _int, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp], _int),
     "vtm_dora_fold": ([_vp, _int, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp], _int),
+    "vtm_loha_delta": ([_vp, _vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp], _int),
+    "vtm_lokr_delta": ([_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _vp, _vp], _int),
+    "vtm_delta_fold": ([_vp, _int, _vp, _i64, _i64, _vp, _vp], _int),
     "vtm_linear_f32": ([_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _int, _vp, _vp, _int, _i64,
                         _i64, _int, _vp], _int),
 }
@@ -1066,4 +1069,70 @@ def dora_fold(w: torch.Tensor, up: torch.Tensor, down: torch.Tensor, magnitude: 
     _check(lib().vtm_dora_fold(_ptr(w), dtype_code(w), _ptr(up), _ptr(down), _ptr(_req(magnitude, "magnitude")),
                                _ptr(_req(norms, "norms")), c_out, c_in, r, k_dora, _ptr(_req(out, "out")), _stream()),
            "vtm_dora_fold")
+    return out
+
+
+def _f32_matrix(what: str, name: str, t: torch.Tensor, device) -> torch.Tensor:
+    _req(t, name)
+    if t.dtype != torch.float32 or t.dim() != 2 or t.device != device:
+        raise RuntimeError(f"{what}: {name} must be an fp32 matrix on the operands' device")
+    return t
+
+
+def _delta_out(what: str, out: Optional[torch.Tensor], accumulate: bool, c_out: int, c_in: int, device) -> torch.Tensor:
+    if out is None:
+        if accumulate:
+            raise RuntimeError(f"{what}: accumulate needs the delta to add to (out)")
+        return torch.empty((c_out, c_in), dtype=torch.float32, device=device)
+    if tuple(_f32_matrix(what, "out", out, device).shape) != (c_out, c_in):
+        raise RuntimeError(f"{what}: out must be ({c_out}, {c_in})")
+    return out
+
+
+@_on_device
+def loha_delta(w1a: torch.Tensor, w1b: torch.Tensor, w2a: torch.Tensor, w2b: torch.Tensor,
+               out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
+    """fp32 (c_out, c_in) delta of one LoHa adapter, (w1a @ w1b) * (w2a @ w2b) elementwise (the adapter's scale already in
+    w1a): written to `out` (a new tensor when None) or, with ``accumulate``, added to it; see include/vidtome_hip.h
+    vtm_loha_delta."""
+    dev = w1a.device
+    for name, t in (("w1a", w1a), ("w1b", w1b), ("w2a", w2a), ("w2b", w2b)):
+        _f32_matrix("loha_delta", name, t, dev)
+    (c_out, r), c_in = w1a.shape, w1b.shape[1]
+    if tuple(w1b.shape) != (r, c_in) or tuple(w2a.shape) != (c_out, r) or tuple(w2b.shape) != (r, c_in):
+        raise RuntimeError("loha_delta: w1a / w2a must be (c_out, r) and w1b / w2b (r, c_in) with one rank r")
+    out = _delta_out("loha_delta", out, accumulate, c_out, c_in, dev)
+    _check(lib().vtm_loha_delta(_ptr(w1a), _ptr(w1b), _ptr(w2a), _ptr(w2b), c_out, c_in, r, int(bool(accumulate)), _ptr(out),
+                                _stream()), "vtm_loha_delta")
+    return out
+
+
+@_on_device
+def lokr_delta(w1: torch.Tensor, w2: torch.Tensor, out: Optional[torch.Tensor] = None,
+               accumulate: bool = False) -> torch.Tensor:
+    """fp32 (a1 a2, b1 b2) delta of one LoKr adapter, kron(w1 (a1, b1), w2 (a2, b2)) (the adapter's scale already in w1):
+    written to `out` or, with ``accumulate``, added to it; see include/vidtome_hip.h vtm_lokr_delta."""
+    dev = w1.device
+    _f32_matrix("lokr_delta", "w1", w1, dev), _f32_matrix("lokr_delta", "w2", w2, dev)
+    (a1, b1), (a2, b2) = w1.shape, w2.shape
+    out = _delta_out("lokr_delta", out, accumulate, a1 * a2, b1 * b2, dev)
+    _check(lib().vtm_lokr_delta(_ptr(w1), _ptr(w2), a1, b1, a2, b2, a1 * a2, b1 * b2, int(bool(accumulate)), _ptr(out),
+                                _stream()), "vtm_lokr_delta")
+    return out
+
+
+@_on_device
+def delta_fold(w: torch.Tensor, delta: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32(w) + delta rounded once to w's dtype: w (c_out, c_in), delta fp32 of the same shape; see
+    include/vidtome_hip.h vtm_delta_fold."""
+    _req(w, "w")
+    if w.dim() != 2 or tuple(_f32_matrix("delta_fold", "delta", delta, w.device).shape) != tuple(w.shape):
+        raise RuntimeError("delta_fold: delta must be an fp32 tensor of w's (c_out, c_in) shape on its device")
+    if out is None:
+        out = torch.empty_like(w)
+    if out.dtype != w.dtype or tuple(out.shape) != tuple(w.shape) or out.device != w.device:
+        raise RuntimeError("delta_fold: out must have w's shape, dtype and device")
+    c_out, c_in = w.shape
+    _check(lib().vtm_delta_fold(_ptr(w), dtype_code(w), _ptr(delta), c_out, c_in, _ptr(_req(out, "out")), _stream()),
+           "vtm_delta_fold")
     return out

@@ -11,6 +11,12 @@
 // the DoRA adapter as the first k_dora columns of up / rows of down.  The norms take a reduction over all of c_in: one
 // workgroup per 64-row band walks the column tiles in order (fixed summation order, the same bits on every call); the fold
 // is the tile kernel above with two chains, k < k_dora scaled per row by magnitude / norm, and k >= k_dora added as is.
+//
+// vtm_loha_delta / vtm_lokr_delta / vtm_delta_fold: the same for LyCORIS layers (PEFT LoHaConfig / LoKrConfig), whose
+// forward adds x (s (W1a W1b) * (W2a W2b))^T (LoHa, * elementwise) or x (s kron(W1, W2))^T (LoKr) per active adapter.  The
+// two delta kernels write (or add to) an fp32 delta of the projection's size, one adapter per call in PEFT's order; LoHa's
+// two low-rank products are the tile chains above, multiplied once; LoKr's is one product per element.  vtm_delta_fold
+// adds the summed delta to fp32(W) and rounds once to the model dtype.
 #include "common.h"
 
 namespace {
@@ -202,6 +208,58 @@ int launch_dora(const void *w, const float *up, const float *down, const float *
     return vtm::launch_status("vtm_dora_fold");
 }
 
+// delta[o, i] (+)= chain(w1a, w1b)[o, i] * chain(w2a, w2b)[o, i]: the two k-ascending fmaf chains of tile_chain through the
+// same staging, one after the other, then one fp32 product (and, accumulating, one fp32 addition to what delta holds).
+__global__ __launch_bounds__(THREADS) void loha_delta_kernel(const float *__restrict__ w1a, const float *__restrict__ w1b,
+                                                             const float *__restrict__ w2a, const float *__restrict__ w2b,
+                                                             int64_t c_out, int64_t c_in, int64_t r, int accumulate,
+                                                             float *__restrict__ delta) {
+    __shared__ __attribute__((aligned(16))) float us[KT][TILE + 4];
+    __shared__ __attribute__((aligned(16))) float ds[KT][TILE];
+    const int t = threadIdx.x, tx = t % 16, ty = t / 16;
+    const int64_t o0 = (int64_t)blockIdx.y * TILE, i0 = (int64_t)blockIdx.x * TILE;
+    float a1[4][4] = {}, a2[4][4] = {};
+    tile_chain(us, ds, a1, w1a, w1b, o0, i0, c_out, c_in, r, 0, r);
+    tile_chain(us, ds, a2, w2a, w2b, o0, i0, c_out, c_in, r, 0, r);
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const int64_t o = o0 + 4 * ty + p;
+        if (o >= c_out) continue;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int64_t i = i0 + 4 * tx + q;
+            if (i >= c_in) continue;
+            const float v = a1[p][q] * a2[p][q];
+            delta[o * c_in + i] = accumulate ? delta[o * c_in + i] + v : v;
+        }
+    }
+}
+
+// delta[i1 * a2 + i2, j1 * b2 + j2] (+)= w1[i1, j1] * w2[i2, j2]: one workgroup per 256 columns of one output row.
+__global__ __launch_bounds__(THREADS) void lokr_delta_kernel(const float *__restrict__ w1, const float *__restrict__ w2,
+                                                             int64_t b1, int64_t a2, int64_t b2, int64_t c_in,
+                                                             int accumulate, float *__restrict__ delta) {
+    const int64_t o = blockIdx.x, i = (int64_t)blockIdx.y * THREADS + threadIdx.x;
+    if (i >= c_in) return;
+    const int64_t i1 = o / a2, i2 = o % a2, j1 = i / b2, j2 = i % b2;
+    const float v = w1[i1 * b1 + j1] * w2[i2 * b2 + j2];
+    delta[o * c_in + i] = accumulate ? delta[o * c_in + i] + v : v;
+}
+
+// out[e] = round_dtype(fp32(w[e]) + delta[e])
+template <typename T>
+__global__ __launch_bounds__(THREADS) void delta_fold_kernel(const T *__restrict__ w, const float *__restrict__ delta,
+                                                             int64_t n, T *__restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+    if (e < n) out[e] = from_f32<T>(vtm::to_f32(w[e]) + delta[e]);
+}
+
+template <typename T> int launch_delta_fold(const void *w, const float *delta, int64_t n, void *out, hipStream_t s) {
+    hipLaunchKernelGGL(delta_fold_kernel<T>, dim3((unsigned)vtm::cdiv(n, THREADS)), dim3(THREADS), 0, s, (const T *)w, delta, n,
+                       (T *)out);
+    return vtm::launch_status("vtm_delta_fold");
+}
+
 }  // namespace
 
 VTM_EXPORT int vtm_lora_fold(const void *w, int dtype, const float *up, const float *down, int64_t c_out, int64_t c_in,
@@ -254,5 +312,54 @@ VTM_EXPORT int vtm_dora_fold(const void *w, int dtype, const float *up, const fl
         case VTM_F16: return launch_dora<__half>(w, up, down, magnitude, norms, c_out, c_in, r, k_dora, out, s);
         case VTM_BF16: return launch_dora<vtm_bf16>(w, up, down, magnitude, norms, c_out, c_in, r, k_dora, out, s);
         default: return vtm::fail(VTM_EINVAL, "vtm_dora_fold: unsupported dtype %d", dtype);
+    }
+}
+
+VTM_EXPORT int vtm_loha_delta(const float *w1a, const float *w1b, const float *w2a, const float *w2b, int64_t c_out,
+                              int64_t c_in, int64_t r, int accumulate, float *delta, vtm_stream_t stream) {
+    VTM_REQUIRE(w1a && w1b && w2a && w2b && delta, "vtm_loha_delta: null pointer");
+    VTM_REQUIRE(c_out > 0 && c_in > 0 && r > 0, "vtm_loha_delta: bad sizes (c_out %lld, c_in %lld, r %lld)", (long long)c_out,
+                (long long)c_in, (long long)r);
+    VTM_REQUIRE(vtm::cdiv(c_out, TILE) <= 65535 && vtm::cdiv(c_in, TILE) <= (1ll << 31) - 1,
+                "vtm_loha_delta: c_out %lld / c_in %lld too large", (long long)c_out, (long long)c_in);
+    VTM_REQUIRE(accumulate == 0 || accumulate == 1, "vtm_loha_delta: accumulate %d is not 0 / 1", accumulate);
+    const dim3 grid((unsigned)vtm::cdiv(c_in, TILE), (unsigned)vtm::cdiv(c_out, TILE)), block(THREADS);
+    hipLaunchKernelGGL(loha_delta_kernel, grid, block, 0, vtm::as_stream(stream), w1a, w1b, w2a, w2b, c_out, c_in, r,
+                       accumulate, delta);
+    return vtm::launch_status("vtm_loha_delta");
+}
+
+VTM_EXPORT int vtm_lokr_delta(const float *w1, const float *w2, int64_t a1, int64_t b1, int64_t a2, int64_t b2, int64_t c_out,
+                              int64_t c_in, int accumulate, float *delta, vtm_stream_t stream) {
+    constexpr int64_t LIM = (1ll << 31) - 1;
+    VTM_REQUIRE(w1 && w2 && delta, "vtm_lokr_delta: null pointer");
+    VTM_REQUIRE(a1 > 0 && b1 > 0 && a2 > 0 && b2 > 0 && c_out > 0 && c_in > 0,
+                "vtm_lokr_delta: bad sizes (%lld x %lld kron %lld x %lld for %lld x %lld)", (long long)a1, (long long)b1,
+                (long long)a2, (long long)b2, (long long)c_out, (long long)c_in);
+    VTM_REQUIRE(a1 <= LIM && b1 <= LIM && a2 <= LIM && b2 <= LIM && a1 * a2 == c_out && b1 * b2 == c_in,
+                "vtm_lokr_delta: %lld x %lld kron %lld x %lld is not %lld x %lld", (long long)a1, (long long)b1, (long long)a2,
+                (long long)b2, (long long)c_out, (long long)c_in);
+    VTM_REQUIRE(c_out <= LIM && vtm::cdiv(c_in, THREADS) <= 65535, "vtm_lokr_delta: c_out %lld / c_in %lld too large",
+                (long long)c_out, (long long)c_in);
+    VTM_REQUIRE(accumulate == 0 || accumulate == 1, "vtm_lokr_delta: accumulate %d is not 0 / 1", accumulate);
+    const dim3 grid((unsigned)c_out, (unsigned)vtm::cdiv(c_in, THREADS)), block(THREADS);
+    hipLaunchKernelGGL(lokr_delta_kernel, grid, block, 0, vtm::as_stream(stream), w1, w2, b1, a2, b2, c_in, accumulate, delta);
+    return vtm::launch_status("vtm_lokr_delta");
+}
+
+VTM_EXPORT int vtm_delta_fold(const void *w, int dtype, const float *delta, int64_t c_out, int64_t c_in, void *out,
+                              vtm_stream_t stream) {
+    constexpr int64_t LIM = (1ll << 31) - 1;
+    VTM_REQUIRE(w && delta && out, "vtm_delta_fold: null pointer");
+    VTM_REQUIRE(c_out > 0 && c_in > 0, "vtm_delta_fold: bad sizes (c_out %lld, c_in %lld)", (long long)c_out, (long long)c_in);
+    VTM_REQUIRE(c_out <= LIM && c_in <= LIM && vtm::cdiv(c_out * c_in, THREADS) <= LIM,
+                "vtm_delta_fold: c_out %lld / c_in %lld too large", (long long)c_out, (long long)c_in);
+    hipStream_t s = vtm::as_stream(stream);
+    const int64_t n = c_out * c_in;
+    switch (dtype) {
+        case VTM_F32: return launch_delta_fold<float>(w, delta, n, out, s);
+        case VTM_F16: return launch_delta_fold<__half>(w, delta, n, out, s);
+        case VTM_BF16: return launch_delta_fold<vtm_bf16>(w, delta, n, out, s);
+        default: return vtm::fail(VTM_EINVAL, "vtm_delta_fold: unsupported dtype %d", dtype);
     }
 }

@@ -29,6 +29,19 @@ DoRA adapter is already in the base weight (PEFT's ``merge()`` writes ``r (W + s
 any merged adapter.  The state token adds the magnitude's (pointer, version).  The extra memory is the LoRA fold's: one
 folded copy per adapted projection.
 
+LyCORIS layers (PEFT's ``LoHaConfig`` / ``LoKrConfig``, the same ten projections) are recognised as two more kinds, LOHA
+and LOKR: a ``base_layer`` (a plain Linear), ``active_adapters``, ``merged``, ``merged_adapters``, ``disable_adapters``, a
+``scaling`` dict and the factor ParameterDicts -- ``hada_w1_a`` (c_out, r), ``hada_w1_b`` (r, c_in), ``hada_w2_a``,
+``hada_w2_b`` for LoHa; ``lokr_w1`` (a1, b1) or the pair ``lokr_w1_a`` / ``lokr_w1_b``, and ``lokr_w2`` (a2, b2) or the pair
+``lokr_w2_a`` / ``lokr_w2_b`` with a1 a2 = c_out, b1 b2 = c_in for LoKr.  Their forward adds ``F.linear(x, delta_a)`` per active
+adapter, ``delta_a = s_a (W1a W1b) * (W2a W2b)`` (elementwise) or ``s_a kron(W1, W2)``, so the layer is the Linear
+``W + sum_a delta_a`` with the base bias (these adapters carry none): vtm_loha_delta / vtm_lokr_delta sum the deltas in
+fp32 in PEFT's adapter order and vtm_delta_fold adds them to the base weight and rounds once (the fp32 delta is a
+temporary of the fold; what stays is one folded copy, as for LoRA).  The token covers every factor tensor's (pointer,
+version).  Not recognised: Tucker / conv forms (an active adapter with a ``hada_t1`` / ``hada_t2`` / ``lokr_t2`` entry),
+``rank_dropout`` / ``module_dropout`` > 0 in training mode, merged and disabled at once, a layer that also has ``lora_A``
+(or both families' factors), and any shape mismatch.
+
 Anything else -- DoRA after another adapter or on more than one adapter (which running result PEFT scales there has
 changed between releases), DoRA without a magnitude vector or with a ``lora_B`` bias, ``fan_in_fan_out``, dropout with
 p > 0 in training mode, adapters that are not Linears, other wrappers -- is not recognised and the patched block keeps the
@@ -43,6 +56,10 @@ import torch
 from . import _lib
 
 PLAIN, PEFT, LEGACY = "plain", "peft", "legacy"
+LOHA, LOKR = "loha", "lokr"
+_WRAPPED = (PEFT, LOHA, LOKR)           # the kinds whose base weight lives in ``base_layer``
+_LOHA_DICTS = ("hada_w1_a", "hada_w1_b", "hada_w2_a", "hada_w2_b")
+_LOKR_DICTS = ("lokr_w1", "lokr_w1_a", "lokr_w1_b", "lokr_w2", "lokr_w2_a", "lokr_w2_b")
 
 
 def _plain(m) -> bool:
@@ -134,8 +151,92 @@ def _legacy_ok(m) -> bool:
             and _adapter_linear(up, down.out_features, m.out_features, bias_ok=True))
 
 
+def _entry(m, dict_name: str, a: str):
+    """LyCORIS: adapter `a`'s entry in the ParameterDict `dict_name` of the layer, or None."""
+    d = getattr(m, dict_name, None)
+    try:
+        return d[a] if d is not None and a in d else None
+    except TypeError:
+        return None
+
+
+def _lyco_kind(m) -> Optional[str]:
+    """LOHA / LOKR by the factor dicts the layer carries, "" for a layer that carries both families', None for neither."""
+    loha = any(hasattr(m, n) for n in _LOHA_DICTS)
+    lokr = any(hasattr(m, n) for n in _LOKR_DICTS)
+    return "" if loha and lokr else LOHA if loha else LOKR if lokr else None
+
+
+def _lyco_active(m, kind: str):
+    """LyCORIS: the active adapters that have weights on this layer, in PEFT's order."""
+    names = m.active_adapters
+    names = [names] if isinstance(names, str) else list(names)
+    has = (lambda a: _entry(m, "hada_w1_a", a) is not None) if kind == LOHA else \
+        (lambda a: _entry(m, "lokr_w1", a) is not None or _entry(m, "lokr_w1_a", a) is not None)
+    return [a for a in names if has(a)]
+
+
+def _matrix(t, rows: Optional[int] = None, cols: Optional[int] = None) -> bool:
+    return (isinstance(t, torch.Tensor) and t.is_floating_point() and t.dim() == 2 and min(t.shape) > 0
+            and rows in (None, t.shape[0]) and cols in (None, t.shape[1]))
+
+
+def _lokr_factor(m, which: str, a: str):
+    """LoKr: adapter `a`'s factor "w1" / "w2" as (W,) or the low-rank pair (Wa (rows, r), Wb (r, cols)), or None."""
+    full, lo_a, lo_b = (_entry(m, f"lokr_{which}{sfx}", a) for sfx in ("", "_a", "_b"))
+    if full is not None:
+        return (full,) if lo_a is None and lo_b is None and _matrix(full) else None
+    if not (_matrix(lo_a) and _matrix(lo_b, rows=lo_a.shape[1])):
+        return None
+    return (lo_a, lo_b)
+
+
+def _lyco_factors(m, kind: str, a: str):
+    """Adapter `a`'s factor tensors when they multiply out to the base weight's shape, else None: LoHa (w1a, w1b, w2a, w2b)
+    with one rank; LoKr (factor w1, factor w2), each as `_lokr_factor` gives it."""
+    c_out, c_in = m.base_layer.out_features, m.base_layer.in_features
+    if kind == LOHA:
+        w1a, w1b, w2a, w2b = (_entry(m, n, a) for n in _LOHA_DICTS)
+        if not (_matrix(w1a, rows=c_out) and _matrix(w1b, rows=w1a.shape[1], cols=c_in)
+                and _matrix(w2a, rows=c_out, cols=w1a.shape[1]) and _matrix(w2b, rows=w1a.shape[1], cols=c_in)):
+            return None
+        return (w1a, w1b, w2a, w2b)
+    f1, f2 = _lokr_factor(m, "w1", a), _lokr_factor(m, "w2", a)
+    if f1 is None or f2 is None:
+        return None
+    if f1[0].shape[0] * f2[0].shape[0] != c_out or f1[-1].shape[1] * f2[-1].shape[1] != c_in:
+        return None
+    return (f1, f2)
+
+
+def _lyco_ok(m, kind: str) -> bool:
+    if not all(hasattr(m, a) for a in ("base_layer", "active_adapters", "merged", "merged_adapters", "disable_adapters",
+                                       "scaling")):
+        return False
+    if not _plain(m.base_layer) or not isinstance(m.scaling, dict):
+        return False
+    if m.disable_adapters and m.merged:
+        return False            # PEFT's forward unmerges first (a side effect the module path performs)
+    for a in _lyco_active(m, kind):
+        if any(_entry(m, t, a) is not None for t in ("hada_t1", "hada_t2", "lokr_t2")):
+            return False        # Tucker / conv forms
+        if a not in m.scaling or _lyco_factors(m, kind, a) is None:
+            return False
+        for drop in ("rank_dropout", "module_dropout"):
+            p = getattr(m, drop, 0.0)
+            p = p.get(a, 0.0) if isinstance(p, dict) else p
+            if m.training and float(p or 0.0) > 0:
+                return False
+    return True
+
+
 def recognise(m) -> Optional[str]:
-    """PLAIN / PEFT / LEGACY, or None when the fused path must not read this projection (the module path keeps running)."""
+    """PLAIN / PEFT / LEGACY / LOHA / LOKR, or None when the fused path must not read this projection (the module path
+    keeps running)."""
+    if not isinstance(m, torch.nn.Linear) and hasattr(m, "base_layer"):
+        kind = _lyco_kind(m)
+        if kind is not None:
+            return kind if kind and not hasattr(m, "lora_A") and _lyco_ok(m, kind) else None
     if isinstance(m, torch.nn.Linear):
         name = type(m).__name__
         if name not in ("Linear", "LoRACompatibleLinear"):
@@ -150,7 +251,7 @@ def recognise(m) -> Optional[str]:
 
 def base_linear(m) -> torch.nn.Linear:
     """The Linear holding the base weight (shapes, dtype and device of the effective weight) of a recognised projection."""
-    return m.base_layer if recognise(m) == PEFT else m
+    return m.base_layer if recognise(m) in _WRAPPED else m
 
 
 def _tkey(t: Optional[torch.Tensor]):
@@ -174,24 +275,67 @@ def _adapters(m, kind: str):
              _magnitude(m, a) if _flag(m.use_dora, a) else None) for a in _active(m)]
 
 
+def _lyco_terms(m, kind: str):
+    """[(name, scale, factor tensors as `_lyco_factors` gives them)] of the LyCORIS adapters the forward adds."""
+    if m.disable_adapters or m.merged:
+        return []
+    return [(a, m.scaling[a], _lyco_factors(m, kind, a)) for a in _lyco_active(m, kind)]
+
+
+def _tkeys(ts) -> tuple:
+    return tuple(_tkeys(t) if isinstance(t, tuple) else _tkey(t) for t in ts)
+
+
 def state_token(m, kind: Optional[str] = None) -> tuple:
     """Everything the effective weight of a LoRA layer depends on that the fold cannot see in the tensors themselves."""
     kind = kind or recognise(m)
-    base = m.base_layer if kind == PEFT else m
+    base = m.base_layer if kind in _WRAPPED else m
     tok = (kind, _param_key(base.weight, base.bias))
-    if kind == PEFT:
+    if kind in _WRAPPED:
         merged = tuple(getattr(m, "merged_adapters", ()))
         tok += (bool(m.disable_adapters), bool(m.merged), merged)
+        if kind != PEFT:
+            return tok + tuple((a, float(s), _tkeys(ts)) for a, s, ts in _lyco_terms(m, kind))
     elif kind == LEGACY:
         tok += (m.lora_layer.network_alpha, m.lora_layer.rank)
     return tok + tuple((a, float(s), _tkey(A), _tkey(B), _tkey(bB)) + (() if mag is None else ("dora", _tkey(mag)))
                        for a, s, A, B, bB, mag in _adapters(m, kind))
 
 
+def _fold_lycoris(m, kind: str, w: torch.Tensor):
+    """The folded weight of a LoHa / LoKr layer, or None when its forward adds no adapter right now.  The fp32 delta is a
+    temporary: the adapters' deltas summed in PEFT's order, added to fp32(w) and rounded once."""
+    terms = _lyco_terms(m, kind)
+    if not terms:
+        return None
+    f32 = lambda t: t.detach().to(device=w.device, dtype=torch.float32).contiguous()
+
+    def factor(f, s=None):      # a LoKr factor as one fp32 matrix; a low-rank pair is multiplied out by vtm_lora_fold from zero
+        first = f32(f[0]) if s is None else (f32(f[0]) * float(s)).contiguous()
+        if len(f) == 1:
+            return first
+        second = f32(f[1])
+        zero = torch.zeros((first.shape[0], second.shape[1]), dtype=torch.float32, device=w.device)
+        return _lib.lora_fold(zero, first, second)
+
+    with torch.no_grad():
+        delta = None
+        for _, s, ts in terms:
+            if kind == LOHA:
+                delta = _lib.loha_delta((f32(ts[0]) * float(s)).contiguous(), f32(ts[1]), f32(ts[2]), f32(ts[3]), out=delta,
+                                        accumulate=delta is not None)
+            else:
+                delta = _lib.lokr_delta(factor(ts[0], s), factor(ts[1]), out=delta, accumulate=delta is not None)
+        return _lib.delta_fold(w.contiguous(), delta)
+
+
 def _fold(m, kind: str):
     """(weight, bias, folded?) of the adapted layer, in the base weight's dtype on its device."""
-    base = m.base_layer if kind == PEFT else m
+    base = m.base_layer if kind in _WRAPPED else m
     w, b = base.weight.detach(), None if base.bias is None else base.bias.detach()
+    if kind in (LOHA, LOKR):
+        wf = _fold_lycoris(m, kind, w)
+        return (w, b, False) if wf is None else (wf, b, True)
     ads = _adapters(m, kind)
     if not ads:
         return w, b, False
@@ -216,7 +360,7 @@ def _fold(m, kind: str):
 def linear_params(m, dtype: Optional[torch.dtype] = None, device=None
                   ) -> Optional[Tuple[torch.Tensor, Optional[torch.Tensor], tuple]]:
     """(weight, bias, key) of the Linear the projection computes, or None when `m` is neither a plain Linear nor a
-    recognised LoRA layer.  A plain Linear gives its own tensors, key = their (pointer, version, dtype, device).  A LoRA
+    recognised LoRA / LyCORIS layer.  A plain Linear gives its own tensors, key = their (pointer, version, dtype, device).  A LoRA
     layer gives the folded weight / bias (one copy of the projection weight in the model dtype, cached on the module under
     its state token, which is also the key); a chunk on another HIP stream than the fold's waits for it on the device.
     ``dtype`` / ``device``: the tensors are returned converted (a no-op when they already are; not cached)."""
