@@ -320,7 +320,7 @@ int vtm_unmerge_add(const void *y, int64_t M, const int32_t *inv, const void *re
  * is read without a transpose.  dtype VTM_F16 or VTM_BF16 (16-bit MFMA, fp32 accumulation) or VTM_F32 (fp32 operands,
  * products and accumulation on the f32 MFMA, csrc/attention_f32.hip: about 16x the matrix time); d in
  * {8,16,32,40,64,80,96,128,160}.  The same dtypes for vtm_attention_kv, _bounded and _shared_bounded; the fp32 path
- * fits the workspace the *_ws_bytes functions return and takes its split plan only when the workspace holds it.
+ * takes its split plans only when the workspace holds them: size it with the *_ws_bytes_dtype functions.
  * share_groups > 1 = the PnP injection branch (pnp_utils.py:57-67,86-90): probabilities of sample
  * b come from q/k of sample b % (B / share_groups), v stays per sample.
  * ---------------------------------------------------------------------------------------------- */
@@ -335,6 +335,10 @@ int vtm_attention(const void *q, int64_t ldq, const void *k, int64_t ldk, const 
  * accumulators, running max, denominator) live in this workspace and are merged by a second kernel.  ws may be NULL
  * (no splitting, slower for such shapes). */
 size_t vtm_attention_ws_bytes(int64_t B, int64_t h, int64_t Mq, int64_t Mk, int64_t d);
+/* The same for a call of element type `dtype`.  VTM_F16 / VTM_BF16: exactly vtm_attention_ws_bytes.  VTM_F32: the size the
+ * fp32 kernel's own plans take (other query rows per workgroup, other resident workgroups per CU, another partial record:
+ * neither size bounds the other, and an fp32 launch handed the 16-bit size may silently run without its split tail). */
+size_t vtm_attention_ws_bytes_dtype(int dtype, int64_t B, int64_t h, int64_t Mq, int64_t Mk, int64_t d);
 
 /* The same kernel with separate query / key lengths: the block's cross-attention `self.attn2(...)`
  * (vidtome/patch.py:178-183; SD: Mk = 77 text tokens per frame).  q (B, Mqp, .) / out as above; k (B, Mkp, .),
@@ -421,6 +425,8 @@ int vtm_attention_kv_shared_bounded(const void *q, int64_t ldq, const void *k, i
  * work item is split in two along the key axis (one partial record per workgroup, merged by a second kernel); with less
  * workspace than this the launch falls back to the plain plan of vtm_attention_ws_bytes */
 size_t vtm_attention_kv_bounded_ws_bytes(int64_t B, int64_t h, int64_t Mq, int64_t Mk, int64_t d);
+/* ... for a call of element type `dtype` (see vtm_attention_ws_bytes_dtype) */
+size_t vtm_attention_kv_bounded_ws_bytes_dtype(int dtype, int64_t B, int64_t h, int64_t Mq, int64_t Mk, int64_t d);
 
 /* vtm_transpose_cols -- V^T of a block that does not merge (patch.py:157-162 at the sites beyond max_downsample: per-frame
  * attention): the q | k | v projection GEMM leaves v as columns of its token-major output, the attention core reads V

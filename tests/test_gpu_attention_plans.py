@@ -15,12 +15,21 @@ arithmetic, partial-record layout and combine, so each is pinned here on its own
   split piece), large finite garbage in every operand element the kernels must not read, operands with ld = 2C / 3C and
   an output window with ldo > C inside a larger buffer whose gap columns and guard rows must keep their canaries.
 
-Bars (unchanged from the rest of the suite): 1e-3 (fp16) / 8e-3 (bf16) of max(1, |ref|max)."""
+The fp32 family (attention_f32_kernel, csrc/attention_f32.hip: 32-key tiles, 4 waves, its own partial record and combine
+kernel, sharing done in-kernel) goes through the same planner and is pinned by the same harness as a fourth kind, "f32":
+fp32 operands in the same windows, 1e30 in the V^T columns no kernel may use, a 32-bit NaN canary around the output
+window (rows Mq .. Mqp included), the workspace checked record by record.  Also here: split pieces that hold no key tile
+(129 tiles cut 16 ways, every family), and the workspace the Python binding hands to an fp32 launch.
+
+Bars (unchanged from the rest of the suite): 1e-3 (fp16) / 8e-3 (bf16) of max(1, |ref|max); fp32: 2e-5 of |ref|max per
+launch (BAR of test_gpu_fp32_attention.py, derived there from the fp32 rounding of the longest sums)."""
 import zlib
 
 import numpy as np
 import pytest
 import torch
+
+from test_gpu_fp32_attention import BAR               # 2e-5 of the output scale (derivation: that module's docstring)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -28,10 +37,13 @@ KV = 64                                               # keys per tile (attention
 QW = 32                                               # queries per wave (attention_common.h:20)
 DEVPLAN_HEADER = 256                                  # attention_plan.h:326
 PLAN_TIERS, PLAN_MAX_SPLIT = 8, 16                    # attention_plan.h:169-170
+KT32 = 32                                             # keys per tile of the fp32 kernel (attention_f32.hip:30)
 TOL = {torch.float16: 1e-3, torch.bfloat16: 8e-3}
-DT_CODE = {torch.float16: 1, torch.bfloat16: 2}
+DT_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 KERNEL_DIMS = (8, 16, 32, 64, 80, 96, 128, 160)
+F32_DIMS = (8, 16, 32, 40, 64, 80, 96, 128, 160)
 CANARY = 0x7E5A                                       # a NaN in fp16 and in bf16: no kernel result has these bits
+CANARY32 = 0x7FC5A5A5                                 # a quiet NaN with a payload no fp32 arithmetic produces
 GUARD_ROWS = 16
 # score of a planted key for its query, natural-log units: 14, capped at 1.5 sqrt(d).  The same key gives every other query
 # a score k_j . q_m = PLANT_LOGIT cos(q_i, q_m) |q_m| / |q_i|, spread ~ PLANT_LOGIT / sqrt(d): the cap keeps those scores
@@ -41,6 +53,8 @@ GUARD_ROWS = 16
 # moves its query's output by ten times the bar and more
 PLANT_LOGIT, PLANT_SPREAD = 14.0, 1.5
 GARBAGE_K, GARBAGE_V, GARBAGE_Q = 200.0, 30000.0, 200.0
+# fp32: a probability of 2e-5 / 1e30 leaking onto a key behind Mk still moves the output by the whole bar
+GARBAGE_V32 = 1e30
 
 
 @pytest.fixture(scope="module")
@@ -87,11 +101,20 @@ def rec16(D):                                         # attention16_parts.h:12
 
 class Family:
     """Launch constants of one kernel family: query rows per workgroup, resident workgroups per CU, bytes of one
-    key-split workgroup's partial record, the query blocks from which (sample, head) pairs are pinned to XCDs."""
+    key-split workgroup's partial record, the query blocks from which (sample, head) pairs are pinned to XCDs, keys per
+    tile (what a device plan counts and what the pieces of a split item are cut from)."""
 
     def __init__(self, kind, d, ng=1):
         self.kind, self.d, self.ng = kind, d, ng
-        if kind == "k":                               # the Family of attention.hip:612-624
+        self.key_tile = KV
+        if kind == "f32":                             # the Family of attention_f32.hip:405-419
+            nqh = 1 if d >= 128 else 2                # query halves per wave (attention_f32.hip:34)
+            self.QB = 4 * 16 * nqh                    # 4 waves (attention_f32.hip:29, 35)
+            self.wg = 2 if d <= 128 else 1            # attention_f32.hip:37
+            self.rec = (cdiv(d, 16) * 4 * nqh + 1) * 256 * 4     # attention_f32.hip:42-44
+            self.xcd_min = 64                         # attention_f32.hip:36
+            self.key_tile = KT32                      # attention_f32.hip:30, 413
+        elif kind == "k":                               # the Family of attention.hip:612-624
             self.QB, self.wg = waves_for(d) * QW, 2 if d <= 48 else 1
             self.rec = rec_floats(d) * waves_for(d) * 64 * 4
             self.xcd_min = 64
@@ -146,6 +169,14 @@ def ws_bytes16g(ng, src, h, Mq, Mk, bounded, n_cus):  # attention_plan.h:415-420
     F = Family("16g", 40, ng)
     n = plan_tail(src, h, Mq, Mk, F.QB, 1, F.rec, False, n_cus)["ws_bytes"]
     return max(n, devplan_ws_bytes(n_cus, F.rec)) if bounded else n
+
+
+def ws_bytes_f32(B, h, Mq, Mk, d, bounded, n_cus):    # attention_f32.hip: ws_bytes_f32 (ws_devplan_min_tiles = 0)
+    if B <= 0 or h <= 0 or Mq <= 0 or Mk <= 0 or d not in F32_DIMS:
+        return 0
+    F = Family("f32", d)
+    n = plan_tail(B, h, Mq, Mk, F.QB, F.wg, F.rec, bounded, n_cus)["ws_bytes"]
+    return max(n, devplan_ws_bytes(F.slots(n_cus), F.rec)) if bounded else n
 
 
 def ws_bytes_any(B, h, Mq, Mk, d, bounded, n_cus):    # attention.hip:636-648
@@ -206,9 +237,11 @@ class Selection:
     """What attention_any / vtm_attention_kv_folded launch for a call: family, plan, combine kernel, and the work items
     that run key-split as (position in the grid order, pieces, first partial record)."""
 
-    def __init__(self, call, d, B, h, Mq, Mk, share, ldvt, ws_bytes, counts, n_cus):
+    def __init__(self, call, d, B, h, Mq, Mk, share, ldvt, ws_bytes, counts, n_cus, f32=False):
         bounded = counts is not None                  # (a query count is what makes a launch bounded)
-        if call == "folded":                          # attention.hip:738-739
+        if f32:                                       # attention.hip: attention_any, dtype VTM_F32 -- whatever share_groups
+            kind = "f32"                              # is: the grid runs over all B samples, host_split_all, its own combine
+        elif call == "folded":                          # attention.hip:738-739
             kind = "16s" if d == 40 else "k"
         else:                                         # attention.hip:686-696
             ng = shape16_for(d, share)
@@ -229,8 +262,8 @@ class Selection:
         # the device plan: attention_plan.h:368-369
         if bounded and ws_bytes is not None and ws_bytes >= devplan_ws_bytes(slots, F.rec) and \
                 nqb_max * h * self.items_B >= 2 * slots:
-            self.plan, self.combine = "device", "16" if kind != "k" else "plain"
-            self.header = device_plan(self.counts, h, F.QB, slots, cdiv(Mk, KV))
+            self.plan, self.combine = "device", "f32" if f32 else "16" if kind != "k" else "plain"
+            self.header = device_plan(self.counts, h, F.QB, slots, cdiv(Mk, F.key_tile))
             self.nqb = self.header[0]
             xg = xcd_pairs if self.nqb >= F.xcd_min else 0
             self.rec_base = DEVPLAN_HEADER
@@ -251,6 +284,8 @@ class Selection:
         self.plan = "split_all" if p["split_all"] else "tail" if p["nsplit"] > 1 else "single"
         if self.plan == "single":
             self.combine = None
+        elif f32:                                     # attention_f32.hip: launch_combine
+            self.combine = "f32"
         elif kind != "k":
             self.combine = "16"
         else:                                         # attention.hip:600-602
@@ -271,15 +306,16 @@ class Selection:
         return self.counts is None or qb * self.F.QB < self.counts[b]
 
 
-def pieces(Mk, ns):
-    """Key ranges of the `ns` pieces of a split item over Mk keys (attention.hip:534-536, attention16.hip:320-322)."""
-    ntiles = cdiv(Mk, KV)
+def pieces(Mk, ns, tile=KV):
+    """Key ranges of the pieces of an item split `ns` ways over Mk keys that hold a tile (attention.hip:534-536,
+    attention16.hip:320-322; tile = 32: attention_f32.hip:327-329).  Fewer than `ns` ranges: the last pieces are empty."""
+    ntiles = cdiv(Mk, tile)
     tps = cdiv(ntiles, ns)
     out = []
     for s in range(ns):
         tb, te = s * tps, min(s * tps + tps, ntiles)
         if tb < te:
-            out.append((tb * KV, min(te * KV, Mk)))
+            out.append((tb * tile, min(te * tile, Mk)))
     return out
 
 
@@ -299,6 +335,7 @@ def run_case(L, oracle, call, dtype, d, B, h, Mq, Mk, expect, share=1, counts=No
     (B, Mk) multiplicities, 0 = no such key -- the oracle attends over the sequence with the copies.  `expect` =
     (family, plan, combine).  Returns the Selection."""
     n_cus = cus()
+    f32 = dtype == torch.float32
     C = h * d
     scale = d ** -0.5
     src = B // share
@@ -310,6 +347,9 @@ def run_case(L, oracle, call, dtype, d, B, h, Mq, Mk, expect, share=1, counts=No
     v = torch.randn(B, Mk, C, generator=g, device=DEV).to(dtype)
     q, k = qbuf[:, :, :C], kbuf[:, :, C:2 * C]
     q[:, Mq:] = GARBAGE_Q
+    if f32 and share > 1:                             # probabilities come from the source samples' q / k alone
+        q[src:] = GARBAGE_Q
+        k[src:] = GARBAGE_K
     # the device-side key count of every sample (folded keys: the distinct ones)
     if mult is not None:
         mult = torch.as_tensor(mult)
@@ -317,7 +357,7 @@ def run_case(L, oracle, call, dtype, d, B, h, Mq, Mk, expect, share=1, counts=No
     else:
         kc = [Mk] * B
     sel = Selection(call, d, B, h, Mq, Mk, share, ldvt,
-                    None if ws is None else _ws_size(L, call, d, B, h, Mq, Mk, counts, ws), counts, n_cus)
+                    None if ws is None else _ws_size(L, call, d, B, h, Mq, Mk, counts, ws, f32), counts, n_cus, f32)
     assert (sel.kind, sel.plan, sel.combine) == expect, ("the shape does not select the plan it names",
                                                          (sel.kind, sel.plan, sel.combine), expect)
     # rows compared: first, last and two random rows of every query block below the count, and count - 1
@@ -342,7 +382,7 @@ def run_case(L, oracle, call, dtype, d, B, h, Mq, Mk, expect, share=1, counts=No
         targets = {}
         for ns in tiers or [1]:
             cand = [lin for lin, n in live_split if n == ns and sel.where(lin)[0] % src == bs] if tiers else []
-            for lo, hi in pieces(mk, ns):
+            for lo, hi in pieces(mk, ns, sel.F.key_tile):
                 for j in (lo, hi - 1):
                     targets.setdefault(j, cand)
         targets.setdefault(mk - 1, [])
@@ -369,9 +409,9 @@ def run_case(L, oracle, call, dtype, d, B, h, Mq, Mk, expect, share=1, counts=No
         k[b, kc[b]:] = GARBAGE_K
     vt = torch.empty(B, C, ldvt, dtype=dtype, device=DEV)
     vt[:, :, :Mk] = v.transpose(1, 2)
-    vt[:, :, Mk:] = GARBAGE_V
+    vt[:, :, Mk:] = GARBAGE_V32 if f32 else GARBAGE_V
     for b in range(B):
-        vt[b, :, kc[b]:] = GARBAGE_V
+        vt[b, :, kc[b]:] = GARBAGE_V32 if f32 else GARBAGE_V
     kbias = None
     if mult is not None:
         kbias = torch.empty(B, Mk, dtype=torch.int32)
@@ -383,10 +423,11 @@ def run_case(L, oracle, call, dtype, d, B, h, Mq, Mk, expect, share=1, counts=No
         kbias = kbias.to(DEV)
     # output window (B, Mqp, C) with ldo > C inside a buffer with a guard block behind the last row
     ldo = C + 24
-    obuf = torch.full(((B * Mqp + GUARD_ROWS) * ldo,), CANARY, dtype=torch.int16, device=DEV)
+    canary = CANARY32 if f32 else CANARY
+    obuf = torch.full(((B * Mqp + GUARD_ROWS) * ldo,), canary, dtype=torch.int32 if f32 else torch.int16, device=DEV)
     wsb, nb = None, 0
     if ws is not None:
-        nb = _ws_size(L, call, d, B, h, Mq, Mk, counts, ws)
+        nb = _ws_size(L, call, d, B, h, Mq, Mk, counts, ws, f32)
         wsb = torch.full((nb + 65536,), -1, dtype=torch.int8, device=DEV)
     qc = None if counts is None else torch.tensor(counts, dtype=torch.int32, device=DEV)
     kcd = torch.tensor(kc, dtype=torch.int32, device=DEV) if mult is not None else None
@@ -405,14 +446,16 @@ def run_case(L, oracle, call, dtype, d, B, h, Mq, Mk, expect, share=1, counts=No
     torch.cuda.synchronize()
     # 1. nothing written outside the (B, Mqp, C) window
     ob = obuf.view(B * Mqp + GUARD_ROWS, ldo)
-    assert bool((ob[:B * Mqp, C:] == CANARY).all()), "a write into the gap columns past C"
-    assert bool((ob[B * Mqp:] == CANARY).all()), "a write behind the last output row"
+    assert bool((ob[:B * Mqp, C:] == canary).all()), "a write into the gap columns past C"
+    assert bool((ob[B * Mqp:] == canary).all()), "a write behind the last output row"
+    if f32:
+        assert bool((ob[:B * Mqp].view(B, Mqp, ldo)[:, Mq:] == canary).all()), "a write into the rows Mq .. Mqp"
     # 2. the plan the launch took
     if wsb is not None:
         _check_workspace(sel, wsb, nb)
     # 3. the oracle, over each sample's own keys (folded: with the copies)
     out = ob[:B * Mqp, :C].contiguous().view(dtype).view(B, Mqp, C)
-    worst, scale_max = 0.0, 1.0
+    worst, scale_max = 0.0, 0.0 if f32 else 1.0       # (fp32: of max|ref| over the launch, not of max(1, .))
     for b in range(B):
         bs = b % src
         ridx = torch.tensor(sorted(rows[b]), device=DEV)
@@ -427,13 +470,30 @@ def run_case(L, oracle, call, dtype, d, B, h, Mq, Mk, expect, share=1, counts=No
         assert np.isfinite(got).all(), (b, "non-finite output")
         worst = max(worst, float(np.abs(got - ref).max()))
         scale_max = max(scale_max, float(np.abs(ref).max()))
-    assert worst < TOL[dtype] * scale_max, (sel.kind, sel.plan, d, str(dtype), worst, scale_max)
+    print(f"{sel.kind} {sel.plan} d={d} {dtype}: worst {worst:.3g} of scale {scale_max:.3g} = {worst / scale_max:.3g}")
+    if f32:
+        assert scale_max > 0.05, "the comparison should not be about zeros"
+        assert worst <= BAR * scale_max, (sel.kind, sel.plan, d, worst, scale_max, worst / scale_max)
+    else:
+        assert worst < TOL[dtype] * scale_max, (sel.kind, sel.plan, d, str(dtype), worst, scale_max)
     return sel
 
 
-def _ws_size(L, call, d, B, h, Mq, Mk, counts, ws):
+def _binding_ws(L, dtype, B, h, Mq, Mk, d, bounded):
+    """The workspace size _lib.attention / _lib.attention_kv hand to a launch of `dtype` operands (_lib._attention_ws, and
+    for a launch with a q_count the larger of the two exports); 0 where they pass None."""
+    code = DT_CODE[dtype]
+    nb = int(L.lib().vtm_attention_ws_bytes_dtype(code, B, h, Mq, Mk, d))
+    if bounded:
+        nb = max(nb, int(L.lib().vtm_attention_kv_bounded_ws_bytes_dtype(code, B, h, Mq, Mk, d)))
+    return nb
+
+
+def _ws_size(L, call, d, B, h, Mq, Mk, counts, ws, f32=False):
     if ws != "lib":
         return int(ws)
+    if f32:
+        return max(_binding_ws(L, torch.float32, B, h, Mq, Mk, d, counts is not None), 65536)
     nb = int(L.lib().vtm_attention_ws_bytes(B, h, Mq, Mk, d))
     if counts is not None:                            # _lib.attention_kv: the larger of the two
         nb = max(nb, int(L.lib().vtm_attention_kv_bounded_ws_bytes(B, h, Mq, Mk, d)))
@@ -535,7 +595,7 @@ def _plan_case(L, oracle, kind, dtype, d, plan, fold=False, ng=1, src=1, h=8):
         ws = p["ws_bytes"]
     combine = None
     if EXPECT[plan] != "single":
-        combine = "16" if kind != "k" else ("plain" if (pv16_for(d) or EXPECT[plan] != "tail") else "parts")
+        combine = "f32" if kind == "f32" else "16" if kind != "k" else ("plain" if (pv16_for(d) or EXPECT[plan] != "tail") else "parts")
     mult = _mult(B, Mk, d + B) if fold else None
     return run_case(L, oracle, call, dtype, d, B, h, Mq, Mk, (kind, EXPECT[plan], combine), share=share, counts=counts,
                     ws=ws, mult=mult, seed=zlib.crc32(f"{kind}/{plan}/{ng}/{src}".encode()) % 1000)
@@ -607,7 +667,7 @@ def _xcd_threshold_case(L, oracle, kind, dtype, d, B, side):
     F = Family(kind, d)
     S, thr = F.slots(n_cus), F.xcd_min
     assert (B * h) % 8 == 0
-    plan_of = lambda n: device_plan([77] * (B - 1) + [n * F.QB], h, F.QB, S, cdiv(Mk, KV))
+    plan_of = lambda n: device_plan([77] * (B - 1) + [n * F.QB], h, F.QB, S, cdiv(Mk, F.key_tile))
     if side == "below_split":
         live = next((n for n in range(thr - 1, 0, -1) if plan_of(n)[1] >= 2), None)
         assert live is not None, "no count below the threshold gives this device a split tier"
@@ -616,7 +676,8 @@ def _xcd_threshold_case(L, oracle, kind, dtype, d, B, side):
     Mq = max(thr, live) * F.QB
     counts = [77] * (B - 1) + [(live - 1) * F.QB + F.QB // 3]
     assert cdiv(Mq, F.QB) * h * B >= 2 * S, "the shape does not take the device plan"
-    sel = run_case(L, oracle, "bounded", dtype, d, B, h, Mq, Mk, (kind, "device", "16" if kind != "k" else "plain"),
+    sel = run_case(L, oracle, "bounded", dtype, d, B, h, Mq, Mk,
+                   (kind, "device", "f32" if kind == "f32" else "16" if kind != "k" else "plain"),
                    counts=counts, seed=zlib.crc32(f"xcd/{kind}/{side}".encode()) % 1000)
     assert sel.nqb == live and (live >= thr) == (side in ("at", "above")), (sel.nqb, live, thr)
     if side in ("below_split", "above"):
@@ -712,3 +773,152 @@ def test_top_blocks_bounded_at_full_size(L, oracle, name, B, h, d, Mq, Mk, expec
     """cfg-4 / cfg-5's largest self-attention launches, query-bounded (0.78 / 0.9 live), against the oracle."""
     counts = _live_counts(Family(expect[0], d), B, h, Mq, Mk)
     run_case(L, oracle, "bounded", torch.float16, d, B, h, Mq, Mk, expect, counts=counts, seed=5)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the fp32 family: attention_f32_kernel under every plan
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("plan", PLANS)
+@pytest.mark.parametrize("d", F32_DIMS)
+def test_attention_f32_plans(L, oracle, d, plan):
+    """attention_f32_kernel<D>: every head dim under every plan -- 128-row blocks on 2 workgroups per CU below d = 128,
+    64-row blocks from there on, one workgroup per CU and the LDS opt-in at d = 160, the half chunk of d = 8 / 40;
+    attention_f32_combine_kernel behind every split plan.  A device plan counts 33 x 2 key tiles where the host tail
+    counts 33."""
+    _plan_case(L, oracle, "f32", torch.float32, d, plan)
+
+
+@pytest.mark.parametrize("plan", ["single", "tail", "device"])
+@pytest.mark.parametrize("ng", [2, 3])
+@pytest.mark.parametrize("d", [40, 160])
+def test_attention_f32_shared_plans(L, oracle, d, ng, plan):
+    """Shared probabilities in attention_f32_kernel (b % src_batch): vtm_attention_kv over 2 and 3 groups under the single
+    and the host tail plan, vtm_attention_kv_shared_bounded under the device plan.  The grid runs over all samples; the
+    sharing samples' q / k hold garbage and their expected rows come from the source's."""
+    _plan_case(L, oracle, "f32", torch.float32, d, plan, ng=ng)
+
+
+@pytest.mark.parametrize("side", XCD_SIDES)
+@pytest.mark.parametrize("d,B", [(64, 2), (160, 1)])
+def test_attention_f32_plans_around_the_xcd_threshold(L, oracle, d, B, side):
+    """attention_f32_kernel / attention_f32_combine_kernel on both sides of F_XCD_MIN_NQB = 64 live blocks: d = 64 (two
+    samples of 8 heads on 2 workgroups per CU: 64 blocks of 128 rows are the two rounds a device plan asks for) and
+    d = 160 (one sample, 64-row blocks, one workgroup per CU)."""
+    _xcd_threshold_case(L, oracle, "f32", torch.float32, d, B, side)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# split pieces that hold no tile
+# ---------------------------------------------------------------------------------------------------------------------
+EMPTY_PIECE_CASES = [("f32", torch.float32, 40, "device"), ("f32", torch.float32, 160, "device")] + \
+    [(kind, dt, d, plan) for kind, d in (("k", 64), ("16s", 40)) for dt in DTYPES for plan in ("tail", "device")]
+
+
+@pytest.mark.parametrize("kind,dtype,d,plan", EMPTY_PIECE_CASES,
+                         ids=[f"{k}-{str(t).split('.')[-1]}-d{d}-{p}" for k, t, d, p in EMPTY_PIECE_CASES])
+def test_split_pieces_without_a_tile(L, oracle, kind, dtype, d, plan):
+    """129 key tiles cut 16 ways: tps = ceil(129 / 16) = 9, piece 14 holds tiles 126 .. 128 and piece 15 starts at tile 135,
+    behind the last key.  Its workgroup must read nothing, still leave a record (max = -inf, denominator 0), and the
+    combine kernel must pass over it.  fp32: 129 tiles of 32 keys under a device plan (the host tail counts 64-key
+    tiles and splits 65 of them at most 8 ways); 16-bit: 129 tiles of 64 keys under the host tail (B h = 16 items in
+    the last round) and under a device plan.  Shapes from this device's slots: 2 samples of 8 heads; tail: one whole
+    round and 16 items; device: two rounds and a sixteenth, which the plan gives one 16-way tier."""
+    n_cus, h, B = cus(), 8, 2
+    F = Family(kind, d)
+    S, P = F.slots(n_cus), B * h
+    Mk = 4100 if kind == "f32" else 8200              # 128 whole tiles and 4 / 8 keys of another
+    assert cdiv(Mk, F.key_tile) == 129 and len(pieces(Mk, 16, F.key_tile)) < 16, "no piece of this split is empty"
+    if plan == "tail":
+        nqb = S // P + 1
+        Mq, counts, call = (nqb - 1) * F.QB + F.QB // 2 + 3, None, "kv"
+        combine = "16" if kind != "k" else "parts" if P * 4 <= n_cus else "plain"
+    else:
+        nqb = cdiv(2 * S + S // 16, P)
+        Mq, counts, call = nqb * F.QB, [77, (nqb - 1) * F.QB + F.QB // 3], "bounded"
+        combine = "f32" if kind == "f32" else "16" if kind != "k" else "plain"
+    sel = run_case(L, oracle, call, dtype, d, B, h, Mq, Mk, (kind, plan, combine), counts=counts,
+                   seed=zlib.crc32(f"empty/{kind}/{plan}".encode()) % 1000)
+    live16 = [lin for lin, ns, _ in sel.split if ns == 16 and sel.live(lin)]
+    assert live16, ("the shape does not give a live item a 16-way split", sel.plan, sel.header)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the workspace the Python binding hands to an fp32 launch
+# ---------------------------------------------------------------------------------------------------------------------
+def _mid_block_shape(n_cus):
+    """One sample of 8 heads at d = 80 whose fp32 plan has a short last round: one round of 128-row blocks and 4 blocks per
+    head more over 13 056 keys.  256 CUs: Mq = 8704, the cfg-2 mid block's launch."""
+    F = Family("f32", 80)
+    return 1, 8, 80, (F.slots(n_cus) // 8 + 4) * F.QB, 13056
+
+
+def test_fp32_and_16bit_plans_want_different_workspaces():
+    """The shape that showed it, on 256 CUs, by the restated planners alone: the 16-bit planner sees 136 items of 512 rows
+    on 256 slots (no whole round, no workspace), the fp32 planner 544 items of 128 rows on 512 slots -- a last round of 32
+    items split 16 ways.  Neither family's size bounds the other's: the size has to be asked with the dtype."""
+    B, h, d, Mq, Mk = _mid_block_shape(256)
+    assert (Mq, Mk) == (8704, 13056)
+    assert ws_bytes_any(B, h, Mq, Mk, d, False, 256) == 0
+    assert ws_bytes_f32(B, h, Mq, Mk, d, False, 256) == 32 * 16 * 41984
+    assert ws_bytes_f32(2, 8, 34816, 52224, 40, False, 256) < ws_bytes_any(2, 8, 34816, 52224, 40, False, 256)
+
+
+def test_binding_workspace_holds_the_fp32_plans(L):
+    """What _lib.attention / _lib.attention_kv hand to an fp32 launch (_binding_ws) is what the restated fp32 plans take --
+    unbounded and bounded, all nine head dims, over a grid that crosses the planner's thresholds and holds the mid-block
+    shape above -- and the 16-bit sizes asked with a dtype are the ones asked without."""
+    n_cus = cus()
+    lib = L.lib()
+    mid = _mid_block_shape(n_cus)
+    n = 0
+    for d in F32_DIMS:
+        shapes = [(B, h, Mq, Mk) for B in (1, 2, 3) for h in (5, 8) for Mq in (100, 4100, 8448, 8704, 17408, 34816)
+                  for Mk in (77, 1000, 2100, 4100, 13056, 52224)] + [(mid[0], mid[1], mid[3], mid[4])]
+        for B, h, Mq, Mk in shapes:
+            for bounded in (False, True):
+                want = ws_bytes_f32(B, h, Mq, Mk, d, bounded, n_cus)
+                if bounded:                           # _lib.attention_kv: the larger of the two exports
+                    want = max(want, ws_bytes_f32(B, h, Mq, Mk, d, False, n_cus))
+                got = _binding_ws(L, torch.float32, B, h, Mq, Mk, d, bounded)
+                assert got >= want, ("the binding hands an fp32 launch less than its plan takes", d, B, h, Mq, Mk, bounded,
+                                     got, want)
+                assert got == want, (d, B, h, Mq, Mk, bounded, got, want)
+                for dt in DTYPES:
+                    assert int(lib.vtm_attention_ws_bytes_dtype(DT_CODE[dt], B, h, Mq, Mk, d)) == \
+                        int(lib.vtm_attention_ws_bytes(B, h, Mq, Mk, d))
+                    assert int(lib.vtm_attention_kv_bounded_ws_bytes_dtype(DT_CODE[dt], B, h, Mq, Mk, d)) == \
+                        int(lib.vtm_attention_kv_bounded_ws_bytes(B, h, Mq, Mk, d))
+                n += 1
+    assert n > 3000
+    assert ws_bytes_f32(*mid[:2], mid[3], mid[4], 80, False, n_cus) > 0, "the mid-block shape has no tail on this device"
+
+
+def test_binding_gives_fp32_its_host_tail(L, oracle):
+    """_lib.attention_kv on the mid-block shape in fp32: the launch leaves every record of its 16-way tail in the binding's
+    workspace (prefilled with 0xFF), and rows of whole and of split items agree with the oracle."""
+    n_cus = cus()
+    B, h, d, Mq, Mk = _mid_block_shape(n_cus)
+    F = Family("f32", d)
+    p = plan_tail(B, h, Mq, Mk, F.QB, F.wg, F.rec, False, n_cus)
+    assert p["nsplit"] > 1 and p["ws_bytes"] > 0, ("the shape does not select the plan it names", p)
+    C = h * d
+    g = torch.Generator(device=DEV).manual_seed(5)
+    q = torch.randn(B, Mq, C, generator=g, device=DEV)
+    k = torch.randn(B, Mk, C, generator=g, device=DEV)
+    vt = torch.randn(B, C, Mk, generator=g, device=DEV)
+    ws, nb = L._attention_ws(B, h, Mq, Mk, d, q.device, q.dtype)
+    assert ws is not None and nb >= p["ws_bytes"], (nb, p)
+    ws.fill_(255)
+    o = L.attention_kv(q, k, vt, h, Mq, Mk, d ** -0.5)
+    torch.cuda.synchronize()
+    w = ws[:ws.numel() // 4 * 4].view(torch.int32)
+    assert bool((w[:p["ws_bytes"] // 4] != -1).all()), "a record of the tail was not written: the launch took no tail"
+    assert bool((w[p["ws_bytes"] // 4:] == -1).all()), "a write past the tail's records"
+    rs = np.random.default_rng(11)
+    rows = np.unique(np.concatenate([np.arange(4), rs.integers(0, Mq, 40), np.arange(Mq - 4, Mq)]))
+    ridx = torch.from_numpy(rows).to(DEV)
+    ref = oracle.attention_qkv(q[:, ridx].cpu().numpy(), k.cpu().numpy(),
+                               np.ascontiguousarray(vt.transpose(1, 2).cpu().numpy()), h, d ** -0.5)
+    err = float(np.abs(o[:, ridx].cpu().numpy() - ref).max()) / float(np.abs(ref).max())
+    print(f"fp32 mid block through the binding: {err:.3g} of max|ref|")
+    assert err <= BAR, err

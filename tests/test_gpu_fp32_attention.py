@@ -98,9 +98,11 @@ def test_attention_kv_mq_ne_mk(L, oracle, d, Mq, Mk):
 @pytest.mark.parametrize("frac", [0.15, 0.55, 0.97])
 @pytest.mark.parametrize("share", [1, 3])
 def test_bounded_launches(L, oracle, d, frac, share):
-    """vtm_attention_kv_bounded / _shared_bounded (fp32): only the first q_count[b] rows are live.  The launches cover at
-    least two rounds, so the device-planned tail (whole items, then tiers split 2 .. 16 ways) runs; live fractions from
-    a fraction of a round to nearly all."""
+    """vtm_attention_kv_bounded / _shared_bounded (fp32): only the first q_count[b] rows are live, from a fraction of a
+    round to nearly all.  The launches are sized for at least two rounds and the binding's workspace holds a device
+    plan, so they are planned on the device -- asserted through the restated selection of test_gpu_attention_plans.py,
+    which pins that plan's tiers and records on shapes of its own."""
+    from test_gpu_attention_plans import Selection, _binding_ws, cus
     h = 8
     B = 3 if share == 3 else 2
     Mq, Mk = 9000, 6000
@@ -109,6 +111,9 @@ def test_bounded_launches(L, oracle, d, frac, share):
     if share > 1:
         cnt = [cnt[0]] * B                   # align_batch: every sample of a group has the same live rows
     q_count = torch.tensor(cnt, dtype=torch.int32, device=DEV)
+    sel = Selection("shared_bounded" if share > 1 else "bounded", d, B, h, Mq, Mk, share, vt.shape[2],
+                    _binding_ws(L, torch.float32, B, h, Mq, Mk, d, True), cnt, cus(), f32=True)
+    assert (sel.kind, sel.plan) == ("f32", "device"), ("the shape does not select the plan it names", sel.kind, sel.plan)
     o = L.attention_kv(q, k, vt, h, Mq, Mk, d ** -0.5, q_count=q_count, share_groups=share)
     rs = np.random.default_rng(d)
     lo = min(cnt)
@@ -124,7 +129,8 @@ def test_bounded_launches(L, oracle, d, frac, share):
     ("cfg-5 top block", 2, 5, 64, 64513, 90319),
 ])
 def test_full_size_vs_oracle(L, oracle, name, B, h, d, Mq, Mk):
-    """The full-size launches on sampled query rows (first and last blocks, the key-split tail, rows spread over the rest)."""
+    """The full-size launches on sampled query rows (first and last blocks, rows spread over the rest), under whichever
+    plan the shape takes on this device (the plans themselves are pinned in test_gpu_attention_plans.py)."""
     q, k, vt = _inputs(B, h, d, Mq, Mk, seed=Mq + Mk)
     o = L.attention_kv(q, k, vt, h, Mq, Mk, d ** -0.5)
     rs = np.random.default_rng(Mq)
@@ -132,6 +138,44 @@ def test_full_size_vs_oracle(L, oracle, name, B, h, d, Mq, Mk):
     ref = _ref(oracle, q, k, vt, h, d, Mk, rows)
     got = o[:, torch.from_numpy(rows).to(DEV)].cpu().numpy()
     assert _err(got, ref) <= BAR, (name, _err(got, ref))
+
+
+@pytest.mark.parametrize("d", [40, 64, 160])
+@pytest.mark.parametrize("case", ["spike_late", "spike_every_tile", "all_very_negative", "wide_range"])
+def test_attention_rescale_paths_fp32(L, oracle, d, case):
+    """The online-softmax corner cases of test_attention_rescale_paths (test_gpu_parity.py) on attention_f32_kernel: the
+    running maximum jumps late (the deferred-rescale branch, taken by both query halves of a wave under one __all),
+    grows in every 32-key tile, sits far below zero, or the logits span +-40.  d = 40 ends its contraction on the half
+    chunk, d = 160 has one query half per wave.  M = 700 is not a multiple of 32: the last live wave's second half
+    (rows 688 .. 703) is partly past M.  The bar is BAR in all four cases: a plain float32 CPU restatement of wide_range
+    (numpy float32 matmul and softmax on the same inputs) is within 2.0e-6 / 2.8e-6 / 2.4e-6 of the float64 oracle at
+    d = 40 / 64 / 160, so fp32 score rounding does meet BAR there and no allowance is made."""
+    B, h, M = 1, 2, 700          # 22 key tiles of 32
+    C = h * d
+    g = torch.Generator().manual_seed(77 + d)
+    q = torch.randn(B, M, C, generator=g)
+    k = torch.randn(B, M, C, generator=g)
+    v = torch.randn(B, M, C, generator=g)
+    if case == "spike_late":
+        k[:, 600] = 6.0 * q[:, 17]                     # one key dominates query 17 from tile 18 on
+        k[:, 333, :d] = 5.0 * q[:, 400, :d]
+    elif case == "spike_every_tile":
+        for t in range(22):
+            k[:, min(32 * t + 5, M - 1)] = (0.5 + 0.225 * t) * q[:, 3]
+    elif case == "all_very_negative":
+        k = -3.0 * q[:, :1].expand(B, M, C).clone() + 0.05 * k   # every score of query 0 ~ -3 |q|^2 / sqrt(d)
+        q[:, 1:] = 3.0 * q[:, :1] + 0.05 * q[:, 1:]
+    else:
+        q, k = 3.0 * q, 3.0 * k
+    Mp = _pad8(M)
+    pad = lambda t: torch.nn.functional.pad(t, (0, 0, 0, Mp - M))
+    o = L.attention(pad(q).to(DEV), pad(k).to(DEV), pad(v).to(DEV).transpose(1, 2).contiguous(), h, M, d ** -0.5, 1)
+    assert o.dtype == torch.float32
+    got = o[:, :M].cpu().numpy()
+    ref = oracle.attention_qkv(q.numpy(), k.numpy(), v.numpy(), h, d ** -0.5)
+    assert np.isfinite(got).all()
+    print(f"fp32 rescale paths d={d} {case}: {_err(got, ref):.3g} of max|ref|")
+    assert _err(got, ref) <= BAR, (d, case, _err(got, ref))
 
 
 def test_folded_keys_reject_fp32(L):

@@ -66,6 +66,7 @@ _SIGNATURES = {
     "vtm_attention": ([_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _f32,
                        _int, _vp, ctypes.c_size_t, _vp], _int),
     "vtm_attention_ws_bytes": ([_i64, _i64, _i64, _i64, _i64], ctypes.c_size_t),
+    "vtm_attention_ws_bytes_dtype": ([_int, _i64, _i64, _i64, _i64, _i64], ctypes.c_size_t),
     "vtm_attention_kv": ([_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                           _f32, _int, _vp, ctypes.c_size_t, _vp], _int),
     "vtm_attention_kv_sets": ([_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _f32,
@@ -80,6 +81,7 @@ _SIGNATURES = {
     "vtm_attention_kv_shared_bounded": ([_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                          _f32, _int, _vp, _vp, ctypes.c_size_t, _vp], _int),
     "vtm_attention_kv_bounded_ws_bytes": ([_i64, _i64, _i64, _i64, _i64], ctypes.c_size_t),
+    "vtm_attention_kv_bounded_ws_bytes_dtype": ([_int, _i64, _i64, _i64, _i64, _i64], ctypes.c_size_t),
     "vtm_anchor_maps": ([_vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp], _int),
     "vtm_transpose_cols": ([_vp, _i64, _int, _i64, _i64, _i64, _vp, _i64, _vp], _int),
     "vtm_fold_keys_ws_bytes": ([_i64, _i64, _i64], ctypes.c_size_t),
@@ -543,9 +545,10 @@ SPLIT_ALL_BOUNDED = os.environ.get("VIDTOME_ATT_SPLIT_ALL", "1") != "0"
 FOLD_KEYS = os.environ.get("VIDTOME_FOLD_KEYS", "1") != "0"
 
 
-def _attention_ws(B: int, heads: int, Mq: int, Mk: int, d: int, device):
-    """Workspace for the split last round of an attention launch (None when the shape needs none)."""
-    nb = int(lib().vtm_attention_ws_bytes(B, heads, Mq, Mk, d))
+def _attention_ws(B: int, heads: int, Mq: int, Mk: int, d: int, device, dtype: torch.dtype = torch.float16):
+    """Workspace for the split last round of an attention launch of `dtype` operands (None when the shape needs none;
+    fp32 launches have plans of their own, the two 16-bit types share theirs)."""
+    nb = int(lib().vtm_attention_ws_bytes_dtype(_DT[dtype], B, heads, Mq, Mk, d))
     if nb == 0:
         return None, 0
     return _workspace("attention", nb, device), nb
@@ -573,7 +576,7 @@ def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, M:
     B, Mp, C = q.shape
     d = C // heads
     out = _attention_out(q, k, vt, M, Mp)
-    ws, nb = _attention_ws(B, heads, M, M, d, q.device)
+    ws, nb = _attention_ws(B, heads, M, M, d, q.device, q.dtype)
     _check(lib().vtm_attention(q.data_ptr(), q.stride(1), k.data_ptr(), k.stride(1), vt.data_ptr(), vt.stride(1),
                                out.data_ptr(), C, dtype_code(q), B, heads, M, Mp, d, float(scale),
                                int(share_groups), _ptr(ws), nb, _stream()), "vtm_attention")
@@ -634,11 +637,11 @@ def attention_kv(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int,
     Mkp = k.shape[1]
     d = C // heads
     out = _attention_out(q, k, vt, Mq, Mkp)
-    ws, nb = _attention_ws(B, heads, Mq, Mk, d, q.device) if use_workspace else (None, 0)
+    ws, nb = _attention_ws(B, heads, Mq, Mk, d, q.device, q.dtype) if use_workspace else (None, 0)
     if q_count is not None and (q_count.dtype != torch.int32 or q_count.numel() != B or not q_count.is_cuda):
         raise RuntimeError("attention_kv: q_count must be a (B,) int32 device tensor")
     if q_count is not None and use_workspace and SPLIT_ALL_BOUNDED:
-        nb2 = int(lib().vtm_attention_kv_bounded_ws_bytes(B, heads, Mq, Mk, d))
+        nb2 = int(lib().vtm_attention_kv_bounded_ws_bytes_dtype(_DT[q.dtype], B, heads, Mq, Mk, d))
         if nb2 > nb:
             ws, nb = _workspace("attention", nb2, q.device), nb2
     if share_groups != 1 and q_count is not None:
@@ -687,7 +690,7 @@ def attention_kv_range(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads
         return attention_kv(q, k, vt, heads, Mq, Mk, scale)
     d = C // heads
     out = _attention_out(q, k, vt, Mq, Mkp)
-    ws, nb = _attention_ws(B, heads, Mq, Mk, d, q.device)
+    ws, nb = _attention_ws(B, heads, Mq, Mk, d, q.device, q.dtype)
     es = k.element_size()
     # (sample b's keys start at k + (b * Mkp + start) * ldk: the row count Mkp stays the sample stride)
     _check(lib().vtm_attention_kv(q.data_ptr(), q.stride(1), k.data_ptr() + start * k.stride(1) * es, k.stride(1),

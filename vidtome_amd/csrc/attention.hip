@@ -676,6 +676,15 @@ VTM_EXPORT size_t vtm_attention_kv_bounded_ws_bytes(int64_t B, int64_t h, int64_
     return ws_bytes_any(B, h, Mq, Mk, d, true);
 }
 
+// ... for a call of element type `dtype`: VTM_F32 launches go to attention_f32_kernel's family, whose plans are its own
+VTM_EXPORT size_t vtm_attention_ws_bytes_dtype(int dtype, int64_t B, int64_t h, int64_t Mq, int64_t Mk, int64_t d) {
+    return dtype == VTM_F32 ? ws_bytes_f32(B, h, Mq, Mk, d, false) : ws_bytes_any(B, h, Mq, Mk, d, false);
+}
+
+VTM_EXPORT size_t vtm_attention_kv_bounded_ws_bytes_dtype(int dtype, int64_t B, int64_t h, int64_t Mq, int64_t Mk, int64_t d) {
+    return dtype == VTM_F32 ? ws_bytes_f32(B, h, Mq, Mk, d, true) : ws_bytes_any(B, h, Mq, Mk, d, true);
+}
+
 static int attention_any(const void *q, int64_t ldq, const void *k, int64_t ldk, const void *vt, int64_t ldvt,
                          void *out, int64_t ldo, int dtype, int64_t B, int64_t h, int64_t Mq, int64_t Mqp, int64_t Mk,
                          int64_t Mkp, int64_t d, float scale, int share_groups, void *ws, size_t ws_bytes,

@@ -428,4 +428,9 @@ int attention_f32(const Call &c, int64_t d) {
     return with_head_dim(d, [&](auto dim) { return planned_launch(c, make_family<decltype(dim)::value>()); });
 }
 
+size_t ws_bytes_f32(int64_t B, int64_t h, int64_t Mq, int64_t Mk, int64_t d, bool bounded) {
+    if (B <= 0 || h <= 0 || Mq <= 0 || Mk <= 0) return 0;
+    return with_head_dim(d, [&](auto dim) { return ws_bytes(make_family<decltype(dim)::value>(), B, h, Mq, Mk, bounded); });
+}
+
 }  // namespace vtm_att

@@ -154,6 +154,9 @@ Family family16g(int dtype, int ng);
 int attention16g(const Call &c, int ng);
 // attention_f32.hip: dtype VTM_F32, every head dim (attention_f32_kernel; never folded)
 int attention_f32(const Call &c, int64_t d);
+// ... and the workspace of the largest plan its family can take for a call of this shape (qb, wg_per_cu and rec_bytes differ
+// from the 16-bit families', so neither size bounds the other)
+size_t ws_bytes_f32(int64_t B, int64_t h, int64_t Mq, int64_t Mk, int64_t d, bool bounded);
 
 }  // namespace vtm_att
 
