@@ -239,6 +239,20 @@ int vtm_partition_global(const int32_t *cur_local, int64_t B, int64_t Ml, int64_
                          int32_t *a_rows, int32_t *b_rows, int32_t *seed_table, int64_t tokens,
                          const int32_t *anchor_pos, vtm_stream_t stream);
 
+/* vtm_partition_2d -- the per-frame src/dst partition of bipartite_soft_matching_random2d (merge.py:493-528) for one frame
+ * of h x w tokens (token (y, x) = y * w + x) and strides sx <= w, sy <= h: of every sy x sx cell (i, j) of the
+ * hsy x wsx = (h / sy) x (w / sx) grid, token (i * sy + d / sx, j * sx + d % sx) is dst, d = draws[i * wsx + j] = the
+ * reference's `torch.randint(sy * sx, (hsy, wsx, 1))` draw of that cell (the host makes it on the reference's generator and
+ * copies it over); draws == NULL = `no_rand` (every d is 0: the cell's top left token).  A draw outside [0, sx * sy) is taken
+ * modulo sx * sy (as an unsigned number), so that every cell has exactly one dst token whatever the array holds.  Every other token is src, the rows >= hsy * sy and columns >= wsx * sx of a frame the strides do not
+ * divide included.  Outputs: b_idx (hsy * wsx) = the dst tokens, a_idx (h * w - hsy * wsx) = the src tokens (may be NULL
+ * when there are none: sx == sy == 1), both in ASCENDING TOKEN ORDER.  The reference gets the two lists from an argsort of a
+ * buffer that holds -1 at dst and 0 at src tokens; torch's argsort is not stable by contract, so the order among equal keys
+ * is implementation-defined there -- as everywhere in this library the canonical order is the stable one (ties by ascending
+ * index).  One launch; h * w < 2^31. */
+int vtm_partition_2d(int64_t h, int64_t w, int64_t sx, int64_t sy, const int32_t *draws, int32_t *b_idx, int32_t *a_idx,
+                     vtm_stream_t stream);
+
 /* vtm_anchor_pos -- token positions of a new anchor set (the host tracks them next to module.global_tokens so that the
  * next global level can be seeded): anchors_out[b, p] = pool[b, amap[b, p]] (patch.py:80; amap == NULL: the first M pool
  * rows, patch.py:82), pool = [joined chunk: L rows, position = row % tokens | old anchors: old_pos (B, Mg) or NULL].

@@ -57,6 +57,7 @@ _SIGNATURES = {
     "vtm_partition_counts": ([_i64, _i64, _i64, _i64, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64)], _int),
     "vtm_partition_local": ([_vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp], _int),
     "vtm_partition_global": ([_vp, _i64, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp], _int),
+    "vtm_partition_2d": ([_i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp], _int),
     "vtm_plan_apply": ([_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp,
                         _vp, _vp], _int),
     "vtm_compose": ([_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp], _int),
@@ -391,6 +392,25 @@ def partition_local(cur: Optional[torch.Tensor], B: int, N_in: int, unm_pre: int
     _check(lib().vtm_partition_local(_ptr(cur), B, N_in, unm_pre, tnum, ts, randf, _ptr(a_pos), _ptr(b_pos),
                                      _ptr(a_rows), _ptr(b_rows), Ns, Nd, _stream()), "vtm_partition_local")
     return a_pos, b_pos, a_rows, b_rows
+
+
+@_on_device
+def partition_2d(device, h: int, w: int, sx: int, sy: int, draws: Optional[torch.Tensor]
+                 ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(a_idx (N - hsy * wsx,), b_idx (hsy * wsx,)) int32 of bipartite_soft_matching_random2d (merge.py:493-528), both in
+    ascending token order; ``draws`` = the (hsy * wsx,) int32 cell draws on the device, None = no_rand."""
+    h, w, sx, sy = int(h), int(w), int(sx), int(sy)
+    if min(h, w, sx, sy) <= 0 or sx > w or sy > h:
+        raise ValueError(f"partition_2d: strides ({sx}, {sy}) must lie in [1, w] x [1, h] of a {w} x {h} frame")
+    Nd = (h // sy) * (w // sx)
+    if draws is not None and (draws.dtype != torch.int32 or draws.numel() != Nd or not draws.is_contiguous()
+                              or not draws.is_cuda):
+        raise RuntimeError(f"partition_2d: the draws must be {Nd} contiguous int32 on the GPU")
+    i32 = dict(dtype=torch.int32, device=device)
+    a_idx, b_idx = torch.empty((h * w - Nd,), **i32), torch.empty((Nd,), **i32)
+    _check(lib().vtm_partition_2d(h, w, sx, sy, _ptr(draws), _ptr(b_idx), _ptr(a_idx) or None, _stream()),
+           "vtm_partition_2d")
+    return a_idx, b_idx
 
 
 @_on_device

@@ -80,6 +80,62 @@ __global__ __launch_bounds__(256) void partition_global_kernel(
     }
 }
 
+// merge.py:493-528: the per-frame 2-D partition of bipartite_soft_matching_random2d.  Cell (i, j) of the hsy x wsx grid of
+// sy x sx cells keeps ONE dst token, (i * sy + d / sx, j * sx + d % sx) for its draw d; everything else -- the rows and
+// columns behind the last whole cell included -- is src.  Both lists come out in ascending token order (the stable sort of
+// the reference's -1 / 0 buffer).  A cell row's sy * w tokens hold exactly wsx dst tokens, so the lists of cell row i start at
+// i * wsx and i * (sy * w - wsx): one workgroup per cell row ranks its own tokens (ballot + popcount inside a wave, the four
+// wave totals through LDS, a running count from one 256-token chunk to the next) and nothing crosses workgroups.  The
+// workgroups behind the hsy-th take the rows below the last cell row, 256 tokens each: all src, at token - hsy * wsx.
+__global__ __launch_bounds__(256) void partition_2d_kernel(int64_t h, int64_t w, int64_t sx, int64_t sy, int64_t hsy,
+                                                           int64_t wsx, const int32_t *__restrict__ draws,
+                                                           int32_t *__restrict__ b_idx, int32_t *__restrict__ a_idx) {
+    __shared__ int32_t wave_cnt[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t i = blockIdx.x;
+    if (i >= hsy) {
+        const int64_t t = (hsy * sy) * w + (i - hsy) * 256 + tid;
+        if (t < h * w) a_idx[t - hsy * wsx] = (int32_t)t;
+        return;
+    }
+    const int64_t n = sy * w, t0 = i * n;
+    const uint32_t cell = (uint32_t)(sx * sy);
+    int64_t dst_before = i * wsx;                         // dst tokens in front of this chunk
+    for (int64_t c0 = 0; c0 < n; c0 += 256) {
+        const int64_t q = c0 + tid;
+        const bool valid = q < n;
+        bool is_dst = false;
+        if (valid) {
+            const int64_t dy = q / w, x = q % w, j = x / sx;
+            if (j < wsx) {
+                // (a draw outside [0, sx * sy) is taken modulo the cell size: every cell then still has exactly one dst
+                // token, which is what keeps every index below inside its list)
+                const uint32_t d = draws ? (uint32_t)draws[i * wsx + j] % cell : 0u;
+                is_dst = dy == (int64_t)(d / (uint32_t)sx) && x - j * sx == (int64_t)(d % (uint32_t)sx);
+            }
+        }
+        const unsigned long long bal = __ballot(is_dst);
+        const int in_wave = __popcll(bal & ((1ull << lane) - 1ull));
+        if (lane == 0) wave_cnt[wave] = __popcll(bal);
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int v = wave_cnt[k];
+            if (k < wave) before += v;
+            total += v;
+        }
+        __syncthreads();                                  // (wave_cnt is rewritten by the next chunk)
+        if (valid) {
+            const int64_t rank = dst_before + before + in_wave;      // dst tokens in front of this one
+            const int64_t t = t0 + q;
+            if (is_dst) b_idx[rank] = (int32_t)t;
+            else a_idx[t - rank] = (int32_t)t;
+        }
+        dst_before += total;
+    }
+}
+
 // positions of the rows of a new anchor set (patch.py:80,82): anchors_out[b, p] = pool[b, amap[b, p]] with pool =
 // [joined chunk (L rows, position = row % tokens) | old anchors (their tracked positions)]; amap == nullptr: rows 0 .. M-1
 // of the pool themselves
@@ -486,6 +542,18 @@ VTM_EXPORT int vtm_partition_global(const int32_t *cur_local, int64_t B, int64_t
                        vtm::as_stream(stream), cur_local, B, Ml, anchor_base, Mg, local_is_src, a_pos,
                        b_pos, a_rows, b_rows, seed_table, tokens, anchor_pos);
     return vtm::launch_status("vtm_partition_global");
+}
+
+VTM_EXPORT int vtm_partition_2d(int64_t h, int64_t w, int64_t sx, int64_t sy, const int32_t *draws, int32_t *b_idx,
+                                int32_t *a_idx, vtm_stream_t stream) {
+    VTM_REQUIRE(h > 0 && w > 0 && sx > 0 && sy > 0 && sx <= w && sy <= h, "vtm_partition_2d: bad sizes");
+    VTM_REQUIRE(h < (1ll << 31) && w < (1ll << 31) && h * w < (1ll << 31), "vtm_partition_2d: index space overflow");
+    const int64_t hsy = h / sy, wsx = w / sx;
+    VTM_REQUIRE(b_idx && (a_idx || h * w == hsy * wsx), "vtm_partition_2d: null pointer");
+    const int64_t tail_blocks = vtm::cdiv((h - hsy * sy) * w, 256);
+    hipLaunchKernelGGL(partition_2d_kernel, dim3((unsigned)(hsy + tail_blocks)), dim3(256), 0, vtm::as_stream(stream), h, w, sx,
+                       sy, hsy, wsx, draws, b_idx, a_idx);
+    return vtm::launch_status("vtm_partition_2d");
 }
 
 VTM_EXPORT int vtm_anchor_pos(const int32_t *amap, int64_t B, int64_t M, int64_t L, int64_t tokens, const int32_t *old_pos,

@@ -5,6 +5,8 @@ Public surface mirrors the reference (same names, argument meaning, return proto
 * ``do_nothing``                           <- vidtome/merge.py:5-6
 * ``bipartite_soft_matching_randframe``    <- vidtome/merge.py:20-159   (local merging)
 * ``bipartite_soft_matching_2s``           <- vidtome/merge.py:343-463  (global merging)
+* ``bipartite_soft_matching_random2d``     <- vidtome/merge.py:467-579  (per-frame 2-D merging: the original ToMe / ToMeSD
+  matcher; a ``(merge, unmerge)`` pair, ``merge`` in "mean" mode by default -- not used by ``compute_merge``)
 
 Each matcher returns ``(merge, unmerge, ret_dict)`` closures like the reference, but the closures hold
 *composed row maps* on the device instead of index tensors + gather/scatter code: in ``replace`` mode (the
@@ -12,8 +14,8 @@ only mode the reference's ``compute_merge`` ever uses, patch.py:45-46,73-75) mer
 selection, so ``merge`` is one gather and ``unmerge`` is one gather with the inverse map.
 
 The arithmetic lives in libvidtome_hip.so (``_lib``): fused normalise+split, fused score+row-max on the
-fp32 MFMA, radix argsort, index planning.  Nothing here touches the CPU except the two RNG draws the
-reference also makes on its generator (merge.py:57-58, patch.py:62).
+fp32 MFMA, radix argsort, index planning.  Nothing here touches the CPU except the RNG draws the
+reference also makes on its generator (merge.py:57-58, 500-501, patch.py:62).
 """
 from __future__ import annotations
 
@@ -175,13 +177,19 @@ def order_level(Ns: int, Nd: int, tokens: int, align_batch: bool) -> bool:
 
 
 def _run_level(x0: torch.Tensor, x1: Optional[torch.Tensor], parts, ratio: float, align_batch: bool,
-               want_indices: bool, seed=None, planner: Optional[MatchPlanner] = None, reorder: bool = False) -> Level:
+               want_indices: bool, seed=None, planner: Optional[MatchPlanner] = None, reorder: bool = False,
+               r: Optional[int] = None) -> Level:
     """normalise+split -> fused score/top-1 -> argsort -> index split  (merge.py:84-117 / 389-421).  ``reorder``: the level's
     rows are NOT in (frame, position) order (every level but the first local one) -- the matcher is then handed both lists
-    sorted by token position and reports in the original indexing; everything behind it sees the reference's order."""
+    sorted by token position and reports in the original indexing; everything behind it sees the reference's order.
+    ``r``: the number of src tokens to merge where the caller states it as a count (bipartite_soft_matching_random2d,
+    merge.py:542) instead of a ratio."""
     a_pos, b_pos, a_rows, b_rows = parts
     Ns, Nd = a_rows.shape[1], b_rows.shape[1]
-    r = min(Ns, int(Ns * ratio))                       # merge.py:90 (Python float -> int truncation)
+    if r is None:
+        r = min(Ns, int(Ns * ratio))                   # merge.py:90 (Python float -> int truncation)
+    else:
+        r = min(Ns, int(r))                            # merge.py:542
     if MATCH_MODE == "exact" or x0.shape[2] > 1280:    # plain fp32-MFMA kernel (filter window holds for C <= 1280)
         a_op, _ = _lib.normalize_gather(x0, x1, a_rows)
         b_op, _ = _lib.normalize_gather(x0, x1, b_rows)
@@ -343,3 +351,56 @@ def bipartite_soft_matching_2s(metric: torch.Tensor, src_len: int, ratio: float,
                 "unm_idx": level.unm_idx, "src_idx": level.src_idx, "dst_idx": level.dst_idx,
                 "level": level}
     return merge, unmerge, ret_dict
+
+
+def spatial_level(metric: torch.Tensor, w: int, h: int, sx: int, sy: int, r: int,
+                  draws: Optional[torch.Tensor]) -> Level:
+    """The level of bipartite_soft_matching_random2d (merge.py:493-550) on metric (B, h * w, C): the 2-D partition
+    (vtm_partition_2d; ``draws`` = the hsy * wsx cell draws on the device as int32, None = no_rand), then the matcher, the sort
+    and the index split of every other level -- never aligned, never seeded (dst tokens are scattered over the frame, one per
+    cell: no src token has a dst token at its own position)."""
+    B, N, _ = metric.shape
+    a_pos, b_pos = _lib.partition_2d(metric.device, h, w, sx, sy, draws)
+    a_rows, b_rows = a_pos.expand(B, -1).contiguous(), b_pos.expand(B, -1).contiguous()
+    if a_pos.numel() == 0:
+        # sx == sy == 1: every token is dst and b_idx = 0 .. N - 1, so "cat([unm, dst])" and its inverse are the identity map;
+        # there is no score to take a maximum of (merge.py:542: r = min(0, r) = 0)
+        none = torch.empty((B, 0), dtype=torch.int32, device=metric.device)
+        return Level(N, 0, N, 0, b_rows, b_rows, a_pos, b_pos, torch.empty((B, 0), dtype=torch.int64, device=metric.device),
+                     none, none, none)
+    return _run_level(metric, None, (a_pos, b_pos, a_rows, b_rows), 0.0, False, True, r=r)
+
+
+def bipartite_soft_matching_random2d(metric: torch.Tensor, w: int, h: int, sx: int, sy: int, r: int,
+                                     no_rand: bool = False, generator: torch.Generator = None
+                                     ) -> Tuple[Callable, Callable]:
+    """vidtome/merge.py:467-579, same signature and the same ``(merge, unmerge)`` pair: one random dst token per sy x sx cell
+    of the h x w frame, the r most similar src tokens merged into their nearest dst token.  ``merge(x, mode="mean")`` takes
+    torch.scatter_reduce's modes (merge.py:558; there is no "replace" here), ``unmerge(x)`` restores the N positions
+    (merge.py:562-577).  a_idx / b_idx are in ascending token order (include/vidtome_hip.h, vtm_partition_2d).  The closures
+    carry ``.level`` (the index tensors the reference keeps in closure cells) for parity tests."""
+    if r <= 0:
+        return do_nothing, do_nothing                              # merge.py:487-488: before any draw
+    metric = _check_metric(metric)
+    B, N, _ = metric.shape
+    if N != h * w:
+        raise ValueError(f"metric holds {N} tokens per sample, a {w} x {h} frame has {h * w}")
+    with torch.no_grad():
+        draws = None
+        if not no_rand:                                            # merge.py:500-501, on the generator's own device
+            hsy, wsx = h // sy, w // sx
+            draws = torch.randint(sy * sx, size=(hsy, wsx, 1), device=generator.device, generator=generator)
+            draws = draws.reshape(-1).to(device=metric.device, dtype=torch.int32)
+        level = spatial_level(metric, w, h, sx, sy, r, draws)
+    merge_any, unmerge_any = _make_closures(level, N, None, "mean")
+
+    def merge(x: torch.Tensor, mode="mean") -> torch.Tensor:
+        if mode not in _lib.REDUCE_MODES:                          # (the level machinery's "replace" included)
+            raise ValueError(f"merge mode {mode!r}: expected one of {sorted(_lib.REDUCE_MODES)}")
+        return merge_any(x, mode)
+
+    def unmerge(x: torch.Tensor) -> torch.Tensor:
+        return unmerge_any(x)
+
+    merge.level = unmerge.level = level
+    return merge, unmerge
