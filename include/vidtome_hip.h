@@ -95,6 +95,33 @@ int vtm_match(const float *a, const float *b, int64_t B, int64_t Ns, int64_t Nd,
               int64_t Nd_pad, int64_t C_pad, int align, uint64_t *best, vtm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * vtm_match_masked -- vtm_match with the receptive field of bipartite_soft_matching_random2d_hier / _2f: replaces
+ *     mask = torch.norm(src_coord[:, :, None, :] - dst_coord[:, None, :, :], dim=-1) > rec_field
+ *     scores = a @ b.transpose(-1, -2);  scores[mask] = 0
+ * (vidtome/merge.py:233-241 and 646-654) in front of the same row maximum (merge.py:249-282 / 662-699).  Neither the
+ * scores nor the mask are materialised.
+ * a, b, B .. align, best: as vtm_match.  coord: the coordinate pool (Bc, P, 4) fp32, Bc = B or 1 (one set of coordinates
+ * for every sample), 16-byte aligned, unused components 0; a_rows (B, Ns) / b_rows (B, Nd) int32: the pool row of every
+ * src / dst row (the lists the operands were gathered with).
+ * A pair is masked when s = sum_c (sc_c - dc_c)^2 > T, s in fp32 over the four components in ascending order.  T is the
+ * host's: the largest fp32 t with fl32(sqrt(t)) <= rec_field (-INFINITY for rec_field < 0: every pair is masked); a
+ * correctly rounded sqrt is monotone, so s > T is the reference's `norm > rec_field` without a device sqrt.  A masked
+ * score is +0.0f whatever it was (NaN included, as the assignment does); a pair with a NaN coordinate is unmasked
+ * (NaN > x is false).  PROMISE: bit parity with the reference for integer-valued coordinates with |value| <= 2048 in at
+ * most 4 components, where s is exact; for other coordinates torch's norm may round differently, and a pair EXACTLY at the
+ * boundary may then fall on the other side.
+ * A 256 x 128 tile whose src and dst coordinate boxes are further apart than the field (same arithmetic on the per-component
+ * gaps; exact, no margin; a box holding a non-finite value never qualifies) is all zeros and runs no MFMA: a pre-pass writes
+ * the boxes into `ws`.  VTM_DEBUG_NOBOXSKIP=1 in the environment (read once per process) runs every tile: same bits.
+ * ws: vtm_match_masked_ws_bytes(B, Ns_pad, Nd_pad) bytes, 16-byte aligned (VTM_EWORKSPACE when ws_bytes is less).
+ * ---------------------------------------------------------------------------------------------- */
+size_t vtm_match_masked_ws_bytes(int64_t B, int64_t Ns_pad, int64_t Nd_pad);
+int vtm_match_masked(const float *a, const float *b, int64_t B, int64_t Ns, int64_t Nd, int64_t Ns_pad,
+                     int64_t Nd_pad, int64_t C_pad, int align, const float *coord, int64_t Bc, int64_t P,
+                     const int32_t *a_rows, const int32_t *b_rows, float T, void *ws, size_t ws_bytes,
+                     uint64_t *best, vtm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * vtm_match_filtered -- the same packed result as vtm_normalize_gather x2 + vtm_match, BIT FOR BIT, several
  * times faster: an fp16-MFMA filter pass (operands hi = fp16(1024*xhat), one product hi_dst * hi_src;
  * the residual lo terms are a build-time option) collects for every src row the dst rows whose approximate score lies within a

@@ -11,7 +11,9 @@ from __future__ import annotations
 
 import ctypes
 import functools
+import math
 import os
+import struct
 import threading
 from typing import Optional, Tuple
 
@@ -37,6 +39,9 @@ _SIGNATURES = {
     "vtm_pad_k": ([_i64], _i64),
     "vtm_normalize_gather": ([_vp, _i64, _vp, _i64, _int, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _vp], _int),
     "vtm_match": ([_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _vp, _vp], _int),
+    "vtm_match_masked_ws_bytes": ([_i64, _i64, _i64], ctypes.c_size_t),
+    "vtm_match_masked": ([_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _vp, _i64, _i64, _vp, _vp, _f32, _vp,
+                          ctypes.c_size_t, _vp, _vp], _int),
     "vtm_match_filtered_ws_bytes": ([_i64, _i64, _i64, _i64, _int], ctypes.c_size_t),
     "vtm_match_filtered": ([_vp, _i64, _vp, _i64, _int, _i64, _i64, _vp, _i64, _vp, _i64, _int, _vp, ctypes.c_size_t,
                             _vp, _vp, _vp], _int),
@@ -251,6 +256,63 @@ def match(a: torch.Tensor, b: torch.Tensor, Ns: int, Nd: int, align: bool) -> to
     best = torch.empty((1 if align else B, Ns), dtype=torch.int64, device=a.device)
     _check(lib().vtm_match(_ptr(a), _ptr(b), B, Ns, Nd, Ns_pad, Nd_pad, C_pad, int(align), _ptr(best), _stream()),
            "vtm_match")
+    return best
+
+
+def _f32_round(v: float) -> float:
+    return struct.unpack("<f", struct.pack("<f", v))[0]
+
+
+def _f32_step(v: float, up: bool) -> float:
+    """The neighbour of the non-negative finite fp32 ``v`` (towards +inf / towards 0)."""
+    bits = struct.unpack("<I", struct.pack("<f", v))[0]
+    return struct.unpack("<f", struct.pack("<I", bits + 1 if up else bits - 1))[0]
+
+
+_F32_MAX = struct.unpack("<f", struct.pack("<I", 0x7F7FFFFF))[0]
+
+
+def mask_threshold(rec_field: float) -> float:
+    """T of vtm_match_masked: the largest fp32 t with fl32(sqrt(t)) <= fl32(rec_field), so that ``s > T`` on the squared
+    distance is the reference's ``torch.norm(...) > rec_field`` (merge.py:235; torch compares an fp32 tensor with a Python
+    number in fp32).  -inf for a negative field (every distance exceeds it), +inf for NaN / +inf (none does).  Pure host
+    arithmetic: sqrt in double and one rounding equal the correctly rounded fp32 sqrt (53 >= 2 * 24 + 2)."""
+    rec = float(rec_field)
+    if rec != rec:
+        return math.inf
+    rec = math.copysign(math.inf, rec) if abs(rec) > _F32_MAX * (1 + 2.0 ** -25) else _f32_round(rec)
+    if rec < 0:
+        return -math.inf
+    if rec == math.inf:
+        return math.inf
+    ok = lambda t: _f32_round(math.sqrt(t)) <= rec
+    sq = rec * rec                                   # exact in double
+    t = _F32_MAX if sq >= _F32_MAX else _f32_round(sq)
+    while t > 0.0 and not ok(t):
+        t = _f32_step(t, False)
+    while t < _F32_MAX and ok(_f32_step(t, True)):
+        t = _f32_step(t, True)
+    return t
+
+
+@_on_device
+def match_masked(a: torch.Tensor, b: torch.Tensor, Ns: int, Nd: int, align: bool, coord: torch.Tensor,
+                 a_rows: torch.Tensor, b_rows: torch.Tensor, T: float) -> torch.Tensor:
+    """``match`` with the receptive field: coord (B or 1, P, 4) fp32 coordinate pool, a_rows (B, Ns) / b_rows (B, Nd) int32
+    rows of it, T = mask_threshold(rec_field).  Same packed keys; see include/vidtome_hip.h."""
+    _req(coord, "coord"), _req(a_rows, "a_rows"), _req(b_rows, "b_rows")
+    B, G, _, Ns_pad, _ = a.shape
+    C_pad, Nd_pad = G * 8, b.shape[3]
+    if coord.dtype != torch.float32 or coord.dim() != 3 or coord.shape[2] != 4 or coord.shape[0] not in (1, B):
+        raise RuntimeError(f"match_masked: the coordinate pool must be (B or 1, P, 4) fp32, got {tuple(coord.shape)} {coord.dtype}")
+    if a_rows.dtype != torch.int32 or b_rows.dtype != torch.int32 or a_rows.shape != (B, Ns) or b_rows.shape != (B, Nd):
+        raise RuntimeError("match_masked: a_rows / b_rows must be (B, Ns) / (B, Nd) int32")
+    best = torch.empty((1 if align else B, Ns), dtype=torch.int64, device=a.device)
+    nbytes = lib().vtm_match_masked_ws_bytes(B, Ns_pad, Nd_pad)
+    ws = _workspace("match_masked", nbytes, a.device)
+    _check(lib().vtm_match_masked(_ptr(a), _ptr(b), B, Ns, Nd, Ns_pad, Nd_pad, C_pad, int(align), _ptr(coord), coord.shape[0],
+                                  coord.shape[1], _ptr(a_rows), _ptr(b_rows), T, _ptr(ws), nbytes, _ptr(best), _stream()),
+           "vtm_match_masked")
     return best
 
 

@@ -7,6 +7,9 @@ Public surface mirrors the reference (same names, argument meaning, return proto
 * ``bipartite_soft_matching_2s``           <- vidtome/merge.py:343-463  (global merging)
 * ``bipartite_soft_matching_random2d``     <- vidtome/merge.py:467-579  (per-frame 2-D merging: the original ToMe / ToMeSD
   matcher; a ``(merge, unmerge)`` pair, ``merge`` in "mean" mode by default -- not used by ``compute_merge``)
+* ``bipartite_soft_matching_random2d_hier`` <- vidtome/merge.py:162-340 (random-frame matching with a receptive field:
+  ``coord`` / ``rec_field``, ``adhere_src``, ``b_select`` / ``unm_modi`` on the closures -- not used by ``compute_merge``)
+* ``bipartite_soft_matching_2f``           <- vidtome/merge.py:582-767  (the same over a ``[src_len | N - src_len]`` split)
 
 Each matcher returns ``(merge, unmerge, ret_dict)`` closures like the reference, but the closures hold
 *composed row maps* on the device instead of index tensors + gather/scatter code: in ``replace`` mode (the
@@ -20,7 +23,7 @@ reference also makes on its generator (merge.py:57-58, 500-501, patch.py:62).
 from __future__ import annotations
 
 import os
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Callable, Optional, Tuple
 
 import torch
@@ -404,3 +407,132 @@ def bipartite_soft_matching_random2d(metric: torch.Tensor, w: int, h: int, sx: i
 
     merge.level = unmerge.level = level
     return merge, unmerge
+
+
+# ---- the receptive-field matchers (merge.py:162-340, 582-767) ---------------------------------------------------------------
+def _coord_pool(coord: torch.Tensor, metric: torch.Tensor) -> torch.Tensor:
+    """coord (B or 1, N, c <= 4) -> the (B or 1, N, 4) fp32 coordinate pool of vtm_match_masked (unused components 0)."""
+    B, N, _ = metric.shape
+    if coord.dim() != 3 or coord.shape[1] != N or coord.shape[0] not in (1, B):
+        raise ValueError(f"coord must be [B, N, c] for a metric of {B} x {N} tokens, got {tuple(coord.shape)}")
+    c = coord.shape[2]
+    if not 1 <= c <= 4:
+        raise ValueError(f"coord has {c} components per token; the masked matcher takes 1 to 4")
+    pool = torch.zeros((coord.shape[0], N, 4), dtype=torch.float32, device=metric.device)
+    pool[:, :, :c] = coord.to(device=metric.device, dtype=torch.float32)
+    return pool
+
+
+def masked_level(x0: torch.Tensor, parts, ratio: float, align_batch: bool, coord: torch.Tensor, rec_field: float) -> Level:
+    """A level whose scores are zeroed outside the receptive field before the row maximum (merge.py:233-241): normalise+split ->
+    masked exact matcher (vtm_match_masked) -> argsort -> index split.  The filtered matcher's pruning takes a score for a
+    cosine, which a masked 0 is not; so: no filter, no seeds, no planner, no position order."""
+    a_pos, b_pos, a_rows, b_rows = parts
+    Ns, Nd = a_rows.shape[1], b_rows.shape[1]
+    r = min(Ns, int(Ns * ratio))                       # merge.py:244-245
+    a_op, _ = _lib.normalize_gather(x0, None, a_rows)
+    b_op, _ = _lib.normalize_gather(x0, None, b_rows)
+    best = _lib.match_masked(a_op, b_op, Ns, Nd, align_batch, coord, a_rows, b_rows, _lib.mask_threshold(rec_field))
+    perm = _lib.sort_desc(best)
+    new_cur, inv, unm_idx, src_idx, dst_idx = _lib.plan_apply(best, perm, a_pos, b_pos, a_rows, b_rows, r, align_batch, True)
+    return Level(Ns + Nd, Ns, Nd, r, new_cur, inv, a_pos, b_pos, best, unm_idx, src_idx, dst_idx)
+
+
+def _select(level: Level, b_select) -> Level:
+    """The level of the samples ``b_select`` (an int or a list, merge.py:292-295): their maps apply to the rows of x in turn."""
+    if b_select is None:
+        return level
+    sel = torch.as_tensor(b_select if isinstance(b_select, (list, tuple)) else [b_select], dtype=torch.long,
+                          device=level.new_cur.device)
+    pick = lambda t: t.index_select(0, sel).contiguous()
+    return replace(level, new_cur=pick(level.new_cur), inv=pick(level.inv), unm_idx=pick(level.unm_idx),
+                   src_idx=pick(level.src_idx), dst_idx=pick(level.dst_idx))
+
+
+def _rf_closures(level: Level, merge_mode: str, out_slice: Optional[Tuple[int, int]], fold_first_rows: bool):
+    """The closures of the two receptive-field matchers: merge(x, mode=None, b_select=None, **kw) and
+    unmerge(x, b_select=None, unm_modi=None, **kw) (merge.py:289-337 / 706-764).  ``fold_first_rows``: the non-replace modes
+    fold src rows 0 .. r - 1 instead of the matched ones (bipartite_soft_matching_2f)."""
+    def merge(x: torch.Tensor, mode=None, b_select=None, **kwarg) -> torch.Tensor:
+        lv = _select(level, b_select)
+        mode = mode if mode is not None else merge_mode
+        if mode == "replace" or not fold_first_rows:
+            return _merge_with_mode(lv, x, mode)
+        x = x.contiguous()
+        out = _lib.gather_rows(x, None, lv.new_cur)
+        B = x.shape[0]
+        src_rows = lv.a_pos[:lv.r].to(torch.int32).expand(B, -1).contiguous()
+        dst_rows = lv.b_pos.to(torch.int32).expand(B, -1).contiguous()
+        return _lib.merge_reduce(x, src_rows, dst_rows, lv.dst_idx.contiguous(), mode, out, lv.Ns - lv.r)
+
+    def unmerge(x: torch.Tensor, b_select=None, unm_modi=None, **kwarg) -> torch.Tensor:
+        inv = _select(level, b_select).inv
+        if out_slice is not None:                       # merge.py:759-762
+            inv = inv[:, out_slice[0]:out_slice[1]].contiguous()
+        if unm_modi == "zero":                          # merge.py:326-328: the un-merged part restores as zeros
+            x = x.clone()
+            x[:, :level.unm_num] = 0
+        return _lib.unmerge_add(x.contiguous(), inv, None)
+
+    return merge, unmerge
+
+
+def _rf_dict(level: Level) -> dict:
+    return {"unm_num": level.unm_num, "a_idx": level.a_pos, "b_idx": level.b_pos, "unm_idx": level.unm_idx,
+            "src_idx": level.src_idx, "dst_idx": level.dst_idx, "level": level}
+
+
+def bipartite_soft_matching_random2d_hier(metric: torch.Tensor, frame_num: int, ratio: float, unm_pre: int,
+                                          generator: torch.Generator, target_stride: int = 4, adhere_src: bool = False,
+                                          merge_mode: str = "replace", scores=None, coord: Optional[torch.Tensor] = None,
+                                          rec_field: float = 2):
+    """vidtome/merge.py:162-340, same signature: bipartite_soft_matching_randframe (``adhere_src`` is its ``align_batch``)
+    with a receptive field -- given ``coord`` (B, N, c <= 4), every score whose src and dst coordinates are further apart than
+    ``rec_field`` counts as 0 in the row maximum (merge.py:233-241; bit parity for integer-valued coordinates up to 2048 in
+    magnitude, include/vidtome_hip.h) -- and with ``b_select`` / ``unm_modi="zero"`` on the closures.  ``scores`` is accepted
+    and ignored (the reference overwrites it, merge.py:238).  ``ratio <= 0`` returns the 2-tuple of merge.py:181-182, before
+    any draw; c > 4 raises ValueError.  ``ret_dict`` carries the index tensors and the level like randframe's."""
+    if ratio <= 0:
+        return do_nothing, do_nothing
+    metric = _check_metric(metric)
+    B, N, _ = metric.shape
+    F = frame_num
+    tnum = (N - unm_pre) // F
+    pool = None if coord is None else _coord_pool(coord, metric)
+    with torch.no_grad():
+        ts = min(target_stride, F)
+        randf = draw_randf(generator, ts)                                   # merge.py:197-198
+        if pool is None:
+            level = local_level(metric, None, N, F, ratio, unm_pre, randf, target_stride, adhere_src, True,
+                                tokens=tnum if unm_pre == 0 else None)
+        else:
+            parts = _lib.partition_local(None, B, N, unm_pre, tnum, ts, randf, metric.device)
+            level = masked_level(metric, parts, ratio, adhere_src, pool, rec_field)
+    merge, unmerge = _rf_closures(level, merge_mode, None, False)
+    return merge, unmerge, _rf_dict(level)
+
+
+def bipartite_soft_matching_2f(metric: torch.Tensor, src_len: int, ratio: float, adhere_src: bool,
+                               merge_mode: str = "replace", scores=None, coord: Optional[torch.Tensor] = None,
+                               rec_field: float = 2, unmerge_chunk: int = 0):
+    """vidtome/merge.py:582-767, same signature: bipartite_soft_matching_2s over the ``[src_len | N - src_len]`` split with
+    the receptive field and the closure keywords of bipartite_soft_matching_random2d_hier; ``unmerge`` returns the
+    ``unmerge_chunk`` part.  The non-replace merge modes reproduce the reference AS WRITTEN: its gather of the matched src
+    rows is commented out (merge.py:718), so ``scatter_reduce`` folds the FIRST r src rows -- rows 0 .. r - 1 of x, in that
+    order -- into ``dst_idx``; that row list is what vtm_merge_reduce is handed here."""
+    if ratio <= 0:
+        return do_nothing, do_nothing
+    metric = _check_metric(metric)
+    B, N, _ = metric.shape
+    pool = None if coord is None else _coord_pool(coord, metric)
+    with torch.no_grad():
+        if pool is None:
+            level = global_level(metric[:, :src_len].contiguous(), metric[:, src_len:].contiguous(), None, src_len, True,
+                                 ratio, adhere_src, True)
+        else:
+            cur = torch.arange(src_len, dtype=torch.int32, device=metric.device).expand(B, src_len).contiguous()
+            parts = _lib.partition_global(cur, src_len, N - src_len, True)
+            level = masked_level(metric, parts, ratio, adhere_src, pool, rec_field)
+    sl = (0, src_len) if unmerge_chunk == 0 else (src_len, N)
+    merge, unmerge = _rf_closures(level, merge_mode, sl, True)
+    return merge, unmerge, _rf_dict(level)
