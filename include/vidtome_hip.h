@@ -686,6 +686,33 @@ int vtm_lokr_delta(const float *w1, const float *w2, int64_t a1, int64_t b1, int
 int vtm_delta_fold(const void *w, int dtype, const float *delta, int64_t c_out, int64_t c_in, void *out,
                    vtm_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * vtm_groupnorm_silu -- the norm + activation pairs of the PnP feature-injection resnet (utils/pnp_utils.py:113-114
+ * `norm1` + `nonlinearity`; :133-142 `+ temb`, `norm2`, `nonlinearity`): out = act(GroupNorm(x [+ add])) on an NCHW
+ * tensor in one launch.  x, out: (B, C, HW) contiguous in `dtype`, 16-byte aligned, not the same buffer; add: (B, C) in
+ * `dtype` or NULL (the projected time embedding); gamma, beta: (C) in `dtype` or NULL; `groups` divides C (else
+ * VTM_EINVAL); act: 0 none, 1 SiLU.
+ * Rounding points of torch's separate ops: x' = round(x + add[b, c]); fp32 statistics over each (sample, group),
+ * the mean first (its sum carried in fp64), then the centred sum of squares (biased variance);
+ * y = round((x' - mean) * rstd * gamma + beta); z = round(y / (1 + exp(-y))).  Any group size (C / groups) * HW < 2^31
+ * and any HW (group starts need not be 16-byte aligned); a group that fits the LDS is read once, a larger one keeps
+ * its first ~160 KiB on chip and re-reads the rest.
+ * ---------------------------------------------------------------------------------------------- */
+int vtm_groupnorm_silu(const void *x, const void *add, const void *gamma, const void *beta, int dtype, int64_t B,
+                       int64_t C, int64_t HW, int64_t groups, float eps, int act, void *out, vtm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * vtm_resnet_tail -- the end of the same resnet (utils/pnp_utils.py:146-162: the injection copies of the source
+ * sample's features, the residual and the division by `output_scale_factor`) in one pass:
+ *   out[b] = (shortcut[b] + hidden[row(b)]) / scale,   row(b) = b % period for b < inject_rows, else b - inject_rows + period.
+ * shortcut, out: (B, M) contiguous in `dtype`; hidden holds only the rows that were computed: (period + B - inject_rows, M),
+ * or (B, M) with inject_rows = 0 (row(b) = b, the plain residual).  inject_rows in [0, B]; inject_rows > 0 needs
+ * period > 0 (else VTM_EINVAL).  Bit-identical to torch's `(shortcut + hidden_full) / scale` in `dtype`: the sum rounded
+ * to `dtype`, then multiplied by the fp32 reciprocal of `scale` and rounded again.
+ * ---------------------------------------------------------------------------------------------- */
+int vtm_resnet_tail(const void *shortcut, const void *hidden, int dtype, int64_t B, int64_t M, int64_t inject_rows,
+                    int64_t period, double scale, void *out, vtm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

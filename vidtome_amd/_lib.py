@@ -113,6 +113,8 @@ _SIGNATURES = {
     "vtm_loha_delta": ([_vp, _vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp], _int),
     "vtm_lokr_delta": ([_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _vp, _vp], _int),
     "vtm_delta_fold": ([_vp, _int, _vp, _i64, _i64, _vp, _vp], _int),
+    "vtm_groupnorm_silu": ([_vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _f32, _int, _vp, _vp], _int),
+    "vtm_resnet_tail": ([_vp, _vp, _int, _i64, _i64, _i64, _i64, ctypes.c_double, _vp, _vp], _int),
     "vtm_linear_f32": ([_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _int, _vp, _vp, _int, _i64,
                         _i64, _int, _vp], _int),
 }
@@ -927,6 +929,40 @@ def geglu(x: torch.Tensor) -> torch.Tensor:
     xc = x.contiguous()
     out = torch.empty(xc.shape[:-1] + (D,), dtype=x.dtype, device=x.device)
     _check(lib().vtm_geglu(_ptr(xc), dtype_code(xc), xc.numel() // (2 * D), D, _ptr(out), _stream()), "vtm_geglu")
+    return out
+
+
+@_on_device
+def groupnorm_silu(x: torch.Tensor, groups: int, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor], eps: float,
+                   add: Optional[torch.Tensor] = None, act: bool = True) -> torch.Tensor:
+    """act(GroupNorm(x [+ add[:, :, None, None]])) on a contiguous NCHW tensor in one launch (pnp_utils.py:113-114 and
+    :133-142); ``add`` is the (B, C) projected time embedding, ``act`` selects SiLU."""
+    _req(x, "x")
+    B, C = x.shape[0], x.shape[1]
+    for name, p, shape in (("weight", weight, (C,)), ("bias", bias, (C,)), ("add", add, (B, C))):
+        if p is not None and (p.dtype != x.dtype or tuple(p.shape) != shape or p.device != x.device or not p.is_contiguous()):
+            raise RuntimeError(f"vidtome_amd: groupnorm_silu {name} must be a contiguous {shape} {x.dtype} tensor on {x.device}")
+    out = torch.empty_like(x)
+    _check(lib().vtm_groupnorm_silu(_ptr(x), _ptr(add), _ptr(weight), _ptr(bias), dtype_code(x), B, C,
+                                    x.numel() // max(B * C, 1), int(groups), float(eps), int(bool(act)), _ptr(out), _stream()),
+           "vtm_groupnorm_silu")
+    return out
+
+
+@_on_device
+def resnet_tail(shortcut: torch.Tensor, hidden: torch.Tensor, inject_rows: int, period: int, scale: float) -> torch.Tensor:
+    """(shortcut + hidden[row(b)]) / scale, bit-identical to the torch expression (pnp_utils.py:146-162): output row b adds
+    compact row ``b % period`` of ``hidden`` for b < inject_rows, else row ``b - inject_rows + period``."""
+    _req(shortcut, "shortcut"), _req(hidden, "hidden")
+    B = shortcut.shape[0]
+    M = shortcut.numel() // max(B, 1)
+    rows = B if inject_rows == 0 else period + B - inject_rows
+    if hidden.dtype != shortcut.dtype or hidden.device != shortcut.device or tuple(hidden.shape) != (rows,) + tuple(shortcut.shape[1:]):
+        raise RuntimeError(f"vidtome_amd: resnet_tail hidden must be {(rows,) + tuple(shortcut.shape[1:])} {shortcut.dtype}, "
+                           f"got {tuple(hidden.shape)} {hidden.dtype}")
+    out = torch.empty_like(shortcut)
+    _check(lib().vtm_resnet_tail(_ptr(shortcut), _ptr(hidden), dtype_code(shortcut), B, M, int(inject_rows), int(period),
+                                 float(scale), _ptr(out), _stream()), "vtm_resnet_tail")
     return out
 
 

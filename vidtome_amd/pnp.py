@@ -8,8 +8,18 @@ semantics are attributes read by ``vidtome_amd.patch.self_attention``: the share
 
 If a pipeline already called the reference's own ``register_attention_control``, nothing needs to be
 re-registered: ``patch._pnp_num_inputs`` recognises that closure and routes it to the same kernel mode.
+
+``register_conv_control`` (utils/pnp_utils.py:108-172) is the other half of PnP: at injection timesteps the uncond / cond
+samples of ``up_blocks[1].resnets[1]`` take the SOURCE sample's main-branch features.  The reference computes the main
+branch (two GroupNorm + SiLU, two 3x3 convolutions) for every sample and then overwrites two thirds of the result; here
+only the rows whose result survives are computed, the norm + activation pairs are one launch each
+(``vtm_groupnorm_silu``, the second with the projected time embedding folded in), and the injection copies, the residual
+and the division by ``output_scale_factor`` are one pass (``vtm_resnet_tail``).  The convolutions stay the library's.
 """
 from __future__ import annotations
+
+import torch
+import torch.nn.functional as F
 
 
 def register_attention_control(model, injection_schedule, num_inputs):
@@ -43,4 +53,145 @@ def register_time(model, t):
             setattr(blk.attn1, "t", t)
             if getattr(blk, "attn2", None) is not None:
                 setattr(blk.attn2, "t", t)
+    return model
+
+
+# ---- feature injection: the resnet of up_blocks[1].resnets[1] (utils/pnp_utils.py:108-172) ----
+
+def _conv_target(model):
+    return model.unet.up_blocks[1].resnets[1]
+
+
+def _injection_rows(module, batch: int):
+    """(inject_rows, period) of this call: output rows [period, inject_rows) take the main-branch result of row
+    ``b % period``; (0, 0) when nothing is injected.  pnp_utils.py:146-155: with sbs = B // num_inputs the rows [sbs, 2 sbs)
+    and, for more than two inputs, [2 sbs, 3 sbs) are overwritten by rows [0, sbs); every other row keeps its own."""
+    schedule = getattr(module, "injection_schedule", None)
+    t = getattr(module, "t", None)
+    if schedule is None or not (t in schedule or t == 1000):
+        return 0, 0
+    sbs = batch // module.vtm_conv_num_inputs
+    if sbs == 0:
+        return 0, 0
+    return (3 if module.vtm_conv_num_inputs > 2 else 2) * sbs, sbs
+
+
+def _surviving(t, inject_rows: int, period: int):
+    """The rows whose main-branch result is used: the source rows and the rows behind the injected ones."""
+    if t is None or inject_rows == 0:
+        return t
+    return t[:period] if inject_rows == t.shape[0] else torch.cat((t[:period], t[inject_rows:]))
+
+
+def _is_silu(fn) -> bool:
+    return isinstance(fn, torch.nn.SiLU) or fn is F.silu
+
+
+def _fused_route(module, x) -> bool:
+    """Whether the HIP kernels serve this call (the conditions of DESIGN.md "PnP feature injection")."""
+    if not (x.is_cuda and x.dim() == 4 and x.is_contiguous() and x.dtype in (torch.float16, torch.bfloat16, torch.float32)):
+        return False
+    if getattr(module, "upsample", None) is not None or getattr(module, "downsample", None) is not None:
+        return False
+    if getattr(module, "time_embedding_norm", "default") != "default" or not _is_silu(module.nonlinearity):
+        return False
+    dropout = getattr(module, "dropout", None)
+    if dropout is not None and module.training and getattr(dropout, "p", 0.0) > 0:
+        return False
+    for norm in (module.norm1, module.norm2):
+        if type(norm) is not torch.nn.GroupNorm:
+            return False
+        if any(p is not None and (p.dtype != x.dtype or p.device != x.device) for p in (norm.weight, norm.bias)):
+            return False
+    return True
+
+
+def _project_temb(module, temb):
+    return None if temb is None else module.time_emb_proj(module.nonlinearity(temb))
+
+
+def _aligned(t):
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def _main_branch_fused(module, x, temb):
+    from . import _lib
+    n1, n2 = module.norm1, module.norm2
+    h = module.conv1(_lib.groupnorm_silu(_aligned(x), n1.num_groups, n1.weight, n1.bias, n1.eps))
+    add = _project_temb(module, temb)
+    if add is not None:
+        add = add.to(h.dtype).contiguous()
+    h = _lib.groupnorm_silu(_aligned(h), n2.num_groups, n2.weight, n2.bias, n2.eps, add=add)
+    return module.conv2(h)
+
+
+def _main_branch_torch(module, x, temb, resample):
+    """The resnet's main branch in plain torch, for everything the kernels do not cover (CPU tensors, channels_last,
+    up / down-sampling, scale_shift time embedding, training-mode dropout)."""
+    h = module.nonlinearity(module.norm1(x))
+    if resample is not None:
+        h = resample(h)
+    h = module.conv1(h)
+    add = _project_temb(module, temb)
+    scale_shift = getattr(module, "time_embedding_norm", "default") == "scale_shift"
+    if add is not None and not scale_shift:
+        h = h + add[:, :, None, None]
+    h = module.norm2(h)
+    if add is not None and scale_shift:
+        scale, shift = add[:, :, None, None].chunk(2, dim=1)
+        h = h * (1 + scale) + shift
+    h = module.nonlinearity(h)
+    dropout = getattr(module, "dropout", None)
+    if dropout is not None:
+        h = dropout(h)
+    return module.conv2(h)
+
+
+def _conv_forward(module):
+    def forward(input_tensor, temb=None, *args, **kwargs):
+        inject_rows, period = _injection_rows(module, input_tensor.shape[0])
+        x_main, temb_main = _surviving(input_tensor, inject_rows, period), _surviving(temb, inject_rows, period)
+        up, down = getattr(module, "upsample", None), getattr(module, "downsample", None)
+        resample = up if up is not None else down
+        fused = _fused_route(module, input_tensor)
+        hidden = _main_branch_fused(module, x_main, temb_main) if fused \
+            else _main_branch_torch(module, x_main, temb_main, resample)
+        shortcut = input_tensor if resample is None else resample(input_tensor)
+        if module.conv_shortcut is not None:
+            shortcut = module.conv_shortcut(shortcut)
+        scale = module.output_scale_factor
+        if fused:
+            from . import _lib
+            return _lib.resnet_tail(shortcut.contiguous(), hidden.contiguous(), inject_rows, period, float(scale))
+        if inject_rows:
+            rows = [b % period if b < inject_rows else b - inject_rows + period for b in range(input_tensor.shape[0])]
+            hidden = hidden[torch.tensor(rows, device=hidden.device)]
+        return (shortcut + hidden) / scale
+
+    forward.vtm_conv_control = True
+    return forward
+
+
+def register_conv_control(model, injection_schedule, num_inputs):
+    """utils/pnp_utils.py:108-172: feature injection on up_blocks[1].resnets[1].  Registering again keeps the one closure and
+    replaces the schedule and the input count."""
+    if num_inputs < 2:
+        raise ValueError("register_conv_control: num_inputs must be at least 2 (the source and one sample to inject into)")
+    module = _conv_target(model)
+    setattr(module, "injection_schedule", injection_schedule)
+    setattr(module, "vtm_conv_num_inputs", int(num_inputs))
+    if not getattr(module.__dict__.get("forward"), "vtm_conv_control", False):
+        module.forward = _conv_forward(module)
+    return model
+
+
+def unregister_conv_control(model):
+    """Give up_blocks[1].resnets[1] its class's forward back."""
+    module = _conv_target(model)
+    if getattr(module.__dict__.get("forward"), "vtm_conv_control", False):
+        del module.forward
+    for name in ("injection_schedule", "vtm_conv_num_inputs"):
+        if name in module.__dict__:
+            delattr(module, name)
     return model
