@@ -27,6 +27,7 @@
 //     PV matrix work gone); P^T moves from the 32-query accumulator layout to the two 16-query B operands
 //     with v_permlane16_swap -- 8 swaps per tile, still no LDS round trip (PV16 below).
 #include "attention_plan.h"
+#include "attention_stage.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -178,12 +179,8 @@ __global__ __launch_bounds__(waves_for(D) * 64, (D <= 48 ? 4 : D <= 96 ? 4 : 1))
     // sequence (vtm_fold_keys); the bias rides in two more spare k-slots (channels D + 2, D + 3 of the K row = hi + lo of
     // log2(multiplicity), against ones in the query), and the number of keys is a DEVICE value (k_count[b] <= Mk_arg).
     static_assert(!FOLD || (BIAS && D % 8 == 0 && D % 16 == 8), "key folding needs the spare k-slots of a d % 16 == 8 head");
-    constexpr int K_STRIDE = DK * 16 + 8;  // elements; (DK*8+4) words = 4 x odd -> conflict-free b128
-    constexpr int DCH = D / 8;             // 16-byte chunks per K row
-    constexpr int K_CHUNKS = KV * DCH;     // per tile
-    constexpr int V_CHUNKS = D * (KV / 8);
-    constexpr int K_PER_T = (K_CHUNKS + NT - 1) / NT;
-    constexpr int V_PER_T = (V_CHUNKS + NT - 1) / NT;
+    using Stage = KvStage<T, D, NT>;
+    constexpr int K_STRIDE = Stage::K_STRIDE;
     constexpr int SK_TILE = KV * K_STRIDE, SV_TILE = VROWS * VT_STRIDE;
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -224,21 +221,15 @@ __global__ __launch_bounds__(waves_for(D) * 64, (D <= 48 ? 4 : D <= 96 ? 4 : 1))
         }
     }
 
-    // Q fragments (B operand of S^T = K Q^T): lane (query l31, half hi) holds d = 16 ks + 8 hi + 0..7
     vec qf[DK];
     {
         const int64_t qi = q0 + l31;
-        const T *qp = q + (bq * Mp + (qi < M ? qi : 0)) * ldq + h * D;
+        load_q_frags<T, D>(qf, q + (bq * Mp + (qi < M ? qi : 0)) * ldq + h * D, qi < M, hi);
+        if constexpr (BIAS) {
 #pragma unroll
-        for (int ks = 0; ks < DK; ++ks) {
-            const int d0 = ks * 16 + hi * 8;
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (d0 < D && qi < M) v = *reinterpret_cast<const uint4 *>(qp + d0);
-            qf[ks] = *reinterpret_cast<vec *>(&v);
-            if constexpr (BIAS) {
+            for (int ks = 0; ks < DK; ++ks)
 #pragma unroll
                 for (int e = 0; e < 8; ++e) qf[ks][e] = (elem)((float)qf[ks][e] * scale_log2e);
-            }
         }
         if constexpr (FOLD) {   // channels D + 2, D + 3 (lane half BIAS_HI, elements BIAS_E + 2, + 3) meet the key's bias pair
             if (hi == BIAS_HI) {
@@ -248,96 +239,39 @@ __global__ __launch_bounds__(waves_for(D) * 64, (D <= 48 ? 4 : D <= 96 ? 4 : 1))
         }
     }
 
-    // hoisted staging addresses: chunk c = tid + 256 i ; K: (row c / DCH, 16-byte piece c % DCH);
-    // V^T: (channel row c / 8, key piece c % 8).  Tiles are fetched with buffer loads: a wave-uniform descriptor of
-    // the (sample, head) slice, a per-thread 32-bit byte offset computed once, and a scalar tile offset that advances by
-    // 64 rows / 64 keys per tile -- no vector address arithmetic inside the loop (the kernel is VALU-bound at d = 40).
-    // The descriptors carry no real bound (ragged tiles are masked explicitly below).
-    uint32_t kgo[K_PER_T], vgo[V_PER_T];   // byte offsets relative to the tile base
-    int koff[K_PER_T], voff[V_PER_T], krow[K_PER_T], vkey[V_PER_T];
-    bool kok[K_PER_T], vok[V_PER_T];
-#pragma unroll
-    for (int i = 0; i < K_PER_T; ++i) {
-        const int c = tid + i * NT;
-        kok[i] = c < K_CHUNKS;
-        krow[i] = c / DCH;
-        kgo[i] = kok[i] ? (uint32_t)(krow[i] * (int)ldk + (c % DCH) * 8) * 2u : 0u;
-        koff[i] = krow[i] * K_STRIDE + (c % DCH) * 8;
-    }
-#pragma unroll
-    for (int i = 0; i < V_PER_T; ++i) {
-        const int c = tid + i * NT;
-        vok[i] = c < V_CHUNKS;
-        vkey[i] = (c % (KV / 8)) * 8;
-        vgo[i] = vok[i] ? (uint32_t)((c / (KV / 8)) * (int)ldvt + vkey[i]) * 2u : 0u;
-        // inside every 16-key group the tile is stored as [k0-3 | k8-11 | k4-7 | k12-15]: the 8 keys one lane
-        // feeds to a PV k-step (4 hi + {0..3} and 8 + 4 hi + {0..3}) are then one contiguous 16-byte read
-        voff[i] = (c / (KV / 8)) * VT_STRIDE + (vkey[i] & ~15) + ((vkey[i] >> 3) & 1) * 4;
-    }
-    const auto rsrc_k = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(k + bq * Mkp * ldk + h * D), 0, 0x7fffffff, 0x00020000);
-    const auto rsrc_v = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(vt + (b * C + h * D) * ldvt), 0, 0x7fffffff, 0x00020000);
+    // the tile stage: the scalar tile offsets advance by 64 rows / 64 keys per tile
+    Stage stage;
+    stage.init(tid, ldk, ldvt);
+    const auto rsrc_k = kv_rsrc(k + bq * Mkp * ldk + h * D), rsrc_v = kv_rsrc(vt + (b * C + h * D) * ldvt);
     const uint32_t kstep = (uint32_t)(KV * ldk) * 2u, vstep = (uint32_t)KV * 2u;   // bytes per tile
     uint32_t so_k = 0, so_v = 0;                                                    // scalar tile offsets (bytes)
     // FOLD: the first wave also stages the tile's 64 bias words (one per key) into the K rows
-    const auto rsrc_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(FOLD ? k_bias + b * ldkb : nullptr), 0, 0x7fffffff, 0x00020000);
+    const auto rsrc_b = kv_rsrc(FOLD ? k_bias + b * ldkb : nullptr);
     uint32_t so_b = 0, rbias = 0;
     [[maybe_unused]] const uint32_t bgo = (uint32_t)(tid & (KV - 1)) * 4u;
-    auto fetch = [](const auto &rsrc, uint32_t voff_, uint32_t soff_) {
-        return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff_, soff_, 0));
-    };
 
-    uint4 rk[K_PER_T], rv[V_PER_T];
-    auto issue_full = [&]() {   // tile completely inside [0, M): no bounds logic
-        // unconditional: surplus threads re-read chunk 0 (their kgo / vgo is 0) and simply do not store it --
-        // a load inside a divergent branch makes the compiler wait for ALL outstanding loads right after it
-#pragma unroll
-        for (int i = 0; i < K_PER_T; ++i) rk[i] = fetch(rsrc_k, kgo[i], so_k);
-#pragma unroll
-        for (int i = 0; i < V_PER_T; ++i) rv[i] = fetch(rsrc_v, vgo[i], so_v);
-        if constexpr (FOLD) {   // (every wave fetches the 64 words -- no load behind a branch, see above -- the first one stores them)
+    auto issue_full = [&]() {   // tile completely inside [0, Mk): no bounds logic
+        stage.issue_full(rsrc_k, rsrc_v, so_k, so_v);
+        if constexpr (FOLD) {   // (every wave fetches the 64 words -- no load behind a branch -- the first one stores them)
             rbias = __builtin_amdgcn_raw_buffer_load_b32(rsrc_b, bgo, so_b, 0);
             so_b += (uint32_t)KV * 4u;
         }
         so_k += kstep;
         so_v += vstep;
     };
-    auto issue_tail = [&](int64_t key0) {   // ragged last tile: rows / keys >= M read as zero
-#pragma unroll
-        for (int i = 0; i < K_PER_T; ++i) {
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (kok[i] && key0 + krow[i] < Mk) v = fetch(rsrc_k, kgo[i], so_k);
-            rk[i] = v;
-        }
-#pragma unroll
-        for (int i = 0; i < V_PER_T; ++i) {
-            uint4 v = make_uint4(0, 0, 0, 0);
-            const int64_t key = key0 + vkey[i];
-            if (vok[i] && key < Mk) {   // ldvt >= Mk rounded up to 8: the 16-byte piece is inside the row
-                v = fetch(rsrc_v, vgo[i], so_v);
-                mask_keys(v, (int)(Mk - key));   // p is 0 there, but 0 * garbage may be NaN
-            }
-            rv[i] = v;
-        }
+    auto issue_tail = [&](int64_t key0) {   // ragged last tile: rows / keys >= Mk read as zero
+        stage.issue_masked(rsrc_k, rsrc_v, so_k, so_v, key0, Mk);
         if constexpr (FOLD) {
             rbias = 0u;
             if (key0 + (tid & (KV - 1)) < Mk) rbias = __builtin_amdgcn_raw_buffer_load_b32(rsrc_b, bgo, so_b, 0);
         }
     };
     auto write_lds = [&](int buf) {
-        elem *dk = sK + buf * SK_TILE, *dv = sV + buf * SV_TILE;
+        elem *dk = sK + buf * SK_TILE;
         if constexpr (FOLD) {
             if (wave == 0) *reinterpret_cast<uint32_t *>(dk + tid * K_STRIDE + D + 2) = rbias;
         }
-#pragma unroll
-        for (int i = 0; i < K_PER_T; ++i)
-            if (kok[i]) *reinterpret_cast<uint4 *>(dk + koff[i]) = rk[i];
-#pragma unroll
-        for (int i = 0; i < V_PER_T; ++i)
-            if (vok[i]) {   // keys 0-3 and 4-7 of the chunk go to the two halves of the 16-key group
-                uint2 *dst = reinterpret_cast<uint2 *>(dv + voff[i]);
-                dst[0] = make_uint2(rv[i].x, rv[i].y);
-                dst[2] = make_uint2(rv[i].z, rv[i].w);
-            }
+        stage.write(dk, sV + buf * SV_TILE);
     };
 
     f32x16 o[PV16 ? 1 : DV];          // 32-row blocks: o[dv][r] = row 32 dv + (r & 3) + 8 (r >> 2) + 4 hi of query l31

@@ -14,6 +14,7 @@
 //
 // Reference: the `self.attn1(...)` call at vidtome/patch.py:157-162 = `sa_forward`, utils/pnp_utils.py:47-95.
 #include "attention16_parts.h"
+#include "attention_stage.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -113,6 +114,8 @@ __global__ __launch_bounds__(NT16, 2) void attention16s_kernel(
         }
     }
 
+    // the tile stage of KvStage (attention_stage.h: chunking, swizzle, unconditional full-tile loads, masks), written out
+    // here because the shared form moved spills into this kernel's tile loop (profiles/attention_stage_resources.txt)
     uint32_t kgo[K_PER_T], vgo[V_PER_T];
     int koff[K_PER_T], voff[V_PER_T], krow[K_PER_T], vkey[V_PER_T];
     bool kok[K_PER_T], vok[V_PER_T];
@@ -132,10 +135,10 @@ __global__ __launch_bounds__(NT16, 2) void attention16s_kernel(
         vgo[i] = vok[i] ? (uint32_t)((c / (KV / 8)) * (int)ldvt + vkey[i]) * 2u : 0u;
         voff[i] = (c / (KV / 8)) * VT_STRIDE + (vkey[i] & ~15) + ((vkey[i] >> 3) & 1) * 4;
     }
-    const auto rsrc_k = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(k + bq * Mkp * ldk + h * D), 0, 0x7fffffff, 0x00020000);
-    const auto rsrc_v = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(vt + (b * C + h * D) * ldvt), 0, 0x7fffffff, 0x00020000);
+    const auto rsrc_k = kv_rsrc(k + bq * Mkp * ldk + h * D);
+    const auto rsrc_v = kv_rsrc(vt + (b * C + h * D) * ldvt);
     const uint32_t kstep = (uint32_t)(KV * ldk) * 2u, vstep = (uint32_t)KV * 2u;
-    const auto rsrc_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(FOLD ? k_bias + b * ldkb : nullptr), 0, 0x7fffffff, 0x00020000);
+    const auto rsrc_b = kv_rsrc(FOLD ? k_bias + b * ldkb : nullptr);
     uint32_t rbias = 0;
     [[maybe_unused]] const uint32_t bgo = (uint32_t)(tid & (KV - 1)) * 4u;
     auto fetch = [](const auto &rsrc, uint32_t voff_, uint32_t soff_) {

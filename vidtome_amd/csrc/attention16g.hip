@@ -16,6 +16,7 @@
 // of three samples, two score tiles and two packed P inside 256.  Arithmetic per query and tile identical to
 // attention_kernel's PV16 path.
 #include "attention16_parts.h"
+#include "attention_stage.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -80,18 +81,16 @@ __global__ __launch_bounds__(NT16, 2) void attention16g_kernel(
     vec qf[DK];
     {
         const int64_t qi = q0 + l31;
-        const T *qp = q + (b * Mp + (qi < M ? qi : 0)) * ldq + h * D;
+        load_q_frags<T, D>(qf, q + (b * Mp + (qi < M ? qi : 0)) * ldq + h * D, qi < M, hi);
 #pragma unroll
-        for (int ks = 0; ks < DK; ++ks) {
-            const int d0 = ks * 16 + hi * 8;
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (d0 < D && qi < M) v = *reinterpret_cast<const uint4 *>(qp + d0);
-            qf[ks] = *reinterpret_cast<vec *>(&v);
+        for (int ks = 0; ks < DK; ++ks)
 #pragma unroll
             for (int e = 0; e < 8; ++e) qf[ks][e] = (elem)((float)qf[ks][e] * scale_log2e);
-        }
     }
 
+    // the tile stage of KvStage (attention_stage.h: chunking, swizzle, unconditional full-tile loads, masks), written out
+    // here because the shared form moved spills into this kernel's tile loop (profiles/attention_stage_resources.txt);
+    // V^T: the tiles of the NG value groups, src_batch * C rows of one descriptor apart
     uint32_t kgo[K_PER_T], vgo[V_PER_T];
     int koff[K_PER_T], voff[V_PER_T], krow[K_PER_T], vkey[V_PER_T];
     bool kok[K_PER_T], vok[V_PER_T];
@@ -112,8 +111,8 @@ __global__ __launch_bounds__(NT16, 2) void attention16g_kernel(
         vgo[i] = vok[i] ? (uint32_t)(((int64_t)gi * src_batch * C + cc / (KV / 8)) * ldvt + vkey[i]) * 2u : 0u;
         voff[i] = gi * SV_TILE1 + (cc / (KV / 8)) * VT_STRIDE + (vkey[i] & ~15) + ((vkey[i] >> 3) & 1) * 4;
     }
-    const auto rsrc_k = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(k + b * Mkp * ldk + h * D), 0, 0x7fffffff, 0x00020000);
-    const auto rsrc_v = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(vt + (b * C + h * D) * ldvt), 0, 0x7fffffff, 0x00020000);
+    const auto rsrc_k = kv_rsrc(k + b * Mkp * ldk + h * D);
+    const auto rsrc_v = kv_rsrc(vt + (b * C + h * D) * ldvt);
     const uint32_t kstep = (uint32_t)(KV * ldk) * 2u, vstep = (uint32_t)KV * 2u;
     auto fetch = [](const auto &rsrc, uint32_t voff_, uint32_t soff_) {
         return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff_, soff_, 0));

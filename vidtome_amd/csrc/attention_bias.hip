@@ -16,6 +16,7 @@
 //     leading masked tiles give 0, not NaN.  A sample whose keys are ALL -inf ends as 0 / 0 = NaN, as torch's SDPA does;
 //   * no key split, no workspace, no combine kernel: the key axis is a few hundred keys, the launch streams q and out.
 #include "attention_plan.h"
+#include "attention_stage.h"
 
 #include <cmath>
 
@@ -45,14 +46,11 @@ __global__ __launch_bounds__(bias_waves(D) * 64, bias_wg_per_cu(D) * bias_waves(
     using vec = typename F::vec;
     using elem = typename F::elem;
     constexpr int WAVES = bias_waves(D), NT = WAVES * 64;
-    constexpr bool SPLIT_P = std::is_same_v<T, vtm_bf16>;   // P as hi + lo parts (see tile)
-    constexpr int DK = (D + 15) / 16;      // k-steps of the QK^T contraction
+    using Stage = KvStage<T, D, NT>;
+    constexpr int DK = Stage::DK;          // k-steps of the QK^T contraction
     constexpr int DV = (D + 31) / 32;      // 32-row blocks of O^T
     constexpr int VROWS = DV * 32;
-    constexpr int K_STRIDE = DK * 16 + 8;  // elements; conflict-free b128 reads (see attention.hip)
-    constexpr int DCH = D / 8;             // 16-byte chunks per K row
-    constexpr int K_CHUNKS = KV * DCH, V_CHUNKS = D * (KV / 8);
-    constexpr int K_PER_T = (K_CHUNKS + NT - 1) / NT, V_PER_T = (V_CHUNKS + NT - 1) / NT;
+    constexpr int K_STRIDE = Stage::K_STRIDE;
     constexpr float LOG2E = 1.4426950408889634f;
 
     __shared__ __attribute__((aligned(16))) elem sK[KV * K_STRIDE];
@@ -65,89 +63,27 @@ __global__ __launch_bounds__(bias_waves(D) * 64, bias_wg_per_cu(D) * bias_waves(
     const int64_t b = w.b, h = w.h, q0 = w.q0 + wave * QW;
     const int64_t C = H * D;
 
-    // one-time LDS init: the K pad columns meet Q's zero padding and the V^T pad rows feed O^T rows nobody stores, but
-    // garbage there could be NaN; tile stores never touch them
-    for (int i = tid; i < KV * (K_STRIDE - D); i += NT)
-        sK[(i / (K_STRIDE - D)) * K_STRIDE + D + i % (K_STRIDE - D)] = (elem)0.0f;
-    for (int i = tid; i < (VROWS - D) * VT_STRIDE; i += NT) sV[D * VT_STRIDE + i] = (elem)0.0f;
+    zero_kv_pads<T, D, NT>(sK, sV, tid);
 
-    // Q fragments (B operand of S^T = K Q^T): lane (query l31, half hi) holds d = 16 ks + 8 hi + 0..7
     vec qf[DK];
     {
         const int64_t qi = q0 + l31;
-        const T *qp = q + (b * Mp + (qi < M ? qi : 0)) * ldq + h * D;
-#pragma unroll
-        for (int ks = 0; ks < DK; ++ks) {
-            const int d0 = ks * 16 + hi * 8;
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (d0 < D && qi < M) v = *reinterpret_cast<const uint4 *>(qp + d0);
-            qf[ks] = *reinterpret_cast<vec *>(&v);
-        }
+        load_q_frags<T, D>(qf, q + (b * Mp + (qi < M ? qi : 0)) * ldq + h * D, qi < M, hi);
     }
 
-    // staging addresses, as in attention_kernel: chunk c = tid + NT i; K: (row c / DCH, 16-byte piece c % DCH); V^T:
-    // (channel row c / 8, key piece c % 8), stored as [k0-3 | k8-11 | k4-7 | k12-15] inside every 16-key group
-    uint32_t kgo[K_PER_T], vgo[V_PER_T];
-    int koff[K_PER_T], voff[V_PER_T], krow[K_PER_T], vkey[V_PER_T];
-    bool kok[K_PER_T], vok[V_PER_T];
-#pragma unroll
-    for (int i = 0; i < K_PER_T; ++i) {
-        const int c = tid + i * NT;
-        kok[i] = c < K_CHUNKS;
-        krow[i] = c / DCH;
-        kgo[i] = kok[i] ? (uint32_t)(krow[i] * (int)ldk + (c % DCH) * 8) * 2u : 0u;
-        koff[i] = krow[i] * K_STRIDE + (c % DCH) * 8;
-    }
-#pragma unroll
-    for (int i = 0; i < V_PER_T; ++i) {
-        const int c = tid + i * NT;
-        vok[i] = c < V_CHUNKS;
-        vkey[i] = (c % (KV / 8)) * 8;
-        vgo[i] = vok[i] ? (uint32_t)((c / (KV / 8)) * (int)ldvt + vkey[i]) * 2u : 0u;
-        voff[i] = (c / (KV / 8)) * VT_STRIDE + (vkey[i] & ~15) + ((vkey[i] >> 3) & 1) * 4;
-    }
-    // (the descriptors carry no real bound: every fetch is guarded by Mk below)
-    const auto rsrc_k = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(k + b * Mkp * ldk + h * D), 0, 0x7fffffff, 0x00020000);
-    const auto rsrc_v = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(vt + (b * C + h * D) * ldvt), 0, 0x7fffffff, 0x00020000);
-    auto fetch = [](const auto &rsrc, uint32_t voff_, uint32_t soff_) {
-        return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff_, soff_, 0));
-    };
+    Stage stage;
+    stage.init(tid, ldk, ldvt);
+    const auto rsrc_k = kv_rsrc(k + b * Mkp * ldk + h * D), rsrc_v = kv_rsrc(vt + (b * C + h * D) * ldvt);
     const float *brow = bias + b * bias_batch_stride;   // this sample's row: one value per key, for every head and query
 
-    uint4 rk[K_PER_T], rv[V_PER_T];
     float rb = -INFINITY;   // threads 0 .. 63: the bias of key key0 + tid of the tile in flight
     auto issue = [&](int key0) {   // the tile of keys [key0, key0 + 64): rows / keys >= Mk read as zero, their bias as -inf
-        const uint32_t so_k = (uint32_t)key0 * (uint32_t)ldk * 2u, so_v = (uint32_t)key0 * 2u;
-#pragma unroll
-        for (int i = 0; i < K_PER_T; ++i) {
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (kok[i] && key0 + krow[i] < Mk) v = fetch(rsrc_k, kgo[i], so_k);
-            rk[i] = v;
-        }
-#pragma unroll
-        for (int i = 0; i < V_PER_T; ++i) {
-            uint4 v = make_uint4(0, 0, 0, 0);
-            const int key = key0 + vkey[i];
-            if (vok[i] && key < Mk) {   // key % 8 == 0 and ldvt % 8 == 0, ldvt >= Mk: the 16-byte piece is inside the row
-                v = fetch(rsrc_v, vgo[i], so_v);
-                mask_keys(v, Mk - key);   // p is 0 there, but 0 * garbage may be NaN
-            }
-            rv[i] = v;
-        }
+        stage.issue_masked(rsrc_k, rsrc_v, (uint32_t)key0 * (uint32_t)ldk * 2u, (uint32_t)key0 * 2u, key0, Mk);
         rb = -INFINITY;
         if (tid < KV && key0 + tid < Mk) rb = brow[key0 + tid];
     };
     auto write_lds = [&]() {
-#pragma unroll
-        for (int i = 0; i < K_PER_T; ++i)
-            if (kok[i]) *reinterpret_cast<uint4 *>(sK + koff[i]) = rk[i];
-#pragma unroll
-        for (int i = 0; i < V_PER_T; ++i)
-            if (vok[i]) {
-                uint2 *dst = reinterpret_cast<uint2 *>(sV + voff[i]);
-                dst[0] = make_uint2(rv[i].x, rv[i].y);
-                dst[2] = make_uint2(rv[i].z, rv[i].w);
-            }
+        stage.write(sK, sV);
         if (tid < KV) sB[tid] = rb * LOG2E;   // (-inf stays -inf)
     };
 
@@ -197,33 +133,13 @@ __global__ __launch_bounds__(bias_waves(D) * 64, bias_wg_per_cu(D) * bias_waves(
         }
         // (only masked keys so far: -inf - (-inf) would be NaN; against 0 every p of such a query is exp2(-inf) = 0)
         const float m_use = m_run == -INFINITY ? 0.0f : m_run;
-        // per 16-key step: p of keys 16 st + (e & 3) + 8 (e >> 2) + 4 hi, packed to the operand type, then O^T += V^T P^T with
-        // k-slot (hi, e) <-> key 16 st + 8 (e >> 2) + 4 hi + (e & 3).  bf16 keeps 8 bits of P: there P goes in as hi + lo (two
-        // MFMAs on the same V^T fragment), so that its rounding stays below the operands' own; the denominator is summed from
-        // what the numerator sees.
+        // per 16-key step: p of keys 16 st + (e & 3) + 8 (e >> 2) + 4 hi
 #pragma unroll
         for (int st = 0; st < 4; ++st) {
-            float p[8], plo[8];
+            float p[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) p[e] = __builtin_amdgcn_exp2f(s[st >> 1][8 * (st & 1) + e] - m_use);
-            vec ph, pl;
-            F::pack8(ph, p);
-            if constexpr (SPLIT_P) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) plo[e] = p[e] - (float)ph[e];
-                F::pack8(pl, plo);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) l_run += (float)ph[e] + (float)pl[e];
-            } else {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) l_run += (float)ph[e];
-            }
-#pragma unroll
-            for (int dv = 0; dv < DV; ++dv) {
-                const vec vf = *reinterpret_cast<const vec *>(sV + (dv * 32 + l31) * VT_STRIDE + 8 * hi + st * 16);
-                o[dv] = F::mfma(vf, ph, o[dv]);
-                if constexpr (SPLIT_P) o[dv] = F::mfma(vf, pl, o[dv]);
-            }
+            pv_step_split<T, D>(o, l_run, p, sV + l31 * VT_STRIDE + 8 * hi + st * 16);
         }
     };
 
@@ -244,21 +160,7 @@ __global__ __launch_bounds__(bias_waves(D) * 64, bias_wg_per_cu(D) * bias_waves(
 
     const float inv_l = 1.0f / (l_run + __shfl_xor(l_run, 32, 64));
     const int64_t qi = q0 + l31;
-    if (qi < M) {
-        T *op = out + (b * Mp + qi) * ldo + h * D;
-#pragma unroll
-        for (int dv = 0; dv < DV; ++dv)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int d0 = dv * 32 + 8 * g + 4 * hi;
-                if (d0 < D) {   // D % 8 == 0 and d0 % 4 == 0 -> the 4 channels are all valid
-                    elem w4[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) w4[e] = (elem)(o[dv][g * 4 + e] * inv_l);
-                    *reinterpret_cast<uint2 *>(op + d0) = *reinterpret_cast<uint2 *>(w4);
-                }
-            }
-    }
+    if (qi < M) store_rows32<T, D>(o, inv_l, out + (b * Mp + qi) * ldo + h * D, hi);
 }
 
 template <typename T, int D>
