@@ -158,12 +158,17 @@ def test_cross_attention_sends_the_call_where_it_belongs(monkeypatch):
 
 
 def test_attn1_mask_keeps_its_own_path():
-    """A mask on attn1 never meets the recogniser: the self-attention segment asks `attention_mask is None` as before."""
+    """A mask on attn1 never meets the recogniser: attn1's route asks `attention_mask is not None` as the segments did, and
+    every form the recogniser takes on attn2 sends attn1 to its module forward."""
     import inspect
     from vidtome_amd import patch as vpatch
-    for fn in (vpatch.self_attention_segment, vpatch.patched_self_attention_segment):
-        src = inspect.getsource(fn)
-        assert "key_bias" not in src and "attention_mask is" in src
+    for fn in (vpatch.attn1_route, vpatch.self_attention_segment, vpatch.patched_self_attention_segment):
+        assert "key_bias" not in inspect.getsource(fn)
+    assert "attention_mask is" in inspect.getsource(vpatch.attn1_route)
+    blk = standin.BasicTransformerBlock(C, HEADS).half()
+    assert vpatch.attn1_route(blk, _x()) != "module"                       # (only the mask sends it there)
+    for what, make in ACCEPTED.items():
+        assert vpatch.attn1_route(blk, _x(), None, make()) == "module", what
 
 
 def test_header_declares_and_lib_binds_the_export():

@@ -1,0 +1,312 @@
+"""Digest of what vidtome_amd/patch.py launches and computes, for a bit-for-bit A/B of two versions of the host layer on ONE
+built library: one line per call -- case name, the ordered vidtome_amd._lib wrappers it went through, sha256 of its output,
+sha256 of ``module.global_tokens``.
+
+    VIDTOME_HIP_LIB=<libvidtome_hip.so> python tools/block_digest.py [--package DIR] [--out FILE]
+
+``--package DIR``: the directory that holds the ``vidtome_amd`` package to import (default: this tree).  Two runs on the same
+library compare with `diff`: every input is seeded on the CPU, and so is every draw of the block generator.
+
+Cases (fp16 unless named; batch 2, 4 frames, latent 16 x 16, local_merge_ratio 0.5, the self-attention segment of one site):
+  route/*      one call per row of the attn1 route table (tests/test_gpu_attn1_route.py), `merge_global=False`
+  chunks/*     the rows / panels / f32 / blas routes over four chunks of one clip with `merge_global=True`: the first stores its
+               tokens, the second has the local chunk on the src side (the coin threshold `global_rand` is switched per chunk, as
+               `smoke()` does), the third on the dst side behind anchors that carry content ids, the fourth is ONE frame.  The
+               tool fails unless a local-is-src chunk with compacted queries, a local-is-dst chunk, a folded-key launch
+               (d = 40) and a single-frame chunk all occurred, and prints which did
+  pnp/*        PnP shared probabilities with `align_batch=True` (live query rows under sharing)
+  nolive/*     the rows route with LIVE_QUERIES off
+  unmerged/*   sites that do not merge (`max_downsample=1`, 64 tokens): bf16 C = 640, fp32 C = 320 with fp32_projections
+  cross/*      `cross_attention`, `norm_cross_attention_residual` and the whole block forward: plain, masked, IP-Adapter,
+               IP-Adapter with region masks, and 250 tokens (no multiple of 8), under both FF_MODEs; the whole forward of an fp32
+               block with fp32_projections"""
+import argparse
+import hashlib
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DEV = "cuda"
+B, FRAMES, LATENT = 2, 4, (16, 16)
+SPIED = ("layernorm", "layernorm_panels", "gather_rows", "gather_panels", "to_panels", "transpose_cols", "linear_rows",
+         "linear_panels", "linear_f32", "attention", "attention_kv", "attention_kv_bias", "attention_kv_sets",
+         "attention_kv_sets_masked", "compact_queries", "fold_keys", "compose", "anchor_maps", "unmerge_add", "ff_geglu", "geglu")
+
+# name -> (dtype, C, heads, options); the expected route of each row is tests/test_gpu_attn1_route.py's table
+ROUTE_CASES = {
+    "fp16 C=320 heads 8": (torch.float16, 320, 8, {}),
+    "fp16 C=64 heads 8": (torch.float16, 64, 8, {}),
+    "bf16 C=320": (torch.bfloat16, 320, 8, {}),
+    "fp16 C=640": (torch.float16, 640, 8, {}),
+    "fp16 C=640 bias on to_v": (torch.float16, 640, 8, {"v_bias": True}),
+    "fp16 C=480 heads 12": (torch.float16, 480, 12, {}),
+    "fp16 block, fp32 to_out": (torch.float16, 320, 8, {"f32_out": True}),
+    "fp32 C=320": (torch.float32, 320, 8, {}),
+    "fp32 C=320 fp32_projections": (torch.float32, 320, 8, {"fp32_projections": True}),
+    "PROJ_MODE=rows C=640": (torch.float16, 640, 8, {"proj_mode": "rows"}),
+    "PROJ_MODE=panels C=320": (torch.float16, 320, 8, {"proj_mode": "panels"}),
+    "PROJ_MODE=blas C=320": (torch.float16, 320, 8, {"proj_mode": "blas"}),
+    "un-merged fp16 C=640": (torch.float16, 640, 8, {"unmerged": True}),
+    "un-merged fp16 C=320": (torch.float16, 320, 8, {"unmerged": True}),
+    "PnP sharing fp16 C=320": (torch.float16, 320, 8, {"pnp": True}),
+    "attention_mask given": (torch.float16, 320, 8, {"mask": True}),
+}
+
+
+def sha(t):
+    if t is None:
+        return "-"
+    return hashlib.sha256(t.detach().contiguous().view(torch.uint8).cpu().numpy().tobytes()).hexdigest()[:24]
+
+
+class Spy:
+    """Records the names of the _lib wrappers that run inside the `with` block, in order; every wrapper calls through."""
+
+    def __init__(self, _lib, names=SPIED):
+        self._lib, self.names, self.calls, self.kwargs = _lib, names, [], []
+
+    def __enter__(self):
+        self.orig = {n: getattr(self._lib, n) for n in self.names}
+        for n, fn in self.orig.items():
+            setattr(self._lib, n, self._wrap(n, fn))
+        return self
+
+    def _wrap(self, name, fn):
+        def spied(*a, **kw):
+            self.calls.append(name)
+            self.kwargs.append(kw)
+            return fn(*a, **kw)
+        return spied
+
+    def __exit__(self, *exc):
+        for n, fn in self.orig.items():
+            setattr(self._lib, n, fn)
+
+
+def site_block(vidtome_amd, S, dtype, C, heads, unmerged=False, full=False, seed=0, **patch_kw):
+    """A patched one-site model and its block: 256 tokens per frame, or 64 at a site that does not merge."""
+    site = S.Site("site", 2 if unmerged else 1, C, heads)
+    unet = S.SiteUNet([site], seed=seed, full=full).to(device=DEV, dtype=dtype).eval()
+    vidtome_amd.apply_patch(unet, local_merge_ratio=0.5, batch_size=B, max_downsample=1 if unmerged else 2, **patch_kw)
+    unet.set_size(LATENT)
+    blk = unet.blocks[0]
+    blk.generator = torch.Generator().manual_seed(123)
+    return unet, site, blk
+
+
+class CountingAttention(torch.nn.Module):
+    """attn1's own forward for the "module" route: counts its calls and returns zeros."""
+    calls = 0
+
+    def forward(self, x, encoder_hidden_states=None, attention_mask=None, **kw):
+        self.calls += 1
+        return torch.zeros_like(x)
+
+
+def route_case(vidtome_amd, name):
+    """(model, block, hidden states, attention_mask, restore) of one ROUTE_CASES row; call ``restore()`` afterwards."""
+    from vidtome_amd import patch as vpatch, sites as S
+    dtype, C, heads, opt = ROUTE_CASES[name]
+    unet, site, blk = site_block(vidtome_amd, S, dtype, C, heads, unmerged=opt.get("unmerged", False))
+    attn = blk.attn1
+    if opt.get("v_bias"):
+        g = torch.Generator().manual_seed(9)
+        attn.to_v.bias = torch.nn.Parameter(torch.randn(C, generator=g).to(device=DEV, dtype=dtype))
+    if opt.get("f32_out"):
+        attn.to_out[0].float()
+    if opt.get("fp32_projections"):
+        vidtome_amd.update_patch(unet, fp32_projections=True)
+    if opt.get("pnp"):
+        attn.injection_schedule, attn.t, attn.vtm_num_inputs = [981], 981, B
+    mask = None
+    if opt.get("mask"):
+        attn.__class__ = type("Attention", (CountingAttention, type(attn)), {})
+        mask = torch.zeros(B * FRAMES, 1, 128, dtype=dtype, device=DEV)
+    keep = vpatch.PROJ_MODE, vpatch.FUSED_PROJ
+    if "proj_mode" in opt:
+        vpatch.PROJ_MODE, vpatch.FUSED_PROJ = opt["proj_mode"], opt["proj_mode"] != "blas"
+    h = S.synthetic_hidden(site, B, FRAMES, LATENT, dtype, DEV, seed=50, clip_seed=7)
+
+    def restore():
+        vpatch.PROJ_MODE, vpatch.FUSED_PROJ = keep
+        vidtome_amd.remove_patch(unet)
+    return unet, blk, h, mask, restore
+
+
+def emit(out, name, spy, y, blk):
+    out.append(f"{name} | {' '.join(spy.calls)} | out {sha(y)} | anchors {sha(getattr(blk, 'global_tokens', None))}")
+
+
+def run_routes(vidtome_amd, out):
+    from vidtome_amd import _lib, patch as vpatch
+    for name in ROUTE_CASES:
+        torch.manual_seed(123)
+        unet, blk, h, mask, restore = route_case(vidtome_amd, name)
+        try:
+            with torch.no_grad(), Spy(_lib) as spy:
+                y = vpatch.self_attention_segment(blk, h, None, mask, None)
+            emit(out, f"route/{name}", spy, y, blk)
+        finally:
+            restore()
+
+
+def run_chunks(vidtome_amd, out, name, dtype, C, seen, fp32_projections=False, proj_mode=None, pnp=False, live=True,
+               chunks=((FRAMES, None), (FRAMES, 0.0), (FRAMES, 1.0), (1, 1.0)), **patch_kw):
+    """Chunks of one clip through one merging site with a global level; ``chunks``: (frames, coin threshold) per chunk."""
+    from vidtome_amd import _lib, patch as vpatch, sites as S
+    torch.manual_seed(123)
+    unet, site, blk = site_block(vidtome_amd, S, dtype, C, 8, merge_global=True, global_merge_ratio=0.5, **patch_kw)
+    if fp32_projections:
+        vidtome_amd.update_patch(unet, fp32_projections=True)
+    if pnp:
+        blk.attn1.injection_schedule, blk.attn1.t, blk.attn1.vtm_num_inputs = [981], 981, B
+    keep = vpatch.PROJ_MODE, vpatch.FUSED_PROJ, vpatch.LIVE_QUERIES
+    if proj_mode is not None:
+        vpatch.PROJ_MODE, vpatch.FUSED_PROJ = proj_mode, proj_mode != "blas"
+    vpatch.LIVE_QUERIES = live
+    try:
+        for ck, (frames, coin) in enumerate(chunks):
+            if coin is not None:
+                unet._tome_info["args"]["global_rand"] = coin
+            h = S.synthetic_hidden(site, B, frames, LATENT, dtype, DEV, seed=50 + ck, clip_seed=7)
+            with torch.no_grad(), Spy(_lib) as spy:
+                y = vpatch.self_attention_segment(blk, h)
+            emit(out, f"{name} chunk {ck}", spy, y, blk)
+            if "anchor_maps" in spy.calls:                       # a global level ran
+                seen.add("local-is-src, compacted queries" if "compact_queries" in spy.calls else "local-is-dst")
+                if frames == 1:
+                    seen.add("single-frame chunk")
+            if any(n == "attention_kv" and kw.get("k_fold") is not None for n, kw in zip(spy.calls, spy.kwargs)) and C // 8 == 40:
+                seen.add("folded-key launch (d = 40)")
+    finally:
+        vpatch.PROJ_MODE, vpatch.FUSED_PROJ, vpatch.LIVE_QUERIES = keep
+        vidtome_amd.remove_patch(unet)
+
+
+def run_unmerged(vidtome_amd, out):
+    from vidtome_amd import _lib, patch as vpatch, sites as S
+    for name, dtype, C, f32p in (("bf16 C=640", torch.bfloat16, 640, False), ("fp32 C=320 fp32_projections", torch.float32, 320, True),
+                                 ("fp32 C=320", torch.float32, 320, False)):
+        torch.manual_seed(123)
+        unet, site, blk = site_block(vidtome_amd, S, dtype, C, 8, unmerged=True)
+        if f32p:
+            vidtome_amd.update_patch(unet, fp32_projections=True)
+        h = S.synthetic_hidden(site, B, FRAMES, LATENT, dtype, DEV, seed=50, clip_seed=7)
+        with torch.no_grad(), Spy(_lib) as spy:
+            y = vpatch.self_attention_segment(blk, h)
+        emit(out, f"unmerged/{name}", spy, y, blk)
+        vidtome_amd.remove_patch(unet)
+
+
+def run_cross(vidtome_amd, out):
+    """attn2 of a full block (C = 320, 77 text tokens of width 768): the two public bodies and the block forward."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ip_adapter_mask_standin
+    import ip_adapter_standin
+    from vidtome_amd import _lib, patch as vpatch, sites as S
+    dt, C, T = torch.float16, 320, 77
+    g = torch.Generator().manual_seed(3)
+    text = torch.randn(B * FRAMES, T, 768, generator=g).to(device=DEV, dtype=dt)
+    keep_bias = torch.arange(T)[None, :] < torch.tensor([57, 30] * FRAMES)[:, None]
+    bias = ((1 - keep_bias.to(dt)) * -10000.0).unsqueeze(1).to(DEV)
+    left, top = torch.zeros(1, 1, *LATENT, device=DEV), torch.zeros(1, 1, *LATENT, device=DEV)
+    left[..., :LATENT[1] // 2] = 1
+    top[:, :, :LATENT[0] // 2] = 1
+    keep_ff = vpatch.FF_MODE
+    try:
+        for ff_mode in ("panels", "blas"):
+            vpatch.FF_MODE = ff_mode
+            for kind in ("plain", "masked", "ip-adapter", "ip-adapter region masks"):
+                torch.manual_seed(123)
+                unet, site, blk = site_block(vidtome_amd, S, dt, C, 8, full=True)
+                enc, mask, kw = text, None, {}
+                if kind == "masked":
+                    mask = bias
+                elif kind == "ip-adapter":
+                    ip_adapter_standin.install(unet, (4, 16), (0.6, 0.3))
+                    enc = (text, ip_adapter_standin.image_states((4, 16), B * FRAMES, 768, dt, DEV))
+                elif kind == "ip-adapter region masks":
+                    ip_adapter_mask_standin.install(unet, (16, 4), (1.0, 0.6))
+                    ims = [torch.randn(B * FRAMES, 1, t, 768, generator=g).to(device=DEV, dtype=dt) for t in (16, 4)]
+                    enc, kw = (text, ims), {"ip_adapter_masks": [left, top]}
+                h = S.synthetic_hidden(site, B, FRAMES, LATENT, dt, DEV, seed=50, clip_seed=7)
+                tag = f"cross/FF_MODE={ff_mode} {kind}"
+                with torch.no_grad():
+                    for n_tok in (h.shape[1], 250):
+                        hn = h[:, :n_tok].contiguous()
+                        if kind == "ip-adapter region masks" and n_tok == 250:
+                            continue                                     # (region masks are given for the whole token grid)
+                        with Spy(_lib) as spy:
+                            y = vpatch.cross_attention(blk.attn2, vpatch.layer_norm(blk.norm2, hn), enc, mask, **kw)
+                        emit(out, f"{tag} cross_attention N={n_tok}", spy, y, blk)
+                        if isinstance(enc, tuple) and n_tok == 250:
+                            continue                                     # (the panel path of an IP-Adapter call asks N % 8 == 0)
+                        with Spy(_lib) as spy:
+                            ip = vpatch.ip_cross_call(blk.attn2, hn, enc, mask, kw) if isinstance(enc, tuple) else None
+                            y = vpatch.norm_cross_attention_residual(blk.norm2, blk.attn2, hn, None if ip else enc, ip,
+                                                                     attention_mask=mask)
+                        emit(out, f"{tag} norm_cross_attention_residual N={n_tok}", spy, y, blk)
+                    with Spy(_lib) as spy:
+                        y = blk(h, encoder_hidden_states=enc, encoder_attention_mask=mask, cross_attention_kwargs=kw or None)
+                    emit(out, f"{tag} block forward", spy, y, blk)
+                vidtome_amd.remove_patch(unet)
+    finally:
+        vpatch.FF_MODE = keep_ff
+
+
+def run_f32_blocks(vidtome_amd, out):
+    """The whole forward of an fp32 block (C = 320) with the fp32_projections opt-in (without it attn2 is the module's own
+    forward, which the site stand-ins do not have)."""
+    from vidtome_amd import _lib, sites as S
+    text = torch.randn(B * FRAMES, 77, 768, generator=torch.Generator().manual_seed(3)).to(DEV)
+    torch.manual_seed(123)
+    unet, site, blk = site_block(vidtome_amd, S, torch.float32, 320, 8, full=True)
+    vidtome_amd.update_patch(unet, fp32_projections=True)
+    h = S.synthetic_hidden(site, B, FRAMES, LATENT, torch.float32, DEV, seed=50, clip_seed=7)
+    with torch.no_grad(), Spy(_lib) as spy:
+        y = blk(h, encoder_hidden_states=text)
+    emit(out, "cross/fp32 C=320 fp32_projections block forward", spy, y, blk)
+    vidtome_amd.remove_patch(unet)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--package", default=ROOT, help="directory holding the vidtome_amd package to import")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(args.package))
+    import vidtome_amd
+    from vidtome_amd import patch as vpatch
+    assert os.path.dirname(os.path.abspath(vpatch.__file__)) == os.path.join(os.path.abspath(args.package), "vidtome_amd")
+    out, seen = [], set()
+    run_routes(vidtome_amd, out)
+    f16, f32 = torch.float16, torch.float32
+    run_chunks(vidtome_amd, out, "chunks/rows fp16 C=320", f16, 320, seen)
+    run_chunks(vidtome_amd, out, "chunks/panels fp16 C=640", f16, 640, seen)
+    run_chunks(vidtome_amd, out, "chunks/f32 C=320 fp32_projections", f32, 320, seen, fp32_projections=True)
+    run_chunks(vidtome_amd, out, "chunks/blas fp32 C=320", f32, 320, seen)
+    run_chunks(vidtome_amd, out, "chunks/blas fp16 C=320 PROJ_MODE=blas", f16, 320, seen, proj_mode="blas")
+    want = {"local-is-src, compacted queries", "local-is-dst", "folded-key launch (d = 40)", "single-frame chunk"}
+    three = ((FRAMES, None), (FRAMES, 0.0), (FRAMES, 1.0))
+    run_chunks(vidtome_amd, out, "pnp/aligned rows fp16 C=320", f16, 320, set(), pnp=True, chunks=three, align_batch=True)
+    run_chunks(vidtome_amd, out, "pnp/aligned panels fp16 C=640", f16, 640, set(), pnp=True, chunks=three, align_batch=True)
+    run_chunks(vidtome_amd, out, "pnp/unaligned rows fp16 C=320", f16, 320, set(), pnp=True, chunks=three)
+    run_chunks(vidtome_amd, out, "nolive/rows fp16 C=320", f16, 320, set(), live=False, chunks=three)
+    run_unmerged(vidtome_amd, out)
+    run_cross(vidtome_amd, out)
+    run_f32_blocks(vidtome_amd, out)
+    torch.cuda.synchronize()
+    out.append("occurred in chunks/*: " + "; ".join(sorted(seen)))
+    text = "\n".join(out) + "\n"
+    sys.stdout.write(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text)
+    if seen != want:
+        raise SystemExit(f"block_digest: did not occur: {sorted(want - seen)}")
+
+
+if __name__ == "__main__":
+    main()

@@ -408,13 +408,34 @@ def _built_before(mark, device) -> None:
 
 
 def _linear(m: torch.nn.Module, dtype=None, device=None):
-    """(weight, bias, key) of a projection the caller's predicate accepted (lora.linear_params: its own tensors, or the
-    folded ones of a LoRA layer).  Every weight / bias read of the fused path goes through here: a direct `.weight` read of
-    a LoRA wrapper would be its BASE weight and silently drop the adapter."""
+    """(contiguous weight, bias, key) of a projection the caller's predicate accepted (lora.linear_params: its own tensors,
+    or the folded ones of a LoRA layer), converted to ``dtype`` / ``device`` when given.  Every weight / bias read of the
+    fused path goes through here: a direct `.weight` read of a LoRA wrapper would be its BASE weight and silently drop the
+    adapter."""
     p = lora.linear_params(m, dtype, device)
     if p is None:
         raise RuntimeError(f"vidtome_amd: {type(m).__name__} is not a projection the fused path can read")
-    return p
+    w, b, key = p
+    return w.contiguous(), b, key
+
+
+def _apply_linear(m: torch.nn.Module, x: torch.Tensor, dtype=None) -> torch.Tensor:
+    """`m(x)` for a projection lora.linear_params reads, as a library GEMM: F.linear with its (effective) weight and bias --
+    exactly what a plain Linear's forward computes -- or with both converted to ``dtype`` (the tokens') when given."""
+    w, b, _ = _linear(m, dtype)
+    return F.linear(x, w, b)
+
+
+def _scale(attn: torch.nn.Module, C: int) -> float:
+    """The softmax scale of an attention module over C channels: its own, or head_dim ** -0.5."""
+    return getattr(attn, "scale", None) or (C // attn.heads) ** -0.5
+
+
+def _plain_layernorm(norm: torch.nn.Module, x: torch.Tensor) -> bool:
+    """A plain torch.nn.LayerNorm over the channel axis of ``x`` whose weight and bias, where present, are of the tokens'
+    dtype -- what vtm_layernorm / vtm_layernorm_panels compute.  (Each caller adds the widths and dtypes its kernel takes.)"""
+    return (type(norm) is torch.nn.LayerNorm and len(norm.normalized_shape) == 1 and norm.normalized_shape[0] == x.shape[-1]
+            and (norm.weight is None or norm.weight.dtype == x.dtype) and (norm.bias is None or norm.bias.dtype == x.dtype))
 
 
 def _fused_weights(attn: torch.nn.Module, dtype, device):
@@ -527,19 +548,68 @@ def _has_bias(lin: torch.nn.Module) -> bool:
     return lora.linear_params(lin)[1] is not None
 
 
-def fused_projections_ok(attn: torch.nn.Module, x: torch.Tensor) -> bool:
-    """The gather-fused projection GEMM (vtm_linear_rows) takes fp16 / bf16 tokens with C % 32 == 0."""
-    if not FUSED_PROJ or x.dtype not in (torch.float16, torch.bfloat16) or x.shape[-1] % 32 \
-            or not _proj_dtypes_ok(attn, x.dtype):
-        return False
-    return PROJ_MODE == "rows" or (PROJ_MODE == "auto" and x.shape[-1] <= 320)
+def _attn1_kwargs(cross_attention_kwargs) -> dict:
+    """What of ``cross_attention_kwargs`` a plain processor on attn1 gets to see.  ``ip_adapter_masks`` is read by the
+    IP-Adapter processors on attn2 alone: Diffusers' ``Attention.forward`` drops, without a word, the arguments a processor's
+    ``__call__`` does not take, and the plain processors ``fused_attention_ok`` accepts do not take it -- so region masks
+    do not send attn1 to its module forward.  (Whenever the module IS called it gets the kwargs untouched.)"""
+    return {k: v for k, v in (cross_attention_kwargs or {}).items() if k != "ip_adapter_masks"}
 
 
-def panel_projections_ok(attn: torch.nn.Module, x: torch.Tensor) -> bool:
-    """The panel-GEMM projections (vtm_gather_panels / vtm_layernorm_panels + vtm_linear_panels): fp16 / bf16 tokens,
-    C % 64 == 0, no bias on to_v (V^T = W_v X^T is computed with the roles of the operands swapped)."""
-    return (PROJ_MODE in ("auto", "panels") and x.dtype in (torch.float16, torch.bfloat16) and x.shape[-1] % 64 == 0
-            and _proj_dtypes_ok(attn, x.dtype) and not _has_bias(attn.to_v))
+def _fp32_projections(block: torch.nn.Module) -> bool:
+    """The block's ``fp32_projections`` opt-in (``update_patch(model, fp32_projections=True)``)."""
+    return getattr(block, "fp32_projections", False) is True
+
+
+def attn1_route(block: torch.nn.Module, x: torch.Tensor, encoder_hidden_states=None, attention_mask=None,
+                cross_attention_kwargs=None) -> str:
+    """How the block computes ``attn1`` on tokens like ``x`` (their device, rank, dtype and width are read).  Launches nothing
+    (but the first look at a LoRA-adapted to_v folds its adapters, lora.linear_params).
+      "module"  attn1's own forward on the materialised merged tokens, like the reference (patch.py:157-162): a masked call,
+                processor kwargs, attn1 as a cross-attention, or a module that is not the plain arithmetic
+                (``fused_attention_ok``).  SD never does the first three on attn1
+      "rows"    self_attention_rows on vtm_linear_rows: fp16 / bf16 tokens, C % 32 == 0
+      "panels"  self_attention_panels (vtm_gather_panels + vtm_linear_panels; the un-merged sites take
+                unmerged_self_attention_residual): fp16 / bf16 tokens, C % 64 == 0, no bias on to_v (V^T = W_v X^T is computed
+                with the roles of the operands swapped)
+      "f32"     self_attention_rows on vtm_linear_f32: fp32 tokens with C % 8 == 0 and the block's ``fp32_projections``
+      "blas"    self_attention: library GEMMs over materialised merged tokens
+    The three hand-written projection paths ask that all four projection weights are of the tokens' dtype."""
+    attn = block.attn1
+    if attention_mask is not None or _attn1_kwargs(cross_attention_kwargs) \
+            or (encoder_hidden_states is not None and block.only_cross_attention) or not fused_attention_ok(attn, x):
+        return "module"
+    C = x.shape[-1]
+    if x.dtype == torch.float32:
+        return "f32" if _fp32_projections(block) and C % 8 == 0 and _proj_dtypes_ok(attn, torch.float32) else "blas"
+    if not _proj_dtypes_ok(attn, x.dtype):                 # fp16 / bf16: fused_attention_ok admits no other dtype
+        return "blas"
+    if FUSED_PROJ and C % 32 == 0 and (PROJ_MODE == "rows" or (PROJ_MODE == "auto" and C <= 320)):
+        return "rows"
+    if PROJ_MODE in ("auto", "panels") and C % 64 == 0 and not _has_bias(attn.to_v):
+        return "panels"
+    return "blas"
+
+
+def _attn1_params(attn: torch.nn.Module, C: int, q_rows: Optional[torch.Tensor], aligned: bool):
+    """(heads, scale, share groups) of an attn1 call, before any device work.  Under PnP sharing every group reads the source
+    sample's q / k (and its q_count): per-sample query rows are the same rows only when the matching was aligned."""
+    share = _pnp_share_groups(attn)
+    if share != 1 and q_rows is not None and not aligned:
+        raise RuntimeError("vidtome_amd: q_rows with PnP shared probabilities need every sample of a group to have the same "
+                           "rows -- align_batch matching (pass aligned=True)")
+    return attn.heads, _scale(attn, C), share
+
+
+def _attn1_core(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, M: int, Mq: Optional[int], scale: float,
+                share: int, q_count: Optional[torch.Tensor] = None, k_fold=None) -> torch.Tensor:
+    """The attention core of attn1 over M keys: every row a query (``Mq`` None, vtm_attention), or Mq query rows of their
+    own -- the first q_count[b] of them live -- and / or folded keys (vtm_attention_kv)."""
+    if k_fold is not None:                                 # (folded keys: never under sharing)
+        return _lib.attention_kv(q, k, vt, heads, M if Mq is None else Mq, M, scale, q_count=q_count, k_fold=k_fold)
+    if Mq is None:
+        return _lib.attention(q, k, vt, heads, M, scale, share)
+    return _lib.attention_kv(q, k, vt, heads, Mq, M, scale, q_count=q_count, share_groups=share)
 
 
 def _panel_weight(lin: torch.nn.Module):
@@ -550,19 +620,18 @@ def _panel_weight(lin: torch.nn.Module):
 
 
 def self_attention_panels(attn: torch.nn.Module, x0: torch.Tensor, x1: Optional[torch.Tensor], rows: Optional[torch.Tensor],
-                          q_rows: Optional[torch.Tensor] = None, q_count: Optional[torch.Tensor] = None) -> torch.Tensor:
+                          q_rows: Optional[torch.Tensor] = None, q_count: Optional[torch.Tensor] = None,
+                          aligned: bool = False) -> torch.Tensor:
     """``attn1(merged)`` like self_attention_rows, with the projections as panel GEMMs: the merged rows (and the live-query
     rows) are gathered ONCE into the k-panel layout, sample b at rows b * Mpad (Mpad = M rounded up to 256), and
         k    = X W_k^T                     one launch over all samples  -> (B, Mpad, C)
         v^T  = W_v X_b^T                   one launch per sample, the weight as "token" operand -> (B, C, Mpad): no transpose
         q    = X_q W_q^T, out = O W_o^T + b
-    Returns (B, Mq rounded up to 256, C); rows >= Mq (or the per-sample q_count) are not meaningful."""
+    Returns (B, Mq rounded up to 256, C); rows >= Mq (or the per-sample q_count) are not meaningful.  ``aligned``: the
+    matching was align_batch's (``_attn1_params``)."""
     B, _, C = x0.shape
     M = x0.shape[1] if rows is None else rows.shape[1]
-    heads = attn.heads
-    scale = getattr(attn, "scale", None) or (C // heads) ** -0.5
-    share = _pnp_share_groups(attn)
-    # (q_rows under PnP sharing: the caller vouches that every sample of a group has the same rows -- align_batch)
+    heads, scale, share = _attn1_params(attn, C, q_rows, aligned)
     Mpad = _lib.panel_rows(M)
     xp = _lib.gather_panels(x0, x1, rows, None, M)                       # (C / 8, B * Mpad, 8)
     wq, bq = _panel_weight(attn.to_q)
@@ -573,16 +642,13 @@ def self_attention_panels(attn: torch.nn.Module, x0: torch.Tensor, x1: Optional[
     M8 = (M + 7) // 8 * 8
     for b in range(B):
         _lib.linear_panels(wv, C, xp[:, b * Mpad:(b + 1) * Mpad], M8, None, out=vt[b])
-    if q_rows is None:
-        q_op = _lib.linear_panels(xp, B * Mpad, wq, C, bq).view(B, Mpad, C)
-        o = _lib.attention(q_op, k_op, vt, heads, M, scale, share)
-        Mq, Mqpad = M, Mpad
-    else:
+    Mq, Mqpad, qp = None, Mpad, xp
+    if q_rows is not None:
         Mq = q_rows.shape[1]
         Mqpad = _lib.panel_rows(Mq)
         qp = _lib.gather_panels(x0, x1, rows, q_rows, Mq)
-        q_op = _lib.linear_panels(qp, B * Mqpad, wq, C, bq).view(B, Mqpad, C)
-        o = _lib.attention_kv(q_op, k_op, vt, heads, Mq, M, scale, q_count=q_count, share_groups=share)
+    q_op = _lib.linear_panels(qp, B * Mqpad, wq, C, bq).view(B, Mqpad, C)
+    o = _attn1_core(q_op, k_op, vt, heads, M, Mq, scale, share, q_count)
     wo, bo = _panel_weight(_out_linear(attn))
     op = _lib.to_panels(o.view(B * Mqpad, C))
     return _lib.linear_panels(op, B * Mqpad, wo, C, bo).view(B, Mqpad, C)
@@ -597,15 +663,13 @@ def unmerged_site(block: torch.nn.Module, x: torch.Tensor) -> bool:
     return downsample > info["args"]["max_downsample"]
 
 
-def unmerged_self_attention_ok(block: torch.nn.Module, x: torch.Tensor) -> bool:
-    norm, attn = block.norm1, block.attn1
+def unmerged_self_attention_ok(block: torch.nn.Module, x: torch.Tensor, route: Optional[str] = None) -> bool:
+    """``unmerged_self_attention_residual`` may run: the "panels" route (``route``: what ``attn1_route`` answered for a plain
+    attn1 call, when the caller has asked already) behind a plain norm1, without PnP sharing, at a site that does not merge."""
     # (any token count: q and k are row ranges of the dense (BF, N, 3C) projection -- the cores address a row as
     # (sample * N + row) * ld with ld % 8 == 0 -- and only V^T needs a padded row, which vtm_transpose_cols writes)
-    return (x.is_cuda and x.dim() == 3 and type(norm) is torch.nn.LayerNorm and len(norm.normalized_shape) == 1
-            and norm.normalized_shape[0] == x.shape[-1] and (norm.weight is None or norm.weight.dtype == x.dtype)
-            and (norm.bias is None or norm.bias.dtype == x.dtype) and fused_attention_ok(attn, x)
-            and panel_projections_ok(attn, x) and not fused_projections_ok(attn, x) and _pnp_share_groups(attn) == 1
-            and unmerged_site(block, x))
+    return ((route or attn1_route(block, x)) == "panels" and _plain_layernorm(block.norm1, x)
+            and _pnp_share_groups(block.attn1) == 1 and unmerged_site(block, x))
 
 
 def unmerged_self_attention_residual(block: torch.nn.Module, hidden_states: torch.Tensor) -> torch.Tensor:
@@ -615,8 +679,7 @@ def unmerged_self_attention_residual(block: torch.nn.Module, hidden_states: torc
     ``unmerged_self_attention_ok``."""
     attn, norm = block.attn1, block.norm1
     BF, N, C = hidden_states.shape
-    heads = attn.heads
-    scale = getattr(attn, "scale", None) or (C // heads) ** -0.5
+    heads, scale = attn.heads, _scale(attn, C)
     hs = hidden_states.contiguous()
     n = BF * N
 
@@ -642,131 +705,73 @@ def unmerged_self_attention_residual(block: torch.nn.Module, hidden_states: torc
 def self_attention_segment(block: torch.nn.Module, hidden_states: torch.Tensor, encoder_hidden_states=None,
                            attention_mask=None, cross_attention_kwargs=None) -> torch.Tensor:
     """patch.py:146-169 for the plain-LayerNorm block: norm1 -> compute_merge -> attn1 -> unmerge -> + residual."""
-    if (encoder_hidden_states is None or not block.only_cross_attention) and attention_mask is None \
-            and not _attn1_kwargs(cross_attention_kwargs) and unmerged_self_attention_ok(block, hidden_states):
+    route = attn1_route(block, hidden_states, encoder_hidden_states, attention_mask, cross_attention_kwargs)
+    if unmerged_self_attention_ok(block, hidden_states, route):
         return unmerged_self_attention_residual(block, hidden_states)
-    return patched_self_attention_segment(block, hidden_states, layer_norm(block.norm1, hidden_states),
-                                          encoder_hidden_states, attention_mask, cross_attention_kwargs, None)
-
-
-def _attn1_kwargs(cross_attention_kwargs) -> dict:
-    """What of ``cross_attention_kwargs`` a plain processor on attn1 gets to see.  ``ip_adapter_masks`` is read by the
-    IP-Adapter processors on attn2 alone: Diffusers' ``Attention.forward`` drops, without a word, the arguments a processor's
-    ``__call__`` does not take, and the plain processors ``fused_attention_ok`` accepts do not take it -- so region masks
-    do not send attn1 to its module forward.  (Whenever the module IS called it gets the kwargs untouched.)"""
-    return {k: v for k, v in (cross_attention_kwargs or {}).items() if k != "ip_adapter_masks"}
-
-
-def _weight(m: torch.nn.Module, dtype) -> torch.Tensor:
-    w = _linear(m)[0]
-    return w if (w.dtype == dtype and w.is_contiguous()) else w.to(dtype).contiguous()
-
-
-def _bias(m: torch.nn.Module, dtype) -> Optional[torch.Tensor]:
-    b = _linear(m)[1]
-    return None if b is None else b.to(dtype)
+    norm_hidden_states = layer_norm(block.norm1, hidden_states)
+    # (the route reads the tokens' dtype: a norm1 that changes it is routed on its output)
+    return patched_self_attention_segment(block, hidden_states, norm_hidden_states, encoder_hidden_states, attention_mask,
+                                          cross_attention_kwargs, None,
+                                          route=route if norm_hidden_states.dtype == hidden_states.dtype else None)
 
 
 def self_attention_rows(attn: torch.nn.Module, x0: torch.Tensor, x1: Optional[torch.Tensor],
                         rows: Optional[torch.Tensor], q_rows: Optional[torch.Tensor] = None,
-                        q_count: Optional[torch.Tensor] = None, plan: Optional["MergePlan"] = None) -> torch.Tensor:
+                        q_count: Optional[torch.Tensor] = None, plan: Optional["MergePlan"] = None,
+                        fp32_core: bool = False, aligned: bool = False) -> torch.Tensor:
     """``attn1(merged)`` (patch.py:157-162; arithmetic of pnp_utils.py:47-95) with ``merged[b, i] = pool[b, rows[b, i]]``
-    never materialised: every projection is a vtm_linear_rows GEMM that fetches its A rows through the composed merge
-    map (pool = x0 | x1, ``rows`` None = the rows of x0 as they are), k and v for all M rows (v channel-major, what the
-    PV contraction reads), q -- and the output projection -- only for the ``q_rows`` positions when given (the rows
-    unmerge() reads).  Returns (B, Mq rounded up to 8, C); rows >= Mq are not meaningful.
-    With a ``plan`` whose anchors carried content ids and a head dim that has spare contraction slots (40), k and v are
-    projected for the duplicate-free key list only (MergePlan.key_fold) and every key carries log2 of its multiplicity."""
+    never materialised: every projection is a GEMM that fetches its A rows through the composed merge map (pool = x0 | x1,
+    ``rows`` None = the rows of x0 as they are), k and v for all M rows (v channel-major, what the PV contraction reads),
+    q -- and the output projection -- only for the ``q_rows`` positions when given (the rows unmerge() reads).
+    Returns (B, Mq rounded up to 8, C); rows >= Mq are not meaningful.  ``aligned``: the matching was align_batch's
+    (``_attn1_params``).
+    fp16 / bf16 tokens: vtm_linear_rows.  With a ``plan`` whose anchors carried content ids and a head dim that has spare
+    contraction slots (40), k and v are projected for the duplicate-free key list only (MergePlan.key_fold) and every key
+    carries log2 of its multiplicity.
+    fp32 tokens (the block's ``fp32_projections``): vtm_linear_f32, which writes q / k / V^T in fp32 for the fp32 core
+    (``fp32_core``, the block's ``fp32_attention``) or rounds them once to fp16 at its store for the fp16 core; the output
+    projection reads the core's output as fp32.  fp32 keys are never folded."""
     B, _, C = x0.shape
     M = x0.shape[1] if rows is None else rows.shape[1]
-    Mp = (M + 7) // 8 * 8
-    heads = attn.heads
-    scale = getattr(attn, "scale", None) or (C // heads) ** -0.5
-    share = _pnp_share_groups(attn)
-    # (q_rows under PnP sharing: the caller vouches that every sample of a group has the same rows -- align_batch)
+    heads, scale, share = _attn1_params(attn, C, q_rows, aligned)
     dt = x0.dtype
+    f32 = dt == torch.float32
+    gemm, out_kw = _lib.linear_rows, {}
+    if f32:
+        gemm, out_kw = _lib.linear_f32, {"out_dtype": torch.float32 if fp32_core else torch.float16}
     wqk, bqk = _fused_weights(attn, dt, x0.device)
-    bv = _bias(attn.to_v, dt)
+    wv, bv, _ = _linear(attn.to_v, dt)
     fold = None
-    if plan is not None and rows is not None and share == 1 and (C // heads) in (8, 40):
+    if not f32 and plan is not None and rows is not None and share == 1 and (C // heads) in (8, 40):
         fold = plan.key_fold(dt)
+    key_sel = k_fold = None
     if fold is not None:
         key_sel, k_bias, k_count = fold
-        vt = _lib.linear_rows(x0, x1, rows, key_sel, M, _weight(attn.to_v, dt), bv, transposed=True)
-        k_op = _lib.linear_rows(x0, x1, rows, key_sel, M, wqk[C:], None if bqk is None else bqk[C:])
+        k_fold = (k_count, k_bias)
+    vt = gemm(x0, x1, rows, key_sel, M, wv, bv, transposed=True, **out_kw)                         # (B, C, Mp)
+    if q_rows is None and fold is None:
+        Mq = M
+        qk = gemm(x0, x1, rows, None, M, wqk, bqk, **out_kw)                                       # (B, Mp, 2C): q | k
+        o = _attn1_core(qk[:, :, :C], qk[:, :, C:], vt, heads, M, None, scale, share)
+    else:
         Mq = M if q_rows is None else q_rows.shape[1]
-        q_op = _lib.linear_rows(x0, x1, rows, q_rows, Mq, wqk[:C], None if bqk is None else bqk[:C])
-        o = _lib.attention_kv(q_op, k_op, vt, heads, Mq, M, scale, q_count=q_count, k_fold=(k_count, k_bias))
-        to_out = _out_linear(attn)
-        return _lib.linear_rows(o, None, None, None, Mq, _weight(to_out, dt), _bias(to_out, dt))
-    vt = _lib.linear_rows(x0, x1, rows, None, M, _weight(attn.to_v, dt), bv, transposed=True)     # (B, C, Mp)
-    if q_rows is None:
-        qk = _lib.linear_rows(x0, x1, rows, None, M, wqk, bqk)                                   # (B, Mp, 2C): q | k
-        o = _lib.attention(qk[:, :, :C], qk[:, :, C:], vt, heads, M, scale, share)
-        Mq = M
-    else:
-        Mq = q_rows.shape[1]
-        k_op = _lib.linear_rows(x0, x1, rows, None, M, wqk[C:], None if bqk is None else bqk[C:])
-        q_op = _lib.linear_rows(x0, x1, rows, q_rows, Mq, wqk[:C], None if bqk is None else bqk[:C])
-        o = _lib.attention_kv(q_op, k_op, vt, heads, Mq, M, scale, q_count=q_count, share_groups=share)
-    to_out = _out_linear(attn)
-    return _lib.linear_rows(o, None, None, None, Mq, _weight(to_out, dt), _bias(to_out, dt))
-
-
-def _fp32_projections(block: torch.nn.Module) -> bool:
-    """The block's ``fp32_projections`` opt-in (``update_patch(model, fp32_projections=True)``)."""
-    return getattr(block, "fp32_projections", False) is True
-
-
-def f32_projections_ok(attn: torch.nn.Module, x: torch.Tensor) -> bool:
-    """attn1's projections as fp32 GEMMs (vtm_linear_f32): fp32 tokens with C % 8 == 0 and all four projection weights
-    (and the biases that exist) fp32.  The caller has checked ``fused_attention_ok`` and the block's opt-in."""
-    return x.is_cuda and x.dtype == torch.float32 and x.shape[-1] % 8 == 0 and _proj_dtypes_ok(attn, torch.float32)
-
-
-def self_attention_f32(attn: torch.nn.Module, x0: torch.Tensor, x1: Optional[torch.Tensor], rows: Optional[torch.Tensor],
-                       q_rows: Optional[torch.Tensor] = None, q_count: Optional[torch.Tensor] = None,
-                       fp32_core: bool = False) -> torch.Tensor:
-    """``attn1(merged)`` of an fp32 model like self_attention_rows: every projection is a vtm_linear_f32 GEMM whose A rows
-    are fetched through the composed merge map (``rows`` None = the rows of x0 as they are: the un-merged sites), q | k for
-    all M rows (or q for the ``q_rows`` positions only), V^T channel-major.  q / k / V^T are written in fp32 for the fp32
-    core (``fp32_core``, the block's ``fp32_attention``) or rounded once to fp16 at the GEMM's store for the fp16 core; the
-    output projection reads the core's output as fp32.  Keys are never folded (fp32 keys never are).
-    Returns (B, Mq rounded up to 8, C) fp32; rows >= Mq are not meaningful."""
-    B, _, C = x0.shape
-    M = x0.shape[1] if rows is None else rows.shape[1]
-    heads = attn.heads
-    scale = getattr(attn, "scale", None) or (C // heads) ** -0.5
-    share = _pnp_share_groups(attn)
-    # (q_rows under PnP sharing: the caller vouches that every sample of a group has the same rows -- align_batch)
-    f32 = torch.float32
-    core = f32 if fp32_core else torch.float16
-    wqk, bqk = _fused_weights(attn, f32, x0.device)
-    vt = _lib.linear_f32(x0, x1, rows, None, M, _weight(attn.to_v, f32), _bias(attn.to_v, f32), out_dtype=core,
-                         transposed=True)                                                      # (B, C, Mp)
-    if q_rows is None:
-        qk = _lib.linear_f32(x0, x1, rows, None, M, wqk, bqk, out_dtype=core)                   # (B, Mp, 2C): q | k
-        o = _lib.attention(qk[:, :, :C], qk[:, :, C:], vt, heads, M, scale, share)
-        Mq = M
-    else:
-        Mq = q_rows.shape[1]
-        k_op = _lib.linear_f32(x0, x1, rows, None, M, wqk[C:], None if bqk is None else bqk[C:], out_dtype=core)
-        q_op = _lib.linear_f32(x0, x1, rows, q_rows, Mq, wqk[:C], None if bqk is None else bqk[:C], out_dtype=core)
-        o = _lib.attention_kv(q_op, k_op, vt, heads, Mq, M, scale, q_count=q_count, share_groups=share)
-    to_out = _out_linear(attn)
-    return _lib.linear_f32(o.float(), None, None, None, Mq, _weight(to_out, f32), _bias(to_out, f32))
+        k_op = gemm(x0, x1, rows, key_sel, M, wqk[C:], None if bqk is None else bqk[C:], **out_kw)
+        q_op = gemm(x0, x1, rows, q_rows, Mq, wqk[:C], None if bqk is None else bqk[:C], **out_kw)
+        o = _attn1_core(q_op, k_op, vt, heads, M, Mq, scale, share, q_count, k_fold)
+    wo, bo, _ = _linear(_out_linear(attn), dt)
+    return gemm(o.float() if f32 else o, None, None, None, Mq, wo, bo)
 
 
 def self_attention(attn: torch.nn.Module, x: torch.Tensor, M: Optional[int] = None,
                    q_rows: Optional[torch.Tensor] = None, q_count: Optional[torch.Tensor] = None,
-                   fp32_core: bool = False) -> torch.Tensor:
+                   fp32_core: bool = False, aligned: bool = False) -> torch.Tensor:
     """``attn1(x)`` for self-attention without mask (patch.py:157-162), arithmetic of pnp_utils.py:47-95:
     q,k,v projections -> softmax(q k^T * scale) v per head -> to_out[0] (+ dropout(0)), on MATERIALISED tokens with
     library GEMMs (torch -> hipBLASLt) for the projections: the path of fp32 models, of channel counts the
     gather-fused GEMM does not take, and of VIDTOME_PROJ=blas (see self_attention_rows for the default).
     x is (B, Mp, C) whose first M rows per sample are the sequence.  With ``q_rows`` (B, Mq) only those rows act
     as queries (every row stays a key / value) and the result is (B, Mq rounded up to 8, C) in q_rows order.
-    The caller has checked ``fused_attention_ok(attn, x)``.
+    The caller has checked ``fused_attention_ok(attn, x)``.  ``aligned``: the matching was align_batch's (``_attn1_params``).
 
     fp16 / bf16 models run everything in their dtype.  fp32 models keep the four projections in fp32 and by default only
     the attention core's operands (q, k, v^T) are rounded to fp16 for the MFMA (fp32 accumulation, fp32 softmax): the
@@ -775,10 +780,7 @@ def self_attention(attn: torch.nn.Module, x: torch.Tensor, M: Optional[int] = No
     MFMA (csrc/attention_f32.hip), about 16x the matrix time of the fp16 core; the flag means nothing to 16-bit models."""
     B, Mp, C = x.shape
     M = Mp if M is None else M
-    heads = attn.heads
-    scale = getattr(attn, "scale", None) or (C // heads) ** -0.5
-    share = _pnp_share_groups(attn)
-    # (q_rows under PnP sharing: the caller vouches that every sample of a group has the same rows -- align_batch)
+    heads, scale, share = _attn1_params(attn, C, q_rows, aligned)
     if x.shape[1] % 8:
         # keep the transposed V (B, C, Mp) 16-byte aligned per row
         pad = 8 - x.shape[1] % 8
@@ -812,12 +814,9 @@ def self_attention(attn: torch.nn.Module, x: torch.Tensor, M: Optional[int] = No
     if bv is not None:
         vt = vt + bv[None, :, None]
     vt = vt.to(core)
-    if q_rows is None:
-        o = _lib.attention(q_op, k_op, vt, heads, M, scale, share)
-    else:
-        o = _lib.attention_kv(q_op, k_op, vt, heads, q_rows.shape[1], M, scale, q_count=q_count, share_groups=share)
-        # (q_count: rows past the count are undefined; the output projection is row-wise, so they stay confined to
-        # rows unmerge() never reads)
+    # (q_count: rows past the count are undefined; the output projection is row-wise, so they stay confined to
+    # rows unmerge() never reads)
+    o = _attn1_core(q_op, k_op, vt, heads, M, None if q_rows is None else q_rows.shape[1], scale, share, q_count)
     o = o.to(x.dtype)
     wo, bo, _ = _linear(_out_linear(attn), o.dtype)
     return F.linear(o, wo, bo)
@@ -838,8 +837,8 @@ def _cross_kv(to_k: torch.nn.Module, to_v: torch.nn.Module, enc: torch.Tensor, C
         if panels:
             _warn_once("lib-cross-kv", f"vidtome_amd: attn2's k / v projections run as library GEMMs (conditioning width "
                                        f"{D} is not a multiple of 64, or to_k / to_v are not of the tokens' dtype)")
-        k = _apply_linear(to_k, enc)
-        vt = _apply_linear(to_v, enc).transpose(1, 2).contiguous()
+        k = _apply_linear(to_k, enc, dt)
+        vt = _apply_linear(to_v, enc, dt).transpose(1, 2).contiguous()
     return k, vt
 
 
@@ -925,8 +924,7 @@ def norm_cross_attention_residual(norm: torch.nn.Module, attn: torch.nn.Module, 
     With ``attention_mask`` (the plain case only; ``fused_cross_ok`` has accepted its form, ``key_bias``) the core is
     vtm_attention_kv_bias; everything around it is the same."""
     B, N, C = hidden_states.shape
-    heads = attn.heads
-    scale = getattr(attn, "scale", None) or (C // heads) ** -0.5
+    heads, scale = attn.heads, _scale(attn, C)
     dt = hidden_states.dtype
     hs = hidden_states.contiguous()
     n = B * N
@@ -947,12 +945,6 @@ def norm_cross_attention_residual(norm: torch.nn.Module, attn: torch.nn.Module, 
     return _lib.linear_panels(op, n, wo, C, bo, resid=hs.view(n, C)).view(B, N, C)
 
 
-def _apply_linear(m: torch.nn.Module, t: torch.Tensor) -> torch.Tensor:
-    """The projection as a library GEMM in the tokens' dtype."""
-    w, b, _ = _linear(m, t.dtype)
-    return F.linear(t, w, b)
-
-
 def fused_cross_ok(norm: torch.nn.Module, attn: torch.nn.Module, x: torch.Tensor, encoder_hidden_states,
                    attention_mask, kwargs, processors=_PLAIN_PROCESSORS) -> bool:
     # (an IP-Adapter block hands a TUPLE as encoder_hidden_states: not a tensor, not this path -- see ip_cross_call)
@@ -960,10 +952,8 @@ def fused_cross_ok(norm: torch.nn.Module, attn: torch.nn.Module, x: torch.Tensor
     return (FF_MODE == "panels" and isinstance(encoder_hidden_states, torch.Tensor) and not kwargs
             and encoder_hidden_states.dim() == 3 and x.dim() == 3 and x.is_cuda and x.dtype in (torch.float16, torch.bfloat16)
             and (attention_mask is None or _key_bias_ok(attention_mask, x.shape[0], encoder_hidden_states.shape[1], x.device))
-            and type(norm) is torch.nn.LayerNorm and len(norm.normalized_shape) == 1
-            and norm.normalized_shape[0] == x.shape[-1] and x.shape[-1] % 64 == 0
-            and (norm.weight is None or norm.weight.dtype == x.dtype) and (norm.bias is None or norm.bias.dtype == x.dtype)
-            and _proj_dtypes_ok(attn, x.dtype) and fused_attention_ok(attn, x, self_attn=False, processors=processors))
+            and _plain_layernorm(norm, x) and x.shape[-1] % 64 == 0 and _proj_dtypes_ok(attn, x.dtype)
+            and fused_attention_ok(attn, x, self_attn=False, processors=processors))
 
 
 def ip_cross_call(attn: torch.nn.Module, x: torch.Tensor, encoder_hidden_states, attention_mask, kwargs,
@@ -988,10 +978,7 @@ def ip_cross_call(attn: torch.nn.Module, x: torch.Tensor, encoder_hidden_states,
 
 def _f32_layernorm_ok(norm: torch.nn.Module, x: torch.Tensor) -> bool:
     """A plain LayerNorm over the channel axis of fp32 tokens that vtm_layernorm takes."""
-    return (type(norm) is torch.nn.LayerNorm and len(norm.normalized_shape) == 1 and norm.normalized_shape[0] == x.shape[-1]
-            and x.shape[-1] % 8 == 0 and x.shape[-1] <= 2048
-            and (norm.weight is None or norm.weight.dtype == torch.float32)
-            and (norm.bias is None or norm.bias.dtype == torch.float32))
+    return x.dtype == torch.float32 and _plain_layernorm(norm, x) and x.shape[-1] % 8 == 0 and x.shape[-1] <= 2048
 
 
 def f32_cross_ok(block: torch.nn.Module, norm: torch.nn.Module, attn: torch.nn.Module, x: torch.Tensor,
@@ -1011,20 +998,17 @@ def norm_cross_attention_f32(norm: torch.nn.Module, attn: torch.nn.Module, hidde
     attention core (whatever ``fp32_attention`` says: the module forward it replaces is fp32, and 77 keys keep it cheap)
     and the output GEMM with the residual add in its epilogue.  The caller has checked ``f32_cross_ok``."""
     B, N, C = hidden_states.shape
-    heads = attn.heads
-    scale = getattr(attn, "scale", None) or (C // heads) ** -0.5
+    heads, scale = attn.heads, _scale(attn, C)
     f32 = torch.float32
     hs = hidden_states.contiguous()
     enc = encoder_hidden_states.to(f32).contiguous()
     Mk = enc.shape[1]
     xn = _lib.layernorm(hs, norm.weight, norm.bias, norm.eps)
-    q = _lib.linear_f32(xn, None, None, None, N, _weight(attn.to_q, f32), _bias(attn.to_q, f32))          # (B, N8, C)
-    k = _lib.linear_f32(enc, None, None, None, Mk, _weight(attn.to_k, f32), _bias(attn.to_k, f32))        # (B, Mkp, C)
-    vt = _lib.linear_f32(enc, None, None, None, Mk, _weight(attn.to_v, f32), _bias(attn.to_v, f32),
-                         transposed=True)                                                                  # (B, C, Mkp)
+    q = _lib.linear_f32(xn, None, None, None, N, *_linear(attn.to_q, f32)[:2])                             # (B, N8, C)
+    k = _lib.linear_f32(enc, None, None, None, Mk, *_linear(attn.to_k, f32)[:2])                           # (B, Mkp, C)
+    vt = _lib.linear_f32(enc, None, None, None, Mk, *_linear(attn.to_v, f32)[:2], transposed=True)         # (B, C, Mkp)
     o = _lib.attention_kv(q, k, vt, heads, N, Mk, scale)
-    to_out = _out_linear(attn)
-    return _lib.linear_f32(o, None, None, None, N, _weight(to_out, f32), _bias(to_out, f32), epilogue="resid", resid=hs,
+    return _lib.linear_f32(o, None, None, None, N, *_linear(_out_linear(attn), f32)[:2], epilogue="resid", resid=hs,
                            out=torch.empty_like(hs))
 
 
@@ -1039,33 +1023,25 @@ def cross_attention(attn: torch.nn.Module, x: torch.Tensor, encoder_hidden_state
              and encoder_hidden_states.dim() == 3 and x.dtype in (torch.float16, torch.bfloat16)
              and fused_attention_ok(attn, x, self_attn=False)
              and (attention_mask is None or _key_bias_ok(attention_mask, x.shape[0], encoder_hidden_states.shape[1], x.device)))
-    if not plain:
-        ip = ip_cross_call(attn, x, encoder_hidden_states, attention_mask, kwargs)
-        if ip is None:
-            return attn(x, encoder_hidden_states=encoder_hidden_states, attention_mask=attention_mask, **kwargs)
-        B, N, C = x.shape
-        scale = getattr(attn, "scale", None) or (C // attn.heads) ** -0.5
-        xq = F.pad(x, (0, 0, 0, -N % 8)) if N % 8 else x
-        o = _ip_core(attn, ip, _apply_linear(attn.to_q, xq), N, scale, False)
-        return _apply_linear(_out_linear(attn), o)[:, :N]
+    ip = None if plain else ip_cross_call(attn, x, encoder_hidden_states, attention_mask, kwargs)
+    if not plain and ip is None:
+        return attn(x, encoder_hidden_states=encoder_hidden_states, attention_mask=attention_mask, **kwargs)
     B, N, C = x.shape
-    enc = encoder_hidden_states.to(x.dtype)
-    Mk = enc.shape[1]
-    heads = attn.heads
-    scale = getattr(attn, "scale", None) or (C // heads) ** -0.5
-    Np, Mkp = (N + 7) // 8 * 8, (Mk + 7) // 8 * 8
-    if Np != N:
-        x = F.pad(x, (0, 0, 0, Np - N))
-    if Mkp != Mk:
-        enc = F.pad(enc, (0, 0, 0, Mkp - Mk))
-    q = _apply_linear(attn.to_q, x)
-    k = _apply_linear(attn.to_k, enc)
-    vt = _apply_linear(attn.to_v, enc).transpose(1, 2).contiguous()     # (B, C, Mkp): 77 keys, negligible
-    if attention_mask is None:
-        o = _lib.attention_kv(q, k, vt, heads, N, Mk, scale)
+    heads, scale = attn.heads, _scale(attn, C)
+    xq = F.pad(x, (0, 0, 0, -N % 8)) if N % 8 else x
+    q = _apply_linear(attn.to_q, xq, x.dtype)
+    if ip is not None:
+        o = _ip_core(attn, ip, q, N, scale, False)
     else:
-        o = _lib.attention_kv_bias(q, k, vt, heads, N, Mk, scale, key_bias(attention_mask, B, Mk, x.device))
-    return _apply_linear(_out_linear(attn), o)[:, :N]
+        Mk = encoder_hidden_states.shape[1]
+        enc = _pad_keys(encoder_hidden_states, x.dtype)
+        k = _apply_linear(attn.to_k, enc, x.dtype)
+        vt = _apply_linear(attn.to_v, enc, x.dtype).transpose(1, 2).contiguous()     # (B, C, Mkp): 77 keys, negligible
+        if attention_mask is None:
+            o = _lib.attention_kv(q, k, vt, heads, N, Mk, scale)
+        else:
+            o = _lib.attention_kv_bias(q, k, vt, heads, N, Mk, scale, key_bias(attention_mask, B, Mk, x.device))
+    return _apply_linear(_out_linear(attn), o, o.dtype)[:, :N]
 
 
 # ----------------------------------------------------------------------------------------------------
@@ -1103,15 +1079,13 @@ def fused_ff_ok(norm: torch.nn.Module, ff: torch.nn.Module, x: torch.Tensor) -> 
     if FF_MODE != "panels" or not x.is_cuda or x.dtype not in (torch.float16, torch.bfloat16):
         return False
     lin = _geglu_ff(ff)
-    if lin is None or type(norm) is not torch.nn.LayerNorm or len(norm.normalized_shape) != 1:
+    if lin is None or not _plain_layernorm(norm, x):
         return False
     proj, out = (lora.base_linear(m) for m in lin)
     C = x.shape[-1]
     D = proj.out_features // 2
-    return (norm.normalized_shape[0] == C and C % 64 == 0 and C <= 2048 and proj.in_features == C and D % 64 == 0
-            and out.in_features == D and out.out_features == C and proj.weight.dtype == x.dtype
-            and out.weight.dtype == x.dtype and (norm.weight is None or norm.weight.dtype == x.dtype)
-            and (norm.bias is None or norm.bias.dtype == x.dtype))
+    return (C % 64 == 0 and C <= 2048 and proj.in_features == C and D % 64 == 0 and out.in_features == D
+            and out.out_features == C and proj.weight.dtype == x.dtype and out.weight.dtype == x.dtype)
 
 
 def norm_feed_forward_residual(norm: torch.nn.Module, ff: torch.nn.Module, hidden_states: torch.Tensor) -> torch.Tensor:
@@ -1162,8 +1136,8 @@ def norm_feed_forward_f32(norm: torch.nn.Module, ff: torch.nn.Module, hidden_sta
     hs = hidden_states.contiguous()
     n = hs.numel() // C
     xn = _lib.layernorm(hs, norm.weight, norm.bias, norm.eps).view(1, n, C)
-    h = _lib.linear_f32(xn, None, None, None, n, _weight(proj, f32), _bias(proj, f32), epilogue="geglu")   # (1, n8, D)
-    y = _lib.linear_f32(h, None, None, None, n, _weight(out, f32), _bias(out, f32), epilogue="resid", resid=hs.view(1, n, C),
+    h = _lib.linear_f32(xn, None, None, None, n, *_linear(proj, f32)[:2], epilogue="geglu")               # (1, n8, D)
+    y = _lib.linear_f32(h, None, None, None, n, *_linear(out, f32)[:2], epilogue="resid", resid=hs.view(1, n, C),
                         out=torch.empty((1, n, C), dtype=f32, device=hs.device))
     return y.view(hidden_states.shape)
 
@@ -1172,20 +1146,12 @@ def feed_forward(ff: torch.nn.Module, x: torch.Tensor) -> torch.Tensor:
     """`self.ff(norm_hidden_states)` (patch.py:192).  The Diffusers feed-forward of SD blocks is
     [GEGLU(proj: Linear C -> 8C), Dropout, Linear 4C -> C]; when that shape is recognised the gated activation
     runs as vtm_geglu (the two Linears stay library GEMMs), otherwise the module runs unchanged."""
-    net = getattr(ff, "net", None)
-    if (net is not None and len(net) == 3 and net[0].__class__.__name__ == "GEGLU" and hasattr(net[0], "proj")
-            and _readable_linear(net[0].proj) and _readable_linear(net[2]) and x.is_cuda and not ff.training
-            and x.dtype in (torch.float16, torch.bfloat16, torch.float32)
-            and lora.base_linear(net[0].proj).out_features % 16 == 0):
-        return _linear_call(net[2], _lib.geglu(_linear_call(net[0].proj, x)))
+    lin = _geglu_ff(ff)
+    # (not in training: stricter than _geglu_ff's own dropout clause, which is then true whatever the Dropout's p)
+    if (lin is not None and not ff.training and x.is_cuda and x.dtype in (torch.float16, torch.bfloat16, torch.float32)
+            and lora.base_linear(lin[0]).out_features % 16 == 0):
+        return _apply_linear(lin[1], _lib.geglu(_apply_linear(lin[0], x)))
     return ff(x)
-
-
-def _linear_call(m: torch.nn.Module, x: torch.Tensor) -> torch.Tensor:
-    """`m(x)` for a projection lora.linear_params reads: F.linear with its (effective) weight and bias, which is exactly
-    what a plain Linear's forward computes."""
-    w, b, _ = _linear(m)
-    return F.linear(x, w, b)
 
 
 # ----------------------------------------------------------------------------------------------------
@@ -1193,52 +1159,46 @@ def _linear_call(m: torch.nn.Module, x: torch.Tensor) -> torch.Tensor:
 # ----------------------------------------------------------------------------------------------------
 def patched_self_attention_segment(block: torch.nn.Module, hidden_states: torch.Tensor,
                                    norm_hidden_states: torch.Tensor, encoder_hidden_states=None,
-                                   attention_mask=None, cross_attention_kwargs=None, gate_msa=None
-                                   ) -> torch.Tensor:
-    """patch.py:148-169: compute_merge -> attn1(merged) -> unmerge -> + residual."""
+                                   attention_mask=None, cross_attention_kwargs=None, gate_msa=None,
+                                   route: Optional[str] = None) -> torch.Tensor:
+    """patch.py:148-169: compute_merge -> attn1(merged) -> unmerge -> + residual.  ``route``: what ``attn1_route`` answered
+    for this call, when the caller has asked already."""
     cross_attention_kwargs = cross_attention_kwargs if cross_attention_kwargs is not None else {}
-    custom = encoder_hidden_states is not None and block.only_cross_attention
-    fused = not (custom or attention_mask is not None or _attn1_kwargs(cross_attention_kwargs)) \
-        and fused_attention_ok(block.attn1, norm_hidden_states)
-    by_rows = fused and fused_projections_ok(block.attn1, norm_hidden_states)
-    by_panels = fused and not by_rows and panel_projections_ok(block.attn1, norm_hidden_states)
-    by_f32 = fused and _fp32_projections(block) and f32_projections_ok(block.attn1, norm_hidden_states)
-    m_a, u_a, merged = compute_merge(block, norm_hidden_states, block._tome_info,
-                                     materialize=not (by_rows or by_panels or by_f32))
+    if route is None:
+        route = attn1_route(block, norm_hidden_states, encoder_hidden_states, attention_mask, cross_attention_kwargs)
+    # ("module" and "blas" read the merged tokens; the other routes' projections gather through the map)
+    m_a, u_a, merged = compute_merge(block, norm_hidden_states, block._tome_info, materialize=route in ("module", "blas"))
     plan = getattr(m_a, "plan", None)
-    if not fused:
+    attn = block.attn1
+    if route == "module":
         # not the hot path (SD never masks self-attention nor makes attn1 a cross-attention; LoRA'd / custom
         # attention modules are not the plain arithmetic): run the module's own attention on the merged tokens
         # exactly as the reference does
         M = plan.M if plan is not None else merged.shape[1]
-        attn_output = block.attn1(merged[:, :M],
-                                  encoder_hidden_states=encoder_hidden_states if block.only_cross_attention else None,
-                                  attention_mask=attention_mask, **cross_attention_kwargs)
+        attn_output = attn(merged[:, :M],
+                           encoder_hidden_states=encoder_hidden_states if block.only_cross_attention else None,
+                           attention_mask=attention_mask, **cross_attention_kwargs)
     else:
         # (PnP injection reads the source sample's q for every group: the live rows must be the same rows in every sample,
         # which align_batch guarantees -- the levels' indices are computed once on the batch-folded tokens, merge.py:73-76)
+        aligned = plan is not None and plan.aligned
         live = (plan is not None and plan.q_rows is not None and gate_msa is None and LIVE_QUERIES
-                and (_pnp_share_groups(block.attn1) == 1 or plan.aligned))
+                and (_pnp_share_groups(attn) == 1 or aligned))
         q_rows = plan.q_rows if live else None
         q_count = plan.q_count if live else None
-        if by_f32:                                                        # fp32 model with fp32_projections
-            fp32_core = getattr(block, "fp32_attention", False)
-            if plan is None:
-                attn_output = self_attention_f32(block.attn1, norm_hidden_states.contiguous(), None, None,
-                                                 fp32_core=fp32_core)
-            else:
-                attn_output = self_attention_f32(block.attn1, plan.x_joined, plan.anchors_in, plan.gather_map, q_rows,
-                                                 q_count, fp32_core=fp32_core)
-        elif by_rows or by_panels:
-            sa = self_attention_rows if by_rows else self_attention_panels
-            if plan is None:                                              # block does not merge: per-frame attention
-                attn_output = sa(block.attn1, norm_hidden_states.contiguous(), None, None)
-            else:
-                attn_output = sa(block.attn1, plan.x_joined, plan.anchors_in, plan.gather_map, q_rows, q_count,
-                                 **({"plan": plan} if by_rows else {}))
+        fp32_core = getattr(block, "fp32_attention", False)
+        if route == "blas":
+            attn_output = self_attention(attn, merged, plan.M if plan is not None else None, q_rows, q_count,
+                                         fp32_core=fp32_core, aligned=aligned)
         else:
-            attn_output = self_attention(block.attn1, merged, plan.M if plan is not None else None, q_rows, q_count,
-                                         fp32_core=getattr(block, "fp32_attention", False))
+            # the pool the projections gather from (block does not merge: per-frame attention on the tokens as they are)
+            pool = (norm_hidden_states.contiguous(), None, None) if plan is None else \
+                (plan.x_joined, plan.anchors_in, plan.gather_map)
+            if route == "panels":
+                attn_output = self_attention_panels(attn, *pool, q_rows, q_count, aligned=aligned)
+            else:                                                         # "rows", "f32": the tokens' dtype says which
+                attn_output = self_attention_rows(attn, *pool, q_rows, q_count, plan=plan, fp32_core=fp32_core,
+                                                  aligned=aligned)
         if live:
             # rows are the chunk's local merged tokens: unmerge with the local levels' map alone
             # (= the global level's unmerge, merge.py:439-460, folded into the choice of queries)
@@ -1258,11 +1218,8 @@ def layer_norm(norm: torch.nn.Module, x: torch.Tensor) -> torch.Tensor:
     """`self.norm1(hidden_states)` (patch.py:146; also norm2 / norm3, patch.py:173-176, 187): a plain
     torch.nn.LayerNorm over the channel axis runs as vtm_layernorm; anything else (AdaLayerNorm variants,
     unusual shapes) is the module's own business."""
-    if (type(norm) is torch.nn.LayerNorm and x.is_cuda and len(norm.normalized_shape) == 1
-            and x.shape[-1] == norm.normalized_shape[0] and x.shape[-1] % 8 == 0 and x.shape[-1] <= 2048
-            and x.dtype in (torch.float16, torch.bfloat16, torch.float32)
-            and (norm.weight is None or norm.weight.dtype == x.dtype)
-            and (norm.bias is None or norm.bias.dtype == x.dtype)):
+    if (_plain_layernorm(norm, x) and x.is_cuda and x.shape[-1] % 8 == 0 and x.shape[-1] <= 2048
+            and x.dtype in (torch.float16, torch.bfloat16, torch.float32)):
         return _lib.layernorm(x, norm.weight, norm.bias, norm.eps)
     return norm(x)
 
