@@ -447,6 +447,24 @@ int vtm_attention_kv_bias(const void *q, int64_t ldq, const void *k, int64_t ldk
                           int64_t Mk, int64_t Mkp, int64_t d, float scale, const float *bias, int64_t ld_bias,
                           int64_t bias_batch_stride, vtm_stream_t stream);
 
+/* vtm_attention_probs -- the head-averaged PROBABILITIES of the `self.attn2(...)` call of vidtome/patch.py:178-183, the
+ * "cross-attention map" that zero-shot video editing reads (LocalBlend-style masks, per-word maps), in fp32:
+ *     out[b, i, j] = (1 / h) * sum_head softmax_j(q[b, i, head] . k[b, j, head] * scale + bias[b * bias_batch_stride + j])
+ * for i < Mq, j < Mk.  q, ldq, k, ldk, dtype, B, h, Mq, Mqp, Mk, Mkp, d, scale exactly as for vtm_attention_kv_bias (heads
+ * interleaved on the channel axis, rows addressed as (b * Mp + i) * ld, ld a multiple of 8, key rows >= Mk never read; Mkp
+ * may be any count >= Mk); q and k 16-byte aligned.  There is no V operand.  bias: a DEVICE pointer to fp32 as for
+ * vtm_attention_kv_bias (ld_bias >= Mk, bias_batch_stride 0 or >= ld_bias), or NULL for none (ld_bias and
+ * bias_batch_stride are then not read; the bits are those of a zero bias).  A bias of -inf gives probability exactly 0; a
+ * sample whose keys are ALL -inf gives NaN for that sample only.  out: fp32, rows of ldo >= Mk elements, sample b at
+ * b * Mq * ldo; rows >= Mq and columns >= Mk are not written.  Limits: dtype VTM_F16 or VTM_BF16, d as for vtm_attention,
+ * 1 <= Mk <= 256 (77-token prompts and 154- / 231-token weighted prompts), h <= 40 (the per-head softmax statistics of a
+ * workgroup's 128 query rows live in LDS), scale > 0.  Deterministic: one launch, no atomics, no workspace and no
+ * (B, h, Mq, Mk) intermediate; the heads are summed in ascending order in fp32 and multiplied by 1 / h once.  On a bad
+ * argument nothing is launched and out is untouched. */
+int vtm_attention_probs(const void *q, int64_t ldq, const void *k, int64_t ldk, float *out, int64_t ldo, int dtype,
+                        int64_t B, int64_t h, int64_t Mq, int64_t Mqp, int64_t Mk, int64_t Mkp, int64_t d, float scale,
+                        const float *bias, int64_t ld_bias, int64_t bias_batch_stride, vtm_stream_t stream);
+
 /* vtm_attention_kv with a DEVICE-side query bound: sample b only has q_count[b] <= Mq meaningful query rows (the
  * compacted live queries of vtm_compact_queries); query blocks that start at or beyond the count exit at once, rows
  * beyond it are not meaningful.  The launch is sized for the host-known bound Mq -- no host round trip. */

@@ -6,5 +6,7 @@ Everything executes in libvidtome_hip.so (hand-written HIP for gfx950); there is
 """
 from . import merge, patch
 from .patch import apply_patch, remove_patch, update_patch, collect_from_patch
+from .maps import register_attention_maps, unregister_attention_maps
 
-__all__ = ["merge", "patch", "apply_patch", "remove_patch", "update_patch", "collect_from_patch"]
+__all__ = ["merge", "patch", "apply_patch", "remove_patch", "update_patch", "collect_from_patch",
+           "register_attention_maps", "unregister_attention_maps"]

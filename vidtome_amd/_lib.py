@@ -25,6 +25,7 @@ LIB_PATH = os.environ.get("VIDTOME_HIP_LIB") or os.path.join(_HERE, "lib", "libv
 
 VTM_F32, VTM_F16, VTM_BF16 = 0, 1, 2
 ROW_PAD, K_PAD = 256, 32
+PROBS_MAX_KEYS, PROBS_MAX_HEADS = 256, 40   # what vtm_attention_probs takes (csrc/attention_probs.hip)
 
 _DT = {torch.float32: VTM_F32, torch.float16: VTM_F16, torch.bfloat16: VTM_BF16}
 
@@ -82,6 +83,8 @@ _SIGNATURES = {
                                       ctypes.POINTER(_int), _vp, _i64, _i64, _vp], _int),
     "vtm_attention_kv_bias": ([_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                _f32, _vp, _i64, _i64, _vp], _int),
+    "vtm_attention_probs": ([_vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _vp, _i64,
+                             _i64, _vp], _int),
     "vtm_attention_kv_bounded": ([_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                   _f32, _vp, _vp, ctypes.c_size_t, _vp], _int),
     "vtm_attention_kv_shared_bounded": ([_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
@@ -883,6 +886,44 @@ def attention_kv_bias(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads:
     _check(lib().vtm_attention_kv_bias(q.data_ptr(), q.stride(1), k.data_ptr(), k.stride(1), vt.data_ptr(), vt.stride(1),
                                        out.data_ptr(), C, dtype_code(q), B, heads, Mq, Mqp, Mk, Mkp, d, float(scale),
                                        bias.data_ptr(), bias.shape[1], batch_stride, _stream()), "vtm_attention_kv_bias")
+    return out
+
+
+@_on_device
+def attention_probs(q: torch.Tensor, k: torch.Tensor, heads: int, Mq: int, Mk: int, scale: float,
+                    bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The head-averaged probabilities of the cross-attention core (vtm_attention_probs): q (B, Mqp, C) and k (B, Mkp, C)
+    views contiguous along the last axis as for attention_kv_bias, fp16 / bf16; ``bias`` None or what attention_kv_bias
+    takes.  Returns mean_head softmax(q K^T * scale + bias) of the first Mq query rows and Mk <= 256 keys, a new
+    (B, Mq, Mk) float32 tensor.  No V operand, no (B, heads, Mq, Mk) intermediate; deterministic."""
+    if not isinstance(q, torch.Tensor) or not isinstance(k, torch.Tensor) or q.dtype not in (torch.float16, torch.bfloat16) \
+            or k.dtype != q.dtype:
+        raise RuntimeError("attention_probs: q and k must share one of fp16 / bf16")
+    if q.dim() != 3 or k.dim() != 3 or not q.is_cuda or k.device != q.device:
+        raise RuntimeError("attention_probs: q must be (B, Mqp, C) and k (B, Mkp, C) on one GPU")
+    B, Mqp, C = q.shape
+    Mkp = k.shape[1]
+    heads, Mq, Mk = int(heads), int(Mq), int(Mk)
+    if k.shape[0] != B or k.shape[2] != C or heads < 1 or C % heads:
+        raise RuntimeError("attention_probs: k must be (B, Mkp, C) with C a multiple of heads")
+    if not (1 <= Mq <= Mqp and 1 <= Mk <= Mkp):
+        raise RuntimeError("attention_probs: Mq / Mk must lie inside q / k")
+    for t, name, rows in ((q, "q", Mqp), (k, "k", Mkp)):
+        if t.stride(2) != 1 or t.stride(1) % 8 or t.stride(1) < C or t.stride(0) != rows * t.stride(1) or t.data_ptr() % 16:
+            raise RuntimeError(f"attention_probs: {name} must be 16-byte aligned rows (stride a multiple of 8), dense over "
+                               "the samples")
+    if bias is not None and (
+            not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or bias.device != q.device or bias.dim() != 2
+            or bias.shape[0] not in (1, B) or bias.shape[1] < Mk or bias.stride(1) != 1
+            or (bias.shape[0] == B and B > 1 and 0 < bias.stride(0) < bias.shape[1])):   # (stride 0: an expanded row)
+        raise RuntimeError("attention_probs: bias must be None or fp32 on q's device, (B, >= Mk) or (1, >= Mk), contiguous "
+                           "along its last axis")
+    out = torch.empty((B, Mq, Mk), dtype=torch.float32, device=q.device)
+    ld_bias = 0 if bias is None else bias.shape[1]
+    batch_stride = bias.stride(0) if bias is not None and bias.shape[0] == B and B > 1 else 0
+    _check(lib().vtm_attention_probs(q.data_ptr(), q.stride(1), k.data_ptr(), k.stride(1), out.data_ptr(), Mk, dtype_code(q),
+                                     B, heads, Mq, Mqp, Mk, Mkp, C // heads, float(scale), _ptr(bias), ld_bias, batch_stride,
+                                     _stream()), "vtm_attention_probs")
     return out
 
 

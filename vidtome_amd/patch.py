@@ -882,11 +882,15 @@ def _ip_key_sets(attn: torch.nn.Module, ip: "ip_adapter.Call", dt, C: int, panel
     return k, vt, sets, rows, table
 
 
-def _ip_core(attn: torch.nn.Module, ip: "ip_adapter.Call", q: torch.Tensor, N: int, scale: float, panels: bool) -> torch.Tensor:
+def _ip_core(attn: torch.nn.Module, ip: "ip_adapter.Call", q: torch.Tensor, N: int, scale: float, panels: bool,
+             probs_to: Optional[torch.nn.Module] = None) -> torch.Tensor:
     """The decoupled cross-attention of an IP-Adapter call on query tokens q (B, Np, C), N <= Np of them meaningful: ONE
     launch over the text keys and every adapter's image keys -- vtm_attention_kv_sets, or vtm_attention_kv_sets_masked when
-    the call carries region masks."""
+    the call carries region masks.  ``probs_to``: a registered block gets the map of the TEXT set, with its own softmax --
+    k rows [0, text length) of the buffer."""
     k, vt, sets, rows, table = _ip_key_sets(attn, ip, q.dtype, q.shape[-1], panels)
+    if probs_to is not None:
+        probs_to.attn2_probs = _probs_rows(q, k, attn.heads, N, ip.text.shape[1], scale)
     if table is None:
         return _lib.attention_kv_sets(q, k, vt, attn.heads, N, sets, scale)
     return _lib.attention_kv_sets_masked(q, k, vt, attn.heads, N, sets, scale, rows, table)
@@ -910,9 +914,63 @@ def key_bias(attention_mask, B: int, Mk: int, device=None) -> Optional[torch.Ten
     return attention_mask[:, 0].to(torch.float32).contiguous()
 
 
+def _probs_torch(q: torch.Tensor, k: torch.Tensor, heads: int, scale: float, bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """The torch restatement of vtm_attention_probs on q (B, N, C) / k (B, Mk, C) rows of any dtype: fp32 scores, base-e
+    softmax, the heads summed in ascending order and divided by their number; bias as ``key_bias`` gives it."""
+    B, N, C = q.shape
+    d = C // heads
+    acc = torch.zeros((B, N, k.shape[1]), dtype=torch.float32, device=q.device)
+    for h in range(heads):
+        s = torch.matmul(q[:, :, h * d:(h + 1) * d].float(), k[:, :, h * d:(h + 1) * d].float().transpose(1, 2)) * scale
+        if bias is not None:
+            s = s + bias[:, None, :]
+        acc += torch.softmax(s, dim=-1)
+    return acc / heads
+
+
+def _probs_rows(q: torch.Tensor, k: torch.Tensor, heads: int, N: int, Mk: int, scale: float,
+                bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The head-averaged probabilities (B, N, Mk) fp32 of a fused attn2 call from the q (B, >= N, C) / k (B, >= Mk, C) rows
+    its core reads: one vtm_attention_probs launch for what the kernel takes (16-bit rows, Mk <= 256, at most 40 heads),
+    else the torch restatement on the same rows."""
+    with torch.no_grad():
+        if q.dtype in (torch.float16, torch.bfloat16) and Mk <= _lib.PROBS_MAX_KEYS and heads <= _lib.PROBS_MAX_HEADS:
+            return _lib.attention_probs(q, k, heads, N, Mk, scale, bias)
+        return _probs_torch(q[:, :N], k[:, :Mk], heads, scale, bias)
+
+
+def _module_path_probs(attn: torch.nn.Module, x: torch.Tensor, encoder_hidden_states, attention_mask) -> Optional[torch.Tensor]:
+    """The map of an attn2 call that ran as the module's own forward (a custom processor, an AdaLayerNorm block, ...): to_q /
+    to_k through lora.linear_params on the module's own inputs, in the tokens' dtype as the module computes them, then the
+    torch restatement.  An IP-Adapter tuple gives the map of its text set.  None (one warning) when the projections are
+    not readable, something stands between them and the scores (norm_cross, norm_q / norm_k, ...) or the mask is not of
+    ``key_bias``'s form; never raises."""
+    try:
+        enc = encoder_hidden_states[0] if isinstance(encoder_hidden_states, tuple) and encoder_hidden_states \
+            else encoder_hidden_states
+        ok = (isinstance(enc, torch.Tensor) and enc.dim() == 3 and x.dim() == 3 and enc.shape[0] == x.shape[0]
+              and all(hasattr(attn, a) for a in ("to_q", "to_k", "heads"))
+              and _readable_linear(attn.to_q) and _readable_linear(attn.to_k)
+              and not any(getattr(attn, a, None) is not None for a in ("group_norm", "spatial_norm", "norm_cross", "norm_q", "norm_k"))
+              and lora.base_linear(attn.to_q).out_features % attn.heads == 0
+              and (attention_mask is None or _key_bias_ok(attention_mask, x.shape[0], enc.shape[1], x.device)))
+        if ok:
+            with torch.no_grad():
+                q = _apply_linear(attn.to_q, x, x.dtype)
+                k = _apply_linear(attn.to_k, enc.to(x.dtype), x.dtype)
+                bias = None if attention_mask is None else key_bias(attention_mask, x.shape[0], enc.shape[1], x.device)
+                return _probs_torch(q, k, attn.heads, _scale(attn, q.shape[-1]), bias)
+    except Exception as e:   # (a forward never fails for its map)
+        _warn_once("maps-failed", f"vidtome_amd: attn2_probs is None: the map of a module-path attn2 call failed ({e})")
+        return None
+    _warn_once("maps-unreadable", "vidtome_amd: attn2_probs is None for an attn2 call on the module path whose to_q / to_k "
+                                  "are not plain projections onto the scores, or whose mask is not an additive (B, 1, K) row")
+    return None
+
+
 def norm_cross_attention_residual(norm: torch.nn.Module, attn: torch.nn.Module, hidden_states: torch.Tensor,
                                   encoder_hidden_states: torch.Tensor, ip: Optional["ip_adapter.Call"] = None,
-                                  attention_mask=None) -> torch.Tensor:
+                                  attention_mask=None, probs_to: Optional[torch.nn.Module] = None) -> torch.Tensor:
     """patch.py:171-185 for the plain case: ``attn2(norm2(hidden_states), encoder_hidden_states) + hidden_states`` with the
     query projection as a panel GEMM fed by the LayerNorm (vtm_layernorm_panels -> vtm_linear_panels: the normalised
     tokens are only ever read by to_q, so they are written once, as panels), k / v^T of the (few) conditioning tokens by the
@@ -922,7 +980,9 @@ def norm_cross_attention_residual(norm: torch.nn.Module, attn: torch.nn.Module, 
     vtm_attention_kv_sets launch over the text keys and every adapter's image keys, or with region masks ONE
     vtm_attention_kv_sets_masked launch (``_ip_core``).
     With ``attention_mask`` (the plain case only; ``fused_cross_ok`` has accepted its form, ``key_bias``) the core is
-    vtm_attention_kv_bias; everything around it is the same."""
+    vtm_attention_kv_bias; everything around it is the same.
+    With ``probs_to`` (a block registered by ``maps.register_attention_maps``) one vtm_attention_probs launch beside the core
+    leaves ``probs_to.attn2_probs`` from the same q / k rows (an IP-Adapter call: the text set's); nothing else changes."""
     B, N, C = hidden_states.shape
     heads, scale = attn.heads, _scale(attn, C)
     dt = hidden_states.dtype
@@ -935,12 +995,15 @@ def norm_cross_attention_residual(norm: torch.nn.Module, attn: torch.nn.Module, 
     if ip is None:
         Mk = encoder_hidden_states.shape[1]
         k, vt = _cross_kv(attn.to_k, attn.to_v, _pad_keys(encoder_hidden_states, dt), C)
-        if attention_mask is None:
+        bias = None if attention_mask is None else key_bias(attention_mask, B, Mk, hs.device)
+        if bias is None:
             o = _lib.attention_kv(q, k, vt, heads, N, Mk, scale)
         else:
-            o = _lib.attention_kv_bias(q, k, vt, heads, N, Mk, scale, key_bias(attention_mask, B, Mk, hs.device))
+            o = _lib.attention_kv_bias(q, k, vt, heads, N, Mk, scale, bias)
+        if probs_to is not None:
+            probs_to.attn2_probs = _probs_rows(q, k, heads, N, Mk, scale, bias)
     else:
-        o = _ip_core(attn, ip, q, N, scale, True)
+        o = _ip_core(attn, ip, q, N, scale, True, probs_to)
     op = _lib.to_panels(o.view(n, C))
     return _lib.linear_panels(op, n, wo, C, bo, resid=hs.view(n, C)).view(B, N, C)
 
@@ -992,7 +1055,7 @@ def f32_cross_ok(block: torch.nn.Module, norm: torch.nn.Module, attn: torch.nn.M
 
 
 def norm_cross_attention_f32(norm: torch.nn.Module, attn: torch.nn.Module, hidden_states: torch.Tensor,
-                             encoder_hidden_states: torch.Tensor) -> torch.Tensor:
+                             encoder_hidden_states: torch.Tensor, probs_to: Optional[torch.nn.Module] = None) -> torch.Tensor:
     """patch.py:171-185 for an fp32 block with ``fp32_projections``: ``attn2(norm2(h), encoder_hidden_states) + h`` as
     vtm_layernorm, the q GEMM, the k / V^T GEMMs of the conditioning tokens (padded to a multiple of 8 rows), the fp32
     attention core (whatever ``fp32_attention`` says: the module forward it replaces is fp32, and 77 keys keep it cheap)
@@ -1008,39 +1071,47 @@ def norm_cross_attention_f32(norm: torch.nn.Module, attn: torch.nn.Module, hidde
     k = _lib.linear_f32(enc, None, None, None, Mk, *_linear(attn.to_k, f32)[:2])                           # (B, Mkp, C)
     vt = _lib.linear_f32(enc, None, None, None, Mk, *_linear(attn.to_v, f32)[:2], transposed=True)         # (B, C, Mkp)
     o = _lib.attention_kv(q, k, vt, heads, N, Mk, scale)
+    if probs_to is not None:                                  # (fp32 rows: the torch restatement)
+        probs_to.attn2_probs = _probs_rows(q, k, heads, N, Mk, scale)
     return _lib.linear_f32(o, None, None, None, N, *_linear(_out_linear(attn), f32)[:2], epilogue="resid", resid=hs,
                            out=torch.empty_like(hs))
 
 
 def cross_attention(attn: torch.nn.Module, x: torch.Tensor, encoder_hidden_states: Optional[torch.Tensor],
-                    attention_mask=None, **kwargs) -> torch.Tensor:
+                    attention_mask=None, probs_to: Optional[torch.nn.Module] = None, **kwargs) -> torch.Tensor:
     """`self.attn2(norm_hidden_states, encoder_hidden_states=..., attention_mask=...)` (patch.py:178-183) -- the
     un-merged tokens attending to the conditioning (77 text tokens in SD).  The plain case (projection Linears, no
     mask, no processor kwargs) runs on vtm_attention_kv, the plain case with a per-key additive mask (``key_bias``) on
     vtm_attention_kv_bias, a recognised IP-Adapter call (``ip_cross_call``) on vtm_attention_kv_sets (with region masks:
-    vtm_attention_kv_sets_masked), with library GEMMs around the core; everything else is the module's own forward."""
+    vtm_attention_kv_sets_masked), with library GEMMs around the core; everything else is the module's own forward.
+    ``probs_to``: a registered block gets ``attn2_probs`` on whichever of these paths the call takes."""
     plain = (isinstance(encoder_hidden_states, torch.Tensor) and not kwargs
              and encoder_hidden_states.dim() == 3 and x.dtype in (torch.float16, torch.bfloat16)
              and fused_attention_ok(attn, x, self_attn=False)
              and (attention_mask is None or _key_bias_ok(attention_mask, x.shape[0], encoder_hidden_states.shape[1], x.device)))
     ip = None if plain else ip_cross_call(attn, x, encoder_hidden_states, attention_mask, kwargs)
     if not plain and ip is None:
+        if probs_to is not None:
+            probs_to.attn2_probs = _module_path_probs(attn, x, encoder_hidden_states, attention_mask)
         return attn(x, encoder_hidden_states=encoder_hidden_states, attention_mask=attention_mask, **kwargs)
     B, N, C = x.shape
     heads, scale = attn.heads, _scale(attn, C)
     xq = F.pad(x, (0, 0, 0, -N % 8)) if N % 8 else x
     q = _apply_linear(attn.to_q, xq, x.dtype)
     if ip is not None:
-        o = _ip_core(attn, ip, q, N, scale, False)
+        o = _ip_core(attn, ip, q, N, scale, False, probs_to)
     else:
         Mk = encoder_hidden_states.shape[1]
         enc = _pad_keys(encoder_hidden_states, x.dtype)
         k = _apply_linear(attn.to_k, enc, x.dtype)
         vt = _apply_linear(attn.to_v, enc, x.dtype).transpose(1, 2).contiguous()     # (B, C, Mkp): 77 keys, negligible
-        if attention_mask is None:
+        bias = None if attention_mask is None else key_bias(attention_mask, B, Mk, x.device)
+        if bias is None:
             o = _lib.attention_kv(q, k, vt, heads, N, Mk, scale)
         else:
-            o = _lib.attention_kv_bias(q, k, vt, heads, N, Mk, scale, key_bias(attention_mask, B, Mk, x.device))
+            o = _lib.attention_kv_bias(q, k, vt, heads, N, Mk, scale, bias)
+        if probs_to is not None:
+            probs_to.attn2_probs = _probs_rows(q, k, heads, N, Mk, scale, bias)
     return _apply_linear(_out_linear(attn), o, o.dtype)[:, :N]
 
 
@@ -1253,31 +1324,37 @@ def make_diffusers_tome_block(block_class: Type[torch.nn.Module]) -> Type[torch.
 
             cross_attention_kwargs = cross_attention_kwargs if cross_attention_kwargs is not None else {}
             if self.attn2 is not None:                                             # patch.py:171-185
+                maps = self if getattr(self, "vtm_attention_maps", False) else None   # maps.register_attention_maps
                 ip = None if self.use_ada_layer_norm else ip_cross_call(
                     self.attn2, hidden_states, encoder_hidden_states, encoder_attention_mask, cross_attention_kwargs,
                     self.norm2)
                 if ip is not None:                                                 # IP-Adapter: text + image key sets
-                    hidden_states = norm_cross_attention_residual(self.norm2, self.attn2, hidden_states, None, ip)
+                    hidden_states = norm_cross_attention_residual(self.norm2, self.attn2, hidden_states, None, ip,
+                                                                  probs_to=maps)
                 elif not self.use_ada_layer_norm and fused_cross_ok(self.norm2, self.attn2, hidden_states,
                                                                     encoder_hidden_states, encoder_attention_mask,
                                                                     cross_attention_kwargs):
                     hidden_states = norm_cross_attention_residual(self.norm2, self.attn2, hidden_states,
                                                                   encoder_hidden_states,
-                                                                  attention_mask=encoder_attention_mask)
+                                                                  attention_mask=encoder_attention_mask, probs_to=maps)
                 elif not self.use_ada_layer_norm and f32_cross_ok(self, self.norm2, self.attn2, hidden_states,
                                                                   encoder_hidden_states, encoder_attention_mask,
                                                                   cross_attention_kwargs):
-                    hidden_states = norm_cross_attention_f32(self.norm2, self.attn2, hidden_states, encoder_hidden_states)
+                    hidden_states = norm_cross_attention_f32(self.norm2, self.attn2, hidden_states, encoder_hidden_states,
+                                                             probs_to=maps)
                 else:
                     norm_hidden_states = (self.norm2(hidden_states, timestep) if self.use_ada_layer_norm
                                           else layer_norm(self.norm2, hidden_states))
                     if self.use_ada_layer_norm and encoder_attention_mask is not None:
                         # AdaLayerNorm blocks keep the module's own forward for a masked call, whatever the mask's form
+                        if maps is not None:
+                            self.attn2_probs = _module_path_probs(self.attn2, norm_hidden_states, encoder_hidden_states,
+                                                                  encoder_attention_mask)
                         attn_output = self.attn2(norm_hidden_states, encoder_hidden_states=encoder_hidden_states,
                                                  attention_mask=encoder_attention_mask, **cross_attention_kwargs)
                     else:
                         attn_output = cross_attention(self.attn2, norm_hidden_states, encoder_hidden_states,
-                                                      encoder_attention_mask, **cross_attention_kwargs)
+                                                      encoder_attention_mask, probs_to=maps, **cross_attention_kwargs)
                     hidden_states = attn_output + hidden_states
 
             if not self.use_ada_layer_norm_zero and fused_ff_ok(self.norm3, self.ff, hidden_states):   # patch.py:187-199
@@ -1421,6 +1498,8 @@ def remove_patch(model: torch.nn.Module):
             module.__dict__.pop("_vtm_match_plans", None)      # the matcher's launch planners (pinned 32-byte buffers)
             module.__dict__.pop("fp32_attention", None)        # update_patch's opt-in: a later apply_patch starts without it
             module.__dict__.pop("fp32_projections", None)      # (likewise)
+            module.__dict__.pop("vtm_attention_maps", None)    # maps.register_attention_maps' switch ...
+            module.__dict__.pop("attn2_probs", None)           # ... and the map of the block's last forward
     _lib.release_workspaces()            # the cached scratch buffers of the patched path (re-created on demand)
     return roots[-1]                     # the reference returns its loop variable: the last tree walked
 
