@@ -430,6 +430,43 @@ int vtm_attention_kv_sets_masked(const void *q, int64_t ldq, const void *k, int6
                                  const int64_t *set_len, const float *set_weight, const int *set_mask, const float *mask,
                                  int64_t ld_mask, int64_t mask_batch_stride, vtm_stream_t stream);
 
+/* vtm_attention_kv_sets_src -- the same sum with a second QUERY operand: chosen sets take their probabilities from the
+ * queries of ANOTHER sample.  What Prompt-to-Prompt's cross-attention control (word swap, refinement, re-weighting) turns
+ * the `self.attn2(...)` call of vidtome/patch.py:178-183 into once the edit is folded into the value operand
+ * (vtm_cross_edit_values): one softmax of the edited sample is the source sample's.  Per head
+ *     out[b, i] = sum_{s < n_sets} w_s * softmax_{j in set s}(Q_s[b, i] . k[b, j] * scale) v[b, j]
+ *     Q_s = set_src[s] ? q_src : q
+ * All arguments of vtm_attention_kv_sets (same layouts, alignment rules, n_sets <= 8, scale > 0, VTM_F16 / VTM_BF16 only,
+ * every head dim of vtm_attention), then: q_src, a DEVICE pointer to (B, Mqp_src >= Mq, .) query rows of the same dtype
+ * and head layout, row (b * Mqp_src + i) * ldq_src, 16-byte aligned, ldq_src a multiple of 8 (it may be another sample
+ * range of the buffer q points into); set_src, n_sets HOST ints, each 0 (the set reads q) or 1 (it reads q_src).  k, vt and
+ * out are indexed by b alone: the keys a q_src set meets are sample b's.  With every set_src[s] == 0 the call IS
+ * vtm_attention_kv_sets (the same kernel; q_src is not looked at), and with q_src == q it gives that call's bits.  One
+ * launch, no workspace.  Rows >= Mq of out are not written.  On a bad argument nothing is launched and out is untouched. */
+int vtm_attention_kv_sets_src(const void *q, int64_t ldq, const void *q_src, int64_t ldq_src, int64_t Mqp_src,
+                              const void *k, int64_t ldk, const void *vt, int64_t ldvt, void *out, int64_t ldo, int dtype,
+                              int64_t B, int64_t h, int64_t Mq, int64_t Mqp, int64_t Mkp, int64_t d, float scale,
+                              int n_sets, const int64_t *set_start, const int64_t *set_len, const float *set_weight,
+                              const int *set_src, vtm_stream_t stream);
+
+/* vtm_cross_edit_values -- the value operand of a Prompt-to-Prompt edited cross-attention call.  The edit replaces the
+ * probabilities of query i by  P_edit[i, n] = a[n] * sum_w P_src[i, w] M[w, n] + b[n] * P_own[i, n]  (M = mapper, a = src_w,
+ * b = own_w: word swap, refinement, re-weighting and the cross_replace_alpha blend are all of this form); it is linear in
+ * the probabilities, so  P_edit V = P_src (M diag(a) V) + P_own (diag(b) V)  and this entry writes the two operands:
+ *     vt_out[b, c, start_src + w] = round_dtype( sum_{n < K} (M[w, n] * a[n]) * V[b, n, c] )
+ *     vt_out[b, c, start_own + n] = round_dtype( b[n] * V[b, n, c] )
+ * with V[b, n, c] = vt[b, c, v_start + n].  vt (B, C, ldvt) and vt_out (B, C, ldvt_out) are channel-major like every V^T of
+ * this library; mapper (K, K) row-major, src_w (K) and own_w (K) are DEVICE pointers to fp32.  The sum is an fp32 fmaf
+ * chain over n ascending from +0 whose multiplier M[w, n] * a[n] is rounded to fp32 first; the own range is one fp32
+ * product; each is rounded to the dtype once.  start_src and start_own are multiples of 8 (a key set of
+ * vtm_attention_kv_sets_src starts on one); the ranges [start_src, start_src + K) and [start_own, start_own + K) must not
+ * overlap and must lie inside ldvt_out; columns outside them are not written.  vt_out may not overlap vt.  1 <= K <= 256
+ * (the limit of vtm_attention_probs), dtype VTM_F16 or VTM_BF16.  One launch, deterministic (no atomics), no workspace.
+ * On a bad argument nothing is launched and vt_out is untouched. */
+int vtm_cross_edit_values(const void *vt, int64_t ldvt, int64_t v_start, int dtype, int64_t B, int64_t C, int64_t K,
+                          const float *mapper, const float *src_w, const float *own_w, void *vt_out, int64_t ldvt_out,
+                          int64_t start_src, int64_t start_own, vtm_stream_t stream);
+
 /* vtm_attention_kv_bias -- the cross-attention core with one additive fp32 term PER KEY on the scores: what an
  * `encoder_attention_mask` turns the `self.attn2(...)` call of vidtome/patch.py:178-183 into (Diffusers' UNet hands the
  * (B, K) mask of a padded prompt on as an additive (B, 1, K) row of 0 / -10000).  Per head

@@ -7,6 +7,8 @@ Everything executes in libvidtome_hip.so (hand-written HIP for gfx950); there is
 from . import merge, patch
 from .patch import apply_patch, remove_patch, update_patch, collect_from_patch
 from .maps import register_attention_maps, unregister_attention_maps
+from .p2p import CrossEdit, register_cross_attention_control, unregister_cross_attention_control
 
 __all__ = ["merge", "patch", "apply_patch", "remove_patch", "update_patch", "collect_from_patch",
-           "register_attention_maps", "unregister_attention_maps"]
+           "register_attention_maps", "unregister_attention_maps",
+           "CrossEdit", "register_cross_attention_control", "unregister_cross_attention_control"]

@@ -81,6 +81,10 @@ _SIGNATURES = {
     "vtm_attention_kv_sets_masked": ([_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _f32,
                                       _int, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_f32),
                                       ctypes.POINTER(_int), _vp, _i64, _i64, _vp], _int),
+    "vtm_attention_kv_sets_src": ([_vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64,
+                                   _i64, _f32, _int, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_f32),
+                                   ctypes.POINTER(_int), _vp], _int),
+    "vtm_cross_edit_values": ([_vp, _i64, _i64, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp], _int),
     "vtm_attention_kv_bias": ([_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                _f32, _vp, _i64, _i64, _vp], _int),
     "vtm_attention_probs": ([_vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _vp, _i64,
@@ -708,14 +712,18 @@ def layernorm(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[to
 @_on_device
 def attention_kv(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, Mq: int, Mk: int, scale: float,
                  use_workspace: bool = True, q_count: Optional[torch.Tensor] = None,
-                 k_fold: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, share_groups: int = 1) -> torch.Tensor:
+                 k_fold: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, share_groups: int = 1,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Cross-attention core (patch.py:178-183): q (B, Mqp, C), k (B, Mkp, C) views contiguous along the last axis,
     vt (B, C, ldvt >= Mk) = v transposed.  Returns (B, Mqp, C).  ``q_count`` (B,) int32 on the device: only the first
     q_count[b] query rows of sample b are meaningful (compact_queries); the other rows of the result are undefined.
     ``k_fold`` = (k_count (B,) int32, k_bias (B, >= Mk) uint32 pairs) from fold_keys: k / vt hold a duplicate-free key
     list, only the first k_count[b] entries are keys, each standing for 2^bias identical ones (head dims 8 and 40).
     ``share_groups`` > 1: the probabilities of the first B / share_groups samples serve every group (pnp_utils.py:57-67);
-    with ``q_count`` the caller vouches that every sample of a group has the same live rows (align_batch) -- no key folding."""
+    with ``q_count`` the caller vouches that every sample of a group has the same live rows (align_batch) -- no key folding.
+    ``out``: a dense (B, Mqp, C) tensor of q's dtype to write into (a sample range of a larger buffer) instead of a new one."""
+    if out is not None and (out.shape != q.shape or out.dtype != q.dtype or out.device != q.device or not out.is_contiguous()):
+        raise RuntimeError("attention_kv: out must be a contiguous tensor of q's shape, dtype and device")
     if share_groups != 1 and k_fold is not None:
         raise RuntimeError("attention_kv: shared probabilities do not go with folded keys")
     if k_fold is not None and q.dtype == torch.float32:
@@ -723,7 +731,8 @@ def attention_kv(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int,
     B, Mqp, C = q.shape
     Mkp = k.shape[1]
     d = C // heads
-    out = _attention_out(q, k, vt, Mq, Mkp)
+    new = _attention_out(q, k, vt, Mq, Mkp, alloc=out is None)
+    out = new if out is None else out
     ws, nb = _attention_ws(B, heads, Mq, Mk, d, q.device, q.dtype) if use_workspace else (None, 0)
     if q_count is not None and (q_count.dtype != torch.int32 or q_count.numel() != B or not q_count.is_cuda):
         raise RuntimeError("attention_kv: q_count must be a (B,) int32 device tensor")
@@ -857,6 +866,85 @@ def attention_kv_sets_masked(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor,
                                               vt.stride(1), out.data_ptr(), C, dtype_code(q), B, heads, Mq, Mqp, Mkp, d,
                                               float(scale), n, starts, lens, weights, (_int * n)(*rows), mask.data_ptr(), ld,
                                               R * ld if mask.dim() == 3 else 0, _stream()), "vtm_attention_kv_sets_masked")
+    return out
+
+
+@_on_device
+def attention_kv_sets_src(q: torch.Tensor, q_src: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, Mq: int, sets,
+                          scale: float, set_src, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """attention_kv_sets with a second query operand (vtm_attention_kv_sets_src): set s takes its probabilities from
+    ``q_src`` (B, Mqp_src >= Mq, C) where ``set_src[s]`` is 1 and from ``q`` where it is 0; k, vt and the result belong to
+    q's samples.  q_src is a view like q (contiguous along the last axis, dense batch stride, 16-byte aligned rows) and may
+    be another sample range of q's buffer.  ``out``: a dense (B, Mqp, C) tensor to write into (rows >= Mq stay as they are)
+    instead of a new one.  With every ``set_src[s] == 0`` this IS attention_kv_sets' launch (the library sends it to the
+    same kernel)."""
+    sets = [(int(s), int(n), float(w)) for s, n, w in sets]
+    src = [int(s) for s in set_src]
+    if len(src) != len(sets):
+        raise RuntimeError(f"attention_kv_sets_src: {len(sets)} sets but {len(src)} set_src entries")
+    if not 1 <= len(sets) <= MAX_KEY_SETS:
+        raise RuntimeError(f"attention_kv_sets_src: 1 .. {MAX_KEY_SETS} key sets, got {len(sets)}")
+    if any(s not in (0, 1) for s in src):
+        raise RuntimeError(f"attention_kv_sets_src: set_src entries are 0 (q) or 1 (q_src), got {src}")
+    if q.dtype not in (torch.float16, torch.bfloat16) or k.dtype != q.dtype or vt.dtype != q.dtype:
+        raise RuntimeError("attention_kv_sets_src: q, k and vt must share one of fp16 / bf16")
+    B, Mqp, C = q.shape
+    Mkp = k.shape[1]
+    d = C // heads
+    _attention_out(q, k, vt, Mq, Mkp, alloc=False)
+    if k.shape[0] != B or vt.shape[0] != B or k.shape[2] != C or vt.shape[1] != C:
+        raise RuntimeError("attention_kv_sets_src: k must be (B, Mkp, C) and vt (B, C, ldvt)")
+    if not isinstance(q_src, torch.Tensor) or q_src.dtype != q.dtype or q_src.device != q.device or q_src.dim() != 3 \
+            or q_src.shape[0] != B or q_src.shape[2] != C or q_src.shape[1] < Mq or q_src.stride(2) != 1 \
+            or q_src.stride(1) % 8 or q_src.stride(0) != q_src.shape[1] * q_src.stride(1) or q_src.data_ptr() % 16:
+        raise RuntimeError("attention_kv_sets_src: q_src must be (B, >= Mq, C) of q's dtype on q's device, 16-byte aligned "
+                           "rows (stride a multiple of 8), dense over the samples")
+    if out is None:
+        out = _attention_out(q, k, vt, Mq, Mkp)
+    elif out.shape != q.shape or out.dtype != q.dtype or out.device != q.device or not out.is_contiguous():
+        raise RuntimeError("attention_kv_sets_src: out must be a contiguous tensor of q's shape, dtype and device")
+    n = len(sets)
+    starts = (_i64 * n)(*[s for s, _, _ in sets])
+    lens = (_i64 * n)(*[m for _, m, _ in sets])
+    weights = (_f32 * n)(*[w for _, _, w in sets])
+    _check(lib().vtm_attention_kv_sets_src(q.data_ptr(), q.stride(1), q_src.data_ptr(), q_src.stride(1), q_src.shape[1],
+                                           k.data_ptr(), k.stride(1), vt.data_ptr(), vt.stride(1), out.data_ptr(), C,
+                                           dtype_code(q), B, heads, Mq, Mqp, Mkp, d, float(scale), n, starts, lens, weights,
+                                           (_int * n)(*src), _stream()), "vtm_attention_kv_sets_src")
+    return out
+
+
+CROSS_EDIT_MAX_KEYS = 256   # what vtm_cross_edit_values takes (csrc/cross_edit.hip): vtm_attention_probs' key limit
+
+
+@_on_device
+def cross_edit_values(vt: torch.Tensor, v_start: int, K: int, mapper: torch.Tensor, src_w: torch.Tensor, own_w: torch.Tensor,
+                      start_src: int = 0, start_own: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The value operand of an edited cross-attention call (vtm_cross_edit_values): vt (B, C, ldvt) = v transposed, fp16 /
+    bf16, whose columns [v_start, v_start + K) are the keys; ``mapper`` (K, K), ``src_w`` (K,), ``own_w`` (K,) contiguous
+    fp32 on vt's device.  Writes (mapper diag(src_w) V)^T to columns [start_src, start_src + K) and (diag(own_w) V)^T to
+    [start_own, start_own + K) of ``out`` (B, C, ldvt_out) and returns it; a new ``out`` has start_own + K rounded up to 8
+    columns and zeros outside the two ranges.  start_own defaults to start_src + K rounded up to 8."""
+    v_start, K, start_src = int(v_start), int(K), int(start_src)
+    start_own = start_src + (K + 7) // 8 * 8 if start_own is None else int(start_own)
+    if not isinstance(vt, torch.Tensor) or vt.dtype not in (torch.float16, torch.bfloat16) or vt.dim() != 3:
+        raise RuntimeError("cross_edit_values: vt must be a (B, C, ldvt) fp16 / bf16 tensor")
+    _req(vt, "vt")
+    if not 1 <= K <= CROSS_EDIT_MAX_KEYS:
+        raise RuntimeError(f"cross_edit_values: K = {K}, 1 .. {CROSS_EDIT_MAX_KEYS} keys are taken")
+    for t, name, shape in ((mapper, "mapper", (K, K)), (src_w, "src_w", (K,)), (own_w, "own_w", (K,))):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != vt.device or tuple(t.shape) != shape \
+                or not t.is_contiguous():
+            raise RuntimeError(f"cross_edit_values: {name} must be a contiguous fp32 {shape} tensor on vt's device")
+    B, C, ldvt = vt.shape
+    if out is None:
+        out = torch.zeros((B, C, max(start_src, start_own) + (K + 7) // 8 * 8), dtype=vt.dtype, device=vt.device)
+    elif out.dim() != 3 or out.shape[:2] != vt.shape[:2] or out.dtype != vt.dtype or out.device != vt.device \
+            or not out.is_contiguous():
+        raise RuntimeError("cross_edit_values: out must be a contiguous (B, C, ldvt_out) tensor of vt's dtype and device")
+    _check(lib().vtm_cross_edit_values(vt.data_ptr(), ldvt, v_start, dtype_code(vt), B, C, K, mapper.data_ptr(),
+                                       src_w.data_ptr(), own_w.data_ptr(), out.data_ptr(), out.shape[2], start_src, start_own,
+                                       _stream()), "vtm_cross_edit_values")
     return out
 
 

@@ -75,6 +75,7 @@ struct Call {
     const struct KeySets *sets = nullptr;   // vtm_attention_kv_sets only: the key ranges, each with a softmax of its own
     const struct SetMasks *set_masks = nullptr;   // vtm_attention_kv_sets_masked only: the per-query weights of the sets
     const struct KeyBias *key_bias = nullptr;     // vtm_attention_kv_bias only: the per-key score bias (attention_bias.hip)
+    const struct SetSrc *set_src = nullptr;       // vtm_attention_kv_sets_src only: the second query operand of the sets
 };
 
 // ---- the key sets of one vtm_attention_kv_sets call (attention_sets.hip): set s = keys [start[s], start[s] + len[s]) ----
@@ -90,6 +91,13 @@ struct SetMasks {
     const float *table;
     int64_t ld, batch_stride;
     int row[MAX_KEY_SETS];
+};
+// ---- the second query operand of a vtm_attention_kv_sets_src call: set s takes the query row (b * Mp + i) * ld of `q`
+// here when bit s of `from_src` is set, else the call's own q ----
+struct SetSrc {
+    const void *q;
+    int64_t ld, Mp;
+    unsigned from_src;
 };
 
 // ---- what planned_launch computed, for a family's launch thunks ----

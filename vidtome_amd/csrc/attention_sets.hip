@@ -6,6 +6,8 @@
 // keeps its query fragments, walks the sets and writes out once.
 // vtm_attention_kv_sets_masked is the same kernel with a weight per QUERY on chosen sets, w_s * mask_s[b, i]: Diffusers'
 // IP-Adapter region masks (one image prompt per region of the frame; every masked image is a set of its own).
+// vtm_attention_kv_sets_src is the same kernel with a second QUERY operand for chosen sets: Prompt-to-Prompt's edited
+// cross-attention, where one softmax of an edited sample is the source sample's (vidtome_amd/p2p.py).
 //
 // Structure (the building blocks of attention.hip, without what a few hundred keys do not need -- no key split, no
 // workspace, no spare-slot tricks):
@@ -36,14 +38,29 @@ constexpr int sets_qb(int D) { return sets_waves(D) * QW; }   // query rows per 
 // vtm_attention_kv_sets_masked.  Without it the kernel is instruction for instruction what it was before the flag.
 __device__ __forceinline__ const SetMasks *masks_of() { return nullptr; }
 __device__ __forceinline__ const SetMasks *masks_of(const SetMasks &m) { return &m; }
+__device__ __forceinline__ const SetMasks *masks_of(const SetSrc &) { return nullptr; }
+// With one trailing SetSrc argument (SRC) chosen sets take their query rows from a second operand: the kernel of
+// vtm_attention_kv_sets_src.  The workgroup keeps ONE set of query fragments and reloads it where the running set's
+// operand differs from the one before it (a workgroup meets each set once; 168 VGPRs at d = 40 / 64 leave no room for
+// a second set of fragments at 2 waves per SIMD).
+__device__ __forceinline__ const SetSrc *src_of() { return nullptr; }
+__device__ __forceinline__ const SetSrc *src_of(const SetMasks &) { return nullptr; }
+__device__ __forceinline__ const SetSrc *src_of(const SetSrc &s) { return &s; }
+// The reload does not fit the 128 VGPRs of two resident workgroups at d <= 32 (fp16 d = 8 spills 6 registers): the SRC
+// kernels keep one workgroup per CU at every head dim.  Stable Diffusion's head dims (40, 64, 80, 160) run at one anyway.
+template <typename... Masks>
+constexpr int sets_wg_per_cu_of(int D) {
+    return (std::is_same_v<Masks, SetSrc> || ...) ? 1 : sets_wg_per_cu(D);
+}
 
 template <typename T, int D, typename... Masks>
-__global__ __launch_bounds__(sets_waves(D) * 64, sets_wg_per_cu(D) * sets_waves(D) / 4) void attention_sets_kernel(
+__global__ __launch_bounds__(sets_waves(D) * 64, sets_wg_per_cu_of<Masks...>(D) * sets_waves(D) / 4) void attention_sets_kernel(
     const T *__restrict__ q, int64_t ldq, const T *__restrict__ k, int64_t ldk, const T *__restrict__ vt, int64_t ldvt,
     T *__restrict__ out, int64_t ldo, int64_t H, int64_t M, int64_t Mp, int64_t Mkp, float scale_log2e, int64_t nqb,
     int xcd_groups, KeySets sets, Masks... masks_arg) {
-    static_assert(sizeof...(Masks) <= 1, "at most one SetMasks");
-    constexpr bool MASKED = sizeof...(Masks) == 1;
+    static_assert(sizeof...(Masks) <= 1, "at most one SetMasks or SetSrc");
+    constexpr bool MASKED = (std::is_same_v<Masks, SetMasks> || ...);
+    constexpr bool SRC = (std::is_same_v<Masks, SetSrc> || ...);
     using F = Frag<T>;
     using vec = typename F::vec;
     using elem = typename F::elem;
@@ -70,6 +87,20 @@ __global__ __launch_bounds__(sets_waves(D) * 64, sets_wg_per_cu(D) * sets_waves(
         const int64_t qi = q0 + l31;
         load_q_frags<T, D>(qf, q + (b * Mp + (qi < M ? qi : 0)) * ldq + h * D, qi < M, hi);
     }
+    // SRC: whether set s reads the second query operand (uniform), and the fragments of a set that does / does not.  (The
+    // load above stays as it is, so that the other instantiations keep their code; a first set on q_src loads again.)
+    [[maybe_unused]] auto from_src = [&](int s) { return ((src_of(masks_arg...)->from_src >> s) & 1u) != 0; };
+    [[maybe_unused]] auto load_q = [&](int s) {
+        const int64_t qi = q0 + l31;
+        const SetSrc &src = *src_of(masks_arg...);
+        if (from_src(s))
+            load_q_frags<T, D>(qf, static_cast<const T *>(src.q) + (b * src.Mp + (qi < M ? qi : 0)) * src.ld + h * D, qi < M,
+                               hi);
+        else
+            load_q_frags<T, D>(qf, q + (b * Mp + (qi < M ? qi : 0)) * ldq + h * D, qi < M, hi);
+    };
+    if constexpr (SRC)
+        if (from_src(0)) load_q(0);
 
     Stage stage;
     stage.init(tid, ldk, ldvt);
@@ -190,6 +221,8 @@ __global__ __launch_bounds__(sets_waves(D) * 64, sets_wg_per_cu(D) * sets_waves(
         if (ns != cs) {
             finish_set(sets.w[cs]);
             if constexpr (MASKED) mw = mw_next;
+            if constexpr (SRC)   // the fragments of the finished set are dead: the next set's, where its operand is another
+                if (more && from_src(ns) != from_src(cs)) load_q(ns);
         }
         if (!more) break;
         __syncthreads();   // every wave has read the tile
@@ -211,6 +244,13 @@ void launch_sets(const Call &c, const Launch &g) {
 }
 
 template <typename T, int D>
+void launch_sets_src(const Call &c, const Launch &g) {
+    hipLaunchKernelGGL((attention_sets_kernel<T, D, SetSrc>), dim3((unsigned)g.wgs), dim3(sets_waves(D) * 64), 0, c.s,
+                       (const T *)c.q, c.ldq, (const T *)c.k, c.ldk, (const T *)c.vt, c.ldvt, (T *)c.out, c.ldo, c.h, c.M, c.Mp,
+                       c.Mkp, g.scale_log2e, g.nqb, g.xcd_groups, *c.sets, *c.set_src);
+}
+
+template <typename T, int D>
 void launch_sets_masked(const Call &c, const Launch &g) {
     hipLaunchKernelGGL((attention_sets_kernel<T, D, SetMasks>), dim3((unsigned)g.wgs), dim3(sets_waves(D) * 64), 0, c.s,
                        (const T *)c.q, c.ldq, (const T *)c.k, c.ldk, (const T *)c.vt, c.ldvt, (T *)c.out, c.ldo, c.h, c.M, c.Mp,
@@ -219,24 +259,28 @@ void launch_sets_masked(const Call &c, const Launch &g) {
 
 // The family: one workgroup per (query block, head, sample), never key-split (no partial record, no combine kernel) -- the
 // planner sizes the grid and pins the (sample, head) pairs to XCDs like every other family's.
+enum SetsKind { SETS_PLAIN, SETS_MASKED, SETS_SRC };
+
 template <typename T, int D>
-Family sets_family(bool masked = false) {
+Family sets_family(SetsKind kind) {
     Family f;
-    f.name = masked ? "vtm_attention_kv_sets_masked" : "vtm_attention_kv_sets";
+    f.name = kind == SETS_MASKED ? "vtm_attention_kv_sets_masked"
+             : kind == SETS_SRC  ? "vtm_attention_kv_sets_src"
+                                 : "vtm_attention_kv_sets";
     f.qb = sets_qb(D);
-    f.wg_per_cu = sets_wg_per_cu(D);
+    f.wg_per_cu = kind == SETS_SRC ? sets_wg_per_cu_of<SetSrc>(D) : sets_wg_per_cu(D);
     f.rec_bytes = 0;
     f.xcd_min_nqb = 64;
     f.host_split_all = false;
-    f.main = masked ? launch_sets_masked<T, D> : launch_sets<T, D>;
+    f.main = kind == SETS_MASKED ? launch_sets_masked<T, D> : kind == SETS_SRC ? launch_sets_src<T, D> : launch_sets<T, D>;
     return f;
 }
 
-// The checks and the launch of both exports; `masks` = nullptr: vtm_attention_kv_sets.
+// The checks and the launch of the three exports; `masks` = `src` = nullptr: vtm_attention_kv_sets (at most one is given).
 int sets_launch(const char *who, const void *q, int64_t ldq, const void *k, int64_t ldk, const void *vt, int64_t ldvt, void *out,
                 int64_t ldo, int dtype, int64_t B, int64_t h, int64_t Mq, int64_t Mqp, int64_t Mkp, int64_t d, float scale,
                 int n_sets, const int64_t *set_start, const int64_t *set_len, const float *set_weight, const SetMasks *masks,
-                vtm_stream_t stream) {
+                vtm_stream_t stream, const SetSrc *src = nullptr) {
     VTM_REQUIRE(q && k && vt && out && set_start && set_len && set_weight, "%s: null pointer", who);
     VTM_REQUIRE(n_sets >= 1 && n_sets <= MAX_KEY_SETS, "%s: n_sets must be 1 .. %d, got %d", who, MAX_KEY_SETS, n_sets);
     VTM_REQUIRE(B > 0 && h > 0 && Mq > 0 && Mqp >= Mq && Mkp > 0 && d > 0, "%s: bad sizes", who);
@@ -272,10 +316,11 @@ int sets_launch(const char *who, const void *q, int64_t ldq, const void *k, int6
            nullptr, vtm::as_stream(stream), false, nullptr, nullptr, 0};
     c.sets = &sets;
     c.set_masks = masks;
-    const bool masked = masks != nullptr;
+    c.set_src = src;
+    const SetsKind kind = masks != nullptr ? SETS_MASKED : src != nullptr ? SETS_SRC : SETS_PLAIN;
     return with_head_dim(d, [&](auto dim) {
         constexpr int D = decltype(dim)::value;
-        return planned_launch(c, dtype == VTM_F16 ? sets_family<__half, D>(masked) : sets_family<vtm_bf16, D>(masked));
+        return planned_launch(c, dtype == VTM_F16 ? sets_family<__half, D>(kind) : sets_family<vtm_bf16, D>(kind));
     });
 }
 
@@ -321,4 +366,30 @@ VTM_EXPORT int vtm_attention_kv_sets_masked(const void *q, int64_t ldq, const vo
                 (long long)((int64_t)rows * ld_mask));
     return sets_launch(who, q, ldq, k, ldk, vt, ldvt, out, ldo, dtype, B, h, Mq, Mqp, Mkp, d, scale, n_sets, set_start, set_len,
                        set_weight, &masks, stream);
+}
+
+VTM_EXPORT int vtm_attention_kv_sets_src(const void *q, int64_t ldq, const void *q_src, int64_t ldq_src, int64_t Mqp_src,
+                                         const void *k, int64_t ldk, const void *vt, int64_t ldvt, void *out, int64_t ldo,
+                                         int dtype, int64_t B, int64_t h, int64_t Mq, int64_t Mqp, int64_t Mkp, int64_t d,
+                                         float scale, int n_sets, const int64_t *set_start, const int64_t *set_len,
+                                         const float *set_weight, const int *set_src, vtm_stream_t stream) {
+    const char *who = "vtm_attention_kv_sets_src";
+    VTM_REQUIRE(set_src, "%s: null pointer", who);
+    VTM_REQUIRE(n_sets >= 1 && n_sets <= MAX_KEY_SETS, "%s: n_sets must be 1 .. %d, got %d", who, MAX_KEY_SETS, n_sets);
+    SetSrc src{q_src, ldq_src, Mqp_src, 0u};
+    for (int s = 0; s < n_sets; ++s) {
+        VTM_REQUIRE(set_src[s] == 0 || set_src[s] == 1, "%s: set_src of set %d is %d (0 = q, 1 = q_src)", who, s, set_src[s]);
+        src.from_src |= (unsigned)set_src[s] << s;
+    }
+    if (src.from_src == 0u)   // every set reads q: the plain kernel, q_src is not looked at
+        return sets_launch(who, q, ldq, k, ldk, vt, ldvt, out, ldo, dtype, B, h, Mq, Mqp, Mkp, d, scale, n_sets, set_start,
+                           set_len, set_weight, nullptr, stream);
+    VTM_REQUIRE(q_src, "%s: a set reads q_src but it is null", who);
+    VTM_REQUIRE((reinterpret_cast<uintptr_t>(q_src) & 15) == 0 && ldq_src % 8 == 0 && ldq_src >= h * d,
+                "%s: q_src must be 16-byte aligned, ldq_src = %lld a multiple of 8 that holds h * d channels", who,
+                (long long)ldq_src);
+    VTM_REQUIRE(Mqp_src >= Mq, "%s: Mqp_src = %lld is shorter than Mq = %lld query rows", who, (long long)Mqp_src,
+                (long long)Mq);
+    return sets_launch(who, q, ldq, k, ldk, vt, ldvt, out, ldo, dtype, B, h, Mq, Mqp, Mkp, d, scale, n_sets, set_start, set_len,
+                       set_weight, nullptr, stream, &src);
 }

@@ -41,9 +41,21 @@ def register_attention_maps(model: torch.nn.Module,
     the UNet (not of a ControlNet); an iterable of module names (the keys ``collect_from_patch`` returns); or a predicate
     ``(name, block) -> bool`` over all patched blocks, a ControlNet's included.  Registering again only changes the
     selection: blocks no longer selected lose the switch and their stored map.  Returns the selected names, sorted."""
+    every, chosen = select_blocks(model, blocks, "register_attention_maps")
+    for (name, blk, _), on in zip(every, chosen):
+        if on:
+            setattr(blk, FLAG, True)
+        else:
+            _clear(blk)
+    return sorted({name for (name, _, _), on in zip(every, chosen) if on})
+
+
+def select_blocks(model: torch.nn.Module, blocks, who: str):
+    """(every patched block as ``_patched_blocks`` lists them, [selected or not]) for the ``blocks`` argument of ``who``
+    (``register_attention_maps`` states its three forms); raises when nothing is patched or a name is not a patched block's."""
     every = _patched_blocks(model)
     if not every:
-        raise RuntimeError("register_attention_maps: nothing is patched (call apply_patch first)")
+        raise RuntimeError(f"{who}: nothing is patched (call apply_patch first)")
     if blocks is None:
         chosen = [in_unet for _, _, in_unet in every]
     elif callable(blocks):
@@ -52,14 +64,9 @@ def register_attention_maps(model: torch.nn.Module,
         names = {blocks} if isinstance(blocks, str) else set(blocks)
         unknown = sorted(names - {name for name, _, _ in every})
         if unknown:
-            raise ValueError(f"register_attention_maps: not patched blocks: {unknown}")
+            raise ValueError(f"{who}: not patched blocks: {unknown}")
         chosen = [name in names for name, _, _ in every]
-    for (name, blk, _), on in zip(every, chosen):
-        if on:
-            setattr(blk, FLAG, True)
-        else:
-            _clear(blk)
-    return sorted({name for (name, _, _), on in zip(every, chosen) if on})
+    return every, chosen
 
 
 def unregister_attention_maps(model: torch.nn.Module) -> None:

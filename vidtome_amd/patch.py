@@ -1116,6 +1116,136 @@ def cross_attention(attn: torch.nn.Module, x: torch.Tensor, encoder_hidden_state
 
 
 # ----------------------------------------------------------------------------------------------------
+# attn2 under Prompt-to-Prompt cross-attention control (vidtome_amd/p2p.py)
+# ----------------------------------------------------------------------------------------------------
+def cross_control(block: torch.nn.Module):
+    """(num_inputs, edits, block name) when ``p2p.register_cross_attention_control`` selected the block and this step
+    injects -- ``attn2.t in injection_schedule or attn2.t == 1000``, the PnP rule (pnp_utils.py:57-58), ``t`` stamped by
+    ``pnp.register_time`` -- else None: the block then launches what it launches without the control."""
+    ctl = block.__dict__.get("vtm_cross_control")
+    if ctl is None or getattr(block, "attn2", None) is None:
+        return None
+    schedule, num_inputs, edits, name = ctl
+    t = getattr(block.attn2, "t", None)
+    if t is None or not (t in schedule or t == 1000):
+        return None
+    return num_inputs, edits, name
+
+
+def cross_control_route(block: torch.nn.Module, x: torch.Tensor, encoder_hidden_states, attention_mask, kwargs, ctl) -> str:
+    """How an injecting block computes its attn2 segment on tokens like ``x``: "panels" (what ``fused_cross_ok`` asks: the
+    LayerNorm -> q panel GEMM -> core -> output GEMM + residual chain of ``norm_cross_attention_residual``) or "blas"
+    (``cross_attention``'s library GEMMs around the core).  Everything else RAISES, naming the block and the reason, before
+    anything is launched: there is no module path under control, an edit is never silently dropped."""
+    num_inputs, edits, name = ctl
+    attn = block.attn2
+
+    def refuse(why: str):
+        raise RuntimeError(f"vidtome_amd: cross-attention control on block '{name}': {why}")
+    enc = encoder_hidden_states
+    if isinstance(enc, tuple) or ip_adapter.is_ip_processor(attn):
+        refuse("an IP-Adapter call is not taken (combining the control with image prompts is out of scope)")
+    if not (isinstance(enc, torch.Tensor) and enc.dim() == 3 and x.dim() == 3 and enc.shape[0] == x.shape[0]):
+        refuse("the conditioning must be a (B F, K, D) tensor with a row set per sample")
+    if x.shape[0] % num_inputs:
+        refuse(f"the batch of {x.shape[0]} samples is not {num_inputs} groups of equal size")
+    K = enc.shape[1]
+    if K > _lib.CROSS_EDIT_MAX_KEYS:
+        refuse(f"K = {K} conditioning tokens, at most {_lib.CROSS_EDIT_MAX_KEYS} are taken")
+    for g, e in sorted(edits.items()):
+        if e.K != K:
+            refuse(f"the edit of group {g} is for K = {e.K} tokens, the conditioning has {K}")
+    if block.use_ada_layer_norm:
+        refuse("AdaLayerNorm blocks are not taken")
+    if x.dtype not in (torch.float16, torch.bfloat16):
+        refuse(f"{x.dtype} blocks are not taken (fp16 / bf16 only)")
+    if attention_mask is not None:
+        refuse("an attention_mask is not taken (combining the control with masks is out of scope)")
+    if kwargs:
+        refuse(f"processor kwargs {sorted(kwargs)} are not taken")
+    if not fused_attention_ok(attn, x, self_attn=False):
+        refuse("attn2 is not the plain arithmetic the fused path computes (fused_attention_ok)")
+    return "panels" if fused_cross_ok(block.norm2, attn, x, enc, None, kwargs) else "blas"
+
+
+def _edited_probs(probs: torch.Tensor, rows: slice, src: slice, edit) -> None:
+    """The head-averaged map of an edited group, in place: head-averaging commutes with the edit."""
+    M, a, b = edit.on(probs.device)
+    probs[rows] = torch.matmul(probs[src], M) * a + probs[rows] * b
+
+
+def _controlled_core(attn: torch.nn.Module, q: torch.Tensor, N: int, enc: torch.Tensor, ctl, scale: float, panels: bool,
+                     probs_to: Optional[torch.nn.Module]) -> torch.Tensor:
+    """The attn2 core of an injecting block on query rows q (B F, Np, C), N <= Np of them meaningful; samples are
+    group-major, b = g * Fg + f, and the source of sample b is b % Fg.  k / v^T of EVERY sample come from the one projection
+    call the block makes without the control.  Contiguous runs of unedited groups (no edit, or the identity) then run the
+    plain core on their slices of q / out -- the bits of an uncontrolled block -- and each edited group is
+        k   = [k(enc[src]) | k(enc[own])]                      two key sets at 0 and K rounded up to 8
+        V^T = [(M diag(a) V_own)^T | (diag(b) V_own)^T]        vtm_cross_edit_values
+        out = softmax(q[src] k_src^T) V' + softmax(q[own] k_own^T) V''     ONE vtm_attention_kv_sets_src launch
+    into its slice of out."""
+    num_inputs, edits, _ = ctl
+    heads, C = attn.heads, q.shape[-1]
+    BF, Np = q.shape[0], q.shape[1]
+    Fg, K = BF // num_inputs, enc.shape[1]
+    K8 = (K + 7) // 8 * 8
+    k, vt = _cross_kv(attn.to_k, attn.to_v, _pad_keys(enc, q.dtype), C, panels)
+    out = (torch.zeros if Np != N else torch.empty)((BF, Np, C), dtype=q.dtype, device=q.device)
+    probs = None if probs_to is None else _probs_rows(q, k, heads, N, K, scale)
+    edited = [g in edits and not edits[g].is_identity for g in range(num_inputs)]
+    src = slice(0, Fg)
+    g = 0
+    while g < num_inputs:
+        if edited[g]:
+            rows = slice(g * Fg, (g + 1) * Fg)
+            M, a, b = edits[g].on(q.device)
+            k_sets = torch.cat([k[src], k[rows]], dim=1)               # (F, 2 K8, C)
+            vt_sets = _lib.cross_edit_values(vt[rows], 0, K, M, a, b, 0, K8,
+                                             out=torch.empty((Fg, C, 2 * K8), dtype=q.dtype, device=q.device))
+            _lib.attention_kv_sets_src(q[rows], q[src], k_sets, vt_sets, heads, N, [(0, K, 1.0), (K8, K, 1.0)], scale, (1, 0),
+                                       out=out[rows])
+            if probs is not None:
+                _edited_probs(probs, rows, src, edits[g])
+            g += 1
+            continue
+        g1 = g
+        while g1 < num_inputs and not edited[g1]:
+            g1 += 1
+        rows = slice(g * Fg, g1 * Fg)
+        _lib.attention_kv(q[rows], k[rows], vt[rows], heads, N, K, scale, out=out[rows])
+        g = g1
+    if probs_to is not None:
+        probs_to.attn2_probs = probs
+    return out
+
+
+def controlled_cross_attention_residual(block: torch.nn.Module, hidden_states: torch.Tensor,
+                                        encoder_hidden_states: torch.Tensor, ctl, route: str,
+                                        probs_to: Optional[torch.nn.Module] = None) -> torch.Tensor:
+    """patch.py:171-185 of an injecting block: ``attn2(norm2(h), enc) + h`` with the probabilities of the edited groups
+    replaced as Prompt-to-Prompt replaces them (``_controlled_core``).  ``route`` is ``cross_control_route``'s answer: around
+    the core stands what the uncontrolled block launches on that route."""
+    norm, attn = block.norm2, block.attn2
+    B, N, C = hidden_states.shape
+    scale = _scale(attn, C)
+    with torch.no_grad():
+        if route == "panels":
+            hs = hidden_states.contiguous()
+            n = B * N
+            wq, bq = _panel_weight(attn.to_q)
+            wo, bo = _panel_weight(_out_linear(attn))
+            xp = _lib.layernorm_panels(hs, norm.weight, norm.bias, norm.eps)
+            q = _lib.linear_panels(xp, n, wq, C, bq).view(B, N, C)
+            o = _controlled_core(attn, q, N, encoder_hidden_states, ctl, scale, True, probs_to)
+            return _lib.linear_panels(_lib.to_panels(o.view(n, C)), n, wo, C, bo, resid=hs.view(n, C)).view(B, N, C)
+        x = layer_norm(norm, hidden_states)
+        xq = F.pad(x, (0, 0, 0, -N % 8)) if N % 8 else x
+        q = _apply_linear(attn.to_q, xq, x.dtype)
+        o = _controlled_core(attn, q, N, encoder_hidden_states, ctl, scale, False, probs_to)
+        return _apply_linear(_out_linear(attn), o, o.dtype)[:, :N] + hidden_states
+
+
+# ----------------------------------------------------------------------------------------------------
 # the rest of the block as panel GEMMs (csrc/ff.hip)
 # ----------------------------------------------------------------------------------------------------
 # VIDTOME_FF: "panels" (default) = norm3 -> GEGLU projection with the gated activation in the GEMM's epilogue -> output
@@ -1325,10 +1455,16 @@ def make_diffusers_tome_block(block_class: Type[torch.nn.Module]) -> Type[torch.
             cross_attention_kwargs = cross_attention_kwargs if cross_attention_kwargs is not None else {}
             if self.attn2 is not None:                                             # patch.py:171-185
                 maps = self if getattr(self, "vtm_attention_maps", False) else None   # maps.register_attention_maps
-                ip = None if self.use_ada_layer_norm else ip_cross_call(
+                control = cross_control(self)                                      # p2p.register_cross_attention_control
+                ip = None if self.use_ada_layer_norm or control is not None else ip_cross_call(
                     self.attn2, hidden_states, encoder_hidden_states, encoder_attention_mask, cross_attention_kwargs,
                     self.norm2)
-                if ip is not None:                                                 # IP-Adapter: text + image key sets
+                if control is not None:                                            # an injecting step: edited probabilities
+                    route = cross_control_route(self, hidden_states, encoder_hidden_states, encoder_attention_mask,
+                                                cross_attention_kwargs, control)
+                    hidden_states = controlled_cross_attention_residual(self, hidden_states, encoder_hidden_states, control,
+                                                                        route, probs_to=maps)
+                elif ip is not None:                                               # IP-Adapter: text + image key sets
                     hidden_states = norm_cross_attention_residual(self.norm2, self.attn2, hidden_states, None, ip,
                                                                   probs_to=maps)
                 elif not self.use_ada_layer_norm and fused_cross_ok(self.norm2, self.attn2, hidden_states,
@@ -1500,6 +1636,7 @@ def remove_patch(model: torch.nn.Module):
             module.__dict__.pop("fp32_projections", None)      # (likewise)
             module.__dict__.pop("vtm_attention_maps", None)    # maps.register_attention_maps' switch ...
             module.__dict__.pop("attn2_probs", None)           # ... and the map of the block's last forward
+            module.__dict__.pop("vtm_cross_control", None)     # p2p.register_cross_attention_control's schedule and edits
     _lib.release_workspaces()            # the cached scratch buffers of the patched path (re-created on demand)
     return roots[-1]                     # the reference returns its loop variable: the last tree walked
 
