@@ -502,6 +502,48 @@ int vtm_attention_probs(const void *q, int64_t ldq, const void *k, int64_t ldk, 
                         int64_t B, int64_t h, int64_t Mq, int64_t Mqp, int64_t Mk, int64_t Mkp, int64_t d, float scale,
                         const float *bias, int64_t ld_bias, int64_t bias_batch_stride, vtm_stream_t stream);
 
+/* vtm_attention_word_map -- ONE weighted column sum of that head-averaged map, added in place: the `self.attn2(...)` call
+ * of vidtome/patch.py:178-183 as a Prompt-to-Prompt LocalBlend reads it (the map of a few chosen words, accumulated over
+ * blocks and denoising steps), without the (B, Mq, Mk) map:
+ *     value[b, i] = (1 / h) * sum_head [ sum_j w[b, j] p_head[i, j] ] / [ sum_j p_head[i, j] ]
+ *     p_head[i, j] = exp(q[b, i, head] . k[b, j, head] * scale + bias[b * bias_batch_stride + j] - running max),   j < Mk
+ *     out[r(b) * ldo + i] = (accumulate ? out[r(b) * ldo + i] : 0) + value[b, i],   i < Mq,   r(b) = out_rows ? out_rows[b] : b
+ * q, ldq, k, ldk, dtype, B, h, Mq, Mqp, Mk, Mkp, d, scale, bias, ld_bias, bias_batch_stride exactly as for
+ * vtm_attention_probs (layouts, alignment, VTM_F16 / VTM_BF16 only, every head dim of vtm_attention, 1 <= Mk <= 256, a bias
+ * of -inf gives probability exactly 0), but there is NO head-count limit beyond h > 0: nothing per head is kept.  weights: a
+ * DEVICE pointer to fp32, w[b, j] = weights[b * w_batch_stride + j]; rows of ld_w >= Mk elements; w_batch_stride, in
+ * elements: 0 when one row serves every sample, else at least ld_w.  The weights are finite (not checked).  out: fp32, row
+ * r at r * ldo, ldo >= Mq; columns >= Mq and rows no r(b) names are not written.  out_rows: a DEVICE pointer to B int64 row
+ * numbers, or NULL; the rows of one call are distinct (the caller's contract: every element then has one writer).
+ * accumulate: 0 overwrites, anything else adds to what out holds (one fp32 addition).  One online-softmax sweep, heads
+ * outer and key tiles inner: the running maximum carries the weighted numerator and the denominator, rescaled together; at
+ * a head's last tile numerator * (1 / denominator) is added to an fp32 accumulator, heads in ascending order, which is
+ * multiplied by 1 / h once.  A sample whose keys are ALL -inf gives NaN for that sample only.  Deterministic: one launch,
+ * no atomics, no workspace; the same operands and the same prior out give the same bits.  On a bad argument nothing is
+ * launched and out is untouched. */
+int vtm_attention_word_map(const void *q, int64_t ldq, const void *k, int64_t ldk, int dtype, int64_t B, int64_t h,
+                           int64_t Mq, int64_t Mqp, int64_t Mk, int64_t Mkp, int64_t d, float scale, const float *bias,
+                           int64_t ld_bias, int64_t bias_batch_stride, const float *weights, int64_t ld_w,
+                           int64_t w_batch_stride, float *out, int64_t ldo, const int64_t *out_rows, int accumulate,
+                           vtm_stream_t stream);
+
+/* vtm_local_blend -- the tail of Prompt-to-Prompt's LocalBlend on accumulated word maps: pool, threshold against the
+ * map's maximum, keep the source latents outside the mask.  acc: DEVICE fp32 (G, F, h, w) contiguous, finite, 1 <= G <= 8
+ * groups; x, x_src, out: (F, C, H, W) contiguous NCHW latents of one dtype (VTM_F32, VTM_F16 or VTM_BF16), H % h == 0 and
+ * W % w == 0.  Per frame f and latent pixel (y, x)
+ *     pooled_g = max of acc[g, f] over the (2 pool + 1)^2 window around (y * h / H, x * w / W), clipped at the border
+ *     mask     = OR_g ( pooled_g > threshold * max(acc[g, f]) )            one fp32 multiply, then the comparison
+ *     out[f, c, y, x] = mask ? x[f, c, y, x] : x_src[f, c, y, x]           a select: the latents are moved, never computed on
+ * pool: the radius, 0 .. 3 (P2P's k = 1 is pool = 1: a 3 x 3 window, stride 1, -inf padding).  Two deliberate differences
+ * from P2P: `pooled > threshold * max` stands for `pooled / max > threshold` (no division; a map that is all 0 gives an
+ * empty mask for its group, as P2P's 0 / 0 comparison does), and the select stands for x_src + mask * (x - x_src), which
+ * rounds in a 16-bit dtype.  out may BE x (no other overlap with x or x_src).  mask_out: DEVICE uint8 (F, H, W) that
+ * receives the mask as 0 / 1, or NULL.  One launch, deterministic (no atomics), no workspace.  On a bad argument nothing is
+ * launched and out is untouched. */
+int vtm_local_blend(const float *acc, int64_t G, int64_t F, int64_t h, int64_t w, const void *x, const void *x_src,
+                    void *out, int dtype, int64_t C, int64_t H, int64_t W, int pool, float threshold, uint8_t *mask_out,
+                    vtm_stream_t stream);
+
 /* vtm_attention_kv with a DEVICE-side query bound: sample b only has q_count[b] <= Mq meaningful query rows (the
  * compacted live queries of vtm_compact_queries); query blocks that start at or beyond the count exit at once, rows
  * beyond it are not meaningful.  The launch is sized for the host-known bound Mq -- no host round trip. */

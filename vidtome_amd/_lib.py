@@ -89,6 +89,9 @@ _SIGNATURES = {
                                _f32, _vp, _i64, _i64, _vp], _int),
     "vtm_attention_probs": ([_vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _vp, _i64,
                              _i64, _vp], _int),
+    "vtm_attention_word_map": ([_vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _vp, _i64, _i64, _vp, _i64,
+                                _i64, _vp, _i64, _vp, _int, _vp], _int),
+    "vtm_local_blend": ([_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _int, _i64, _i64, _i64, _int, _f32, _vp, _vp], _int),
     "vtm_attention_kv_bounded": ([_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                   _f32, _vp, _vp, ctypes.c_size_t, _vp], _int),
     "vtm_attention_kv_shared_bounded": ([_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
@@ -1013,6 +1016,102 @@ def attention_probs(q: torch.Tensor, k: torch.Tensor, heads: int, Mq: int, Mk: i
                                      B, heads, Mq, Mqp, Mk, Mkp, C // heads, float(scale), _ptr(bias), ld_bias, batch_stride,
                                      _stream()), "vtm_attention_probs")
     return out
+
+
+def _key_rows(who: str, t: Optional[torch.Tensor], name: str, q: torch.Tensor, B: int, Mk: int):
+    """(pointer, row length, batch stride) of fp32 per-key rows (B or 1, >= Mk) on q's device, as the bias of
+    attention_kv_bias is handed over; None gives (None, 0, 0)."""
+    if t is None:
+        return None, 0, 0
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != q.device or t.dim() != 2 \
+            or t.shape[0] not in (1, B) or t.shape[1] < Mk or t.stride(1) != 1 \
+            or (t.shape[0] == B and B > 1 and 0 < t.stride(0) < t.shape[1]):   # (stride 0: an expanded row)
+        raise RuntimeError(f"{who}: {name} must be fp32 on q's device, (B, >= Mk) or (1, >= Mk), contiguous along its last axis")
+    return t.data_ptr(), t.shape[1], (t.stride(0) if t.shape[0] == B and B > 1 else 0)
+
+
+@_on_device
+def attention_word_map(q: torch.Tensor, k: torch.Tensor, heads: int, Mq: int, Mk: int, scale: float, weights: torch.Tensor,
+                       out: torch.Tensor, out_rows: Optional[torch.Tensor] = None, accumulate: bool = True,
+                       bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One weighted column sum of the head-averaged cross-attention map, added in place (vtm_attention_word_map): q, k,
+    heads, Mq, Mk, scale and ``bias`` as for attention_probs (any head count); ``weights`` fp32 on q's device, (B, >= Mk) with
+    a row per sample or (1, >= Mk) with one row for all, finite (the caller's business).  ``out`` is fp32 (R, >= Mq) on q's
+    device with unit stride along the row: sample b goes to row ``out_rows[b]`` (int64 (B,) on q's device, distinct rows
+    inside ``out``: the caller's business) or to row b.  ``accumulate``: add to what ``out`` holds, else overwrite.  Returns
+    ``out``.  One launch; no (B, Mq, Mk) map, deterministic."""
+    who = "attention_word_map"
+    if not isinstance(q, torch.Tensor) or not isinstance(k, torch.Tensor) or q.dtype not in (torch.float16, torch.bfloat16) \
+            or k.dtype != q.dtype:
+        raise RuntimeError(f"{who}: q and k must share one of fp16 / bf16")
+    if q.dim() != 3 or k.dim() != 3 or not q.is_cuda or k.device != q.device:
+        raise RuntimeError(f"{who}: q must be (B, Mqp, C) and k (B, Mkp, C) on one GPU")
+    B, Mqp, C = q.shape
+    Mkp = k.shape[1]
+    heads, Mq, Mk = int(heads), int(Mq), int(Mk)
+    if k.shape[0] != B or k.shape[2] != C or heads < 1 or C % heads:
+        raise RuntimeError(f"{who}: k must be (B, Mkp, C) with C a multiple of heads")
+    if not (1 <= Mq <= Mqp and 1 <= Mk <= Mkp):
+        raise RuntimeError(f"{who}: Mq / Mk must lie inside q / k")
+    for t, name, rows in ((q, "q", Mqp), (k, "k", Mkp)):
+        if t.stride(2) != 1 or t.stride(1) % 8 or t.stride(1) < C or (B > 1 and t.stride(0) != rows * t.stride(1)) \
+                or t.data_ptr() % 16:
+            raise RuntimeError(f"{who}: {name} must be 16-byte aligned rows (stride a multiple of 8), dense over the samples")
+    if weights is None:
+        raise RuntimeError(f"{who}: weights are required")
+    b_ptr, ld_bias, b_stride = _key_rows(who, bias, "bias", q, B, Mk)
+    w_ptr, ld_w, w_stride = _key_rows(who, weights, "weights", q, B, Mk)
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != q.device or out.dim() != 2 \
+            or out.shape[1] < Mq or out.stride(1) != 1 or (out.shape[0] > 1 and out.stride(0) < out.shape[1]):
+        raise RuntimeError(f"{who}: out must be fp32 (rows, >= Mq) on q's device, contiguous along its last axis")
+    if out_rows is None:
+        if out.shape[0] < B:
+            raise RuntimeError(f"{who}: out has {out.shape[0]} rows for {B} samples")
+    elif not isinstance(out_rows, torch.Tensor) or out_rows.dtype != torch.int64 or out_rows.device != q.device \
+            or tuple(out_rows.shape) != (B,) or not out_rows.is_contiguous():
+        raise RuntimeError(f"{who}: out_rows must be a contiguous int64 (B,) tensor on q's device")
+    _check(lib().vtm_attention_word_map(q.data_ptr(), q.stride(1), k.data_ptr(), k.stride(1), dtype_code(q), B, heads, Mq, Mqp,
+                                        Mk, Mkp, C // heads, float(scale), b_ptr, ld_bias, b_stride, w_ptr, ld_w, w_stride,
+                                        out.data_ptr(), out.stride(0) if out.shape[0] > 1 else out.shape[1], _ptr(out_rows),
+                                        1 if accumulate else 0, _stream()), "vtm_attention_word_map")
+    return out
+
+
+LOCAL_BLEND_MAX_GROUPS, LOCAL_BLEND_MAX_POOL = 8, 3   # what vtm_local_blend takes (csrc/local_blend.hip)
+
+
+@_on_device
+def local_blend(acc: torch.Tensor, x: torch.Tensor, x_src: torch.Tensor, pool: int, threshold: float,
+                out: Optional[torch.Tensor] = None, return_mask: bool = False):
+    """The LocalBlend tail (vtm_local_blend): ``acc`` (G, F, h, w) fp32 accumulated word maps, ``x`` / ``x_src`` (F, C, H, W)
+    contiguous latents of one dtype, H % h == 0 and W % w == 0.  A pixel is inside the mask when, for any group, the maximum
+    of the map over the (2 pool + 1)^2 window around its cell exceeds ``threshold`` times the map's maximum; ``out`` takes x
+    inside and x_src outside.  ``out`` None: a new tensor; it may be x.  Returns out, or (out, mask uint8 (F, H, W))."""
+    who = "local_blend"
+    if not isinstance(acc, torch.Tensor) or acc.dtype != torch.float32 or acc.dim() != 4 or not acc.is_cuda \
+            or not acc.is_contiguous() or not 1 <= acc.shape[0] <= LOCAL_BLEND_MAX_GROUPS:
+        raise RuntimeError(f"{who}: acc must be a contiguous fp32 (G <= {LOCAL_BLEND_MAX_GROUPS}, F, h, w) tensor on the GPU")
+    G, F, h, w = acc.shape
+    for t, name in ((x, "x"), (x_src, "x_src")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4 or t.device != acc.device or not t.is_contiguous() \
+                or t.dtype not in _DT or t.dtype != x.dtype or t.shape != x.shape:
+            raise RuntimeError(f"{who}: {name} must be a contiguous (F, C, H, W) fp16 / bf16 / fp32 tensor on acc's device, "
+                               "x and x_src alike")
+    if x.shape[0] != F or x.shape[2] % h or x.shape[3] % w:
+        raise RuntimeError(f"{who}: latents {tuple(x.shape)} do not fit maps {tuple(acc.shape)} (F frames, H % h == W % w == 0)")
+    pool = int(pool)
+    if not 0 <= pool <= LOCAL_BLEND_MAX_POOL:
+        raise RuntimeError(f"{who}: pool = {pool}, a radius of 0 .. {LOCAL_BLEND_MAX_POOL} is taken")
+    if out is None:
+        out = torch.empty_like(x)
+    elif not isinstance(out, torch.Tensor) or out.shape != x.shape or out.dtype != x.dtype or out.device != x.device \
+            or not out.is_contiguous():
+        raise RuntimeError(f"{who}: out must be a contiguous tensor like x")
+    _, C, H, W = x.shape
+    mask = torch.empty((F, H, W), dtype=torch.uint8, device=x.device) if return_mask else None
+    _check(lib().vtm_local_blend(acc.data_ptr(), G, F, h, w, x.data_ptr(), x_src.data_ptr(), out.data_ptr(), dtype_code(x), C,
+                                 H, W, pool, float(threshold), _ptr(mask), _stream()), "vtm_local_blend")
+    return (out, mask) if return_mask else out
 
 
 @_on_device

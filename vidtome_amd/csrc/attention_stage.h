@@ -1,7 +1,8 @@
 // What the 16-bit attention kernels (attention.hip, attention16.hip, attention16g.hip, attention_sets.hip,
-// attention_bias.hip) share of their tile handling: the buffer descriptor, the K / V^T tile stage global memory -> staging
-// registers -> LDS, the Q-fragment load and, for the two small cross-attention kernels, the pad initialisation, the split-P
-// PV step and the 32-row output store.  Header-only; everything is __forceinline__ and every loop fully unrolled: the
+// attention_bias.hip, attention_probs.hip, attention_words.hip) share of their tile handling: the buffer descriptor, the
+// K / V^T tile stage global memory -> staging registers -> LDS, the Q-fragment load, the score tile of the map kernels and,
+// for the two small cross-attention kernels, the pad initialisation, the split-P PV step and the 32-row output store.
+// Header-only; everything is __forceinline__ and every loop fully unrolled: the
 // kernels that use a piece keep the registers they had with its text written out, and where they did not, they do not use it
 // (profiles/attention_stage_resources.txt).
 #pragma once
@@ -122,6 +123,27 @@ struct KvStage {
         issue_v(std::false_type{}, rsrc_v, so_v, key0, end);
     }
 
+    // The K half of ANY tile (full or ragged) without a branch around a load: every thread fetches -- a chunk outside the
+    // keys, like a surplus thread's, re-reads chunk 0 of the tile, which exists (key0 < end) -- and write_k_select stores
+    // zeros for it.  The selection waits until the write, so the loads stay in flight behind the step that issued them
+    // (issue_k's guarded fetches of a ragged tile are waited for on the spot, see above); costs a few VALU operations per
+    // chunk on full tiles.  attention_words_kernel uses the pair.
+    template <typename R, typename I = int>
+    __device__ __forceinline__ void issue_k_select(const R &rsrc, uint32_t so, I key0, I end) {
+#pragma unroll
+        for (int i = 0; i < K_PER_T; ++i) {
+            const bool ok = kok[i] && key0 + krow[i] < end;
+            rk[i] = fetch(rsrc, ok ? kgo[i] : 0u, so);
+        }
+    }
+    template <typename I = int>
+    __device__ __forceinline__ void write_k_select(elem *sK_tile, I key0, I end) const {
+#pragma unroll
+        for (int i = 0; i < K_PER_T; ++i)
+            if (kok[i])
+                *reinterpret_cast<uint4 *>(sK_tile + koff[i]) = key0 + krow[i] < end ? rk[i] : make_uint4(0, 0, 0, 0);
+    }
+
     // staging registers -> the LDS tile (never its pad columns / rows)
     __device__ __forceinline__ void write_k(elem *sK_tile) const {
 #pragma unroll
@@ -155,6 +177,41 @@ __device__ __forceinline__ void load_q_frags(typename Frag<T>::vec (&qf)[(D + 15
         if (d0 < D && qi_ok) v = *reinterpret_cast<const uint4 *>(qp + d0);
         qf[ks] = __builtin_bit_cast(vec, v);
     }
+}
+
+// ---- the score tile of the map kernels ----
+// attention_words_kernel uses it; attention_probs_kernel carries the same text written out in its `scores` lambda: calling
+// this helper there kept every instantiation's VGPR / SGPR / LDS numbers but renumbered registers and moved a few
+// instructions, and that kernel's code is pinned (profiles/attention_words_resources.txt).  A change here has to be made
+// there too.
+
+// Scores of the 64-key tile `ct` in LDS against one query per lane, in log2 units: S^T = K Q^T on v_mfma_f32_32x32x16, then
+// fma(S^T, scale * log2(e), slot) with `sB` the sample's bias row times log2(e) (-inf behind the last key: all the bounds
+// logic the scores need).  Lane (l31, hi) holds keys 64 ct + 32 kb + (r & 3) + 8 (r >> 2) + 4 hi of query l31 in s[kb][r].
+template <typename T, int D, int NT>
+__device__ __forceinline__ void qk_scores_biased(f32x16 (&s)[2], const typename Frag<T>::elem *sK, const float *sB,
+                                                 const typename Frag<T>::vec (&qf)[(D + 15) / 16], int ct, float scale_log2e,
+                                                 int l31, int hi) {
+    using F = Frag<T>;
+    using vec = typename F::vec;
+    using elem = typename F::elem;
+    constexpr int DK = KvStage<T, D, NT>::DK, K_STRIDE = KvStage<T, D, NT>::K_STRIDE;
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s[kb][r] = 0.0f;
+        const elem *kp = sK + (kb * 32 + l31) * K_STRIDE + hi * 8;
+#pragma unroll
+        for (int ks = 0; ks < DK; ++ks) s[kb] = F::mfma(*reinterpret_cast<const vec *>(kp + ks * 16), qf[ks], s[kb]);
+    }
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const f32x4 bv = *reinterpret_cast<const f32x4 *>(sB + ct * KV + kb * 32 + 8 * g + 4 * hi);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) s[kb][4 * g + e] = __builtin_fmaf(s[kb][4 * g + e], scale_log2e, bv[e]);
+        }
 }
 
 // ---- the single-buffered tile of attention_sets_kernel / attention_bias_kernel: V^T in 32-row blocks, nothing rides in

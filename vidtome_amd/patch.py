@@ -883,7 +883,7 @@ def _ip_key_sets(attn: torch.nn.Module, ip: "ip_adapter.Call", dt, C: int, panel
 
 
 def _ip_core(attn: torch.nn.Module, ip: "ip_adapter.Call", q: torch.Tensor, N: int, scale: float, panels: bool,
-             probs_to: Optional[torch.nn.Module] = None) -> torch.Tensor:
+             probs_to: Optional[torch.nn.Module] = None, words_to=None) -> torch.Tensor:
     """The decoupled cross-attention of an IP-Adapter call on query tokens q (B, Np, C), N <= Np of them meaningful: ONE
     launch over the text keys and every adapter's image keys -- vtm_attention_kv_sets, or vtm_attention_kv_sets_masked when
     the call carries region masks.  ``probs_to``: a registered block gets the map of the TEXT set, with its own softmax --
@@ -891,6 +891,8 @@ def _ip_core(attn: torch.nn.Module, ip: "ip_adapter.Call", q: torch.Tensor, N: i
     k, vt, sets, rows, table = _ip_key_sets(attn, ip, q.dtype, q.shape[-1], panels)
     if probs_to is not None:
         probs_to.attn2_probs = _probs_rows(q, k, attn.heads, N, ip.text.shape[1], scale)
+    if words_to is not None:                                   # (likewise the text set's)
+        add_word_maps(words_to, q, k, attn.heads, N, ip.text.shape[1], scale)
     if table is None:
         return _lib.attention_kv_sets(q, k, vt, attn.heads, N, sets, scale)
     return _lib.attention_kv_sets_masked(q, k, vt, attn.heads, N, sets, scale, rows, table)
@@ -968,9 +970,74 @@ def _module_path_probs(attn: torch.nn.Module, x: torch.Tensor, encoder_hidden_st
     return None
 
 
+def local_blend_of(block: torch.nn.Module):
+    """(LocalBlend, block name) when ``blend.register_local_blend`` selected the block, else None."""
+    return block.__dict__.get("vtm_local_blend")
+
+
+def _word_groups(words_to, B: int, N: int, K: int, device):
+    """What every route of ``add_word_maps`` starts from: the checks a registered block makes on its call -- the batch is
+    ``num_inputs`` groups, K is the weights' length, N the accumulator's token count -- then (lb, Fg, accumulator
+    (G, num_frames, N), the chunk's rows in it)."""
+    lb, name = words_to
+    if B % lb.num_inputs:
+        raise RuntimeError(f"vidtome_amd: LocalBlend on block '{name}': the batch of {B} samples is not {lb.num_inputs} "
+                           "groups of equal size")
+    if K != lb.K:
+        raise RuntimeError(f"vidtome_amd: LocalBlend on block '{name}': the conditioning has K = {K} tokens, the word "
+                           f"weights are for K = {lb.K}")
+    Fg = B // lb.num_inputs
+    return lb, Fg, lb.accumulator(N, device, name), lb.frame_rows(Fg, device)
+
+
+def add_word_maps(words_to, q: torch.Tensor, k: torch.Tensor, heads: int, N: int, Mk: int, scale: float,
+                  bias: Optional[torch.Tensor] = None, ctl=None) -> None:
+    """A registered block's contribution to its LocalBlend (``words_to`` = ``local_blend_of(block)``) from the q (B F, >= N,
+    C) / k (B F, >= Mk, C) rows the attn2 core reads: for every group g in ``words``, sum_j w_g[j] P[i, j] of the group's
+    samples added into the chunk's frame rows of the group's accumulator plane -- one vtm_attention_word_map launch on the
+    group's sample slice for what the kernel takes (16-bit rows, Mk <= 256), else the torch restatement on the same rows.
+    ``ctl`` (an injecting block under cross-attention control): an edited group's map is P_src . (M (a o w)) + P_own . (b o w),
+    two launches into the same rows -- (a) q and k of the SOURCE group's slice, (b) the group's own."""
+    with torch.no_grad():
+        lb, Fg, acc, rows_out = _word_groups(words_to, q.shape[0], N, Mk, q.device)
+        fused = q.dtype in (torch.float16, torch.bfloat16) and Mk <= _lib.PROBS_MAX_KEYS
+        weights = lb.weights_on(q.device)
+        edits = ctl[1] if ctl is not None else {}
+        for gi, g in enumerate(lb.groups):
+            own = slice(g * Fg, (g + 1) * Fg)
+            if g in edits and not edits[g].is_identity:
+                w_src, w_own = lb.edited_weights(edits[g], gi, q.device)
+                parts = [(slice(0, Fg), w_src), (own, w_own)]
+            else:
+                parts = [(own, weights[gi:gi + 1])]
+            for rows, w in parts:
+                b = None if bias is None else (bias[rows] if bias.shape[0] == q.shape[0] and q.shape[0] > 1 else bias)
+                if fused:
+                    _lib.attention_word_map(q[rows], k[rows], heads, N, Mk, scale, w, acc[gi], rows_out, True, b)
+                else:
+                    acc[gi].index_add_(0, rows_out, torch.matmul(_probs_torch(q[rows, :N], k[rows, :Mk], heads, scale, b), w[0]))
+
+
+def add_word_maps_module_path(words_to, attn: torch.nn.Module, x: torch.Tensor, encoder_hidden_states, attention_mask) -> None:
+    """The same contribution for an attn2 call that runs as the module's own forward: ``_module_path_probs``, then ``@ w``
+    per group.  Where that map is unavailable the call RAISES: a blend built on a silently missing block is wrong."""
+    lb, name = words_to
+    probs = _module_path_probs(attn, x, encoder_hidden_states, attention_mask)
+    if probs is None:
+        raise RuntimeError(f"vidtome_amd: LocalBlend on block '{name}': the map of this module-path attn2 call cannot be read "
+                           "(to_q / to_k are not plain projections onto the scores, or the mask is not an additive (B, 1, K) "
+                           "row)")
+    with torch.no_grad():
+        lb, Fg, acc, rows_out = _word_groups(words_to, probs.shape[0], probs.shape[1], probs.shape[2], probs.device)
+        weights = lb.weights_on(probs.device)
+        for gi, g in enumerate(lb.groups):
+            acc[gi].index_add_(0, rows_out, torch.matmul(probs[g * Fg:(g + 1) * Fg], weights[gi]))
+
+
 def norm_cross_attention_residual(norm: torch.nn.Module, attn: torch.nn.Module, hidden_states: torch.Tensor,
                                   encoder_hidden_states: torch.Tensor, ip: Optional["ip_adapter.Call"] = None,
-                                  attention_mask=None, probs_to: Optional[torch.nn.Module] = None) -> torch.Tensor:
+                                  attention_mask=None, probs_to: Optional[torch.nn.Module] = None,
+                                  words_to=None) -> torch.Tensor:
     """patch.py:171-185 for the plain case: ``attn2(norm2(hidden_states), encoder_hidden_states) + hidden_states`` with the
     query projection as a panel GEMM fed by the LayerNorm (vtm_layernorm_panels -> vtm_linear_panels: the normalised
     tokens are only ever read by to_q, so they are written once, as panels), k / v^T of the (few) conditioning tokens by the
@@ -982,7 +1049,9 @@ def norm_cross_attention_residual(norm: torch.nn.Module, attn: torch.nn.Module, 
     With ``attention_mask`` (the plain case only; ``fused_cross_ok`` has accepted its form, ``key_bias``) the core is
     vtm_attention_kv_bias; everything around it is the same.
     With ``probs_to`` (a block registered by ``maps.register_attention_maps``) one vtm_attention_probs launch beside the core
-    leaves ``probs_to.attn2_probs`` from the same q / k rows (an IP-Adapter call: the text set's); nothing else changes."""
+    leaves ``probs_to.attn2_probs`` from the same q / k rows (an IP-Adapter call: the text set's); nothing else changes.
+    With ``words_to`` (``local_blend_of`` a block registered by ``blend.register_local_blend``) the same rows feed
+    ``add_word_maps``."""
     B, N, C = hidden_states.shape
     heads, scale = attn.heads, _scale(attn, C)
     dt = hidden_states.dtype
@@ -1002,8 +1071,10 @@ def norm_cross_attention_residual(norm: torch.nn.Module, attn: torch.nn.Module, 
             o = _lib.attention_kv_bias(q, k, vt, heads, N, Mk, scale, bias)
         if probs_to is not None:
             probs_to.attn2_probs = _probs_rows(q, k, heads, N, Mk, scale, bias)
+        if words_to is not None:
+            add_word_maps(words_to, q, k, heads, N, Mk, scale, bias)
     else:
-        o = _ip_core(attn, ip, q, N, scale, True, probs_to)
+        o = _ip_core(attn, ip, q, N, scale, True, probs_to, words_to)
     op = _lib.to_panels(o.view(n, C))
     return _lib.linear_panels(op, n, wo, C, bo, resid=hs.view(n, C)).view(B, N, C)
 
@@ -1055,7 +1126,8 @@ def f32_cross_ok(block: torch.nn.Module, norm: torch.nn.Module, attn: torch.nn.M
 
 
 def norm_cross_attention_f32(norm: torch.nn.Module, attn: torch.nn.Module, hidden_states: torch.Tensor,
-                             encoder_hidden_states: torch.Tensor, probs_to: Optional[torch.nn.Module] = None) -> torch.Tensor:
+                             encoder_hidden_states: torch.Tensor, probs_to: Optional[torch.nn.Module] = None,
+                             words_to=None) -> torch.Tensor:
     """patch.py:171-185 for an fp32 block with ``fp32_projections``: ``attn2(norm2(h), encoder_hidden_states) + h`` as
     vtm_layernorm, the q GEMM, the k / V^T GEMMs of the conditioning tokens (padded to a multiple of 8 rows), the fp32
     attention core (whatever ``fp32_attention`` says: the module forward it replaces is fp32, and 77 keys keep it cheap)
@@ -1073,18 +1145,21 @@ def norm_cross_attention_f32(norm: torch.nn.Module, attn: torch.nn.Module, hidde
     o = _lib.attention_kv(q, k, vt, heads, N, Mk, scale)
     if probs_to is not None:                                  # (fp32 rows: the torch restatement)
         probs_to.attn2_probs = _probs_rows(q, k, heads, N, Mk, scale)
+    if words_to is not None:
+        add_word_maps(words_to, q, k, heads, N, Mk, scale)
     return _lib.linear_f32(o, None, None, None, N, *_linear(_out_linear(attn), f32)[:2], epilogue="resid", resid=hs,
                            out=torch.empty_like(hs))
 
 
 def cross_attention(attn: torch.nn.Module, x: torch.Tensor, encoder_hidden_states: Optional[torch.Tensor],
-                    attention_mask=None, probs_to: Optional[torch.nn.Module] = None, **kwargs) -> torch.Tensor:
+                    attention_mask=None, probs_to: Optional[torch.nn.Module] = None, words_to=None, **kwargs) -> torch.Tensor:
     """`self.attn2(norm_hidden_states, encoder_hidden_states=..., attention_mask=...)` (patch.py:178-183) -- the
     un-merged tokens attending to the conditioning (77 text tokens in SD).  The plain case (projection Linears, no
     mask, no processor kwargs) runs on vtm_attention_kv, the plain case with a per-key additive mask (``key_bias``) on
     vtm_attention_kv_bias, a recognised IP-Adapter call (``ip_cross_call``) on vtm_attention_kv_sets (with region masks:
     vtm_attention_kv_sets_masked), with library GEMMs around the core; everything else is the module's own forward.
-    ``probs_to``: a registered block gets ``attn2_probs`` on whichever of these paths the call takes."""
+    ``probs_to``: a registered block gets ``attn2_probs`` on whichever of these paths the call takes; ``words_to``
+    (``local_blend_of``): its LocalBlend gets the word maps likewise."""
     plain = (isinstance(encoder_hidden_states, torch.Tensor) and not kwargs
              and encoder_hidden_states.dim() == 3 and x.dtype in (torch.float16, torch.bfloat16)
              and fused_attention_ok(attn, x, self_attn=False)
@@ -1093,13 +1168,15 @@ def cross_attention(attn: torch.nn.Module, x: torch.Tensor, encoder_hidden_state
     if not plain and ip is None:
         if probs_to is not None:
             probs_to.attn2_probs = _module_path_probs(attn, x, encoder_hidden_states, attention_mask)
+        if words_to is not None:
+            add_word_maps_module_path(words_to, attn, x, encoder_hidden_states, attention_mask)
         return attn(x, encoder_hidden_states=encoder_hidden_states, attention_mask=attention_mask, **kwargs)
     B, N, C = x.shape
     heads, scale = attn.heads, _scale(attn, C)
     xq = F.pad(x, (0, 0, 0, -N % 8)) if N % 8 else x
     q = _apply_linear(attn.to_q, xq, x.dtype)
     if ip is not None:
-        o = _ip_core(attn, ip, q, N, scale, False, probs_to)
+        o = _ip_core(attn, ip, q, N, scale, False, probs_to, words_to)
     else:
         Mk = encoder_hidden_states.shape[1]
         enc = _pad_keys(encoder_hidden_states, x.dtype)
@@ -1112,6 +1189,8 @@ def cross_attention(attn: torch.nn.Module, x: torch.Tensor, encoder_hidden_state
             o = _lib.attention_kv_bias(q, k, vt, heads, N, Mk, scale, bias)
         if probs_to is not None:
             probs_to.attn2_probs = _probs_rows(q, k, heads, N, Mk, scale, bias)
+        if words_to is not None:
+            add_word_maps(words_to, q, k, heads, N, Mk, scale, bias)
     return _apply_linear(_out_linear(attn), o, o.dtype)[:, :N]
 
 
@@ -1175,7 +1254,7 @@ def _edited_probs(probs: torch.Tensor, rows: slice, src: slice, edit) -> None:
 
 
 def _controlled_core(attn: torch.nn.Module, q: torch.Tensor, N: int, enc: torch.Tensor, ctl, scale: float, panels: bool,
-                     probs_to: Optional[torch.nn.Module]) -> torch.Tensor:
+                     probs_to: Optional[torch.nn.Module], words_to=None) -> torch.Tensor:
     """The attn2 core of an injecting block on query rows q (B F, Np, C), N <= Np of them meaningful; samples are
     group-major, b = g * Fg + f, and the source of sample b is b % Fg.  k / v^T of EVERY sample come from the one projection
     call the block makes without the control.  Contiguous runs of unedited groups (no edit, or the identity) then run the
@@ -1216,12 +1295,14 @@ def _controlled_core(attn: torch.nn.Module, q: torch.Tensor, N: int, enc: torch.
         g = g1
     if probs_to is not None:
         probs_to.attn2_probs = probs
+    if words_to is not None:                                   # (the edited groups' maps: add_word_maps)
+        add_word_maps(words_to, q, k, heads, N, K, scale, ctl=ctl)
     return out
 
 
 def controlled_cross_attention_residual(block: torch.nn.Module, hidden_states: torch.Tensor,
                                         encoder_hidden_states: torch.Tensor, ctl, route: str,
-                                        probs_to: Optional[torch.nn.Module] = None) -> torch.Tensor:
+                                        probs_to: Optional[torch.nn.Module] = None, words_to=None) -> torch.Tensor:
     """patch.py:171-185 of an injecting block: ``attn2(norm2(h), enc) + h`` with the probabilities of the edited groups
     replaced as Prompt-to-Prompt replaces them (``_controlled_core``).  ``route`` is ``cross_control_route``'s answer: around
     the core stands what the uncontrolled block launches on that route."""
@@ -1236,12 +1317,12 @@ def controlled_cross_attention_residual(block: torch.nn.Module, hidden_states: t
             wo, bo = _panel_weight(_out_linear(attn))
             xp = _lib.layernorm_panels(hs, norm.weight, norm.bias, norm.eps)
             q = _lib.linear_panels(xp, n, wq, C, bq).view(B, N, C)
-            o = _controlled_core(attn, q, N, encoder_hidden_states, ctl, scale, True, probs_to)
+            o = _controlled_core(attn, q, N, encoder_hidden_states, ctl, scale, True, probs_to, words_to)
             return _lib.linear_panels(_lib.to_panels(o.view(n, C)), n, wo, C, bo, resid=hs.view(n, C)).view(B, N, C)
         x = layer_norm(norm, hidden_states)
         xq = F.pad(x, (0, 0, 0, -N % 8)) if N % 8 else x
         q = _apply_linear(attn.to_q, xq, x.dtype)
-        o = _controlled_core(attn, q, N, encoder_hidden_states, ctl, scale, False, probs_to)
+        o = _controlled_core(attn, q, N, encoder_hidden_states, ctl, scale, False, probs_to, words_to)
         return _apply_linear(_out_linear(attn), o, o.dtype)[:, :N] + hidden_states
 
 
@@ -1455,6 +1536,7 @@ def make_diffusers_tome_block(block_class: Type[torch.nn.Module]) -> Type[torch.
             cross_attention_kwargs = cross_attention_kwargs if cross_attention_kwargs is not None else {}
             if self.attn2 is not None:                                             # patch.py:171-185
                 maps = self if getattr(self, "vtm_attention_maps", False) else None   # maps.register_attention_maps
+                words = local_blend_of(self)                                       # blend.register_local_blend
                 control = cross_control(self)                                      # p2p.register_cross_attention_control
                 ip = None if self.use_ada_layer_norm or control is not None else ip_cross_call(
                     self.attn2, hidden_states, encoder_hidden_states, encoder_attention_mask, cross_attention_kwargs,
@@ -1463,21 +1545,22 @@ def make_diffusers_tome_block(block_class: Type[torch.nn.Module]) -> Type[torch.
                     route = cross_control_route(self, hidden_states, encoder_hidden_states, encoder_attention_mask,
                                                 cross_attention_kwargs, control)
                     hidden_states = controlled_cross_attention_residual(self, hidden_states, encoder_hidden_states, control,
-                                                                        route, probs_to=maps)
+                                                                        route, probs_to=maps, words_to=words)
                 elif ip is not None:                                               # IP-Adapter: text + image key sets
                     hidden_states = norm_cross_attention_residual(self.norm2, self.attn2, hidden_states, None, ip,
-                                                                  probs_to=maps)
+                                                                  probs_to=maps, words_to=words)
                 elif not self.use_ada_layer_norm and fused_cross_ok(self.norm2, self.attn2, hidden_states,
                                                                     encoder_hidden_states, encoder_attention_mask,
                                                                     cross_attention_kwargs):
                     hidden_states = norm_cross_attention_residual(self.norm2, self.attn2, hidden_states,
                                                                   encoder_hidden_states,
-                                                                  attention_mask=encoder_attention_mask, probs_to=maps)
+                                                                  attention_mask=encoder_attention_mask, probs_to=maps,
+                                                                  words_to=words)
                 elif not self.use_ada_layer_norm and f32_cross_ok(self, self.norm2, self.attn2, hidden_states,
                                                                   encoder_hidden_states, encoder_attention_mask,
                                                                   cross_attention_kwargs):
                     hidden_states = norm_cross_attention_f32(self.norm2, self.attn2, hidden_states, encoder_hidden_states,
-                                                             probs_to=maps)
+                                                             probs_to=maps, words_to=words)
                 else:
                     norm_hidden_states = (self.norm2(hidden_states, timestep) if self.use_ada_layer_norm
                                           else layer_norm(self.norm2, hidden_states))
@@ -1486,11 +1569,15 @@ def make_diffusers_tome_block(block_class: Type[torch.nn.Module]) -> Type[torch.
                         if maps is not None:
                             self.attn2_probs = _module_path_probs(self.attn2, norm_hidden_states, encoder_hidden_states,
                                                                   encoder_attention_mask)
+                        if words is not None:
+                            add_word_maps_module_path(words, self.attn2, norm_hidden_states, encoder_hidden_states,
+                                                      encoder_attention_mask)
                         attn_output = self.attn2(norm_hidden_states, encoder_hidden_states=encoder_hidden_states,
                                                  attention_mask=encoder_attention_mask, **cross_attention_kwargs)
                     else:
                         attn_output = cross_attention(self.attn2, norm_hidden_states, encoder_hidden_states,
-                                                      encoder_attention_mask, probs_to=maps, **cross_attention_kwargs)
+                                                      encoder_attention_mask, probs_to=maps, words_to=words,
+                                                      **cross_attention_kwargs)
                     hidden_states = attn_output + hidden_states
 
             if not self.use_ada_layer_norm_zero and fused_ff_ok(self.norm3, self.ff, hidden_states):   # patch.py:187-199
@@ -1637,6 +1724,7 @@ def remove_patch(model: torch.nn.Module):
             module.__dict__.pop("vtm_attention_maps", None)    # maps.register_attention_maps' switch ...
             module.__dict__.pop("attn2_probs", None)           # ... and the map of the block's last forward
             module.__dict__.pop("vtm_cross_control", None)     # p2p.register_cross_attention_control's schedule and edits
+            module.__dict__.pop("vtm_local_blend", None)       # blend.register_local_blend's accumulator
     _lib.release_workspaces()            # the cached scratch buffers of the patched path (re-created on demand)
     return roots[-1]                     # the reference returns its loop variable: the last tree walked
 
