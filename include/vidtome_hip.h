@@ -655,6 +655,43 @@ int vtm_cfg_ddim(const void *x, const void *eps_uncond, const void *eps_cond, in
                  vtm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * vtm_guided_step -- the whole caller-side step of ONE CHUNK in one launch (generate.py:239-311, invert.py:181-211): the
+ * group slice `eps.chunk(batch_size)[-2:]` (generate.py:276), classifier-free guidance (generate.py:278), Diffusers'
+ * guidance rescale (`rescale_noise_cfg`), the prediction type, the DDIM update of `pred_next_x` (generate.py:281-311) with
+ * the stochastic term of eta > 0, and the store of the chunk's frames into the whole-video latents (`noises[chunk] = ...`
+ * followed by the whole-video update).  vtm_cfg_ddim above stays the reference's own expression (epsilon, eta = 0, rounded
+ * per operation); this call computes in fp32 and rounds every stored value once.
+ *   model_out  (groups * F, E) contiguous, group-major: sample g * F + f; E = C * H * W of a latent frame.
+ *   g_uncond, g_cond  the two groups (under PnP groups - 2 and groups - 1); g_cond = -1: no guidance, m = model_out[g_uncond]
+ *              (inversion: one group).
+ *   x, x_out   whole-video latents (n_frames, E); chunk frame f is row frame_ids[f] (DEVICE int32, F entries, distinct,
+ *              inside the video -- the caller's business), or row f when frame_ids is NULL.  x_out may BE x.
+ *   noise, eps_out, x0_out  chunk-local (F, E), optional; noise is required exactly when sigma != 0 (and not read otherwise).
+ *              At least one of x_out, eps_out, x0_out is not NULL.
+ * Per frame and element, in fp32:
+ *     m  = m_u + guidance * (m_c - m_u)                            (g_cond >= 0)
+ *     m  = m * (rescale * std(m_c) / std(m) + 1 - rescale)         (rescale > 0)
+ *     VTM_PRED_EPSILON : x0 = (x - sqrt_beta * m) / sqrt_alpha       eps = m
+ *     VTM_PRED_V       : x0 = sqrt_alpha * x - sqrt_beta * m         eps = sqrt_alpha * m + sqrt_beta * x
+ *     VTM_PRED_SAMPLE  : x0 = m                                      eps = (x - sqrt_alpha * x0) / sqrt_beta
+ *     x_out = c_x0 * x0 + c_eps * eps + sigma * noise ;   eps_out = eps ;   x0_out = x0
+ * std is torch's default (unbiased) over the frame's E fp32 values, two-pass (mean, then squared deviations); std(m) == 0
+ * gives what IEEE arithmetic gives.  Sampling from a_t to a_prev: sqrt_alpha = sqrt(a_t), sqrt_beta = sqrt(1 - a_t),
+ * c_x0 = sqrt(a_prev), c_eps = sqrt(1 - a_prev - sigma^2); inversion is the same call with the two levels exchanged.
+ * rescale == 0: one elementwise grid-stride launch.  rescale > 0 (needs g_cond >= 0 and E >= 2): one workgroup per frame,
+ * fixed reduction order -- a frame's bits depend neither on the other frames of the launch nor on the run, nor on whether
+ * 16-byte accesses were possible (E a multiple of 16 bytes and every pointer 16-byte aligned) or not.  Any E >= 1,
+ * F <= 2^20; F == 0 is VTM_OK.  One launch, no workspace, no atomics.  On a bad argument (VTM_EINVAL) nothing is launched.
+ * ---------------------------------------------------------------------------------------------- */
+#define VTM_PRED_EPSILON 0
+#define VTM_PRED_V       1
+#define VTM_PRED_SAMPLE  2
+int vtm_guided_step(const void *x, const void *model_out, const void *noise, int dtype, int64_t F, int64_t E,
+                    int64_t groups, int64_t g_uncond, int64_t g_cond, const int32_t *frame_ids, int pred_type,
+                    float guidance, float rescale, float sqrt_alpha, float sqrt_beta, float c_x0, float c_eps,
+                    float sigma, void *x_out, void *eps_out, void *x0_out, vtm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * vtm_layernorm -- the block's norm1 (vidtome/patch.py:139-146, the plain torch.nn.LayerNorm branch
  * `norm_hidden_states = self.norm1(hidden_states)`), the first operation of the patched segment and the
  * producer of the matching metric; also usable for norm2 / norm3 (patch.py:173-176, 187).

@@ -113,6 +113,8 @@ _SIGNATURES = {
     "vtm_ff_geglu": ([_vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _int, _vp, _vp], _int),
     "vtm_linear_panels": ([_vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _int, _vp, _i64, _vp], _int),
     "vtm_cfg_ddim": ([_vp, _vp, _vp, _int, _i64, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _vp], _int),
+    "vtm_guided_step": ([_vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _vp, _int, _f32, _f32, _f32, _f32, _f32, _f32, _f32,
+                         _vp, _vp, _vp, _vp], _int),
     "vtm_layernorm": ([_vp, _vp, _vp, _int, _i64, _i64, _f32, _vp, _vp], _int),
     "vtm_geglu": ([_vp, _int, _i64, _i64, _vp, _vp], _int),
     "vtm_linear_rows": ([_vp, _i64, _vp, _i64, _int, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64,
@@ -694,6 +696,117 @@ def cfg_ddim(x: Optional[torch.Tensor], eps_uncond: torch.Tensor, eps_cond: Opti
                               float(a), float(b), float(c), float(d), _ptr(eps_out), _ptr(x_out), _stream()),
            "vtm_cfg_ddim")
     return (x_out, eps_out) if want_eps else (x_out if x is not None else eps_out)
+
+
+PRED_EPSILON, PRED_V, PRED_SAMPLE = 0, 1, 2     # include/vidtome_hip.h VTM_PRED_*
+GUIDED_STEP_THREADS = 1024                      # csrc/guided_step.hip: threads of the per-frame (rescale) workgroup
+
+
+def guided_step_chunk(dtype: torch.dtype) -> int:
+    """Elements of a 16-byte chunk, the unit csrc/guided_step.hip moves and hands to a lane (4 fp32, 8 fp16 / bf16)."""
+    return 16 // torch.empty((), dtype=dtype).element_size()
+
+
+def _frame_rows(frame_ids, n_frames: int, who: str):
+    """frame_ids of a guided step -> (first row, device ids or None, F).  A host sequence / CPU tensor is checked here (range,
+    duplicates); an ascending run start, start + 1, ... needs no ids on the device at all: it is a row offset.  A device
+    int32 tensor is taken as it is."""
+    if frame_ids is None:
+        return 0, None, n_frames
+    if isinstance(frame_ids, torch.Tensor) and frame_ids.is_cuda:
+        if frame_ids.dtype != torch.int32 or frame_ids.dim() != 1 or not frame_ids.is_contiguous():
+            raise RuntimeError(f"{who}: device frame_ids must be a contiguous 1-D int32 tensor")
+        return 0, frame_ids, frame_ids.numel()
+    if isinstance(frame_ids, torch.Tensor):
+        if frame_ids.dim() != 1 or frame_ids.dtype.is_floating_point or frame_ids.dtype == torch.bool:
+            raise RuntimeError(f"{who}: frame_ids must be a 1-D integer tensor")
+        frame_ids = frame_ids.tolist()
+    ids = [int(i) for i in frame_ids]
+    if any(i != j for i, j in zip(ids, frame_ids)):
+        raise RuntimeError(f"{who}: frame_ids must be integers")
+    if any(not 0 <= i < n_frames for i in ids):
+        raise RuntimeError(f"{who}: frame_ids outside [0, {n_frames})")
+    if len(set(ids)) != len(ids):
+        raise RuntimeError(f"{who}: frame_ids holds a frame twice")
+    if ids and ids == list(range(ids[0], ids[0] + len(ids))):
+        return ids[0], None, len(ids)
+    return 0, ids, len(ids)
+
+
+@_on_device
+def guided_step(x: torch.Tensor, model_out: torch.Tensor, sqrt_alpha: float, sqrt_beta: float, c_x0: float, c_eps: float,
+                sigma: float = 0.0, *, groups: int = 2, g_uncond: Optional[int] = None, g_cond: Optional[int] = None,
+                frame_ids=None, pred_type: int = PRED_EPSILON, guidance: float = 7.5, rescale: float = 0.0,
+                noise: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, want_x: bool = True,
+                want_eps: bool = False, want_x0: bool = False):
+    """One chunk's guided DDIM step (vtm_guided_step, include/vidtome_hip.h): ``x`` (n_frames, ...) the whole-video latents,
+    ``model_out`` (groups * F, ...) the UNet output of the chunk, group-major; the chunk's frame f is row ``frame_ids[f]`` of x
+    (a host sequence / CPU tensor, checked and uploaded unless it is an ascending run; or a device int32 tensor, taken as it
+    is; None: the chunk is the whole video).  ``g_uncond`` / ``g_cond`` default to the last two groups (one group: no
+    guidance, g_cond = -1).  ``out`` receives x' in the chunk's rows and may be x; None allocates a new tensor when the chunk
+    is the whole video and otherwise means x (in place: a new tensor would have rows that nobody wrote).  Returns
+    (out or None, eps or None, x0 or None) -- eps / x0 chunk-local (F, ...), allocated when asked for."""
+    who = "guided_step"
+    groups = int(groups)
+    if g_uncond is None:
+        g_uncond = max(groups - 2, 0)
+    if g_cond is None:
+        g_cond = groups - 1 if groups >= 2 else -1
+    g_uncond, g_cond, pred_type = int(g_uncond), int(g_cond), int(pred_type)
+    for t, name in ((x, "x"), (model_out, "model_out")):
+        if not isinstance(t, torch.Tensor) or t.dim() < 2 or t.dtype not in _DT:
+            raise RuntimeError(f"{who}: {name} must be a (frames, ...) fp16 / bf16 / fp32 tensor")
+    if pred_type not in (PRED_EPSILON, PRED_V, PRED_SAMPLE):
+        raise RuntimeError(f"{who}: unknown pred_type {pred_type}")
+    if groups < 1 or not 0 <= g_uncond < groups or not -1 <= g_cond < groups:
+        raise RuntimeError(f"{who}: groups = {groups}, g_uncond = {g_uncond}, g_cond = {g_cond}: a group index outside [0, groups)")
+    if g_uncond == g_cond:
+        raise RuntimeError(f"{who}: g_uncond == g_cond == {g_cond}")
+    sigma, rescale = float(sigma), float(rescale)
+    if not rescale >= 0.0:
+        raise RuntimeError(f"{who}: rescale = {rescale} is negative or NaN")
+    first, ids, F = _frame_rows(frame_ids, x.shape[0], who)
+    E = math.prod(x.shape[1:])
+    if model_out.shape[0] != groups * F or math.prod(model_out.shape[1:]) != E:
+        raise RuntimeError(f"{who}: model_out {tuple(model_out.shape)} is not ({groups} groups * {F} frames, {E} elements)")
+    if model_out.dtype != x.dtype:
+        raise RuntimeError(f"{who}: dtype mismatch: x {x.dtype}, model_out {model_out.dtype}")
+    if rescale > 0.0 and (g_cond < 0 or E < 2):
+        raise RuntimeError(f"{who}: rescale > 0 needs a conditional group and frames of at least 2 elements")
+    if sigma != 0.0 and noise is None:
+        raise RuntimeError(f"{who}: sigma != 0 needs noise")
+    if noise is not None and (not isinstance(noise, torch.Tensor) or noise.dtype != x.dtype or noise.numel() != F * E
+                              or noise.shape[0] != F):
+        raise RuntimeError(f"{who}: noise must be a ({F}, ...) {x.dtype} tensor of the chunk's {F * E} elements")
+    if not (want_x or want_eps or want_x0):
+        raise RuntimeError(f"{who}: no output asked for")
+    if out is not None and (not isinstance(out, torch.Tensor) or out.shape != x.shape or out.dtype != x.dtype
+                            or out.device != x.device):
+        raise RuntimeError(f"{who}: out must be a tensor like x (it may be x)")
+    if E < 1 and F:
+        raise RuntimeError(f"{who}: empty frames")
+    _req(x, "x"), _req(model_out, "model_out")
+    for t, name in ((noise, "noise"), (out, "out"), (ids if isinstance(ids, torch.Tensor) else None, "frame_ids")):
+        if t is not None and _req(t, name).device != x.device:
+            raise RuntimeError(f"{who}: {name} lives on {t.device}, x on {x.device}")
+    if model_out.device != x.device:
+        raise RuntimeError(f"{who}: model_out lives on {model_out.device}, x on {x.device}")
+    if isinstance(ids, list):
+        ids = torch.tensor(ids, dtype=torch.int32, device=x.device)
+    if want_x and out is None:
+        out = torch.empty_like(x) if (frame_ids is None) else x
+    local = (F,) + tuple(model_out.shape[1:])
+    eps = torch.empty(local, dtype=x.dtype, device=x.device) if want_eps else None
+    x0 = torch.empty(local, dtype=x.dtype, device=x.device) if want_x0 else None
+    if F == 0:
+        return (out if want_x else None), eps, x0
+    skip = first * E * x.element_size()
+    _check(lib().vtm_guided_step(x.data_ptr() + skip, model_out.data_ptr(), _ptr(noise if sigma != 0.0 else None),
+                                 dtype_code(x), F, E, groups, g_uncond, g_cond, _ptr(ids), pred_type, float(guidance), rescale,
+                                 float(sqrt_alpha), float(sqrt_beta), float(c_x0), float(c_eps), sigma,
+                                 out.data_ptr() + skip if want_x else None, _ptr(eps), _ptr(x0), _stream()),
+           "vtm_guided_step")
+    return (out if want_x else None), eps, x0
 
 
 @_on_device
