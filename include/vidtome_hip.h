@@ -692,6 +692,44 @@ int vtm_guided_step(const void *x, const void *model_out, const void *noise, int
                     float sigma, void *x_out, void *eps_out, void *x0_out, vtm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * vtm_solver_step -- the caller-side step of ONE CHUNK in one launch for a MULTISTEP solver (DPM-Solver++ 2M / 3M,
+ * sampler.GuidedDPMSolver) and for guidance with more than two terms: a weighted sum over up to VTM_SOLVER_MAX_GROUPS groups
+ * of the UNet output (classifier-free guidance is the weights (1 - s, s); InstructPix2Pix and perturbed-attention guidance
+ * are three weights), the guidance rescale, the prediction type, and a LINEAR update from the latents, the clean-sample
+ * prediction and the clean-sample predictions of the two previous steps, which live per FRAME in whole-video fp32 buffers --
+ * so a video can be stepped chunk by chunk, under any chunking, on any stream.  Sizes, dtypes, frame_ids, the prediction
+ * types and the launch shapes are vtm_guided_step's.
+ *   model_out  (groups * F, E) contiguous, group-major: sample g * F + f.
+ *   w          HOST array of `groups` weights, copied into the kernel arguments.  A group of weight 0 is never read (a PnP
+ *              source group full of NaN stays out).
+ *   g_ref      the group whose per-frame standard deviation the rescale restores (rescale > 0: in range, w[g_ref] != 0,
+ *              E >= 2); ignored when rescale == 0.
+ *   x, x_out   whole-video latents (n_frames, E) in `dtype`; chunk frame f is row frame_ids[f] (DEVICE int32), or row f when
+ *              frame_ids is NULL.  x_out may BE x.
+ *   h1, h2, h_out  whole-video FP32 (n_frames, E), rows as x's: the clean-sample predictions of the previous step and of the
+ *              one before it, and where this step's goes (16-bit history would compound one rounding per step).  Each may be
+ *              NULL; h_out may BE h1 or h2 (every element is read before it is written, by the same thread).
+ *   noise, eps_out, x0_out  chunk-local (F, E) in `dtype`, optional.
+ * Per frame and element, in fp32, every sum started from 0 and taken in the order written:
+ *     m     = sum over g = 0 .. groups - 1 with w[g] != 0 of  w[g] * model_out[g * F + f]
+ *     m     = m * (rescale * std(model_out[g_ref * F + f]) / std(m) + 1 - rescale)                  (rescale > 0)
+ *     x0, eps from m, x, sqrt_alpha, sqrt_beta by pred_type as in vtm_guided_step
+ *     x_out = c_x * x + c_x0 * x0 + c_h1 * h1 + c_h2 * h2 + c_noise * noise
+ *     h_out = x0 (fp32, not rounded) ;   eps_out = eps ;   x0_out = x0
+ * A term of x_out whose coefficient is exactly 0 is absent: its operand is not read (h1, h2, noise may then be NULL; they are
+ * required otherwise) and cannot put a NaN into the sum.  std is vtm_guided_step's: unbiased, two-pass, in the fixed order of
+ * a 1024-thread workgroup per frame, so a frame's bits depend neither on the other frames of the launch nor on the run, nor
+ * on whether 16-byte accesses were possible (E a multiple of 16 bytes of `dtype` and every pointer 16-byte aligned).
+ * At least one of x_out, h_out, eps_out, x0_out is not NULL.  Any E >= 1, F <= 2^20; F == 0 is VTM_OK.  One launch, no
+ * workspace, no atomics.  On a bad argument (VTM_EINVAL) nothing is launched.
+ * ---------------------------------------------------------------------------------------------- */
+#define VTM_SOLVER_MAX_GROUPS 8
+int vtm_solver_step(const void *x, const void *model_out, const void *noise, const float *h1, const float *h2, int dtype,
+                    int64_t F, int64_t E, int64_t groups, const float *w, int64_t g_ref, const int32_t *frame_ids,
+                    int pred_type, float rescale, float sqrt_alpha, float sqrt_beta, float c_x, float c_x0, float c_h1,
+                    float c_h2, float c_noise, void *x_out, float *h_out, void *eps_out, void *x0_out, vtm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * vtm_layernorm -- the block's norm1 (vidtome/patch.py:139-146, the plain torch.nn.LayerNorm branch
  * `norm_hidden_states = self.norm1(hidden_states)`), the first operation of the patched segment and the
  * producer of the matching metric; also usable for norm2 / norm3 (patch.py:173-176, 187).

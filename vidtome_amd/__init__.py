@@ -9,10 +9,10 @@ from .patch import apply_patch, remove_patch, update_patch, collect_from_patch
 from .maps import register_attention_maps, unregister_attention_maps
 from .p2p import CrossEdit, register_cross_attention_control, unregister_cross_attention_control
 from .blend import LocalBlend, register_local_blend, unregister_local_blend
-from .sampler import GuidedDDIM
+from .sampler import GuidedDDIM, GuidedDPMSolver
 
 __all__ = ["merge", "patch", "apply_patch", "remove_patch", "update_patch", "collect_from_patch",
            "register_attention_maps", "unregister_attention_maps",
            "CrossEdit", "register_cross_attention_control", "unregister_cross_attention_control",
            "LocalBlend", "register_local_blend", "unregister_local_blend",
-           "GuidedDDIM"]
+           "GuidedDDIM", "GuidedDPMSolver"]

@@ -115,6 +115,8 @@ _SIGNATURES = {
     "vtm_cfg_ddim": ([_vp, _vp, _vp, _int, _i64, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _vp], _int),
     "vtm_guided_step": ([_vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _vp, _int, _f32, _f32, _f32, _f32, _f32, _f32, _f32,
                          _vp, _vp, _vp, _vp], _int),
+    "vtm_solver_step": ([_vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, ctypes.POINTER(_f32), _i64, _vp, _int, _f32, _f32, _f32,
+                         _f32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp], _int),
     "vtm_layernorm": ([_vp, _vp, _vp, _int, _i64, _i64, _f32, _vp, _vp], _int),
     "vtm_geglu": ([_vp, _int, _i64, _i64, _vp, _vp], _int),
     "vtm_linear_rows": ([_vp, _i64, _vp, _i64, _int, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64,
@@ -806,6 +808,91 @@ def guided_step(x: torch.Tensor, model_out: torch.Tensor, sqrt_alpha: float, sqr
                                  float(sqrt_alpha), float(sqrt_beta), float(c_x0), float(c_eps), sigma,
                                  out.data_ptr() + skip if want_x else None, _ptr(eps), _ptr(x0), _stream()),
            "vtm_guided_step")
+    return (out if want_x else None), eps, x0
+
+
+SOLVER_STEP_THREADS = 1024                      # csrc/solver_step.hip: threads of the per-frame (rescale) workgroup
+SOLVER_MAX_GROUPS = 8                           # include/vidtome_hip.h VTM_SOLVER_MAX_GROUPS
+
+
+@_on_device
+def solver_step(x: torch.Tensor, model_out: torch.Tensor, weights, sqrt_alpha: float, sqrt_beta: float, c_x: float, c_x0: float,
+                c_h1: float = 0.0, c_h2: float = 0.0, c_noise: float = 0.0, *, h1: Optional[torch.Tensor] = None,
+                h2: Optional[torch.Tensor] = None, h_out: Optional[torch.Tensor] = None, g_ref: Optional[int] = None,
+                frame_ids=None, pred_type: int = PRED_EPSILON, rescale: float = 0.0, noise: Optional[torch.Tensor] = None,
+                out: Optional[torch.Tensor] = None, want_x: bool = True, want_eps: bool = False, want_x0: bool = False):
+    """One chunk's step of a multistep solver (vtm_solver_step, include/vidtome_hip.h): ``x``, ``model_out``, ``frame_ids``,
+    ``noise``, ``out`` and the result (out or None, eps or None, x0 or None) as in ``guided_step``.  ``weights``: one host
+    number per group of model_out (their count is the number of groups; a group of weight 0 is never read); ``g_ref``: the
+    group whose per-frame std ``rescale`` restores (default: the last).  ``h1`` / ``h2``: whole-video fp32 tensors shaped like
+    x with the clean-sample predictions of the two previous steps, needed where ``c_h1`` / ``c_h2`` is not 0; ``h_out``: where
+    this step's goes (it may be h1 or h2)."""
+    who = "solver_step"
+    weights = [float(v) for v in weights]
+    groups, pred_type = len(weights), int(pred_type)
+    g_ref = groups - 1 if g_ref is None else int(g_ref)
+    for t, name in ((x, "x"), (model_out, "model_out")):
+        if not isinstance(t, torch.Tensor) or t.dim() < 2 or t.dtype not in _DT:
+            raise RuntimeError(f"{who}: {name} must be a (frames, ...) fp16 / bf16 / fp32 tensor")
+    if pred_type not in (PRED_EPSILON, PRED_V, PRED_SAMPLE):
+        raise RuntimeError(f"{who}: unknown pred_type {pred_type}")
+    if not 1 <= groups <= SOLVER_MAX_GROUPS or not all(math.isfinite(v) for v in weights):
+        raise RuntimeError(f"{who}: {groups} weights {weights}: 1 .. {SOLVER_MAX_GROUPS} finite numbers, one per group")
+    c_x, c_x0, c_h1, c_h2, c_noise, rescale = (float(v) for v in (c_x, c_x0, c_h1, c_h2, c_noise, rescale))
+    if not rescale >= 0.0:
+        raise RuntimeError(f"{who}: rescale = {rescale} is negative or NaN")
+    first, ids, F = _frame_rows(frame_ids, x.shape[0], who)
+    E = math.prod(x.shape[1:])
+    if model_out.shape[0] != groups * F or math.prod(model_out.shape[1:]) != E:
+        raise RuntimeError(f"{who}: model_out {tuple(model_out.shape)} is not ({groups} groups * {F} frames, {E} elements)")
+    if model_out.dtype != x.dtype:
+        raise RuntimeError(f"{who}: dtype mismatch: x {x.dtype}, model_out {model_out.dtype}")
+    if rescale > 0.0 and (not 0 <= g_ref < groups or _f32_round(weights[g_ref]) == 0.0 or E < 2):
+        raise RuntimeError(f"{who}: rescale > 0 needs g_ref = {g_ref} inside [0, {groups}) with a non-zero weight, and frames of "
+                           "at least 2 elements")
+    if c_noise != 0.0 and noise is None:
+        raise RuntimeError(f"{who}: c_noise != 0 needs noise")
+    if noise is not None and (not isinstance(noise, torch.Tensor) or noise.dtype != x.dtype or noise.numel() != F * E
+                              or noise.shape[0] != F):
+        raise RuntimeError(f"{who}: noise must be a ({F}, ...) {x.dtype} tensor of the chunk's {F * E} elements")
+    for t, name, c in ((h1, "h1", c_h1), (h2, "h2", c_h2), (h_out, "h_out", 0.0)):
+        if t is None and c != 0.0:
+            raise RuntimeError(f"{who}: c_{name} != 0 needs {name}")
+        if t is not None and (not isinstance(t, torch.Tensor) or t.shape != x.shape or t.dtype != torch.float32
+                              or t.device != x.device):
+            raise RuntimeError(f"{who}: {name} must be an fp32 tensor shaped like x, on its device")
+    if not (want_x or want_eps or want_x0 or h_out is not None):
+        raise RuntimeError(f"{who}: no output asked for")
+    if out is not None and (not isinstance(out, torch.Tensor) or out.shape != x.shape or out.dtype != x.dtype
+                            or out.device != x.device):
+        raise RuntimeError(f"{who}: out must be a tensor like x (it may be x)")
+    if E < 1 and F:
+        raise RuntimeError(f"{who}: empty frames")
+    _req(x, "x"), _req(model_out, "model_out")
+    for t, name in ((noise, "noise"), (out, "out"), (h1, "h1"), (h2, "h2"), (h_out, "h_out"),
+                    (ids if isinstance(ids, torch.Tensor) else None, "frame_ids")):
+        if t is not None and _req(t, name).device != x.device:
+            raise RuntimeError(f"{who}: {name} lives on {t.device}, x on {x.device}")
+    if model_out.device != x.device:
+        raise RuntimeError(f"{who}: model_out lives on {model_out.device}, x on {x.device}")
+    if isinstance(ids, list):
+        ids = torch.tensor(ids, dtype=torch.int32, device=x.device)
+    if want_x and out is None:
+        out = torch.empty_like(x) if (frame_ids is None) else x
+    local = (F,) + tuple(model_out.shape[1:])
+    eps = torch.empty(local, dtype=x.dtype, device=x.device) if want_eps else None
+    x0 = torch.empty(local, dtype=x.dtype, device=x.device) if want_x0 else None
+    if F == 0:
+        return (out if want_x else None), eps, x0
+    skip, hskip = first * E * x.element_size(), first * E * 4
+
+    def hist(t, used=True):
+        return t.data_ptr() + hskip if (t is not None and used) else None
+    _check(lib().vtm_solver_step(x.data_ptr() + skip, model_out.data_ptr(), _ptr(noise if c_noise != 0.0 else None),
+                                 hist(h1, c_h1 != 0.0), hist(h2, c_h2 != 0.0), dtype_code(x), F, E, groups,
+                                 (_f32 * groups)(*weights), g_ref, _ptr(ids), pred_type, rescale, float(sqrt_alpha),
+                                 float(sqrt_beta), c_x, c_x0, c_h1, c_h2, c_noise, out.data_ptr() + skip if want_x else None,
+                                 hist(h_out), _ptr(eps), _ptr(x0), _stream()), "vtm_solver_step")
     return (out if want_x else None), eps, x0
 
 

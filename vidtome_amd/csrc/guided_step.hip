@@ -19,6 +19,7 @@
 //                  on E alone, so a frame's bits depend neither on the other frames of the launch nor on the run.
 // One launch, no workspace, no atomics.
 #include "common.h"
+#include "step_chunk.h"
 
 #include <algorithm>
 
@@ -35,41 +36,10 @@ struct Step {
     float guidance, rescale, sqrt_alpha, sqrt_beta, c_x0, c_eps, sigma;
 };
 
-template <typename T> __device__ __forceinline__ T from_f32(float v);
-template <> __device__ __forceinline__ float from_f32<float>(float v) { return v; }
-template <> __device__ __forceinline__ __half from_f32<__half>(float v) { return __float2half_rn(v); }
-template <> __device__ __forceinline__ vtm_bf16 from_f32<vtm_bf16>(float v) { return __float2bfloat16(v); }
-
-// the n <= N elements of the chunk at p as fp32 (elements past n: 0, never used)
-template <typename T, bool VEC>
-__device__ __forceinline__ void load_chunk(const T *p, int n, float *v) {
-    constexpr int N = 16 / sizeof(T);
-    if constexpr (VEC) {
-        const uint4 raw = *reinterpret_cast<const uint4 *>(p);
-        const T *e = reinterpret_cast<const T *>(&raw);
-#pragma unroll
-        for (int k = 0; k < N; ++k) v[k] = vtm::to_f32(e[k]);
-    } else {
-#pragma unroll
-        for (int k = 0; k < N; ++k) v[k] = k < n ? vtm::to_f32(p[k]) : 0.0f;
-    }
-}
-
-template <typename T, bool VEC>
-__device__ __forceinline__ void store_chunk(T *p, int n, const float *v) {
-    constexpr int N = 16 / sizeof(T);
-    if constexpr (VEC) {
-        uint4 raw;
-        T *e = reinterpret_cast<T *>(&raw);
-#pragma unroll
-        for (int k = 0; k < N; ++k) e[k] = from_f32<T>(v[k]);
-        *reinterpret_cast<uint4 *>(p) = raw;
-    } else {
-#pragma unroll
-        for (int k = 0; k < N; ++k)
-            if (k < n) p[k] = from_f32<T>(v[k]);
-    }
-}
+using vtm::aligned16;
+using vtm::from_f32;
+using vtm::load_chunk;
+using vtm::store_chunk;
 
 // m = m_u + guidance (m_c - m_u): the same three operations wherever m is needed, so every pass sees the same m
 __device__ __forceinline__ float guide(const Step &s, float mu, float mc) { return s.guided ? mu + s.guidance * (mc - mu) : mu; }
@@ -212,8 +182,6 @@ __global__ __launch_bounds__(GS_THREADS) void guided_step_rescale_kernel(const T
                                  x0_out ? x0_out + local : nullptr, n);
     }
 }
-
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 

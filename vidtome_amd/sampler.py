@@ -15,6 +15,9 @@ The reference does this in torch on the caller's stream (generate.py:239-311, in
 ``run_step(..., streams=...)``.  Beyond the reference's expression (epsilon prediction, eta = 0; kept bit for bit by
 ``_lib.cfg_ddim``) it covers what Diffusers' DDIM step covers: v-prediction and sample prediction, ``guidance_rescale``
 (``rescale_noise_cfg``: per-frame standard deviations) and ``eta > 0``.  Computed in fp32, every stored value rounded once.
+
+``GuidedDPMSolver`` is the same loop for multistep DPM-Solver++ (fewer UNet evaluations) and for guidance with a weight per
+group (vtm_solver_step, csrc/solver_step.hip): its history lives per frame, so it too is stepped chunk by chunk.
 """
 from __future__ import annotations
 
@@ -126,6 +129,224 @@ class GuidedDDIM:
             noise = torch.randn((F,) + tuple(model_out.shape[1:]), dtype=x.dtype, device=x.device, generator=generator)
         res = _lib.guided_step(x, model_out, sqrt_alpha, sqrt_beta, c_x0, c_eps, sigma, groups=groups, frame_ids=frame_ids,
                                pred_type=PREDICTION_TYPES[self.prediction_type], guidance=self.guidance_scale,
+                               rescale=self.guidance_rescale if groups >= 2 else 0.0, noise=noise, out=out,
+                               want_eps="eps" in want, want_x0="x0" in want)
+        asked = dict(eps=res[1], x0=res[2])
+        return res[0] if not want else (res[0],) + tuple(asked[w] for w in want)
+
+
+ALGORITHM_TYPES = ("dpmsolver++", "sde-dpmsolver++")
+
+
+class GuidedDPMSolver:
+    """Multistep DPM-Solver++ (Lu et al.; second order = midpoint) over ``alphas_cumprod`` (indexed by timestep) along
+    ``timesteps`` (descending), one vtm_solver_step launch per chunk.  It solves the ODE DDIM solves, so it starts from the same
+    DDIM-inverted latents, in 20 to 25 steps.  The contract is the formulas below (float64 on the host, folded into five
+    coefficients; the launch computes in fp32); nothing is claimed about the bits of a Diffusers release.
+
+        sampler = GuidedDPMSolver.from_scheduler(pipe.scheduler, solver_order=2, guidance_scale=7.5)
+        sampler.prepare(x)                                       # the history buffers, before any side stream touches them
+        for i, t in enumerate(sampler.timesteps):
+            def process_chunk(chunk):
+                unet_out = unet(torch.cat([x[chunk]] * groups), t, ...).sample
+                sampler.step(x, unet_out, i, groups=groups, frame_ids=chunk, out=x_next)
+            scheduler.run_step(unet, chunks, len(x), process_chunk, streams=streams)
+            x, x_next = x_next, x
+
+    Levels: a_k = alphas_cumprod[timesteps[k]] for k < n, a_n = final_alpha_cumprod (1.0: the last step lands on sigma = 0);
+    alpha = sqrt(a), sigma = sqrt(1 - a), lambda = log(alpha) - log(sigma).  Step i goes from level i (alpha, sigma) to level
+    i + 1 (alpha', sigma'); h = lambda_{i+1} - lambda_i, h0 = lambda_i - lambda_{i-1}, h1 = lambda_{i-1} - lambda_{i-2},
+    r0 = h0 / h, r1 = h1 / h; m0, m1, m2 are the clean-sample predictions of steps i, i - 1, i - 2.
+
+        order 1:  x' = (sigma'/sigma) x - alpha' (e^-h - 1) m0
+        order 2:  D1 = (m0 - m1) / r0 ;   x' = (sigma'/sigma) x - alpha' (e^-h - 1) m0 - 0.5 alpha' (e^-h - 1) D1
+        order 3:  D1_0 = (m0 - m1)/r0, D1_1 = (m1 - m2)/r1, D1 = D1_0 + r0/(r0 + r1) (D1_0 - D1_1), D2 = (D1_0 - D1_1)/(r0 + r1)
+                  x' = (sigma'/sigma) x - alpha' (e^-h - 1) m0 + alpha' ((e^-h - 1)/h + 1) D1 - alpha' ((e^-h - 1 + h)/h^2 - 0.5) D2
+        "sde-dpmsolver++", order 1 / 2:
+                  x' = (sigma'/sigma) e^-h x + alpha' (1 - e^-2h) m0 [+ 0.5 alpha' (1 - e^-2h) D1] + sigma' sqrt(1 - e^-2h) noise
+
+    At sigma' = 0 the limits are taken exactly: x' = m0.  The order of step i, ``have`` = min(i, solver_order - 1) being the
+    number of earlier predictions there are: 1 when solver_order == 1, or have == 0, or i is the last step and
+    (``euler_at_final``, or ``lower_order_final`` and n < 15, or a_n == 1); otherwise 2 when solver_order == 2, or have == 1, or i
+    is the second-to-last step and ``lower_order_final`` and n < 15; otherwise 3.
+
+    Guidance: m = sum_g w[g] * model_out[group g].  ``group_weights`` (one per group of the call) gives w -- e.g.
+    (1 - s, s + p, -p) for perturbed-attention guidance over (uncond, cond, perturbed), (s_T, s_I - s_T, 1 - s_I) for
+    InstructPix2Pix over (text + image, image, none); without it w is (1 - guidance_scale, guidance_scale) on the last two
+    groups and 0 before them ((1,) for one group).  A group of weight 0 is never read.  ``guidance_rescale`` (groups >= 2)
+    restores the per-frame std of group ``rescale_group`` (default: the last).
+
+    History: solver_order - 1 whole-video fp32 tensors shaped like x, a ring over the step index (step i overwrites the
+    prediction of step i - (solver_order - 1), element by element, after reading it).  ``prepare(x)`` allocates them on the
+    current stream; the first ``step`` does it when nobody has, which is too late under ``run_step(streams=...)``: there the
+    caller prepares first.  Step 0 restarts the history; every step must step EVERY frame exactly once (what
+    ``scheduler.get_chunks`` guarantees), and steps come in order: an ``i`` that is neither the current step nor the next
+    raises."""
+
+    def __init__(self, alphas_cumprod, timesteps, final_alpha_cumprod=1.0, prediction_type: str = "epsilon",
+                 solver_order: int = 2, algorithm_type: str = "dpmsolver++", lower_order_final: bool = True,
+                 euler_at_final: bool = False, guidance_scale: float = 7.5, guidance_rescale: float = 0.0,
+                 group_weights=None, rescale_group: Optional[int] = None):
+        who = "GuidedDPMSolver"
+        if prediction_type not in PREDICTION_TYPES:
+            raise ValueError(f"{who}: unknown prediction_type {prediction_type!r} (one of {sorted(PREDICTION_TYPES)})")
+        if algorithm_type not in ALGORITHM_TYPES:
+            raise ValueError(f"{who}: unknown algorithm_type {algorithm_type!r} (one of {ALGORITHM_TYPES})")
+        self.solver_order = int(solver_order)
+        if not 1 <= self.solver_order <= (2 if algorithm_type == "sde-dpmsolver++" else 3):
+            raise ValueError(f"{who}: solver_order {solver_order} ({algorithm_type}: 1 .. "
+                             f"{2 if algorithm_type == 'sde-dpmsolver++' else 3})")
+        self.alphas = [float(a) for a in _host_list(alphas_cumprod, "alphas_cumprod")]
+        self.timesteps = [int(t) for t in _host_list(timesteps, "timesteps")]
+        if not self.timesteps or any(not 0 <= t < len(self.alphas) for t in self.timesteps):
+            raise ValueError(f"{who}: timesteps must be a non-empty sequence inside [0, {len(self.alphas)})")
+        self.final_alpha = float(final_alpha_cumprod)
+        levels = [self.alphas[t] for t in self.timesteps]
+        if any(not 0.0 < a < 1.0 for a in levels) or not 0.0 < self.final_alpha <= 1.0:
+            raise ValueError(f"{who}: every level's alphas_cumprod must lie in (0, 1) (the final one may be 1)")
+        self.prediction_type, self.algorithm_type = prediction_type, algorithm_type
+        self.lower_order_final, self.euler_at_final = bool(lower_order_final), bool(euler_at_final)
+        self.guidance_scale, self.guidance_rescale = float(guidance_scale), float(guidance_rescale)
+        if not self.guidance_rescale >= 0.0:
+            raise ValueError(f"{who}: guidance_rescale must be >= 0")
+        self.group_weights = None if group_weights is None else [float(w) for w in _host_list(group_weights, "group_weights")]
+        self.rescale_group = None if rescale_group is None else int(rescale_group)
+        self.history: list = []                   # solver_order - 1 fp32 tensors like x; step k's prediction in [k % len]
+        self._current: Optional[int] = None       # the step the history belongs to
+
+    @classmethod
+    def from_scheduler(cls, scheduler, **overrides) -> "GuidedDPMSolver":
+        """From a Diffusers-style scheduler after ``set_timesteps``: reads ``alphas_cumprod``, ``timesteps``,
+        ``final_alpha_cumprod`` (1.0 when the scheduler has none) and, where ``config`` has them, ``prediction_type``,
+        ``solver_order``, ``algorithm_type``, ``lower_order_final`` and ``euler_at_final``."""
+        config = getattr(scheduler, "config", None)
+        kw = dict(final_alpha_cumprod=getattr(scheduler, "final_alpha_cumprod", 1.0))
+        for name in ("prediction_type", "solver_order", "algorithm_type", "lower_order_final", "euler_at_final"):
+            if getattr(config, name, None) is not None:
+                kw[name] = getattr(config, name)
+        kw.update(overrides)
+        return cls(scheduler.alphas_cumprod, scheduler.timesteps, **kw)
+
+    def weights(self, groups: int) -> list:
+        """The weight of each of the ``groups`` groups of a call."""
+        groups = int(groups)
+        if self.group_weights is not None:
+            if len(self.group_weights) != groups:
+                raise RuntimeError(f"GuidedDPMSolver: {len(self.group_weights)} group_weights for a call of {groups} groups")
+            return list(self.group_weights)
+        if groups < 1:
+            raise RuntimeError(f"GuidedDPMSolver: groups = {groups}")
+        return [1.0] if groups == 1 else [0.0] * (groups - 2) + [1.0 - self.guidance_scale, self.guidance_scale]
+
+    def order(self, i: int, have: Optional[int] = None) -> int:
+        """The order step ``i`` is taken at (class docstring)."""
+        n = len(self.timesteps)
+        i = int(i)
+        if not 0 <= i < n:
+            raise IndexError(f"GuidedDPMSolver: step {i} outside [0, {n})")
+        most = min(i, self.solver_order - 1)
+        have = most if have is None else int(have)
+        if not 0 <= have <= most:
+            raise ValueError(f"GuidedDPMSolver: have = {have} outside [0, {most}] at step {i}")
+        low = self.lower_order_final and n < 15
+        if self.solver_order == 1 or have == 0 or (i == n - 1 and (self.euler_at_final or low or self.final_alpha == 1.0)):
+            return 1
+        if self.solver_order == 2 or have == 1 or (i == n - 2 and low):
+            return 2
+        return 3
+
+    def _level(self, k: int):
+        a = self.alphas[self.timesteps[k]] if k < len(self.timesteps) else self.final_alpha
+        alpha, sigma = math.sqrt(a), math.sqrt(1.0 - a)
+        return alpha, sigma, (math.log(alpha) - math.log(sigma) if sigma > 0.0 else math.inf)
+
+    def coefficients(self, i: int, have: Optional[int] = None):
+        """(sqrt_alpha, sqrt_beta, c_x, c_x0, c_h1, c_h2, c_noise) of step ``i`` in host float64: alpha and sigma of level i, and
+        x' = c_x x + c_x0 m0 + c_h1 m1 + c_h2 m2 + c_noise noise, the class docstring's update with D1 / D2 multiplied out.
+        ``have``: how many earlier predictions are valid, min(i, solver_order - 1) unless given smaller."""
+        order = self.order(i, have)
+        alpha, sigma, lam = self._level(i)
+        alpha_n, sigma_n, lam_n = self._level(i + 1)
+        if sigma_n == 0.0:                         # h = inf (order 1 by the rule above): the limits, exactly
+            return alpha, sigma, 0.0, 1.0, 0.0, 0.0, 0.0
+        h = lam_n - lam
+        sde = self.algorithm_type == "sde-dpmsolver++"
+        if sde:
+            c_x = sigma_n / sigma * math.exp(-h)
+            lead = -alpha_n * math.expm1(-2.0 * h)                 # alpha' (1 - e^-2h)
+            c_noise = sigma_n * math.sqrt(-math.expm1(-2.0 * h))
+        else:
+            c_x, c_noise = sigma_n / sigma, 0.0
+            lead = -alpha_n * math.expm1(-h)                       # -alpha' (e^-h - 1)
+        if order == 1:
+            return alpha, sigma, c_x, lead, 0.0, 0.0, c_noise
+        r0 = (lam - self._level(i - 1)[2]) / h
+        if order == 2:
+            return alpha, sigma, c_x, lead + 0.5 * lead / r0, -0.5 * lead / r0, 0.0, c_noise
+        r1 = (self._level(i - 1)[2] - self._level(i - 2)[2]) / h
+        c_d1 = alpha_n * (math.expm1(-h) / h + 1.0)
+        c_d2 = -alpha_n * ((math.expm1(-h) + h) / (h * h) - 0.5)
+        # D1 = (1 + k) D1_0 - k D1_1 and D2 = (D1_0 - D1_1) / (r0 + r1), k = r0 / (r0 + r1)
+        k = r0 / (r0 + r1)
+        on_d10 = c_d1 * (1.0 + k) + c_d2 / (r0 + r1)
+        on_d11 = -c_d1 * k - c_d2 / (r0 + r1)
+        return alpha, sigma, c_x, lead + on_d10 / r0, on_d11 / r1 - on_d10 / r0, -on_d11 / r1, c_noise
+
+    def prepare(self, x: torch.Tensor) -> None:
+        """Allocate the solver_order - 1 history tensors for the video ``x`` on the current stream and forget the step."""
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise RuntimeError("GuidedDPMSolver.prepare: x must live on the GPU (vidtome_amd has no CPU path)")
+        self.history = [torch.empty(x.shape, dtype=torch.float32, device=x.device) for _ in range(self.solver_order - 1)]
+        self._current = None
+
+    def _in_sequence(self, i: int) -> None:
+        if i != 0 and (self._current is None or i not in (self._current, self._current + 1)):
+            raise RuntimeError(f"GuidedDPMSolver.step: step {i} out of sequence (the history is at step {self._current}; "
+                               "step 0 restarts it)")
+
+    def step(self, x: torch.Tensor, model_out: torch.Tensor, i: int, *, groups: int = 2, frame_ids=None,
+             noise: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None,
+             out: Optional[torch.Tensor] = None, want: Sequence[str] = ()):
+        """Step ``i`` for one chunk, one vtm_solver_step launch on the current stream.  ``x``, ``model_out`` (groups * F, C, H,
+        W, group-major), ``frame_ids``, ``out`` (it may be x; without it a NEW tensor when ``frame_ids`` is None, otherwise x
+        itself IN PLACE), ``want`` and the result are ``GuidedDDIM.step``'s.  With "sde-dpmsolver++" and no ``noise`` (F, C, H,
+        W), randn of the chunk's shape is drawn from ``generator``."""
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if any(w not in WANT for w in want) or len(set(want)) != len(want):
+            raise ValueError(f"GuidedDPMSolver.step: want names {want}, known: {WANT}")
+        sqrt_alpha, sqrt_beta, c_x, c_x0, c_h1, c_h2, c_noise = self.coefficients(i)
+        tensors = ((x, "x"), (model_out, "model_out")) + (((noise, "noise"),) if noise is not None else ())
+        for t, name in tensors:
+            if not isinstance(t, torch.Tensor) or t.dim() < 2:
+                raise RuntimeError(f"GuidedDPMSolver.step: {name} must be a (frames, ...) tensor")
+        F = x.shape[0] if frame_ids is None else len(frame_ids)
+        groups = int(groups)
+        if groups < 1 or model_out.shape[0] != groups * F:
+            raise RuntimeError(f"GuidedDPMSolver.step: model_out has {model_out.shape[0]} samples, not {groups} groups x {F} "
+                               "frames")
+        weights = self.weights(groups)
+        if model_out.dtype != x.dtype or (noise is not None and noise.dtype != x.dtype):
+            raise RuntimeError(f"GuidedDPMSolver.step: dtype mismatch: x {x.dtype}, model_out {model_out.dtype}"
+                               + (f", noise {noise.dtype}" if noise is not None else ""))
+        i = int(i)
+        self._in_sequence(i)
+        for t, name in tensors:
+            if not t.is_cuda:
+                raise RuntimeError(f"GuidedDPMSolver.step: {name} must live on the GPU (vidtome_amd has no CPU path)")
+        if len(self.history) != self.solver_order - 1 or any(h.shape != x.shape or h.device != x.device for h in self.history):
+            if i != 0:
+                raise RuntimeError(f"GuidedDPMSolver.step: the history of step {i} does not fit x {tuple(x.shape)} on {x.device}")
+            self.prepare(x)
+        self._current = i
+        if c_noise != 0.0 and noise is None:
+            noise = torch.randn((F,) + tuple(model_out.shape[1:]), dtype=x.dtype, device=x.device, generator=generator)
+        ring = len(self.history)
+        res = _lib.solver_step(x, model_out, weights, sqrt_alpha, sqrt_beta, c_x, c_x0, c_h1, c_h2, c_noise,
+                               h1=self.history[(i - 1) % ring] if c_h1 != 0.0 else None,
+                               h2=self.history[(i - 2) % ring] if c_h2 != 0.0 else None,
+                               h_out=self.history[i % ring] if ring else None,
+                               g_ref=groups - 1 if self.rescale_group is None else self.rescale_group, frame_ids=frame_ids,
+                               pred_type=PREDICTION_TYPES[self.prediction_type],
                                rescale=self.guidance_rescale if groups >= 2 else 0.0, noise=noise, out=out,
                                want_eps="eps" in want, want_x0="x0" in want)
         asked = dict(eps=res[1], x0=res[2])
