@@ -53,7 +53,9 @@ class AdaNorm(torch.nn.Module):
 
 
 class OneBlock(standin.ModelMixin):
-    """One full stand-in block at downsample 1 (its Attention.forward raises), 2-D weights N(0, 1 / fan_in) from ``seed``;
+    """One full stand-in block at downsample 1 (its Attention.forward raises), 2-D weights N(0, 1 / fan_in) from ``seed``,
+    the Linear biases N(0, 1 / fan_in) from a generator of their own (torch.nn.Linear draws them from the process-wide RNG:
+    two blocks of one ``seed`` would not hold the same parameters, and the weights keep the values they always had);
     ``storing``: attn2 is a StoringCross with the same weights; ``computing_self``: attn1 computes too."""
 
     def __init__(self, C, heads=HEADS, storing=False, seed=0, computing_self=False):
@@ -65,10 +67,14 @@ class OneBlock(standin.ModelMixin):
             blk.attn1 = ComputingSelf(C, heads)
         self.blocks = torch.nn.ModuleList([blk])
         g = torch.Generator().manual_seed(seed)
+        gb = torch.Generator().manual_seed(seed + 7919)
         with torch.no_grad():
             for p in self.parameters():
                 if p.ndim == 2:
                     p.copy_(torch.randn(p.shape, generator=g) * p.shape[-1] ** -0.5)
+            for m in self.modules():
+                if isinstance(m, torch.nn.Linear) and m.bias is not None:
+                    m.bias.copy_(torch.randn(m.bias.shape, generator=gb) * m.in_features ** -0.5)
 
     def set_size(self, latent_hw):
         self._tome_info["size"] = latent_hw

@@ -254,8 +254,6 @@ def test_registered_block_carries_the_map_and_the_same_output(L, C, dtype, monke
     those rows are checked to be to_q(norm2(h)) / to_k(cond) of the module's weights within operand rounding."""
     import vidtome_amd
     h, cond = AM.inputs(C, dtype, DEV)
-    # (both runs that are compared come behind a warm-up forward: DESIGN.md section 9, profiles/first_forward_bits.txt)
-    _forward(AM.patched(C, dtype, DEV), h, cond)
     seen = _spies(monkeypatch, L)
     plain = AM.patched(C, dtype, DEV)
     base = _forward(plain, h, cond)
