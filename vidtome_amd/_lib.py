@@ -668,12 +668,16 @@ def _attention_out(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, Mq: int, 
 
 @_on_device
 def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, M: int, scale: float,
-              share_groups: int = 1) -> torch.Tensor:
+              share_groups: int = 1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """q, k: (B, Mp, C) views with arbitrary last-dim-contiguous row stride; vt: (B, C, ldvt) = v transposed.
-    Returns out (B, Mp, C) (rows >= M untouched/zero)."""
+    Returns out (B, Mp, C) (rows >= M untouched/zero).  ``out``: a dense (B, Mp, C) tensor of q's dtype to write into (a
+    sample range of a larger buffer) instead of a new one; its rows >= M are left alone."""
+    if out is not None and (out.shape != q.shape or out.dtype != q.dtype or out.device != q.device or not out.is_contiguous()):
+        raise RuntimeError("attention: out must be a contiguous tensor of q's shape, dtype and device")
     B, Mp, C = q.shape
     d = C // heads
-    out = _attention_out(q, k, vt, M, Mp)
+    new = _attention_out(q, k, vt, M, Mp, alloc=out is None)
+    out = new if out is None else out
     ws, nb = _attention_ws(B, heads, M, M, d, q.device, q.dtype)
     _check(lib().vtm_attention(q.data_ptr(), q.stride(1), k.data_ptr(), k.stride(1), vt.data_ptr(), vt.stride(1),
                                out.data_ptr(), C, dtype_code(q), B, heads, M, Mp, d, float(scale),

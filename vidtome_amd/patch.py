@@ -33,7 +33,7 @@ from typing import Any, Callable, Dict, Optional, Tuple, Type
 import torch
 import torch.nn.functional as F
 
-from . import _lib, ip_adapter, lora, merge
+from . import _lib, ip_adapter, lora, merge, pag
 from .utils import init_generator, isinstance_str, join_frame, split_frame
 
 # Attention over the merged sequence computes outputs only for the rows unmerge() reads (see MergePlan.q_rows);
@@ -93,11 +93,13 @@ class MergePlan:
             self._inv = _lib.compose(inv_local, loc, self.L) if inv_local is not None else loc
         return self._inv
 
-    def key_fold(self, dtype) -> Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
-        """(key_sel, k_bias, k_count) of _lib.fold_keys, or None when the anchors carried no content ids."""
+    def key_fold(self, dtype, n: Optional[int] = None) -> Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
+        """(key_sel, k_bias, k_count) of _lib.fold_keys, or None when the anchors carried no content ids.  ``n``: fold the
+        keys of the first n samples only (the org samples of a perturbed-attention batch: the others have no keys)."""
         if self._key_fold is None and self.fold_args is not None:
             cur, L, cid, n_ids = self.fold_args
-            self._key_fold = _lib.fold_keys(cur, L, cid, n_ids, dtype)
+            self._key_fold = _lib.fold_keys(cur, L, cid, n_ids, dtype) if n is None else \
+                _lib.fold_keys(cur[:n], L, cid[:n], n_ids, dtype)
         return self._key_fold
 
     @property
@@ -459,6 +461,7 @@ def _fused_weights(attn: torch.nn.Module, dtype, device):
 
 _HEAD_DIMS = (8, 16, 32, 40, 64, 80, 96, 128, 160)          # instantiations of attention_kernel (attention.hip)
 _PLAIN_PROCESSORS = ("AttnProcessor", "AttnProcessor2_0", "XFormersAttnProcessor")
+_ATTN1_PROCESSORS = _PLAIN_PROCESSORS + tuple(pag.PROCESSORS)   # attn1 alone: a PAG processor there is understood (pag.py)
 _warned = set()
 
 
@@ -561,8 +564,40 @@ def _fp32_projections(block: torch.nn.Module) -> bool:
     return getattr(block, "fp32_projections", False) is True
 
 
+def _pag_batch(block: torch.nn.Module, x: torch.Tensor) -> int:
+    """The leading batch attn1 sees for block tokens like ``x`` (B F, N, C): ``apply_patch``'s batch_size at a site that merges
+    (a sample is a joined chunk), the B F frame rows at one that does not (or before anything is patched)."""
+    info = getattr(block, "_tome_info", None)
+    if info is None or unmerged_site(block, x):
+        return x.shape[0]
+    return info["args"]["batch_size"]
+
+
+def _pag_org(attn: torch.nn.Module, B: int) -> Optional[int]:
+    """n_org of a perturbed-attention attn1 call over a leading batch of B (pag.split), None for a plain call.  The processor
+    form never gets here with a batch that does not split (``attn1_route``); the registered form raises."""
+    groups = pag.groups_of(attn)
+    return None if groups is None else pag.split(B, groups)[0]
+
+
+def _pag_check(block: torch.nn.Module, x: torch.Tensor, route: str) -> None:
+    """Before the first launch of a fused segment: a registered perturbed-attention batch that does not split raises."""
+    if route != "module":
+        _pag_org(block.attn1, _pag_batch(block, x))
+
+
+def _lead(t: Optional[torch.Tensor], n: Optional[int]) -> Optional[torch.Tensor]:
+    """The first n samples of a per-sample operand (a contiguous view), the operand itself for n None."""
+    return t if t is None or n is None else t[:n]
+
+
+def _tail(t: Optional[torch.Tensor], n: int) -> Optional[torch.Tensor]:
+    """The samples from n on (a contiguous view)."""
+    return None if t is None else t[n:]
+
+
 def attn1_route(block: torch.nn.Module, x: torch.Tensor, encoder_hidden_states=None, attention_mask=None,
-                cross_attention_kwargs=None) -> str:
+                cross_attention_kwargs=None, gate_msa=None) -> str:
     """How the block computes ``attn1`` on tokens like ``x`` (their device, rank, dtype and width are read).  Launches nothing
     (but the first look at a LoRA-adapted to_v folds its adapters, lora.linear_params).
       "module"  attn1's own forward on the materialised merged tokens, like the reference (patch.py:157-162): a masked call,
@@ -574,10 +609,18 @@ def attn1_route(block: torch.nn.Module, x: torch.Tensor, encoder_hidden_states=N
                 with the roles of the operands swapped)
       "f32"     self_attention_rows on vtm_linear_f32: fp32 tokens with C % 8 == 0 and the block's ``fp32_projections``
       "blas"    self_attention: library GEMMs over materialised merged tokens
-    The three hand-written projection paths ask that all four projection weights are of the tokens' dtype."""
+    The three hand-written projection paths ask that all four projection weights are of the tokens' dtype.
+    Perturbed attention (pag.groups_of: a PAG processor on attn1, or a registered block) keeps the route of the plain block --
+    each body then runs its attention on the org samples only -- except with an AdaLayerNormZero gate (``gate_msa``), under PnP
+    sharing, or, in the processor form, with a batch that does not split into the processor's groups: "module"."""
     attn = block.attn1
     if attention_mask is not None or _attn1_kwargs(cross_attention_kwargs) \
-            or (encoder_hidden_states is not None and block.only_cross_attention) or not fused_attention_ok(attn, x):
+            or (encoder_hidden_states is not None and block.only_cross_attention) \
+            or not fused_attention_ok(attn, x, processors=_ATTN1_PROCESSORS):
+        return "module"
+    groups = pag.groups_of(attn)
+    if groups is not None and (gate_msa is not None or _pnp_share_groups(attn) != 1
+                               or (pag.registered(attn) is None and _pag_batch(block, x) % groups)):
         return "module"
     C = x.shape[-1]
     if x.dtype == torch.float32:
@@ -602,14 +645,27 @@ def _attn1_params(attn: torch.nn.Module, C: int, q_rows: Optional[torch.Tensor],
 
 
 def _attn1_core(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, M: int, Mq: Optional[int], scale: float,
-                share: int, q_count: Optional[torch.Tensor] = None, k_fold=None) -> torch.Tensor:
+                share: int, q_count: Optional[torch.Tensor] = None, k_fold=None,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The attention core of attn1 over M keys: every row a query (``Mq`` None, vtm_attention), or Mq query rows of their
-    own -- the first q_count[b] of them live -- and / or folded keys (vtm_attention_kv)."""
+    own -- the first q_count[b] of them live -- and / or folded keys (vtm_attention_kv).  ``out``: the leading samples of a
+    larger buffer to write into (perturbed attention: the perturbed samples' V follows, ``_pag_out``)."""
+    kw = {} if out is None else {"out": out}
     if k_fold is not None:                                 # (folded keys: never under sharing)
-        return _lib.attention_kv(q, k, vt, heads, M if Mq is None else Mq, M, scale, q_count=q_count, k_fold=k_fold)
+        return _lib.attention_kv(q, k, vt, heads, M if Mq is None else Mq, M, scale, q_count=q_count, k_fold=k_fold, **kw)
     if Mq is None:
-        return _lib.attention(q, k, vt, heads, M, scale, share)
-    return _lib.attention_kv(q, k, vt, heads, Mq, M, scale, q_count=q_count, share_groups=share)
+        return _lib.attention(q, k, vt, heads, M, scale, share, **kw)
+    return _lib.attention_kv(q, k, vt, heads, Mq, M, scale, q_count=q_count, share_groups=share, **kw)
+
+
+def _pag_out(B: int, rows: int, valid: int, C: int, dtype, device) -> torch.Tensor:
+    """The (B, rows, C) buffer the output projection of a perturbed-attention batch reads: the cores write the org samples'
+    attention output into its head, the perturbed samples' V goes into its tail.  Rows >= ``valid`` are padding nobody
+    writes: zero, as the cores' own result has them."""
+    o = torch.empty((B, rows, C), dtype=dtype, device=device)
+    if rows != valid:
+        o[:, valid:].zero_()
+    return o
 
 
 def _panel_weight(lin: torch.nn.Module):
@@ -621,19 +677,22 @@ def _panel_weight(lin: torch.nn.Module):
 
 def self_attention_panels(attn: torch.nn.Module, x0: torch.Tensor, x1: Optional[torch.Tensor], rows: Optional[torch.Tensor],
                           q_rows: Optional[torch.Tensor] = None, q_count: Optional[torch.Tensor] = None,
-                          aligned: bool = False) -> torch.Tensor:
+                          aligned: bool = False, n_org: Optional[int] = None) -> torch.Tensor:
     """``attn1(merged)`` like self_attention_rows, with the projections as panel GEMMs: the merged rows (and the live-query
     rows) are gathered ONCE into the k-panel layout, sample b at rows b * Mpad (Mpad = M rounded up to 256), and
         k    = X W_k^T                     one launch over all samples  -> (B, Mpad, C)
         v^T  = W_v X_b^T                   one launch per sample, the weight as "token" operand -> (B, C, Mpad): no transpose
         q    = X_q W_q^T, out = O W_o^T + b
     Returns (B, Mq rounded up to 256, C); rows >= Mq (or the per-sample q_count) are not meaningful.  ``aligned``: the
-    matching was align_batch's (``_attn1_params``)."""
-    B, _, C = x0.shape
+    matching was align_batch's (``_attn1_params``).  ``n_org`` (perturbed attention, ``_pag_org``): all of the above for the
+    first n_org samples only; the others' rows of O are V = X_q W_v^T, one gather and one GEMM of their own."""
+    Ball, _, C = x0.shape
     M = x0.shape[1] if rows is None else rows.shape[1]
     heads, scale, share = _attn1_params(attn, C, q_rows, aligned)
+    B = Ball if n_org is None else n_org
+    y0, y1, yrows, yq = _lead(x0, n_org), _lead(x1, n_org), _lead(rows, n_org), _lead(q_rows, n_org)
     Mpad = _lib.panel_rows(M)
-    xp = _lib.gather_panels(x0, x1, rows, None, M)                       # (C / 8, B * Mpad, 8)
+    xp = _lib.gather_panels(y0, y1, yrows, None, M)                      # (C / 8, B * Mpad, 8)
     wq, bq = _panel_weight(attn.to_q)
     wk, bk = _panel_weight(attn.to_k)
     wv, _ = _panel_weight(attn.to_v)
@@ -646,12 +705,19 @@ def self_attention_panels(attn: torch.nn.Module, x0: torch.Tensor, x1: Optional[
     if q_rows is not None:
         Mq = q_rows.shape[1]
         Mqpad = _lib.panel_rows(Mq)
-        qp = _lib.gather_panels(x0, x1, rows, q_rows, Mq)
+        qp = _lib.gather_panels(y0, y1, yrows, yq, Mq)
     q_op = _lib.linear_panels(qp, B * Mqpad, wq, C, bq).view(B, Mqpad, C)
-    o = _attn1_core(q_op, k_op, vt, heads, M, Mq, scale, share, q_count)
+    if n_org is None:
+        o = _attn1_core(q_op, k_op, vt, heads, M, Mq, scale, share, q_count)
+    else:
+        o = _pag_out(Ball, Mqpad, M if Mq is None else Mq, C, x0.dtype, x0.device)
+        _attn1_core(q_op, k_op, vt, heads, M, Mq, scale, share, _lead(q_count, n_org), out=o[:n_org])
+        vp = _lib.gather_panels(_tail(x0, n_org), _tail(x1, n_org), _tail(rows, n_org), _tail(q_rows, n_org),
+                                M if Mq is None else Mq)
+        _lib.linear_panels(vp, (Ball - n_org) * Mqpad, wv, C, None, out=o[n_org:].view(-1, C))
     wo, bo = _panel_weight(_out_linear(attn))
-    op = _lib.to_panels(o.view(B * Mqpad, C))
-    return _lib.linear_panels(op, B * Mqpad, wo, C, bo).view(B, Mqpad, C)
+    op = _lib.to_panels(o.view(Ball * Mqpad, C))
+    return _lib.linear_panels(op, Ball * Mqpad, wo, C, bo).view(Ball, Mqpad, C)
 
 
 def unmerged_site(block: torch.nn.Module, x: torch.Tensor) -> bool:
@@ -676,12 +742,16 @@ def unmerged_self_attention_residual(block: torch.nn.Module, hidden_states: torc
     """patch.py:139-169 at a site that does not merge (per-frame attention): ``attn1(norm1(h)) + h`` with norm1 writing
     k-panels (its output is only read by the three projections), ONE GEMM for q | k | v over all frames, the attention core
     per frame, and the output projection with bias and residual in its epilogue.  The caller checked
-    ``unmerged_self_attention_ok``."""
+    ``unmerged_self_attention_ok``.
+    Perturbed attention (``_pag_org`` over the BF frame rows: the batch is frame-minor per sample, the last sample's frames
+    are the perturbed ones): norm1 runs once per part, q | k | v and the core for the org frames only, and the perturbed
+    frames' rows of the core's output buffer are V, a GEMM with to_v's panel weight alone."""
     attn, norm = block.attn1, block.norm1
     BF, N, C = hidden_states.shape
     heads, scale = attn.heads, _scale(attn, C)
     hs = hidden_states.contiguous()
     n = BF * N
+    n_org = _pag_org(attn, BF)
 
     qkv_params = [_linear(m) for m in (attn.to_q, attn.to_k, attn.to_v)]
 
@@ -692,12 +762,26 @@ def unmerged_self_attention_residual(block: torch.nn.Module, hidden_states: torc
             [torch.zeros(C, device=w.device) if x is None else x.detach().float() for x in bs]).contiguous()
         return _lib.to_panels(w), b
     wqkv, bqkv = _packed(attn, "qkv", tuple(p[2] for p in qkv_params), qkv_params[0][0].device, pack_qkv)
+    wo, bo = _panel_weight(_out_linear(attn))
+    if n_org is not None:
+        # (a part of its own each: a panel GEMM fetches whole 256-row tiles from where its operand starts, which a row range
+        # that begins in the middle of norm1's panels does not have behind its last rows)
+        ho, hp = hs[:n_org], hs[n_org:]
+        no = n_org * N
+        qkv = _lib.linear_panels(_lib.layernorm_panels(ho, norm.weight, norm.bias, norm.eps), no, wqkv, 3 * C,
+                                 bqkv).view(n_org, N, 3 * C)
+        vt = _lib.transpose_cols(qkv, 2 * C, C)
+        o = torch.empty((BF, N, C), dtype=hs.dtype, device=hs.device)
+        _lib.attention(qkv[:, :, :C], qkv[:, :, C:2 * C], vt, heads, N, scale, 1, out=o[:n_org])
+        wv, bv = _panel_weight(attn.to_v)
+        _lib.linear_panels(_lib.layernorm_panels(hp, norm.weight, norm.bias, norm.eps), n - no, wv, C, bv,
+                           out=o[n_org:].view(n - no, C))
+        return _lib.linear_panels(_lib.to_panels(o.view(n, C)), n, wo, C, bo, resid=hs.view(n, C)).view(BF, N, C)
     xp = _lib.layernorm_panels(hs, norm.weight, norm.bias, norm.eps)
     qkv = _lib.linear_panels(xp, n, wqkv, 3 * C, bqkv).view(BF, N, 3 * C)
     # (BF, C, N rounded up to 8): V channel-major for the PV contraction, the key columns past N written as zeros
     vt = _lib.transpose_cols(qkv, 2 * C, C)
     o = _lib.attention(qkv[:, :, :C], qkv[:, :, C:2 * C], vt, heads, N, scale, 1)
-    wo, bo = _panel_weight(_out_linear(attn))
     op = _lib.to_panels(o.view(n, C))
     return _lib.linear_panels(op, n, wo, C, bo, resid=hs.view(n, C)).view(BF, N, C)
 
@@ -706,6 +790,7 @@ def self_attention_segment(block: torch.nn.Module, hidden_states: torch.Tensor, 
                            attention_mask=None, cross_attention_kwargs=None) -> torch.Tensor:
     """patch.py:146-169 for the plain-LayerNorm block: norm1 -> compute_merge -> attn1 -> unmerge -> + residual."""
     route = attn1_route(block, hidden_states, encoder_hidden_states, attention_mask, cross_attention_kwargs)
+    _pag_check(block, hidden_states, route)
     if unmerged_self_attention_ok(block, hidden_states, route):
         return unmerged_self_attention_residual(block, hidden_states)
     norm_hidden_states = layer_norm(block.norm1, hidden_states)
@@ -718,7 +803,7 @@ def self_attention_segment(block: torch.nn.Module, hidden_states: torch.Tensor, 
 def self_attention_rows(attn: torch.nn.Module, x0: torch.Tensor, x1: Optional[torch.Tensor],
                         rows: Optional[torch.Tensor], q_rows: Optional[torch.Tensor] = None,
                         q_count: Optional[torch.Tensor] = None, plan: Optional["MergePlan"] = None,
-                        fp32_core: bool = False, aligned: bool = False) -> torch.Tensor:
+                        fp32_core: bool = False, aligned: bool = False, n_org: Optional[int] = None) -> torch.Tensor:
     """``attn1(merged)`` (patch.py:157-162; arithmetic of pnp_utils.py:47-95) with ``merged[b, i] = pool[b, rows[b, i]]``
     never materialised: every projection is a GEMM that fetches its A rows through the composed merge map (pool = x0 | x1,
     ``rows`` None = the rows of x0 as they are), k and v for all M rows (v channel-major, what the PV contraction reads),
@@ -730,7 +815,10 @@ def self_attention_rows(attn: torch.nn.Module, x0: torch.Tensor, x1: Optional[to
     carries log2 of its multiplicity.
     fp32 tokens (the block's ``fp32_projections``): vtm_linear_f32, which writes q / k / V^T in fp32 for the fp32 core
     (``fp32_core``, the block's ``fp32_attention``) or rounds them once to fp16 at its store for the fp16 core; the output
-    projection reads the core's output as fp32.  fp32 keys are never folded."""
+    projection reads the core's output as fp32.  fp32 keys are never folded.
+    ``n_org`` (perturbed attention, ``_pag_org``): q, k, V^T, the key fold and the core for the first n_org samples only; the
+    others' rows of the core's output buffer are V = to_v at the rows the output projection reads (the ``q_rows`` positions,
+    or all M), token-major from the same GEMM -- in fp32 for fp32 tokens, whichever core the org samples take."""
     B, _, C = x0.shape
     M = x0.shape[1] if rows is None else rows.shape[1]
     heads, scale, share = _attn1_params(attn, C, q_rows, aligned)
@@ -743,28 +831,40 @@ def self_attention_rows(attn: torch.nn.Module, x0: torch.Tensor, x1: Optional[to
     wv, bv, _ = _linear(attn.to_v, dt)
     fold = None
     if not f32 and plan is not None and rows is not None and share == 1 and (C // heads) in (8, 40):
-        fold = plan.key_fold(dt)
+        fold = plan.key_fold(dt, n_org)
     key_sel = k_fold = None
     if fold is not None:
         key_sel, k_bias, k_count = fold
         k_fold = (k_count, k_bias)
-    vt = gemm(x0, x1, rows, key_sel, M, wv, bv, transposed=True, **out_kw)                         # (B, C, Mp)
+    y0, y1, yrows, yq = _lead(x0, n_org), _lead(x1, n_org), _lead(rows, n_org), _lead(q_rows, n_org)
+    Mq = M if q_rows is None else q_rows.shape[1]
+    o = core_out = None
+    if n_org is not None:
+        Mqp = (Mq + 7) // 8 * 8
+        # (fp32 tokens on the fp16 core: the core's fp16 output is widened into the fp32 buffer the output projection reads)
+        o = _pag_out(B, Mqp, Mq, C, dt, x0.device)
+        if not f32 or fp32_core:
+            core_out = o[:n_org]
+    vt = gemm(y0, y1, yrows, key_sel, M, wv, bv, transposed=True, **out_kw)                        # (B, C, Mp)
     if q_rows is None and fold is None:
-        Mq = M
-        qk = gemm(x0, x1, rows, None, M, wqk, bqk, **out_kw)                                       # (B, Mp, 2C): q | k
-        o = _attn1_core(qk[:, :, :C], qk[:, :, C:], vt, heads, M, None, scale, share)
+        qk = gemm(y0, y1, yrows, None, M, wqk, bqk, **out_kw)                                      # (B, Mp, 2C): q | k
+        oc = _attn1_core(qk[:, :, :C], qk[:, :, C:], vt, heads, M, None, scale, share, out=core_out)
     else:
-        Mq = M if q_rows is None else q_rows.shape[1]
-        k_op = gemm(x0, x1, rows, key_sel, M, wqk[C:], None if bqk is None else bqk[C:], **out_kw)
-        q_op = gemm(x0, x1, rows, q_rows, Mq, wqk[:C], None if bqk is None else bqk[:C], **out_kw)
-        o = _attn1_core(q_op, k_op, vt, heads, M, Mq, scale, share, q_count, k_fold)
+        k_op = gemm(y0, y1, yrows, key_sel, M, wqk[C:], None if bqk is None else bqk[C:], **out_kw)
+        q_op = gemm(y0, y1, yrows, yq, Mq, wqk[:C], None if bqk is None else bqk[:C], **out_kw)
+        oc = _attn1_core(q_op, k_op, vt, heads, M, Mq, scale, share, _lead(q_count, n_org), k_fold, out=core_out)
     wo, bo, _ = _linear(_out_linear(attn), dt)
-    return gemm(o.float() if f32 else o, None, None, None, Mq, wo, bo)
+    if n_org is None:
+        return gemm(oc.float() if f32 else oc, None, None, None, Mq, wo, bo)
+    if core_out is None:
+        o[:n_org].copy_(oc)
+    gemm(_tail(x0, n_org), _tail(x1, n_org), _tail(rows, n_org), _tail(q_rows, n_org), Mq, wv, bv, out=o[n_org:])
+    return gemm(o, None, None, None, Mq, wo, bo)
 
 
 def self_attention(attn: torch.nn.Module, x: torch.Tensor, M: Optional[int] = None,
                    q_rows: Optional[torch.Tensor] = None, q_count: Optional[torch.Tensor] = None,
-                   fp32_core: bool = False, aligned: bool = False) -> torch.Tensor:
+                   fp32_core: bool = False, aligned: bool = False, n_org: Optional[int] = None) -> torch.Tensor:
     """``attn1(x)`` for self-attention without mask (patch.py:157-162), arithmetic of pnp_utils.py:47-95:
     q,k,v projections -> softmax(q k^T * scale) v per head -> to_out[0] (+ dropout(0)), on MATERIALISED tokens with
     library GEMMs (torch -> hipBLASLt) for the projections: the path of fp32 models, of channel counts the
@@ -777,7 +877,9 @@ def self_attention(attn: torch.nn.Module, x: torch.Tensor, M: Optional[int] = No
     the attention core's operands (q, k, v^T) are rounded to fp16 for the MFMA (fp32 accumulation, fp32 softmax): the
     result is within the 1e-3 class of the fp32 reference, and a warning says so once.  With ``fp32_core`` (the block's
     ``fp32_attention``, set by ``update_patch(model, fp32_attention=True)``) an fp32 model's core runs in fp32 on the f32
-    MFMA (csrc/attention_f32.hip), about 16x the matrix time of the fp16 core; the flag means nothing to 16-bit models."""
+    MFMA (csrc/attention_f32.hip), about 16x the matrix time of the fp16 core; the flag means nothing to 16-bit models.
+    ``n_org`` (perturbed attention, ``_pag_org``): all of this for the first n_org samples; the others' input of the output
+    projection is ``to_v`` of their tokens (of their ``q_rows`` rows), one library GEMM."""
     B, Mp, C = x.shape
     M = Mp if M is None else M
     heads, scale, share = _attn1_params(attn, C, q_rows, aligned)
@@ -786,6 +888,10 @@ def self_attention(attn: torch.nn.Module, x: torch.Tensor, M: Optional[int] = No
         pad = 8 - x.shape[1] % 8
         x = F.pad(x, (0, 0, 0, pad))
         Mp = x.shape[1]
+    x_ptb = q_ptb = None
+    if n_org is not None:
+        x_ptb, q_ptb = x[n_org:], _tail(q_rows, n_org)
+        x, q_rows, q_count, B = x[:n_org], _lead(q_rows, n_org), _lead(q_count, n_org), n_org
     core = x.dtype
     if x.dtype != torch.float32 and PROJ_MODE != "blas":
         # an fp16 / bf16 model normally never gets here: say once that (and why) this module's projections are library GEMMs
@@ -818,6 +924,9 @@ def self_attention(attn: torch.nn.Module, x: torch.Tensor, M: Optional[int] = No
     # rows unmerge() never reads)
     o = _attn1_core(q_op, k_op, vt, heads, M, None if q_rows is None else q_rows.shape[1], scale, share, q_count)
     o = o.to(x.dtype)
+    if x_ptb is not None:
+        xv = x_ptb if q_ptb is None else _lib.gather_rows(x_ptb, None, q_ptb, pad_to=8)
+        o = torch.cat([o, F.linear(xv, wv, bv)])
     wo, bo, _ = _linear(_out_linear(attn), o.dtype)
     return F.linear(o, wo, bo)
 
@@ -1447,7 +1556,9 @@ def patched_self_attention_segment(block: torch.nn.Module, hidden_states: torch.
     for this call, when the caller has asked already."""
     cross_attention_kwargs = cross_attention_kwargs if cross_attention_kwargs is not None else {}
     if route is None:
-        route = attn1_route(block, norm_hidden_states, encoder_hidden_states, attention_mask, cross_attention_kwargs)
+        route = attn1_route(block, norm_hidden_states, encoder_hidden_states, attention_mask, cross_attention_kwargs,
+                            gate_msa)
+    _pag_check(block, norm_hidden_states, route)
     # ("module" and "blas" read the merged tokens; the other routes' projections gather through the map)
     m_a, u_a, merged = compute_merge(block, norm_hidden_states, block._tome_info, materialize=route in ("module", "blas"))
     plan = getattr(m_a, "plan", None)
@@ -1456,6 +1567,11 @@ def patched_self_attention_segment(block: torch.nn.Module, hidden_states: torch.
         # not the hot path (SD never masks self-attention nor makes attn1 a cross-attention; LoRA'd / custom
         # attention modules are not the plain arithmetic): run the module's own attention on the merged tokens
         # exactly as the reference does
+        if pag.registered(attn) is not None:
+            raise RuntimeError("vidtome_amd: this block is registered for perturbed attention (register_perturbed_attention) "
+                               "but its attn1 call keeps the module's own forward, which knows nothing of it (a mask, "
+                               "processor kwargs, an AdaLayerNormZero gate, PnP sharing or a module that is not the plain "
+                               "arithmetic)")
         M = plan.M if plan is not None else merged.shape[1]
         attn_output = attn(merged[:, :M],
                            encoder_hidden_states=encoder_hidden_states if block.only_cross_attention else None,
@@ -1469,18 +1585,20 @@ def patched_self_attention_segment(block: torch.nn.Module, hidden_states: torch.
         q_rows = plan.q_rows if live else None
         q_count = plan.q_count if live else None
         fp32_core = getattr(block, "fp32_attention", False)
+        # perturbed attention: the leading batch the bodies see (the joined chunks; the frame rows where nothing merges)
+        n_org = _pag_org(attn, norm_hidden_states.shape[0] if plan is None else plan.x_joined.shape[0])
         if route == "blas":
             attn_output = self_attention(attn, merged, plan.M if plan is not None else None, q_rows, q_count,
-                                         fp32_core=fp32_core, aligned=aligned)
+                                         fp32_core=fp32_core, aligned=aligned, n_org=n_org)
         else:
             # the pool the projections gather from (block does not merge: per-frame attention on the tokens as they are)
             pool = (norm_hidden_states.contiguous(), None, None) if plan is None else \
                 (plan.x_joined, plan.anchors_in, plan.gather_map)
             if route == "panels":
-                attn_output = self_attention_panels(attn, *pool, q_rows, q_count, aligned=aligned)
+                attn_output = self_attention_panels(attn, *pool, q_rows, q_count, aligned=aligned, n_org=n_org)
             else:                                                         # "rows", "f32": the tokens' dtype says which
                 attn_output = self_attention_rows(attn, *pool, q_rows, q_count, plan=plan, fp32_core=fp32_core,
-                                                  aligned=aligned)
+                                                  aligned=aligned, n_org=n_org)
         if live:
             # rows are the chunk's local merged tokens: unmerge with the local levels' map alone
             # (= the global level's unmerge, merge.py:439-460, folded into the choice of queries)
@@ -1725,6 +1843,7 @@ def remove_patch(model: torch.nn.Module):
             module.__dict__.pop("attn2_probs", None)           # ... and the map of the block's last forward
             module.__dict__.pop("vtm_cross_control", None)     # p2p.register_cross_attention_control's schedule and edits
             module.__dict__.pop("vtm_local_blend", None)       # blend.register_local_blend's accumulator
+            module.__dict__.pop(pag.MARK, None)                # pag.register_perturbed_attention's marker (on attn1)
     _lib.release_workspaces()            # the cached scratch buffers of the patched path (re-created on demand)
     return roots[-1]                     # the reference returns its loop variable: the last tree walked
 
