@@ -19,7 +19,12 @@ Cases (fp16 unless named; batch 2, 4 frames, latent 16 x 16, local_merge_ratio 0
   unmerged/*   sites that do not merge (`max_downsample=1`, 64 tokens): bf16 C = 640, fp32 C = 320 with fp32_projections
   cross/*      `cross_attention`, `norm_cross_attention_residual` and the whole block forward: plain, masked, IP-Adapter,
                IP-Adapter with region masks, and 250 tokens (no multiple of 8), under both FF_MODEs; the whole forward of an fp32
-               block with fp32_projections"""
+               block with fp32_projections
+  cross/* side the block forward behind the public ``register_*`` functions alone, under both FF_MODEs, at 256 and at 10 x 25 =
+               250 tokens: maps registered (plain, masked, IP-Adapter), a LocalBlend registered (plain, IP-Adapter),
+               cross-attention control at an injecting step (four groups: the source, an identity, an edited one, one without an
+               edit) with maps and blend registered, and control outside its schedule with maps, with a blend, with both.  These
+               lines carry two more hashes: ``attn2_probs`` and the LocalBlend accumulator"""
 import argparse
 import hashlib
 import os
@@ -32,7 +37,8 @@ DEV = "cuda"
 B, FRAMES, LATENT = 2, 4, (16, 16)
 SPIED = ("layernorm", "layernorm_panels", "gather_rows", "gather_panels", "to_panels", "transpose_cols", "linear_rows",
          "linear_panels", "linear_f32", "attention", "attention_kv", "attention_kv_bias", "attention_kv_sets",
-         "attention_kv_sets_masked", "compact_queries", "fold_keys", "compose", "anchor_maps", "unmerge_add", "ff_geglu", "geglu")
+         "attention_kv_sets_masked", "attention_kv_sets_src", "cross_edit_values", "attention_probs", "attention_word_map",
+         "compact_queries", "fold_keys", "compose", "anchor_maps", "unmerge_add", "ff_geglu", "geglu")
 
 # name -> (dtype, C, heads, options); the expected route of each row is tests/test_gpu_attn1_route.py's table
 ROUTE_CASES = {
@@ -256,6 +262,121 @@ def run_cross(vidtome_amd, out):
         vpatch.FF_MODE = keep_ff
 
 
+SIDE_CASES = (                      # (name, conditioning, registered, control step: None | "in" | "out", also at 250 tokens)
+    ("maps plain", "plain", ("maps",), None, True),
+    ("maps masked", "masked", ("maps",), None, True),
+    ("maps ip-adapter", "ip-adapter", ("maps",), None, True),
+    ("blend plain", "plain", ("blend",), None, True),
+    ("blend ip-adapter", "ip-adapter", ("blend",), None, True),
+    ("control injecting, maps and blend", "plain", ("maps", "blend"), "in", True),
+    ("control outside the schedule, maps", "plain", ("maps",), "out", False),
+    ("control outside the schedule, blend", "plain", ("blend",), "out", False),
+    ("control outside the schedule, maps and blend", "plain", ("maps", "blend"), "out", False),
+)
+
+
+# attn2 route rows (tests/test_gpu_attn2_route.py holds the expected frame and core of each):
+# name -> (conditioning, FF_MODE, latent, dtype, options)
+CROSS_ROUTE_CASES = {
+    "plain": ("plain", "panels", LATENT, torch.float16, {}),
+    "plain N=250": ("plain", "panels", (10, 25), torch.float16, {}),
+    "masked": ("masked", "panels", LATENT, torch.float16, {}),
+    "ip-adapter": ("ip-adapter", "panels", LATENT, torch.float16, {}),
+    "ip-adapter N=250": ("ip-adapter", "panels", (10, 25), torch.float16, {}),
+    "ip-adapter region masks": ("ip-adapter region masks", "panels", LATENT, torch.float16, {}),
+    "FF_MODE=blas plain": ("plain", "blas", LATENT, torch.float16, {}),
+    "FF_MODE=blas plain N=250": ("plain", "blas", (10, 25), torch.float16, {}),
+    "FF_MODE=blas masked": ("masked", "blas", LATENT, torch.float16, {}),
+    "FF_MODE=blas ip-adapter": ("ip-adapter", "blas", LATENT, torch.float16, {}),
+    "fp16 block, fp32 to_out": ("plain", "panels", LATENT, torch.float16, {"f32_out": True}),
+    "a bool mask": ("bool mask", "panels", LATENT, torch.float16, {"counting": True}),
+    "processor kwargs": ("plain", "panels", LATENT, torch.float16, {"counting": True, "kwargs": {"scale": 1.0}}),
+    "fp32 fp32_projections": ("plain", "panels", LATENT, torch.float32, {"fp32_projections": True}),
+    "fp32": ("plain", "panels", LATENT, torch.float32, {"counting": True}),
+    "control injecting": ("plain", "panels", LATENT, torch.float16, {"control": "in"}),
+    "control injecting N=250": ("plain", "panels", (10, 25), torch.float16, {"control": "in"}),
+    "FF_MODE=blas control injecting": ("plain", "blas", LATENT, torch.float16, {"control": "in"}),
+}
+
+
+def cross_case(vidtome_amd, kind, latent=LATENT, dt=torch.float16, registered=(), control=None, f32_out=False, counting=False,
+               fp32_projections=False, kwargs=None):
+    """(model, block, hidden states, conditioning, mask, cross_attention_kwargs, LocalBlend or None) of one full block (C = 320,
+    77 text tokens of width 768) at ``latent``: everything is switched on through the public ``register_*`` functions; the
+    timestep is stamped as ``pnp.register_time`` stamps it.  ``counting``: attn2's own forward counts its calls and returns
+    zeros (the site stand-ins have none)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import cross_control_standin
+    import ip_adapter_mask_standin
+    import ip_adapter_standin
+    from vidtome_amd import sites as S
+    C, T, n = 320, 77, B * FRAMES
+    g = torch.Generator().manual_seed(3)
+    text = torch.randn(n, T, 768, generator=g).to(device=DEV, dtype=dt)
+    torch.manual_seed(123)
+    unet, site, blk = site_block(vidtome_amd, S, dt, C, 8, full=True)
+    unet.set_size(latent)
+    enc, mask, kw = text, None, dict(kwargs or {})
+    if kind == "masked":
+        keep = torch.arange(T)[None, :] < torch.tensor([57, 30] * FRAMES)[:, None]
+        mask = ((1 - keep.to(dt)) * -10000.0).unsqueeze(1).to(DEV)
+    elif kind == "bool mask":
+        mask = torch.ones(n, 1, T, dtype=torch.bool, device=DEV)
+    elif kind == "ip-adapter":
+        ip_adapter_standin.install(unet, (4, 16), (0.6, 0.3))
+        enc = (text, ip_adapter_standin.image_states((4, 16), n, 768, dt, DEV))
+    elif kind == "ip-adapter region masks":
+        ip_adapter_mask_standin.install(unet, (16, 4), (1.0, 0.6))
+        left, top = torch.zeros(1, 1, *latent, device=DEV), torch.zeros(1, 1, *latent, device=DEV)
+        left[..., :latent[1] // 2] = 1
+        top[:, :, :latent[0] // 2] = 1
+        enc = (text, [torch.randn(n, 1, t, 768, generator=g).to(device=DEV, dtype=dt) for t in (16, 4)])
+        kw["ip_adapter_masks"] = [left, top]
+    if f32_out:
+        blk.attn2.to_out[0].float()
+    if fp32_projections:
+        vidtome_amd.update_patch(unet, fp32_projections=True)
+    if counting:
+        blk.attn2.__class__ = type("Attention", (CountingAttention, type(blk.attn2)), {})
+        if kw:                                               # (processor kwargs send attn1 to its own forward too)
+            blk.attn1.__class__ = type("Attention", (CountingAttention, type(blk.attn1)), {})
+    groups = 4 if control else B
+    lb = None
+    if "maps" in registered:
+        vidtome_amd.register_attention_maps(unet)
+    if "blend" in registered:
+        w = torch.rand(2, T, generator=g)
+        lb = vidtome_amd.LocalBlend({0: w[0], groups // 2: w[1]}, groups, n // groups)
+        vidtome_amd.register_local_blend(unet, lb)
+    if control:
+        swap = cross_control_standin.edit_of(cross_control_standin.specs(T)["replace"])
+        edits = {1: vidtome_amd.CrossEdit.identity(T), 2: swap}
+        vidtome_amd.register_cross_attention_control(unet, [981], groups, edits)
+        blk.attn2.t = 981 if control == "in" else 941
+    h = S.synthetic_hidden(site, B, FRAMES, latent, dt, DEV, seed=50, clip_seed=7)
+    return unet, blk, h, enc, mask, kw, lb
+
+
+def run_cross_side(vidtome_amd, out):
+    """attn2's side launches and its controlled core, through the block forward alone."""
+    from vidtome_amd import _lib, patch as vpatch
+    keep_ff = vpatch.FF_MODE
+    try:
+        for ff_mode in ("panels", "blas"):
+            vpatch.FF_MODE = ff_mode
+            for name, kind, registered, control, odd in SIDE_CASES:
+                for latent in (LATENT, (10, 25)) if odd else (LATENT,):
+                    unet, blk, h, enc, mask, kw, lb = cross_case(vidtome_amd, kind, latent, registered=registered,
+                                                                 control=control)
+                    with torch.no_grad(), Spy(_lib) as spy:
+                        y = blk(h, encoder_hidden_states=enc, encoder_attention_mask=mask, cross_attention_kwargs=kw or None)
+                    emit(out, f"cross/FF_MODE={ff_mode} {name} block forward N={h.shape[1]}", spy, y, blk)
+                    out[-1] += f" | probs {sha(getattr(blk, 'attn2_probs', None))} | blend {sha(None if lb is None else lb._acc)}"
+                    vidtome_amd.remove_patch(unet)
+    finally:
+        vpatch.FF_MODE = keep_ff
+
+
 def run_f32_blocks(vidtome_amd, out):
     """The whole forward of an fp32 block (C = 320) with the fp32_projections opt-in (without it attn2 is the module's own
     forward, which the site stand-ins do not have)."""
@@ -297,6 +418,7 @@ def main():
     run_unmerged(vidtome_amd, out)
     run_cross(vidtome_amd, out)
     run_f32_blocks(vidtome_amd, out)
+    run_cross_side(vidtome_amd, out)
     torch.cuda.synchronize()
     out.append("occurred in chunks/*: " + "; ".join(sorted(seen)))
     text = "\n".join(out) + "\n"

@@ -6,8 +6,8 @@
 Per site, event-timed in ONE process on the same inputs, the variants interleaved repetition by repetition so they share
 the clock:
   unregistered  norm_cross_attention_residual as a block without the control runs it (vtm_attention_kv)
-  fused         controlled_cross_attention_residual: the plain core on [source | uncond], vtm_cross_edit_values and ONE
-                vtm_attention_kv_sets_src launch on the cond group
+  fused         norm_cross_attention_residual with ``ctl=``: the plain core on [source | uncond], vtm_cross_edit_values and
+                ONE vtm_attention_kv_sets_src launch on the cond group
   composed_kv   the same edit from the pieces that existed before: V' = M diag(a) V and V'' = diag(b) V in torch, two
                 vtm_attention_kv launches on the cond group (the source's q / k on V', its own on V'') plus an add
   torch_probs   what a Prompt-to-Prompt processor does: LayerNorm + three library GEMMs, the (B F heads, N, 77)
@@ -85,7 +85,7 @@ def main():
             return vpatch.norm_cross_attention_residual(norm, attn, h, text)
 
         def fused():
-            return vpatch.controlled_cross_attention_residual(blk, h, text, ctl, "panels")
+            return vpatch.norm_cross_attention_residual(norm, attn, h, text, ctl=ctl)
 
         def composed_kv():
             n = G * Fr * N

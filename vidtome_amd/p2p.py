@@ -17,7 +17,7 @@ three controllers and the ``cross_replace_alpha`` blend ``attn_new * aw + (1 - a
     reweight   on top of either (or of the source)     a times eq       the aw part of b times eq
 
 The form is linear in the probabilities, so the patched block never builds them: P_edit V = P_src (M diag(a) V) +
-P_own (diag(b) V), two softmaxes over two key sets with two value operands (patch.controlled_cross_attention_residual:
+P_own (diag(b) V), two softmaxes over two key sets with two value operands (the controlled core of patch._attn2_core:
 vtm_cross_edit_values + one vtm_attention_kv_sets_src launch per edited group).
 
 The batch is group-major like PnP's: sample b = g * (BF / num_inputs) + f, group 0 the source, and the source of sample b is

@@ -28,7 +28,7 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Any, Callable, Dict, Optional, Tuple, Type
+from typing import Any, Callable, Dict, NamedTuple, Optional, Tuple, Type
 
 import torch
 import torch.nn.functional as F
@@ -931,11 +931,16 @@ def self_attention(attn: torch.nn.Module, x: torch.Tensor, M: Optional[int] = No
     return F.linear(o, wo, bo)
 
 
-def _cross_kv(to_k: torch.nn.Module, to_v: torch.nn.Module, enc: torch.Tensor, C: int, panels: bool = True):
-    """k (B, Mkp, C) and v^T (B, C, Mkp) of conditioning tokens ``enc`` (B, Mkp, D) in the tokens' dtype, Mkp % 8 == 0: panel
-    GEMMs when the width allows (``panels``: the FF_MODE == "panels" path), else library GEMMs."""
+def _cross_kv(to_k: torch.nn.Module, to_v: torch.nn.Module, enc: torch.Tensor, C: int, mode: str = "panels"):
+    """k (B, Mkp, C) and v^T (B, C, Mkp) of conditioning tokens ``enc`` (B, Mkp, D) in the tokens' dtype, Mkp % 8 == 0.
+    ``mode`` is the frame's: "panels" -- panel GEMMs when the width allows, else library GEMMs with one warning; "blas" --
+    library GEMMs; "f32" -- vtm_linear_f32 on fp32 tokens of any row count (the GEMM pads its output to a multiple of 8)."""
     B, Mkp, D = enc.shape
     dt = enc.dtype
+    if mode == "f32":
+        return (_lib.linear_f32(enc, None, None, None, Mkp, *_linear(to_k, dt)[:2]),
+                _lib.linear_f32(enc, None, None, None, Mkp, *_linear(to_v, dt)[:2], transposed=True))
+    panels = mode == "panels"
     if panels and D % 64 == 0 and lora.base_linear(to_k).weight.dtype == dt and lora.base_linear(to_v).weight.dtype == dt:
         ep = _lib.to_panels(enc.reshape(B * Mkp, D))                     # the (few) conditioning tokens: 77 per frame in SD
         wk, bk = _panel_weight(to_k)
@@ -958,9 +963,10 @@ def _pad_keys(enc: torch.Tensor, dt) -> torch.Tensor:
     return F.pad(enc, (0, 0, 0, pad)) if pad else enc
 
 
-def _ip_key_sets(attn: torch.nn.Module, ip: "ip_adapter.Call", dt, C: int, panels: bool):
-    """The operands of the IP-Adapter core: text k / v^T as for the plain block, every adapter whose scale is not 0
-    projected the same way with to_k_ip[a] / to_v_ip[a] into its slice of ONE k (B, Mkp, C) and ONE v^T (B, C, Mkp) buffer
+def _ip_key_sets(attn: torch.nn.Module, ip: "ip_adapter.Call", dt, C: int, mode: str):
+    """The operands of the IP-Adapter core: text k / v^T as for the plain block (``mode``: ``_cross_kv``'s), every adapter
+    whose scale is not 0 projected the same way with to_k_ip[a] / to_v_ip[a] into its slice of ONE k (B, Mkp, C) and ONE v^T
+    (B, C, Mkp) buffer
     -> (k, vt, [(start, length, weight)], mask rows, mask table).  With no adapter taking part k / vt ARE the plain block's
     tensors.  Region masks (``ip.masks``): all m_a * T_a image tokens of a masked adapter are projected in one GEMM like any
     other adapter's, then every image's T_a rows go to a set of their own on a multiple of 8 keys; the mask rows name each
@@ -972,11 +978,11 @@ def _ip_key_sets(attn: torch.nn.Module, ip: "ip_adapter.Call", dt, C: int, panel
         sets, active, _, rows = ip_adapter.masked_key_sets(ip.text.shape[1], lens, ip.scales, images)
     else:
         (sets, active, _), rows = ip_adapter.key_sets(ip.text.shape[1], lens, ip.scales), []
-    k, vt = _cross_kv(attn.to_k, attn.to_v, _pad_keys(ip.text, dt), C, panels)
+    k, vt = _cross_kv(attn.to_k, attn.to_v, _pad_keys(ip.text, dt), C, mode)
     if active:
         parts = [(k, vt)]
         for a in active:
-            ka, vta = _cross_kv(ip.k_proj[a], ip.v_proj[a], _pad_keys(ip.images[a], dt), C, panels)
+            ka, vta = _cross_kv(ip.k_proj[a], ip.v_proj[a], _pad_keys(ip.images[a], dt), C, mode)
             t = lens[a] // max(images[a], 1)
             if images[a] > 1 and t % 8:                                 # every image's keys onto a multiple of 8
                 pad = -t % 8
@@ -991,22 +997,6 @@ def _ip_key_sets(attn: torch.nn.Module, ip: "ip_adapter.Call", dt, C: int, panel
     return k, vt, sets, rows, table
 
 
-def _ip_core(attn: torch.nn.Module, ip: "ip_adapter.Call", q: torch.Tensor, N: int, scale: float, panels: bool,
-             probs_to: Optional[torch.nn.Module] = None, words_to=None) -> torch.Tensor:
-    """The decoupled cross-attention of an IP-Adapter call on query tokens q (B, Np, C), N <= Np of them meaningful: ONE
-    launch over the text keys and every adapter's image keys -- vtm_attention_kv_sets, or vtm_attention_kv_sets_masked when
-    the call carries region masks.  ``probs_to``: a registered block gets the map of the TEXT set, with its own softmax --
-    k rows [0, text length) of the buffer."""
-    k, vt, sets, rows, table = _ip_key_sets(attn, ip, q.dtype, q.shape[-1], panels)
-    if probs_to is not None:
-        probs_to.attn2_probs = _probs_rows(q, k, attn.heads, N, ip.text.shape[1], scale)
-    if words_to is not None:                                   # (likewise the text set's)
-        add_word_maps(words_to, q, k, attn.heads, N, ip.text.shape[1], scale)
-    if table is None:
-        return _lib.attention_kv_sets(q, k, vt, attn.heads, N, sets, scale)
-    return _lib.attention_kv_sets_masked(q, k, vt, attn.heads, N, sets, scale, rows, table)
-
-
 def _key_bias_ok(attention_mask, B: int, Mk: int, device=None) -> bool:
     """The mask form ``key_bias`` takes: Diffusers' UNet turns an ``encoder_attention_mask`` (B, K) into the additive
     (B, 1, K) bias ``(1 - mask) * -10000`` in the sample's dtype -- one value per key, for every head and every query."""
@@ -1016,8 +1006,8 @@ def _key_bias_ok(attention_mask, B: int, Mk: int, device=None) -> bool:
 
 
 def key_bias(attention_mask, B: int, Mk: int, device=None) -> Optional[torch.Tensor]:
-    """The per-key score bias of a masked attn2 call for vtm_attention_kv_bias: fp32 rows (B or 1, Mk) from an additive
-    floating-point ``attention_mask`` of shape (B or 1, 1, Mk) on ``device`` (the tokens'; None: not asked), else None --
+    """The per-key score bias of a masked attn2 call for the biased core (``_attn2_core``): fp32 rows (B or 1, Mk) from an
+    additive floating-point ``attention_mask`` of shape (B or 1, 1, Mk) on ``device`` (the tokens'; None: not asked), else None --
     the module path.  Bool / integer masks, 2-D masks, per-query masks (B, N, K) and a key count that is not the
     conditioning's are the module's own business.  One dtype conversion, nothing is read back to the host."""
     if not _key_bias_ok(attention_mask, B, Mk, device):
@@ -1143,82 +1133,6 @@ def add_word_maps_module_path(words_to, attn: torch.nn.Module, x: torch.Tensor, 
             acc[gi].index_add_(0, rows_out, torch.matmul(probs[g * Fg:(g + 1) * Fg], weights[gi]))
 
 
-def norm_cross_attention_residual(norm: torch.nn.Module, attn: torch.nn.Module, hidden_states: torch.Tensor,
-                                  encoder_hidden_states: torch.Tensor, ip: Optional["ip_adapter.Call"] = None,
-                                  attention_mask=None, probs_to: Optional[torch.nn.Module] = None,
-                                  words_to=None) -> torch.Tensor:
-    """patch.py:171-185 for the plain case: ``attn2(norm2(hidden_states), encoder_hidden_states) + hidden_states`` with the
-    query projection as a panel GEMM fed by the LayerNorm (vtm_layernorm_panels -> vtm_linear_panels: the normalised
-    tokens are only ever read by to_q, so they are written once, as panels), k / v^T of the (few) conditioning tokens by the
-    library, the attention core on vtm_attention_kv and the output projection + bias + residual as a panel GEMM too.
-    The caller has checked ``fused_cross_ok``.
-    With ``ip`` (an IP-Adapter call, ``ip_cross_call``; ``encoder_hidden_states`` is then not read) the core is ONE
-    vtm_attention_kv_sets launch over the text keys and every adapter's image keys, or with region masks ONE
-    vtm_attention_kv_sets_masked launch (``_ip_core``).
-    With ``attention_mask`` (the plain case only; ``fused_cross_ok`` has accepted its form, ``key_bias``) the core is
-    vtm_attention_kv_bias; everything around it is the same.
-    With ``probs_to`` (a block registered by ``maps.register_attention_maps``) one vtm_attention_probs launch beside the core
-    leaves ``probs_to.attn2_probs`` from the same q / k rows (an IP-Adapter call: the text set's); nothing else changes.
-    With ``words_to`` (``local_blend_of`` a block registered by ``blend.register_local_blend``) the same rows feed
-    ``add_word_maps``."""
-    B, N, C = hidden_states.shape
-    heads, scale = attn.heads, _scale(attn, C)
-    dt = hidden_states.dtype
-    hs = hidden_states.contiguous()
-    n = B * N
-    wq, bq = _panel_weight(attn.to_q)
-    wo, bo = _panel_weight(_out_linear(attn))
-    xp = _lib.layernorm_panels(hs, norm.weight, norm.bias, norm.eps)
-    q = _lib.linear_panels(xp, n, wq, C, bq).view(B, N, C)             # any N: the core's query row stride is N itself
-    if ip is None:
-        Mk = encoder_hidden_states.shape[1]
-        k, vt = _cross_kv(attn.to_k, attn.to_v, _pad_keys(encoder_hidden_states, dt), C)
-        bias = None if attention_mask is None else key_bias(attention_mask, B, Mk, hs.device)
-        if bias is None:
-            o = _lib.attention_kv(q, k, vt, heads, N, Mk, scale)
-        else:
-            o = _lib.attention_kv_bias(q, k, vt, heads, N, Mk, scale, bias)
-        if probs_to is not None:
-            probs_to.attn2_probs = _probs_rows(q, k, heads, N, Mk, scale, bias)
-        if words_to is not None:
-            add_word_maps(words_to, q, k, heads, N, Mk, scale, bias)
-    else:
-        o = _ip_core(attn, ip, q, N, scale, True, probs_to, words_to)
-    op = _lib.to_panels(o.view(n, C))
-    return _lib.linear_panels(op, n, wo, C, bo, resid=hs.view(n, C)).view(B, N, C)
-
-
-def fused_cross_ok(norm: torch.nn.Module, attn: torch.nn.Module, x: torch.Tensor, encoder_hidden_states,
-                   attention_mask, kwargs, processors=_PLAIN_PROCESSORS) -> bool:
-    # (an IP-Adapter block hands a TUPLE as encoder_hidden_states: not a tensor, not this path -- see ip_cross_call)
-    # An attention_mask of the per-key form (``key_bias``) goes along: the core is then vtm_attention_kv_bias.
-    return (FF_MODE == "panels" and isinstance(encoder_hidden_states, torch.Tensor) and not kwargs
-            and encoder_hidden_states.dim() == 3 and x.dim() == 3 and x.is_cuda and x.dtype in (torch.float16, torch.bfloat16)
-            and (attention_mask is None or _key_bias_ok(attention_mask, x.shape[0], encoder_hidden_states.shape[1], x.device))
-            and _plain_layernorm(norm, x) and x.shape[-1] % 64 == 0 and _proj_dtypes_ok(attn, x.dtype)
-            and fused_attention_ok(attn, x, self_attn=False, processors=processors))
-
-
-def ip_cross_call(attn: torch.nn.Module, x: torch.Tensor, encoder_hidden_states, attention_mask, kwargs,
-                  norm: Optional[torch.nn.Module] = None) -> Optional["ip_adapter.Call"]:
-    """The IP-Adapter call of attn2 when the fused path may take it, else None (the module path): the processor and the
-    call are what `ip_adapter.recognise` understands, and the module is everything ``fused_attention_ok`` asks of attn2
-    apart from the processor's name.  With ``norm`` (norm2): for the panel path of ``norm_cross_attention_residual`` --
-    what ``fused_cross_ok`` asks, on the text tokens; without: for ``cross_attention``'s library GEMMs around the core."""
-    if not ip_adapter.is_ip_processor(attn):
-        return None
-    ip = ip_adapter.recognise(attn, x, encoder_hidden_states, attention_mask, kwargs)
-    if ip is None:
-        return None
-    if norm is not None:
-        # the panel path of an IP-Adapter call still asks N % 8 == 0, as tests/test_ip_adapter_host.py
-        # (test_panel_path_asks_what_fused_cross_ok_asks) pins: other token counts take cross_attention's library GEMMs
-        if x.dim() != 3 or x.shape[1] % 8:
-            return None
-        return ip if fused_cross_ok(norm, attn, x, ip.text, None, None, ip_adapter.PROCESSORS) else None
-    return ip if fused_attention_ok(attn, x, self_attn=False, processors=ip_adapter.PROCESSORS) else None
-
-
 def _f32_layernorm_ok(norm: torch.nn.Module, x: torch.Tensor) -> bool:
     """A plain LayerNorm over the channel axis of fp32 tokens that vtm_layernorm takes."""
     return x.dtype == torch.float32 and _plain_layernorm(norm, x) and x.shape[-1] % 8 == 0 and x.shape[-1] <= 2048
@@ -1234,77 +1148,8 @@ def f32_cross_ok(block: torch.nn.Module, norm: torch.nn.Module, attn: torch.nn.M
             and fused_attention_ok(attn, x, self_attn=False))
 
 
-def norm_cross_attention_f32(norm: torch.nn.Module, attn: torch.nn.Module, hidden_states: torch.Tensor,
-                             encoder_hidden_states: torch.Tensor, probs_to: Optional[torch.nn.Module] = None,
-                             words_to=None) -> torch.Tensor:
-    """patch.py:171-185 for an fp32 block with ``fp32_projections``: ``attn2(norm2(h), encoder_hidden_states) + h`` as
-    vtm_layernorm, the q GEMM, the k / V^T GEMMs of the conditioning tokens (padded to a multiple of 8 rows), the fp32
-    attention core (whatever ``fp32_attention`` says: the module forward it replaces is fp32, and 77 keys keep it cheap)
-    and the output GEMM with the residual add in its epilogue.  The caller has checked ``f32_cross_ok``."""
-    B, N, C = hidden_states.shape
-    heads, scale = attn.heads, _scale(attn, C)
-    f32 = torch.float32
-    hs = hidden_states.contiguous()
-    enc = encoder_hidden_states.to(f32).contiguous()
-    Mk = enc.shape[1]
-    xn = _lib.layernorm(hs, norm.weight, norm.bias, norm.eps)
-    q = _lib.linear_f32(xn, None, None, None, N, *_linear(attn.to_q, f32)[:2])                             # (B, N8, C)
-    k = _lib.linear_f32(enc, None, None, None, Mk, *_linear(attn.to_k, f32)[:2])                           # (B, Mkp, C)
-    vt = _lib.linear_f32(enc, None, None, None, Mk, *_linear(attn.to_v, f32)[:2], transposed=True)         # (B, C, Mkp)
-    o = _lib.attention_kv(q, k, vt, heads, N, Mk, scale)
-    if probs_to is not None:                                  # (fp32 rows: the torch restatement)
-        probs_to.attn2_probs = _probs_rows(q, k, heads, N, Mk, scale)
-    if words_to is not None:
-        add_word_maps(words_to, q, k, heads, N, Mk, scale)
-    return _lib.linear_f32(o, None, None, None, N, *_linear(_out_linear(attn), f32)[:2], epilogue="resid", resid=hs,
-                           out=torch.empty_like(hs))
-
-
-def cross_attention(attn: torch.nn.Module, x: torch.Tensor, encoder_hidden_states: Optional[torch.Tensor],
-                    attention_mask=None, probs_to: Optional[torch.nn.Module] = None, words_to=None, **kwargs) -> torch.Tensor:
-    """`self.attn2(norm_hidden_states, encoder_hidden_states=..., attention_mask=...)` (patch.py:178-183) -- the
-    un-merged tokens attending to the conditioning (77 text tokens in SD).  The plain case (projection Linears, no
-    mask, no processor kwargs) runs on vtm_attention_kv, the plain case with a per-key additive mask (``key_bias``) on
-    vtm_attention_kv_bias, a recognised IP-Adapter call (``ip_cross_call``) on vtm_attention_kv_sets (with region masks:
-    vtm_attention_kv_sets_masked), with library GEMMs around the core; everything else is the module's own forward.
-    ``probs_to``: a registered block gets ``attn2_probs`` on whichever of these paths the call takes; ``words_to``
-    (``local_blend_of``): its LocalBlend gets the word maps likewise."""
-    plain = (isinstance(encoder_hidden_states, torch.Tensor) and not kwargs
-             and encoder_hidden_states.dim() == 3 and x.dtype in (torch.float16, torch.bfloat16)
-             and fused_attention_ok(attn, x, self_attn=False)
-             and (attention_mask is None or _key_bias_ok(attention_mask, x.shape[0], encoder_hidden_states.shape[1], x.device)))
-    ip = None if plain else ip_cross_call(attn, x, encoder_hidden_states, attention_mask, kwargs)
-    if not plain and ip is None:
-        if probs_to is not None:
-            probs_to.attn2_probs = _module_path_probs(attn, x, encoder_hidden_states, attention_mask)
-        if words_to is not None:
-            add_word_maps_module_path(words_to, attn, x, encoder_hidden_states, attention_mask)
-        return attn(x, encoder_hidden_states=encoder_hidden_states, attention_mask=attention_mask, **kwargs)
-    B, N, C = x.shape
-    heads, scale = attn.heads, _scale(attn, C)
-    xq = F.pad(x, (0, 0, 0, -N % 8)) if N % 8 else x
-    q = _apply_linear(attn.to_q, xq, x.dtype)
-    if ip is not None:
-        o = _ip_core(attn, ip, q, N, scale, False, probs_to, words_to)
-    else:
-        Mk = encoder_hidden_states.shape[1]
-        enc = _pad_keys(encoder_hidden_states, x.dtype)
-        k = _apply_linear(attn.to_k, enc, x.dtype)
-        vt = _apply_linear(attn.to_v, enc, x.dtype).transpose(1, 2).contiguous()     # (B, C, Mkp): 77 keys, negligible
-        bias = None if attention_mask is None else key_bias(attention_mask, B, Mk, x.device)
-        if bias is None:
-            o = _lib.attention_kv(q, k, vt, heads, N, Mk, scale)
-        else:
-            o = _lib.attention_kv_bias(q, k, vt, heads, N, Mk, scale, bias)
-        if probs_to is not None:
-            probs_to.attn2_probs = _probs_rows(q, k, heads, N, Mk, scale, bias)
-        if words_to is not None:
-            add_word_maps(words_to, q, k, heads, N, Mk, scale, bias)
-    return _apply_linear(_out_linear(attn), o, o.dtype)[:, :N]
-
-
 # ----------------------------------------------------------------------------------------------------
-# attn2 under Prompt-to-Prompt cross-attention control (vidtome_amd/p2p.py)
+# attn2: the control of an injecting step (vidtome_amd/p2p.py), the route, the core dispatch, one body per frame
 # ----------------------------------------------------------------------------------------------------
 def cross_control(block: torch.nn.Module):
     """(num_inputs, edits, block name) when ``p2p.register_cross_attention_control`` selected the block and this step
@@ -1320,17 +1165,71 @@ def cross_control(block: torch.nn.Module):
     return num_inputs, edits, name
 
 
-def cross_control_route(block: torch.nn.Module, x: torch.Tensor, encoder_hidden_states, attention_mask, kwargs, ctl) -> str:
-    """How an injecting block computes its attn2 segment on tokens like ``x``: "panels" (what ``fused_cross_ok`` asks: the
-    LayerNorm -> q panel GEMM -> core -> output GEMM + residual chain of ``norm_cross_attention_residual``) or "blas"
-    (``cross_attention``'s library GEMMs around the core).  Everything else RAISES, naming the block and the reason, before
-    anything is launched: there is no module path under control, an edit is never silently dropped."""
+def _edited_probs(probs: torch.Tensor, rows: slice, src: slice, edit) -> None:
+    """The head-averaged map of an edited group, in place: head-averaging commutes with the edit."""
+    M, a, b = edit.on(probs.device)
+    probs[rows] = torch.matmul(probs[src], M) * a + probs[rows] * b
+
+
+class Attn2Route(NamedTuple):
+    """``attn2_route``'s answer: the frame, and the recognised IP-Adapter call when the call is one."""
+    frame: str
+    ip: Optional["ip_adapter.Call"] = None
+
+
+def _plain_call_ok(attn: torch.nn.Module, x: torch.Tensor, encoder_hidden_states, attention_mask, kwargs,
+                   processors=_PLAIN_PROCESSORS) -> bool:
+    """A call the plain or the biased core computes on 16-bit tokens: a (B, K, D) conditioning tensor (an IP-Adapter block
+    hands a TUPLE: not this call), no processor kwargs, a module that is the plain arithmetic (``fused_attention_ok``) and no
+    mask or one of ``key_bias``'s form."""
+    enc = encoder_hidden_states
+    return (isinstance(enc, torch.Tensor) and not kwargs and enc.dim() == 3 and x.dtype in (torch.float16, torch.bfloat16)
+            and fused_attention_ok(attn, x, self_attn=False, processors=processors)
+            and (attention_mask is None or _key_bias_ok(attention_mask, x.shape[0], enc.shape[1], x.device)))
+
+
+def _panels_ok(norm: torch.nn.Module, attn: torch.nn.Module, x: torch.Tensor, ip: Optional["ip_adapter.Call"] = None) -> bool:
+    """What the panels frame asks on top of a call the library-GEMM frame takes: FF_MODE "panels", a plain norm2 on device
+    tokens, C % 64 == 0 and the four projection weights in the tokens' dtype.  An IP-Adapter call still asks N % 8 == 0, as
+    tests/test_ip_adapter_host.py (test_panel_path_asks_what_fused_cross_ok_asks) pins: other token counts are "blas"."""
+    return (FF_MODE == "panels" and x.is_cuda and _plain_layernorm(norm, x) and x.shape[-1] % 64 == 0
+            and _proj_dtypes_ok(attn, x.dtype) and (ip is None or x.shape[1] % 8 == 0))
+
+
+def fused_cross_ok(norm: torch.nn.Module, attn: torch.nn.Module, x: torch.Tensor, encoder_hidden_states,
+                   attention_mask, kwargs, processors=_PLAIN_PROCESSORS) -> bool:
+    """``attn2_route``'s "panels" for a call without an IP-Adapter and without control, as a predicate."""
+    return _plain_call_ok(attn, x, encoder_hidden_states, attention_mask, kwargs, processors) and _panels_ok(norm, attn, x)
+
+
+def ip_cross_call(attn: torch.nn.Module, x: torch.Tensor, encoder_hidden_states, attention_mask, kwargs,
+                  norm: Optional[torch.nn.Module] = None) -> Optional["ip_adapter.Call"]:
+    """The IP-Adapter call of attn2 when the fused path may take it, else None (the module path): the processor and the
+    call are what `ip_adapter.recognise` understands (never a masked call), and the module is everything
+    ``fused_attention_ok`` asks of attn2 apart from the processor's name.  With ``norm`` (norm2): for the panels frame;
+    without: for the library GEMMs of ``cross_attention``."""
+    ip = ip_adapter.recognise(attn, x, encoder_hidden_states, attention_mask, kwargs)
+    if ip is None or not fused_attention_ok(attn, x, self_attn=False, processors=ip_adapter.PROCESSORS):
+        return None
+    return ip if norm is None or _panels_ok(norm, attn, x, ip) else None
+
+
+def _attn2_lib_route(attn: torch.nn.Module, x: torch.Tensor, encoder_hidden_states, attention_mask, kwargs) -> Attn2Route:
+    """The half of ``attn2_route`` that is attn2's alone, for the tokens ``x`` its core would read: "blas" or "module"."""
+    if ip_adapter.is_ip_processor(attn):
+        ip = ip_cross_call(attn, x, encoder_hidden_states, attention_mask, kwargs)
+        return Attn2Route("module" if ip is None else "blas", ip)
+    return Attn2Route("blas" if _plain_call_ok(attn, x, encoder_hidden_states, attention_mask, kwargs) else "module")
+
+
+def _refuse_control(block: torch.nn.Module, x: torch.Tensor, enc, attention_mask, kwargs, ctl) -> None:
+    """What an injecting block does not take RAISES, naming the block and the reason, before anything is launched: there is
+    no module path under control, an edit is never silently dropped."""
     num_inputs, edits, name = ctl
     attn = block.attn2
 
     def refuse(why: str):
         raise RuntimeError(f"vidtome_amd: cross-attention control on block '{name}': {why}")
-    enc = encoder_hidden_states
     if isinstance(enc, tuple) or ip_adapter.is_ip_processor(attn):
         refuse("an IP-Adapter call is not taken (combining the control with image prompts is out of scope)")
     if not (isinstance(enc, torch.Tensor) and enc.dim() == 3 and x.dim() == 3 and enc.shape[0] == x.shape[0]):
@@ -1353,86 +1252,188 @@ def cross_control_route(block: torch.nn.Module, x: torch.Tensor, encoder_hidden_
         refuse(f"processor kwargs {sorted(kwargs)} are not taken")
     if not fused_attention_ok(attn, x, self_attn=False):
         refuse("attn2 is not the plain arithmetic the fused path computes (fused_attention_ok)")
-    return "panels" if fused_cross_ok(block.norm2, attn, x, enc, None, kwargs) else "blas"
 
 
-def _edited_probs(probs: torch.Tensor, rows: slice, src: slice, edit) -> None:
-    """The head-averaged map of an edited group, in place: head-averaging commutes with the edit."""
-    M, a, b = edit.on(probs.device)
-    probs[rows] = torch.matmul(probs[src], M) * a + probs[rows] * b
+def attn2_route(block: torch.nn.Module, x: torch.Tensor, encoder_hidden_states, encoder_attention_mask,
+                cross_attention_kwargs, control=None, normed: bool = False) -> Attn2Route:
+    """How the block computes its ``attn2`` segment on tokens like ``x`` (their device, rank, dtype and width are read), and
+    the recognised IP-Adapter call when the call is one.  Launches nothing; `ip_adapter.recognise` runs at most once.
+      "panels"  norm_cross_attention_residual: LayerNorm -> panels, q panel GEMM, core, output panel GEMM + residual.  fp16 /
+                bf16 device tokens, FF_MODE "panels", a plain norm2, C % 64 == 0, the four projection weights in the tokens'
+                dtype (``_panels_ok``), and a call "blas" takes; an IP-Adapter call also asks N % 8 == 0
+      "f32"     norm_cross_attention_f32: fp32 tokens with the block's ``fp32_projections``, a plain norm2, C % 8 == 0 and a
+                conditioning width % 8 == 0, fp32 projection weights, no mask of any form (``f32_cross_ok``)
+      "blas"    cross_attention: library GEMMs around the core.  fp16 / bf16 tokens, a module that is the plain arithmetic
+                (``fused_attention_ok``; an IP-Adapter processor when the call is one), and the call: a (B, K, D)
+                conditioning tensor without processor kwargs, with no mask or one of ``key_bias``'s form
+                (``_plain_call_ok``) -- or what `ip_adapter.recognise` reads (``ip_cross_call``: never with a mask)
+      "module"  attn2's own forward, through cross_attention: everything else
+    An AdaLayerNorm block never takes "panels" or "f32" (its norm2 needs the timestep), and with any non-None mask, even one
+    of ``key_bias``'s form, it is "module".
+    ``control`` (``cross_control``: an injecting step) knows "panels" and "blas" alone, by the same rules; every other call
+    RAISES (``_refuse_control``).
+    Which core runs follows from the call alone: ``_attn2_core``.
+    "panels" and "f32" are decided on the tokens in front of norm2, "blas" / "module" for the tokens the core reads: a norm2
+    that changes the dtype (a module-path LayerNorm under autocast, an AdaLayerNorm in another dtype) makes them differ, and
+    the block then asks again with ``normed`` and the normed tokens -- the question for the two frames that read them."""
+    attn, norm = block.attn2, block.norm2
+    fused = not (normed or block.use_ada_layer_norm)
+    if control is not None:
+        _refuse_control(block, x, encoder_hidden_states, encoder_attention_mask, cross_attention_kwargs, control)
+        route = Attn2Route("blas")
+    elif block.use_ada_layer_norm and encoder_attention_mask is not None:
+        return Attn2Route("module")
+    elif fused and f32_cross_ok(block, norm, attn, x, encoder_hidden_states, encoder_attention_mask, cross_attention_kwargs):
+        return Attn2Route("f32")
+    else:
+        route = _attn2_lib_route(attn, x, encoder_hidden_states, encoder_attention_mask, cross_attention_kwargs)
+    if fused and route.frame == "blas" and _panels_ok(norm, attn, x, route.ip):
+        return route._replace(frame="panels")
+    return route
 
 
-def _controlled_core(attn: torch.nn.Module, q: torch.Tensor, N: int, enc: torch.Tensor, ctl, scale: float, panels: bool,
-                     probs_to: Optional[torch.nn.Module], words_to=None) -> torch.Tensor:
-    """The attn2 core of an injecting block on query rows q (B F, Np, C), N <= Np of them meaningful; samples are
-    group-major, b = g * Fg + f, and the source of sample b is b % Fg.  k / v^T of EVERY sample come from the one projection
-    call the block makes without the control.  Contiguous runs of unedited groups (no edit, or the identity) then run the
-    plain core on their slices of q / out -- the bits of an uncontrolled block -- and each edited group is
+def cross_control_route(block: torch.nn.Module, x: torch.Tensor, encoder_hidden_states, attention_mask, kwargs, ctl) -> str:
+    """``attn2_route``'s frame for an injecting block: "panels" or "blas"; everything else raises."""
+    return attn2_route(block, x, encoder_hidden_states, attention_mask, kwargs, ctl).frame
+
+
+def _attn2_core(attn: torch.nn.Module, q: torch.Tensor, N: int, encoder_hidden_states, kv: str, attention_mask=None,
+                ip: Optional["ip_adapter.Call"] = None, ctl=None, probs_to: Optional[torch.nn.Module] = None,
+                words_to=None) -> torch.Tensor:
+    """The core of an attn2 call on query rows q (B, Np, C), N <= Np of them meaningful -> o (B, Np, C).  ``kv``: how k / v^T
+    are projected, the frame's mode of ``_cross_kv``.  The call alone says which core runs:
+      ``ctl`` (an injecting block)          the controlled core, below
+      ``ip`` without region masks           vtm_attention_kv_sets: ONE launch over the text keys and every adapter's image keys
+      ``ip`` with region masks              vtm_attention_kv_sets_masked, likewise (``_ip_key_sets``); the conditioning is the
+                                            call's, ``encoder_hidden_states`` is not read
+      an accepted mask (``key_bias``)       vtm_attention_kv_bias
+      otherwise                             vtm_attention_kv
+    The controlled core: samples are group-major, b = g * Fg + f, and the source of sample b is b % Fg.  k / v^T of EVERY
+    sample come from the one projection call the block makes without the control.  Contiguous runs of unedited groups (no
+    edit, or the identity) then run the plain core on their slices of q / o -- the bits of an uncontrolled block -- and each
+    edited group is
         k   = [k(enc[src]) | k(enc[own])]                      two key sets at 0 and K rounded up to 8
         V^T = [(M diag(a) V_own)^T | (diag(b) V_own)^T]        vtm_cross_edit_values
-        out = softmax(q[src] k_src^T) V' + softmax(q[own] k_own^T) V''     ONE vtm_attention_kv_sets_src launch
-    into its slice of out."""
-    num_inputs, edits, _ = ctl
+        o   = softmax(q[src] k_src^T) V' + softmax(q[own] k_own^T) V''     ONE vtm_attention_kv_sets_src launch
+    into its slice of o.
+    After the cores, from the same q / k rows (an IP-Adapter call: the text set's, with its own softmax): ``probs_to`` (a
+    block registered by ``maps.register_attention_maps``) gets ``attn2_probs``, one vtm_attention_probs launch, an edited
+    group's rows edited as its probabilities are (``_edited_probs``); then ``words_to`` (``local_blend_of`` a block registered
+    by ``blend.register_local_blend``) gets the word maps (``add_word_maps``)."""
     heads, C = attn.heads, q.shape[-1]
-    BF, Np = q.shape[0], q.shape[1]
-    Fg, K = BF // num_inputs, enc.shape[1]
-    K8 = (K + 7) // 8 * 8
-    k, vt = _cross_kv(attn.to_k, attn.to_v, _pad_keys(enc, q.dtype), C, panels)
-    out = (torch.zeros if Np != N else torch.empty)((BF, Np, C), dtype=q.dtype, device=q.device)
-    probs = None if probs_to is None else _probs_rows(q, k, heads, N, K, scale)
-    edited = [g in edits and not edits[g].is_identity for g in range(num_inputs)]
-    src = slice(0, Fg)
-    g = 0
-    while g < num_inputs:
-        if edited[g]:
-            rows = slice(g * Fg, (g + 1) * Fg)
-            M, a, b = edits[g].on(q.device)
-            k_sets = torch.cat([k[src], k[rows]], dim=1)               # (F, 2 K8, C)
-            vt_sets = _lib.cross_edit_values(vt[rows], 0, K, M, a, b, 0, K8,
-                                             out=torch.empty((Fg, C, 2 * K8), dtype=q.dtype, device=q.device))
-            _lib.attention_kv_sets_src(q[rows], q[src], k_sets, vt_sets, heads, N, [(0, K, 1.0), (K8, K, 1.0)], scale, (1, 0),
-                                       out=out[rows])
-            if probs is not None:
-                _edited_probs(probs, rows, src, edits[g])
-            g += 1
-            continue
-        g1 = g
-        while g1 < num_inputs and not edited[g1]:
-            g1 += 1
-        rows = slice(g * Fg, g1 * Fg)
-        _lib.attention_kv(q[rows], k[rows], vt[rows], heads, N, K, scale, out=out[rows])
-        g = g1
-    if probs_to is not None:
-        probs_to.attn2_probs = probs
-    if words_to is not None:                                   # (the edited groups' maps: add_word_maps)
-        add_word_maps(words_to, q, k, heads, N, K, scale, ctl=ctl)
-    return out
-
-
-def controlled_cross_attention_residual(block: torch.nn.Module, hidden_states: torch.Tensor,
-                                        encoder_hidden_states: torch.Tensor, ctl, route: str,
-                                        probs_to: Optional[torch.nn.Module] = None, words_to=None) -> torch.Tensor:
-    """patch.py:171-185 of an injecting block: ``attn2(norm2(h), enc) + h`` with the probabilities of the edited groups
-    replaced as Prompt-to-Prompt replaces them (``_controlled_core``).  ``route`` is ``cross_control_route``'s answer: around
-    the core stands what the uncontrolled block launches on that route."""
-    norm, attn = block.norm2, block.attn2
-    B, N, C = hidden_states.shape
     scale = _scale(attn, C)
-    with torch.no_grad():
-        if route == "panels":
-            hs = hidden_states.contiguous()
-            n = B * N
-            wq, bq = _panel_weight(attn.to_q)
-            wo, bo = _panel_weight(_out_linear(attn))
-            xp = _lib.layernorm_panels(hs, norm.weight, norm.bias, norm.eps)
-            q = _lib.linear_panels(xp, n, wq, C, bq).view(B, N, C)
-            o = _controlled_core(attn, q, N, encoder_hidden_states, ctl, scale, True, probs_to, words_to)
-            return _lib.linear_panels(_lib.to_panels(o.view(n, C)), n, wo, C, bo, resid=hs.view(n, C)).view(B, N, C)
-        x = layer_norm(norm, hidden_states)
-        xq = F.pad(x, (0, 0, 0, -N % 8)) if N % 8 else x
-        q = _apply_linear(attn.to_q, xq, x.dtype)
-        o = _controlled_core(attn, q, N, encoder_hidden_states, ctl, scale, False, probs_to, words_to)
-        return _apply_linear(_out_linear(attn), o, o.dtype)[:, :N] + hidden_states
+    bias, edited = None, []
+    if ip is not None:
+        Mk = ip.text.shape[1]
+        k, vt, sets, rows, table = _ip_key_sets(attn, ip, q.dtype, C, kv)
+    else:
+        Mk = encoder_hidden_states.shape[1]
+        enc = encoder_hidden_states.to(q.dtype).contiguous() if kv == "f32" else _pad_keys(encoder_hidden_states, q.dtype)
+        k, vt = _cross_kv(attn.to_k, attn.to_v, enc, C, kv)
+        bias = None if attention_mask is None else key_bias(attention_mask, q.shape[0], Mk, q.device)
+    if ctl is not None:
+        num_inputs, edits, _ = ctl
+        Fg, K8 = q.shape[0] // num_inputs, (Mk + 7) // 8 * 8
+        o = (torch.zeros if q.shape[1] != N else torch.empty)(q.shape, dtype=q.dtype, device=q.device)
+        is_edited = [g in edits and not edits[g].is_identity for g in range(num_inputs)]
+        src = slice(0, Fg)
+        g = 0
+        while g < num_inputs:
+            g1 = g + 1
+            if is_edited[g]:
+                own = slice(g * Fg, g1 * Fg)
+                M, a, b = edits[g].on(q.device)
+                k_sets = torch.cat([k[src], k[own]], dim=1)                # (F, 2 K8, C)
+                vt_sets = _lib.cross_edit_values(vt[own], 0, Mk, M, a, b, 0, K8,
+                                                 out=torch.empty((Fg, C, 2 * K8), dtype=q.dtype, device=q.device))
+                _lib.attention_kv_sets_src(q[own], q[src], k_sets, vt_sets, heads, N, [(0, Mk, 1.0), (K8, Mk, 1.0)], scale,
+                                           (1, 0), out=o[own])
+                edited.append((own, edits[g]))
+            else:
+                while g1 < num_inputs and not is_edited[g1]:
+                    g1 += 1
+                run = slice(g * Fg, g1 * Fg)
+                _lib.attention_kv(q[run], k[run], vt[run], heads, N, Mk, scale, out=o[run])
+            g = g1
+    elif ip is not None:
+        o = _lib.attention_kv_sets(q, k, vt, heads, N, sets, scale) if table is None else \
+            _lib.attention_kv_sets_masked(q, k, vt, heads, N, sets, scale, rows, table)
+    elif bias is not None:
+        o = _lib.attention_kv_bias(q, k, vt, heads, N, Mk, scale, bias)
+    else:
+        o = _lib.attention_kv(q, k, vt, heads, N, Mk, scale)
+    if probs_to is not None:
+        probs = _probs_rows(q, k, heads, N, Mk, scale, bias)
+        for own, edit in edited:
+            _edited_probs(probs, own, src, edit)
+        probs_to.attn2_probs = probs
+    if words_to is not None:
+        add_word_maps(words_to, q, k, heads, N, Mk, scale, bias, ctl=ctl)
+    return o
+
+
+def norm_cross_attention_residual(norm: torch.nn.Module, attn: torch.nn.Module, hidden_states: torch.Tensor,
+                                  encoder_hidden_states, ip: Optional["ip_adapter.Call"] = None, attention_mask=None,
+                                  probs_to: Optional[torch.nn.Module] = None, words_to=None, ctl=None) -> torch.Tensor:
+    """patch.py:171-185 on the panels frame: ``attn2(norm2(hidden_states), encoder_hidden_states) + hidden_states`` with the
+    query projection as a panel GEMM fed by the LayerNorm (vtm_layernorm_panels -> vtm_linear_panels: the normalised tokens
+    are only ever read by to_q, so they are written once, as panels), k / v^T of the (few) conditioning tokens as panel GEMMs
+    too, the core (``_attn2_core``: ``ip``, ``attention_mask``, ``ctl``, ``probs_to`` and ``words_to`` are its arguments) and
+    the output projection + bias + residual as a panel GEMM.  The caller has asked ``attn2_route`` (or ``fused_cross_ok``;
+    ``ip_cross_call`` with norm2 for ``ip``; ``cross_control_route`` for ``ctl``)."""
+    B, N, C = hidden_states.shape
+    hs = hidden_states.contiguous()
+    n = B * N
+    wq, bq = _panel_weight(attn.to_q)
+    wo, bo = _panel_weight(_out_linear(attn))
+    xp = _lib.layernorm_panels(hs, norm.weight, norm.bias, norm.eps)
+    q = _lib.linear_panels(xp, n, wq, C, bq).view(B, N, C)             # any N: the core's query row stride is N itself
+    o = _attn2_core(attn, q, N, encoder_hidden_states, "panels", attention_mask, ip, ctl, probs_to, words_to)
+    op = _lib.to_panels(o.view(n, C))
+    return _lib.linear_panels(op, n, wo, C, bo, resid=hs.view(n, C)).view(B, N, C)
+
+
+def norm_cross_attention_f32(norm: torch.nn.Module, attn: torch.nn.Module, hidden_states: torch.Tensor,
+                             encoder_hidden_states: torch.Tensor, probs_to: Optional[torch.nn.Module] = None,
+                             words_to=None) -> torch.Tensor:
+    """patch.py:171-185 for an fp32 block with ``fp32_projections``: ``attn2(norm2(h), encoder_hidden_states) + h`` as
+    vtm_layernorm, the q GEMM, the k / V^T GEMMs of the conditioning tokens (padded to a multiple of 8 rows), the fp32
+    attention core (whatever ``fp32_attention`` says: the module forward it replaces is fp32, and 77 keys keep it cheap; the
+    maps of fp32 rows are the torch restatement) and the output GEMM with the residual add in its epilogue.  The caller has
+    asked ``attn2_route`` (or ``f32_cross_ok``)."""
+    N = hidden_states.shape[1]
+    f32 = torch.float32
+    hs = hidden_states.contiguous()
+    xn = _lib.layernorm(hs, norm.weight, norm.bias, norm.eps)
+    q = _lib.linear_f32(xn, None, None, None, N, *_linear(attn.to_q, f32)[:2])                             # (B, N8, C)
+    o = _attn2_core(attn, q, N, encoder_hidden_states, "f32", probs_to=probs_to, words_to=words_to)
+    return _lib.linear_f32(o, None, None, None, N, *_linear(_out_linear(attn), f32)[:2], epilogue="resid", resid=hs,
+                           out=torch.empty_like(hs))
+
+
+def cross_attention(attn: torch.nn.Module, x: torch.Tensor, encoder_hidden_states, attention_mask=None,
+                    probs_to: Optional[torch.nn.Module] = None, words_to=None, ctl=None, route: Optional[Attn2Route] = None,
+                    **kwargs) -> torch.Tensor:
+    """`self.attn2(norm_hidden_states, encoder_hidden_states=..., attention_mask=...)` (patch.py:178-183) -- the
+    un-merged tokens attending to the conditioning (77 text tokens in SD) -- on the library-GEMM frame: pad to 8 rows, to_q,
+    the core (``_attn2_core``), to_out; or, for everything that frame does not take, the module's own forward.  ``route``:
+    what ``attn2_route`` answered for tokens like ``x``, when the caller has asked already; ``ctl``: an injecting block, whose
+    caller has asked (``cross_control_route``).  ``probs_to`` / ``words_to``: a registered block gets ``attn2_probs`` / its
+    LocalBlend the word maps on whichever of the two the call takes (the module path: the torch restatement)."""
+    if route is None:
+        route = Attn2Route("blas") if ctl is not None else _attn2_lib_route(attn, x, encoder_hidden_states, attention_mask,
+                                                                             kwargs)
+    if route.frame == "module":
+        if probs_to is not None:
+            probs_to.attn2_probs = _module_path_probs(attn, x, encoder_hidden_states, attention_mask)
+        if words_to is not None:
+            add_word_maps_module_path(words_to, attn, x, encoder_hidden_states, attention_mask)
+        return attn(x, encoder_hidden_states=encoder_hidden_states, attention_mask=attention_mask, **kwargs)
+    N = x.shape[1]
+    xq = F.pad(x, (0, 0, 0, -N % 8)) if N % 8 else x
+    q = _apply_linear(attn.to_q, xq, x.dtype)
+    o = _attn2_core(attn, q, N, encoder_hidden_states, "blas", attention_mask, route.ip, ctl, probs_to, words_to)
+    return _apply_linear(_out_linear(attn), o, o.dtype)[:, :N]
 
 
 # ----------------------------------------------------------------------------------------------------
@@ -1656,47 +1657,24 @@ def make_diffusers_tome_block(block_class: Type[torch.nn.Module]) -> Type[torch.
                 maps = self if getattr(self, "vtm_attention_maps", False) else None   # maps.register_attention_maps
                 words = local_blend_of(self)                                       # blend.register_local_blend
                 control = cross_control(self)                                      # p2p.register_cross_attention_control
-                ip = None if self.use_ada_layer_norm or control is not None else ip_cross_call(
-                    self.attn2, hidden_states, encoder_hidden_states, encoder_attention_mask, cross_attention_kwargs,
-                    self.norm2)
-                if control is not None:                                            # an injecting step: edited probabilities
-                    route = cross_control_route(self, hidden_states, encoder_hidden_states, encoder_attention_mask,
-                                                cross_attention_kwargs, control)
-                    hidden_states = controlled_cross_attention_residual(self, hidden_states, encoder_hidden_states, control,
-                                                                        route, probs_to=maps, words_to=words)
-                elif ip is not None:                                               # IP-Adapter: text + image key sets
-                    hidden_states = norm_cross_attention_residual(self.norm2, self.attn2, hidden_states, None, ip,
-                                                                  probs_to=maps, words_to=words)
-                elif not self.use_ada_layer_norm and fused_cross_ok(self.norm2, self.attn2, hidden_states,
-                                                                    encoder_hidden_states, encoder_attention_mask,
-                                                                    cross_attention_kwargs):
-                    hidden_states = norm_cross_attention_residual(self.norm2, self.attn2, hidden_states,
-                                                                  encoder_hidden_states,
-                                                                  attention_mask=encoder_attention_mask, probs_to=maps,
-                                                                  words_to=words)
-                elif not self.use_ada_layer_norm and f32_cross_ok(self, self.norm2, self.attn2, hidden_states,
-                                                                  encoder_hidden_states, encoder_attention_mask,
-                                                                  cross_attention_kwargs):
+                route = attn2_route(self, hidden_states, encoder_hidden_states, encoder_attention_mask, cross_attention_kwargs,
+                                    control)
+                if route.frame == "panels":
+                    hidden_states = norm_cross_attention_residual(self.norm2, self.attn2, hidden_states, encoder_hidden_states,
+                                                                  route.ip, encoder_attention_mask, maps, words, control)
+                elif route.frame == "f32":
                     hidden_states = norm_cross_attention_f32(self.norm2, self.attn2, hidden_states, encoder_hidden_states,
                                                              probs_to=maps, words_to=words)
-                else:
+                else:                                                              # "blas", "module": both read normed tokens
                     norm_hidden_states = (self.norm2(hidden_states, timestep) if self.use_ada_layer_norm
                                           else layer_norm(self.norm2, hidden_states))
-                    if self.use_ada_layer_norm and encoder_attention_mask is not None:
-                        # AdaLayerNorm blocks keep the module's own forward for a masked call, whatever the mask's form
-                        if maps is not None:
-                            self.attn2_probs = _module_path_probs(self.attn2, norm_hidden_states, encoder_hidden_states,
-                                                                  encoder_attention_mask)
-                        if words is not None:
-                            add_word_maps_module_path(words, self.attn2, norm_hidden_states, encoder_hidden_states,
-                                                      encoder_attention_mask)
-                        attn_output = self.attn2(norm_hidden_states, encoder_hidden_states=encoder_hidden_states,
-                                                 attention_mask=encoder_attention_mask, **cross_attention_kwargs)
-                    else:
-                        attn_output = cross_attention(self.attn2, norm_hidden_states, encoder_hidden_states,
-                                                      encoder_attention_mask, probs_to=maps, words_to=words,
-                                                      **cross_attention_kwargs)
-                    hidden_states = attn_output + hidden_states
+                    if control is None and norm_hidden_states.dtype != hidden_states.dtype:
+                        # (the route reads the tokens' dtype: a norm2 that changes it is routed on its output)
+                        route = attn2_route(self, norm_hidden_states, encoder_hidden_states, encoder_attention_mask,
+                                            cross_attention_kwargs, normed=True)
+                    hidden_states = cross_attention(self.attn2, norm_hidden_states, encoder_hidden_states,
+                                                    encoder_attention_mask, probs_to=maps, words_to=words, ctl=control,
+                                                    route=route, **cross_attention_kwargs) + hidden_states
 
             if not self.use_ada_layer_norm_zero and fused_ff_ok(self.norm3, self.ff, hidden_states):   # patch.py:187-199
                 return norm_feed_forward_residual(self.norm3, self.ff, hidden_states)
