@@ -741,6 +741,27 @@ int vtm_layernorm(const void *x, const void *gamma, const void *beta, int dtype,
                   float eps, void *out, vtm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * vtm_layernorm_gather -- norm3 on m(x): `self.norm3(...)` (vidtome/patch.py:187) applied to the rows a "replace"-mode merge
+ * closure selects (merge.py:119-133), for a feed-forward that runs on the merged tokens (tomesd's merge_mlp, which the
+ * reference dropped; patch.py's `merge_mlp` opt-in here).  It replaces vtm_gather_rows followed by vtm_layernorm /
+ * vtm_layernorm_panels: the merged tokens are never written.
+ *   x     (B, L, C) contiguous in `dtype`; gamma, beta (C) in the same dtype or NULL.
+ *   rows  (B, n) int32: output row b * n + i is the LayerNorm of x[b, rows[b, i], :].  Entries may repeat and come in any
+ *         order; n may exceed L.  They are NOT range-checked on the device: every entry must lie in [0, L) -- the caller's
+ *         business (the maps of compute_merge's local levels do).
+ *   out   panel_rows == 0: (B * n, C) token rows.  panel_rows > 0: k-panels [C / 8][panel_rows][8] as vtm_layernorm_panels
+ *         writes them, panel_rows = vtm_panel_rows(B * n) exactly; rows >= B * n of the panels are not written.  fp16 / bf16
+ *         only (fp32: token rows).
+ * The arithmetic is vtm_layernorm's, kernel for kernel (the kernel family is chosen from C and the B * L rows of x): sums in
+ * the same order, the same fused multiply-adds, one rounding.  Output row (b, i) is therefore BIT-EQUAL to row
+ * b * L + rows[b, i] of vtm_layernorm / vtm_layernorm_panels over the same x.  C % 8 == 0, C <= 2048, B <= 65535, L < 2^31;
+ * B == 0 or n == 0 is VTM_OK.  One launch, no workspace.  On a bad argument -- a NULL x / rows / out, an unsupported C or dtype,
+ * a panel_rows that is neither 0 nor vtm_panel_rows(B * n) -- VTM_EINVAL is returned and nothing is launched.
+ * ---------------------------------------------------------------------------------------------- */
+int vtm_layernorm_gather(const void *x, const void *gamma, const void *beta, int dtype, int64_t B, int64_t L, int64_t C,
+                         const int32_t *rows, int64_t n, float eps, void *out, int64_t panel_rows, vtm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * vtm_geglu -- the gated activation inside the block's feed-forward `self.ff(...)` (vidtome/patch.py:187-199;
  * SD blocks use the Diffusers GEGLU feed-forward): x (rows, 2 D) = [value | gate] -> out (rows, D) =
  * value * gelu(gate), exact (erf) gelu, the gate rounded to `dtype` before the product like torch's two ops.

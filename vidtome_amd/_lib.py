@@ -118,6 +118,7 @@ _SIGNATURES = {
     "vtm_solver_step": ([_vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, ctypes.POINTER(_f32), _i64, _vp, _int, _f32, _f32, _f32,
                          _f32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp], _int),
     "vtm_layernorm": ([_vp, _vp, _vp, _int, _i64, _i64, _f32, _vp, _vp], _int),
+    "vtm_layernorm_gather": ([_vp, _vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _f32, _vp, _i64, _vp], _int),
     "vtm_geglu": ([_vp, _int, _i64, _i64, _vp, _vp], _int),
     "vtm_linear_rows": ([_vp, _i64, _vp, _i64, _int, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64,
                          _int, _vp], _int),
@@ -1507,6 +1508,30 @@ def layernorm_panels(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Opti
     out = torch.empty((C // 8, panel_rows(rows), 8), dtype=x.dtype, device=x.device)
     _check(lib().vtm_layernorm_panels(_ptr(xc), _ptr(weight), _ptr(bias), dtype_code(xc), rows, C, float(eps), _ptr(out),
                                       out.shape[1], _stream()), "vtm_layernorm_panels")
+    return out
+
+
+@_on_device
+def layernorm_gather(x: torch.Tensor, rows: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor],
+                     eps: float, panels: bool = True) -> torch.Tensor:
+    """torch.nn.LayerNorm of x[b, rows[b, i], :] (x (B, L, C), rows (B, n) int32 with every entry in [0, L): not checked on the
+    device), as k-panels (C / 8, panel_rows(B n), 8) with sample b at rows b * n, or (``panels=False``) as (B, n, C) token rows.
+    Every row is bit-equal to that row of layernorm_panels / layernorm over x (vtm_layernorm_gather, include/vidtome_hip.h)."""
+    _req(x, "x"), _req(rows, "rows")
+    if x.dim() != 3 or rows.dim() != 2 or rows.shape[0] != x.shape[0] or rows.dtype != torch.int32 or rows.device != x.device:
+        raise RuntimeError("vidtome_amd: layernorm_gather takes x (B, L, C) and rows (B, n) int32 on x's device")
+    B, L, C = x.shape
+    n = rows.shape[1]
+    for name, p in (("weight", weight), ("bias", bias)):
+        if p is not None and (p.dtype != x.dtype or p.numel() != C or p.device != x.device):
+            raise RuntimeError(f"vidtome_amd: layernorm_gather {name} must be a ({C},) {x.dtype} tensor on {x.device}")
+    if panels:
+        out = torch.empty((C // 8, panel_rows(B * n), 8), dtype=x.dtype, device=x.device)
+    else:
+        out = torch.empty((B, n, C), dtype=x.dtype, device=x.device)
+    _check(lib().vtm_layernorm_gather(_ptr(x), _ptr(weight.contiguous() if weight is not None else None),
+                                      _ptr(bias.contiguous() if bias is not None else None), dtype_code(x), B, L, C, _ptr(rows), n,
+                                      float(eps), _ptr(out), out.shape[1] if panels else 0, _stream()), "vtm_layernorm_gather")
     return out
 
 

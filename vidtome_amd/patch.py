@@ -53,10 +53,17 @@ class MergePlan:
     """What ``compute_merge`` produces for one block call: composed maps + the merged tokens."""
 
     __slots__ = ("fsize", "L", "M", "gather_map", "_inv", "_inv_parts", "_merged", "levels", "global_level", "local_chunk",
-                 "x_joined", "anchors_in", "q_rows", "inv_q", "q_count", "pad_to", "fold_args", "_key_fold", "aligned")
+                 "x_joined", "anchors_in", "q_rows", "inv_q", "q_count", "pad_to", "fold_args", "_key_fold", "aligned",
+                 "keep", "inv_local")
 
     def __init__(self):
         self.levels = []
+        # The LOCAL levels alone (None when none ran): keep (B, M_l) the joined-chunk row of every token of the locally merged
+        # sequence (local levels never reference anchor rows: every entry < L), inv_local (B, L) their composed unmerge map.
+        # `gather_map` / `inv` are these too until a global level replaces the first and folds the second into its own; the
+        # feed-forward on merged tokens (merge_mlp, ``ff_route``) runs on the local closures whatever follows them.
+        self.keep = None
+        self.inv_local = None
         self.global_level = None
         self.local_chunk = None
         self.gather_map = None
@@ -261,6 +268,7 @@ def compute_merge(module: torch.nn.Module, x: torch.Tensor, tome_info: Dict[str,
                 n_cur = cur.shape[1]
             curF = (n_cur - unm) // tsize                                          # patch.py:54
         Ml = n_cur
+        plan.keep, plan.inv_local = cur, inv       # (before a global level overwrites the one and folds the other away)
 
         anchors_out = anchors_pos = None
         if args["merge_global"]:                                                   # patch.py:59-82
@@ -787,8 +795,9 @@ def unmerged_self_attention_residual(block: torch.nn.Module, hidden_states: torc
 
 
 def self_attention_segment(block: torch.nn.Module, hidden_states: torch.Tensor, encoder_hidden_states=None,
-                           attention_mask=None, cross_attention_kwargs=None) -> torch.Tensor:
-    """patch.py:146-169 for the plain-LayerNorm block: norm1 -> compute_merge -> attn1 -> unmerge -> + residual."""
+                           attention_mask=None, cross_attention_kwargs=None, plan_to: Optional[list] = None) -> torch.Tensor:
+    """patch.py:146-169 for the plain-LayerNorm block: norm1 -> compute_merge -> attn1 -> unmerge -> + residual.
+    ``plan_to``: a list of the caller's that receives the MergePlan of this call's compute_merge (None where nothing merges)."""
     route = attn1_route(block, hidden_states, encoder_hidden_states, attention_mask, cross_attention_kwargs)
     _pag_check(block, hidden_states, route)
     if unmerged_self_attention_ok(block, hidden_states, route):
@@ -797,7 +806,8 @@ def self_attention_segment(block: torch.nn.Module, hidden_states: torch.Tensor, 
     # (the route reads the tokens' dtype: a norm1 that changes it is routed on its output)
     return patched_self_attention_segment(block, hidden_states, norm_hidden_states, encoder_hidden_states, attention_mask,
                                           cross_attention_kwargs, None,
-                                          route=route if norm_hidden_states.dtype == hidden_states.dtype else None)
+                                          route=route if norm_hidden_states.dtype == hidden_states.dtype else None,
+                                          plan_to=plan_to)
 
 
 def self_attention_rows(attn: torch.nn.Module, x0: torch.Tensor, x1: Optional[torch.Tensor],
@@ -1480,12 +1490,10 @@ def fused_ff_ok(norm: torch.nn.Module, ff: torch.nn.Module, x: torch.Tensor) -> 
             and out.out_features == C and proj.weight.dtype == x.dtype and out.weight.dtype == x.dtype)
 
 
-def norm_feed_forward_residual(norm: torch.nn.Module, ff: torch.nn.Module, hidden_states: torch.Tensor) -> torch.Tensor:
-    """patch.py:187-199 for the plain-LayerNorm block: ``ff(norm3(hidden_states)) + hidden_states`` as three launches:
-    LayerNorm -> k-panels, GEGLU projection with the gated activation in its epilogue -> k-panels, output Linear + bias +
-    residual -> token rows.  The caller has checked ``fused_ff_ok``."""
+def _ff_panel_weights(ff: torch.nn.Module):
+    """(W1 packed in the tile order of vtm_ff_geglu, its fp32 bias in that order or None, D, W2 as k-panels, its fp32 bias or
+    None) of a feed-forward ``fused_ff_ok`` accepted, cached on the two projections."""
     proj, out = _geglu_ff(ff)
-    C = hidden_states.shape[-1]
     pw, pb, pkey = _linear(proj)
     D = pw.shape[0] // 2
 
@@ -1497,6 +1505,15 @@ def norm_feed_forward_residual(norm: torch.nn.Module, ff: torch.nn.Module, hidde
 
     w1, b1 = _packed(proj, "geglu", pkey, pw.device, pack_w1)
     w2, b2 = _panel_weight(out)
+    return w1, b1, D, w2, b2
+
+
+def norm_feed_forward_residual(norm: torch.nn.Module, ff: torch.nn.Module, hidden_states: torch.Tensor) -> torch.Tensor:
+    """patch.py:187-199 for the plain-LayerNorm block: ``ff(norm3(hidden_states)) + hidden_states`` as three launches:
+    LayerNorm -> k-panels, GEGLU projection with the gated activation in its epilogue -> k-panels, output Linear + bias +
+    residual -> token rows.  The caller has checked ``fused_ff_ok``."""
+    C = hidden_states.shape[-1]
+    w1, b1, D, w2, b2 = _ff_panel_weights(ff)
     hs = hidden_states.contiguous()
     n = hs.numel() // C
     xp = _lib.layernorm_panels(hs, norm.weight, norm.bias, norm.eps)
@@ -1546,15 +1563,65 @@ def feed_forward(ff: torch.nn.Module, x: torch.Tensor) -> torch.Tensor:
     return ff(x)
 
 
+def ff_route(block: torch.nn.Module, hidden_states: torch.Tensor, plan: Optional["MergePlan"]) -> str:
+    """How the block computes its feed-forward on hidden states like ``hidden_states`` (B F, N, C) behind the attn1 segment
+    whose compute_merge gave ``plan`` (None: nothing merged).  Launches nothing.
+      "plain"          today's feed-forward over every token (the forward's own choice among norm_feed_forward_residual,
+                       norm_feed_forward_f32 and the module): the block's ``merge_mlp`` opt-in (``update_patch(model,
+                       merge_mlp=True)``) is unset, or there is no local map -- a site that does not merge, a single-frame
+                       chunk, local_merge_ratio <= 0 -- or the block is an AdaLayerNormZero one (its shift / scale / gate are
+                       per frame row)
+      "merged-panels"  ``u(ff(norm3(m(h)))) + h`` over the local levels' closures (tomesd's merge_mlp) as vtm_layernorm_gather
+                       -> vtm_ff_geglu -> vtm_linear_panels -> vtm_unmerge_add: where ``fused_ff_ok`` holds
+      "merged"         the same on every other feed-forward (fp32 models, VIDTOME_FF=blas, a ``ff`` that is not the GEGLU
+                       one, projections the panel path does not read): gathered LayerNorm with token rows out (or
+                       vtm_gather_rows + the norm module), ``feed_forward``, vtm_unmerge_add
+    The global level plays no part: its merged sequence holds other chunks' anchor rows, whose feed-forward output nobody
+    would read.  The matching is the one attn1 used in this forward; nothing is drawn."""
+    if (getattr(block, "merge_mlp", False) is not True or block.use_ada_layer_norm_zero or plan is None
+            or plan.keep is None or plan.inv_local is None):
+        return "plain"
+    return "merged-panels" if fused_ff_ok(block.norm3, block.ff, hidden_states) else "merged"
+
+
+def merged_feed_forward_residual(block: torch.nn.Module, hidden_states: torch.Tensor, plan: "MergePlan", route: str
+                                 ) -> torch.Tensor:
+    """The "merged-panels" / "merged" feed-forward of ``ff_route``: with h the hidden states joined per sample (B, L, C),
+    ``y = ff(norm3(h[b, keep[b, :]]))`` over M_l rows instead of L, ``out[b, i] = y[b, inv_local[b, i]] + h[b, i]``."""
+    norm, ff = block.norm3, block.ff
+    fs = plan.fsize
+    hj = join_frame(hidden_states.contiguous(), fs)
+    B, L, C = hj.shape
+    keep, inv_local = plan.keep, plan.inv_local
+    Ml = keep.shape[1]
+    if route == "merged-panels":
+        # (the panels of all samples are one row range: sample b at rows b * M_l, like norm_feed_forward_residual's b * L)
+        w1, b1, D, w2, b2 = _ff_panel_weights(ff)
+        xp = _lib.layernorm_gather(hj, keep, norm.weight, norm.bias, norm.eps)
+        hp = _lib.ff_geglu(xp, B * Ml, w1, D, b1)
+        y = _lib.linear_panels(hp, B * Ml, w2, C, b2).view(B, Ml, C)
+    else:
+        if _lib_layernorm_ok(norm, hj):
+            xn = _lib.layernorm_gather(hj, keep, norm.weight, norm.bias, norm.eps, panels=False)
+        else:
+            xn = norm(_lib.gather_rows(hj, None, keep))
+        y = feed_forward(ff, xn)
+        if y.dtype != hj.dtype:                 # (a ff that changes the dtype: the add promotes like `ff_output + hidden_states`)
+            return split_frame(torch.gather(y, 1, inv_local.long()[:, :, None].expand(-1, -1, C)) + hj, fs)
+    return split_frame(_lib.unmerge_add(y.contiguous(), inv_local, hj), fs)
+
+
 # ----------------------------------------------------------------------------------------------------
 # patched block
 # ----------------------------------------------------------------------------------------------------
 def patched_self_attention_segment(block: torch.nn.Module, hidden_states: torch.Tensor,
                                    norm_hidden_states: torch.Tensor, encoder_hidden_states=None,
                                    attention_mask=None, cross_attention_kwargs=None, gate_msa=None,
-                                   route: Optional[str] = None) -> torch.Tensor:
+                                   route: Optional[str] = None, plan_to: Optional[list] = None) -> torch.Tensor:
     """patch.py:148-169: compute_merge -> attn1(merged) -> unmerge -> + residual.  ``route``: what ``attn1_route`` answered
-    for this call, when the caller has asked already."""
+    for this call, when the caller has asked already.  ``plan_to``: a list of the caller's that receives this call's
+    MergePlan (None at a site that does not merge) -- how the block's feed-forward reads the maps of THIS forward (``ff_route``)
+    without anything being kept on the module."""
     cross_attention_kwargs = cross_attention_kwargs if cross_attention_kwargs is not None else {}
     if route is None:
         route = attn1_route(block, norm_hidden_states, encoder_hidden_states, attention_mask, cross_attention_kwargs,
@@ -1563,6 +1630,8 @@ def patched_self_attention_segment(block: torch.nn.Module, hidden_states: torch.
     # ("module" and "blas" read the merged tokens; the other routes' projections gather through the map)
     m_a, u_a, merged = compute_merge(block, norm_hidden_states, block._tome_info, materialize=route in ("module", "blas"))
     plan = getattr(m_a, "plan", None)
+    if plan_to is not None:
+        plan_to.append(plan)
     attn = block.attn1
     if route == "module":
         # not the hot path (SD never masks self-attention nor makes attn1 a cross-attention; LoRA'd / custom
@@ -1619,10 +1688,15 @@ def layer_norm(norm: torch.nn.Module, x: torch.Tensor) -> torch.Tensor:
     """`self.norm1(hidden_states)` (patch.py:146; also norm2 / norm3, patch.py:173-176, 187): a plain
     torch.nn.LayerNorm over the channel axis runs as vtm_layernorm; anything else (AdaLayerNorm variants,
     unusual shapes) is the module's own business."""
-    if (_plain_layernorm(norm, x) and x.is_cuda and x.shape[-1] % 8 == 0 and x.shape[-1] <= 2048
-            and x.dtype in (torch.float16, torch.bfloat16, torch.float32)):
+    if _lib_layernorm_ok(norm, x):
         return _lib.layernorm(x, norm.weight, norm.bias, norm.eps)
     return norm(x)
+
+
+def _lib_layernorm_ok(norm: torch.nn.Module, x: torch.Tensor) -> bool:
+    """``norm(x)`` is what vtm_layernorm (and vtm_layernorm_gather with token rows out) computes."""
+    return (_plain_layernorm(norm, x) and x.is_cuda and x.shape[-1] % 8 == 0 and x.shape[-1] <= 2048
+            and x.dtype in (torch.float16, torch.bfloat16, torch.float32))
 
 
 def make_diffusers_tome_block(block_class: Type[torch.nn.Module]) -> Type[torch.nn.Module]:
@@ -1644,13 +1718,16 @@ def make_diffusers_tome_block(block_class: Type[torch.nn.Module]) -> Type[torch.
                 norm_hidden_states = None
 
             # 1. self-attention on merged tokens (the hot path)                    # patch.py:148-169
+            # (merge_mlp: the feed-forward below reads the maps of THIS forward's compute_merge -- carried on a local)
+            plans = [] if getattr(self, "merge_mlp", False) is True else None
+            seg_kw = {} if plans is None else {"plan_to": plans}
             if norm_hidden_states is None:
                 hidden_states = self_attention_segment(self, hidden_states, encoder_hidden_states, attention_mask,
-                                                       cross_attention_kwargs)
+                                                       cross_attention_kwargs, **seg_kw)
             else:
                 hidden_states = patched_self_attention_segment(
                     self, hidden_states, norm_hidden_states, encoder_hidden_states, attention_mask,
-                    cross_attention_kwargs, gate_msa)
+                    cross_attention_kwargs, gate_msa, **seg_kw)
 
             cross_attention_kwargs = cross_attention_kwargs if cross_attention_kwargs is not None else {}
             if self.attn2 is not None:                                             # patch.py:171-185
@@ -1676,6 +1753,9 @@ def make_diffusers_tome_block(block_class: Type[torch.nn.Module]) -> Type[torch.
                                                     encoder_attention_mask, probs_to=maps, words_to=words, ctl=control,
                                                     route=route, **cross_attention_kwargs) + hidden_states
 
+            route = ff_route(self, hidden_states, plans[-1] if plans else None)
+            if route != "plain":                                                   # the feed-forward on the merged local tokens
+                return merged_feed_forward_residual(self, hidden_states, plans[-1], route)
             if not self.use_ada_layer_norm_zero and fused_ff_ok(self.norm3, self.ff, hidden_states):   # patch.py:187-199
                 return norm_feed_forward_residual(self.norm3, self.ff, hidden_states)
             if not self.use_ada_layer_norm_zero and f32_ff_ok(self, self.norm3, self.ff, hidden_states):
@@ -1817,6 +1897,7 @@ def remove_patch(model: torch.nn.Module):
             module.__dict__.pop("_vtm_match_plans", None)      # the matcher's launch planners (pinned 32-byte buffers)
             module.__dict__.pop("fp32_attention", None)        # update_patch's opt-in: a later apply_patch starts without it
             module.__dict__.pop("fp32_projections", None)      # (likewise)
+            module.__dict__.pop("merge_mlp", None)             # (likewise)
             module.__dict__.pop("vtm_attention_maps", None)    # maps.register_attention_maps' switch ...
             module.__dict__.pop("attn2_probs", None)           # ... and the map of the block's last forward
             module.__dict__.pop("vtm_cross_control", None)     # p2p.register_cross_attention_control's schedule and edits
