@@ -484,7 +484,57 @@ int vtm_attention_kv_bias(const void *q, int64_t ldq, const void *k, int64_t ldk
                           int64_t Mk, int64_t Mkp, int64_t d, float scale, const float *bias, int64_t ld_bias,
                           int64_t bias_batch_stride, vtm_stream_t stream);
 
-/* vtm_attention_probs -- the head-averaged PROBABILITIES of the `self.attn2(...)` call of vidtome/patch.py:178-183, the
+/* vtm_frame_order -- the kept rows of a "replace"-mode merge closure in FRAME order: what lets the `self.attn2(...)` call of
+ * vidtome/patch.py:171-185 run on the merged tokens (tomesd's merge_crossattn, which the reference dropped; patch.py's
+ * `merge_crossattn` opt-in here) although its conditioning is given per frame row.  The local levels leave their rows in
+ * matching order (unmerged src rows by score, then dst rows: merge.py:98-117); joined row r of a chunk of F frames of N
+ * tokens belongs to frame r / N, so in ascending order the rows of one frame are one contiguous segment.
+ *   keep        (B, Ml) int32, DEVICE: the joined row of every token of the merged sequence.  The entries of a sample are
+ *               DISTINCT and lie in [0, L = F N); any order.
+ *   inv_local   (B, L) int32, DEVICE: the merged token every joined row is restored from, entries in [0, Ml); repeats are
+ *               the rule.
+ *   keep_sorted (B, Ml): keep[b, :] in ascending order.
+ *   inv_sorted  (B, L): the position in keep_sorted[b, :] of keep[b, inv_local[b, i]] -- the unmerge map of the sorted
+ *               sequence.
+ *   seg_off     (B F + 1) int32: ABSOLUTE row offsets into the (B Ml)-row sequence; segment s = b F + f is the rows of sample
+ *               b whose kept token lies in frame f.  seg_off[0] = 0, seg_off[B F] = B Ml, never decreasing; a frame that
+ *               keeps no row has an empty segment.  This is vtm_attention_kv_segments' seg_off.
+ * All integer and deterministic: a rank over a presence table, no atomics.  ws: vtm_frame_order_ws_bytes(B, F, N) bytes of
+ * scratch (VTM_EWORKSPACE when smaller).  Two small launches; nothing is read back.  Every index is
+ * range-checked on the device before it addresses anything: entries that break the contract (out of range, repeats in keep)
+ * give wrong maps whose entries still lie in [0, Ml) / [0, L), never an access outside the buffers.  1 <= Ml <= L,
+ * B F N < 2^31.  On a bad argument -- a NULL pointer, a size <= 0, Ml outside [1, L] -- VTM_EINVAL is returned and nothing is
+ * launched. */
+size_t vtm_frame_order_ws_bytes(int64_t B, int64_t F, int64_t N);
+int vtm_frame_order(const int32_t *keep, int64_t Ml, const int32_t *inv_local, int64_t B, int64_t F, int64_t N, void *ws,
+                    size_t ws_bytes, int32_t *keep_sorted, int32_t *inv_sorted, int32_t *seg_off, vtm_stream_t stream);
+
+/* vtm_attention_kv_segments -- the cross-attention core over QUERY SEGMENTS of one row range: the `self.attn2(...)` call of
+ * vidtome/patch.py:171-185 on merged tokens in frame order (vtm_frame_order), every row attending to the conditioning of
+ * the frame its kept token lives in.  Per head
+ *     out[i] = softmax_j(q[i] . k[s, j] * scale) v[s, j],   j < Mk,   for seg_off[s] <= i < seg_off[s + 1],   s < n_seg
+ * q and out are ONE row range (rows_total, h d): row i at i * ldq / i * ldo, heads interleaved on the channel axis, 16-byte
+ * aligned (ldq % 8 == 0, ldo % 4 == 0, both >= h d).  Key sample s has k (n_seg, Mkp, .) and vt (n_seg, h d, ldvt >= Mk)
+ * exactly as vtm_attention_kv_bias takes them (Mkp % 8 == 0, vt channel-major).
+ *   seg_off       a DEVICE pointer to n_seg + 1 int32 absolute row offsets, never decreasing, inside [0, rows_total].  Empty
+ *                 segments are legal.  Rows in front of seg_off[0] and rows >= seg_off[n_seg] are not written.
+ *   max_seg_rows  a HOST upper bound on every segment's length (for a chunk's frames: N); it sizes the grid, one query block
+ *                 per 256 (d <= 96) or 128 rows of the bound for every (segment, head), and a workgroup whose block starts
+ *                 behind its segment's device-side length leaves at once.  A bound far above the lengths costs idle
+ *                 workgroups, never a wrong result.
+ *   A segment LONGER than max_seg_rows breaks the contract: its first max_seg_rows rows are computed, the rest are not
+ *   written.  Offsets outside [0, rows_total] are clamped to it and a decreasing pair is an empty segment: whatever seg_off
+ *   holds, nothing outside the rows_total rows of q / out is addressed.
+ * scale > 0.  dtype VTM_F16 or VTM_BF16 (VTM_F32: VTM_EINVAL); d as for vtm_attention; rows_total < 2^31.  P is rounded to
+ * the operand type once for the PV product (bf16: as a hi + lo pair) and the denominator is summed from the same rounded P,
+ * as in vtm_attention_kv_bias.  One launch, no workspace, no key split: the key axis is a few hundred keys, the launch
+ * streams q and out.  On a bad argument nothing is launched and out is untouched. */
+int vtm_attention_kv_segments(const void *q, int64_t ldq, const void *k, int64_t ldk, const void *vt, int64_t ldvt,
+                              void *out, int64_t ldo, int dtype, int64_t rows_total, const int32_t *seg_off, int64_t n_seg,
+                              int64_t max_seg_rows, int64_t h, int64_t Mk, int64_t Mkp, int64_t d, float scale,
+                              vtm_stream_t stream);
+
+/* vtm_attention_probs --the head-averaged PROBABILITIES of the `self.attn2(...)` call of vidtome/patch.py:178-183, the
  * "cross-attention map" that zero-shot video editing reads (LocalBlend-style masks, per-word maps), in fp32:
  *     out[b, i, j] = (1 / h) * sum_head softmax_j(q[b, i, head] . k[b, j, head] * scale + bias[b * bias_batch_stride + j])
  * for i < Mq, j < Mk.  q, ldq, k, ldk, dtype, B, h, Mq, Mqp, Mk, Mkp, d, scale exactly as for vtm_attention_kv_bias (heads

@@ -87,6 +87,10 @@ _SIGNATURES = {
     "vtm_cross_edit_values": ([_vp, _i64, _i64, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp], _int),
     "vtm_attention_kv_bias": ([_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                _f32, _vp, _i64, _i64, _vp], _int),
+    "vtm_frame_order_ws_bytes": ([_i64, _i64, _i64], ctypes.c_size_t),
+    "vtm_frame_order": ([_vp, _i64, _vp, _i64, _i64, _i64, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp], _int),
+    "vtm_attention_kv_segments": ([_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _vp, _i64, _i64, _i64, _i64, _i64,
+                                   _i64, _f32, _vp], _int),
     "vtm_attention_probs": ([_vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _vp, _i64,
                              _i64, _vp], _int),
     "vtm_attention_word_map": ([_vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _vp, _i64, _i64, _vp, _i64,
@@ -1182,6 +1186,63 @@ def attention_kv_bias(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads:
     _check(lib().vtm_attention_kv_bias(q.data_ptr(), q.stride(1), k.data_ptr(), k.stride(1), vt.data_ptr(), vt.stride(1),
                                        out.data_ptr(), C, dtype_code(q), B, heads, Mq, Mqp, Mk, Mkp, d, float(scale),
                                        bias.data_ptr(), bias.shape[1], batch_stride, _stream()), "vtm_attention_kv_bias")
+    return out
+
+
+@_on_device
+def frame_order(keep: torch.Tensor, inv_local: torch.Tensor, F: int, N: int
+                ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The kept rows of a merge closure in frame order (vtm_frame_order, include/vidtome_hip.h): keep (B, M_l) int32, the
+    distinct joined rows in [0, F N) of the merged tokens in any order, inv_local (B, F N) int32 with entries in [0, M_l) ->
+    (keep_sorted (B, M_l) ascending, inv_sorted (B, F N) = the position in keep_sorted of keep[b, inv_local[b, i]], seg_off
+    (B F + 1) int32: absolute offsets into the (B M_l)-row sequence of the rows whose kept token lies in frame f of sample
+    b).  Integer, deterministic, nothing is read back."""
+    _req(keep, "keep"), _req(inv_local, "inv_local")
+    F, N = int(F), int(N)
+    if keep.dim() != 2 or inv_local.dim() != 2 or keep.dtype != torch.int32 or inv_local.dtype != torch.int32 \
+            or inv_local.device != keep.device or inv_local.shape[0] != keep.shape[0] or inv_local.shape[1] != F * N:
+        raise RuntimeError("vidtome_amd: frame_order takes keep (B, M_l) and inv_local (B, F N), int32 on one device")
+    B, Ml = keep.shape
+    dev = keep.device
+    keep_sorted = torch.empty_like(keep)
+    inv_sorted = torch.empty_like(inv_local)
+    seg_off = torch.empty((B * F + 1,), dtype=torch.int32, device=dev)
+    nbytes = lib().vtm_frame_order_ws_bytes(B, F, N)
+    ws = _workspace("frame_order", nbytes, dev)
+    _check(lib().vtm_frame_order(_ptr(keep), Ml, _ptr(inv_local), B, F, N, _ptr(ws), nbytes, _ptr(keep_sorted),
+                                 _ptr(inv_sorted), _ptr(seg_off), _stream()), "vtm_frame_order")
+    return keep_sorted, inv_sorted, seg_off
+
+
+@_on_device
+def attention_kv_segments(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, seg_off: torch.Tensor,
+                          max_seg_rows: int, Mk: int, scale: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The cross-attention core over query segments (vtm_attention_kv_segments): q (rows, C) one row range, contiguous along
+    the last axis; k (n_seg, Mkp, C) and vt (n_seg, C, ldvt >= Mk) as for attention_kv_bias, Mkp a multiple of 8; seg_off
+    (n_seg + 1) int32 on q's device, absolute row offsets that never decrease; ``max_seg_rows`` a host bound on every
+    segment's length.  Row i of segment s is softmax(q[i] K_s^T * scale) V_s; the result is (rows, C), rows outside every
+    segment are not written (``out``: the buffer to write into).  fp16 / bf16 operands only."""
+    if q.dtype not in (torch.float16, torch.bfloat16) or k.dtype != q.dtype or vt.dtype != q.dtype:
+        raise RuntimeError("attention_kv_segments: q, k and vt must share one of fp16 / bf16")
+    if q.dim() != 2 or k.dim() != 3 or vt.dim() != 3 or not q.is_cuda or k.device != q.device or vt.device != q.device:
+        raise RuntimeError("attention_kv_segments: q must be (rows, C), k (n_seg, Mkp, C) and vt (n_seg, C, ldvt) on one GPU")
+    rows, C = q.shape
+    n_seg, Mkp = k.shape[0], k.shape[1]
+    heads, Mk = int(heads), int(Mk)
+    if heads < 1 or C % heads or k.shape[2] != C or vt.shape[0] != n_seg or vt.shape[1] != C or q.stride(1) != 1 \
+            or k.stride(2) != 1 or vt.stride(2) != 1 or k.stride(0) != Mkp * k.stride(1) or vt.stride(0) != C * vt.stride(1):
+        raise RuntimeError("attention_kv_segments: k must be (n_seg, Mkp, C) and vt (n_seg, C, ldvt), dense over the segments")
+    if not isinstance(seg_off, torch.Tensor) or seg_off.dtype != torch.int32 or seg_off.device != q.device \
+            or seg_off.dim() != 1 or seg_off.numel() != n_seg + 1 or not seg_off.is_contiguous():
+        raise RuntimeError("attention_kv_segments: seg_off must be (n_seg + 1,) int32 on q's device")
+    if out is None:
+        out = torch.empty((rows, C), dtype=q.dtype, device=q.device)
+    elif out.shape != (rows, C) or out.dtype != q.dtype or out.device != q.device or out.stride(1) != 1:
+        raise RuntimeError("attention_kv_segments: out must be (rows, C) like q")
+    _check(lib().vtm_attention_kv_segments(q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(1), vt.data_ptr(), vt.stride(1),
+                                           out.data_ptr(), out.stride(0), dtype_code(q), rows, seg_off.data_ptr(), n_seg,
+                                           int(max_seg_rows), heads, Mk, Mkp, C // heads, float(scale), _stream()),
+           "vtm_attention_kv_segments")
     return out
 
 

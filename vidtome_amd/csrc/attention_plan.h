@@ -76,6 +76,7 @@ struct Call {
     const struct SetMasks *set_masks = nullptr;   // vtm_attention_kv_sets_masked only: the per-query weights of the sets
     const struct KeyBias *key_bias = nullptr;     // vtm_attention_kv_bias only: the per-key score bias (attention_bias.hip)
     const struct SetSrc *set_src = nullptr;       // vtm_attention_kv_sets_src only: the second query operand of the sets
+    const struct QuerySegments *segments = nullptr;   // vtm_attention_kv_segments only: the query segments (attention_segments.hip)
 };
 
 // ---- the key sets of one vtm_attention_kv_sets call (attention_sets.hip): set s = keys [start[s], start[s] + len[s]) ----

@@ -54,7 +54,7 @@ class MergePlan:
 
     __slots__ = ("fsize", "L", "M", "gather_map", "_inv", "_inv_parts", "_merged", "levels", "global_level", "local_chunk",
                  "x_joined", "anchors_in", "q_rows", "inv_q", "q_count", "pad_to", "fold_args", "_key_fold", "aligned",
-                 "keep", "inv_local")
+                 "keep", "inv_local", "_frame_order")
 
     def __init__(self):
         self.levels = []
@@ -64,6 +64,7 @@ class MergePlan:
         # feed-forward on merged tokens (merge_mlp, ``ff_route``) runs on the local closures whatever follows them.
         self.keep = None
         self.inv_local = None
+        self._frame_order = None        # the two in frame order, for attn2 on merged tokens (``frame_order``): on first use
         self.global_level = None
         self.local_chunk = None
         self.gather_map = None
@@ -108,6 +109,14 @@ class MergePlan:
             self._key_fold = _lib.fold_keys(cur, L, cid, n_ids, dtype) if n is None else \
                 _lib.fold_keys(cur[:n], L, cid[:n], n_ids, dtype)
         return self._key_fold
+
+    def frame_order(self) -> Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
+        """(keep_sorted, inv_sorted, seg_off) of _lib.frame_order over the local levels' maps, or None when no local level
+        ran: the kept rows in ascending order -- frame by frame --, the unmerge map of that order and the absolute offsets
+        of every (sample, frame)'s rows in the (B M_l)-row sequence.  ``keep`` / ``inv_local`` stay as they are."""
+        if self._frame_order is None and self.keep is not None and self.inv_local is not None:
+            self._frame_order = _lib.frame_order(self.keep, self.inv_local, self.fsize, self.L // self.fsize)
+        return self._frame_order
 
     @property
     def merged(self) -> torch.Tensor:
@@ -1611,6 +1620,63 @@ def merged_feed_forward_residual(block: torch.nn.Module, hidden_states: torch.Te
     return split_frame(_lib.unmerge_add(y.contiguous(), inv_local, hj), fs)
 
 
+def cross_merge_route(block: torch.nn.Module, hidden_states: torch.Tensor, plan: Optional["MergePlan"],
+                      route: "Attn2Route", encoder_hidden_states=None, encoder_attention_mask=None) -> str:
+    """How the block computes its attn2 segment on hidden states like ``hidden_states`` (B F, N, C) behind the attn1 segment
+    whose compute_merge gave ``plan`` (None: nothing merged), ``route`` being what ``attn2_route`` answered for this call.
+    Launches nothing.
+      "merged-panels"  ``u(attn2(norm2(m(h)), context)) + h`` over the local levels' closures (tomesd's merge_crossattn), every
+                       merged row attending to the conditioning of the frame its kept token lives in
+                       (``merged_cross_attention_residual``)
+      "plain"          today's attn2 over every token, whatever ``route`` says.  Whenever ANY of these holds: the block's
+                       ``merge_crossattn`` opt-in (``update_patch(model, merge_crossattn=True)``) is unset; there is no local
+                       map -- a site that does not merge, a single-frame chunk, local_merge_ratio <= 0; the route is not the
+                       plain "panels" frame -- "module", "blas", "f32", an AdaLayerNorm block; an ``encoder_attention_mask``
+                       is present; the call is an IP-Adapter one; the block is registered for cross-attention control
+                       (injecting at this step or not), attention maps or LocalBlend -- all of these read or edit per-token
+                       rows; ``encoder_hidden_states`` is not a tensor with one row set per frame row (B F of them).
+    The global level plays no part, as in ``ff_route``; the matching is the one attn1 used in this forward; nothing is
+    drawn."""
+    if (getattr(block, "merge_crossattn", False) is not True or plan is None or plan.keep is None or plan.inv_local is None
+            or route.frame != "panels" or route.ip is not None or block.use_ada_layer_norm
+            or encoder_attention_mask is not None
+            or block.__dict__.get("vtm_cross_control") is not None or getattr(block, "vtm_attention_maps", False)
+            or local_blend_of(block) is not None
+            or not isinstance(encoder_hidden_states, torch.Tensor) or encoder_hidden_states.dim() != 3
+            or hidden_states.dim() != 3 or encoder_hidden_states.shape[0] != hidden_states.shape[0]
+            or hidden_states.shape[0] % plan.fsize or hidden_states.shape[1] * plan.fsize != plan.L):
+        return "plain"
+    return "merged-panels"
+
+
+def merged_cross_attention_residual(block: torch.nn.Module, hidden_states: torch.Tensor, encoder_hidden_states: torch.Tensor,
+                                    plan: "MergePlan") -> torch.Tensor:
+    """The "merged-panels" attn2 segment of ``cross_merge_route``: with h the hidden states joined per sample (B, L, C),
+    L = F N, ``y[b, j] = attn2(norm2(h[b, keep[b, j]]), encoder_hidden_states[b F + keep[b, j] // N])`` over M_l rows
+    instead of L, ``out[b, i] = y[b, inv_local[b, i]] + h[b, i]``.  The kept rows are taken in frame order
+    (``MergePlan.frame_order``: a permutation of the M_l rows that the unmerge map undoes), so the rows of one frame are one
+    segment of the merged sequence and the core serves it with that frame's keys: vtm_layernorm_gather -> panels, the q panel
+    GEMM, k / V^T of every frame row's conditioning as today (``_cross_kv``), vtm_attention_kv_segments, the output panel GEMM
+    with bias, vtm_unmerge_add with the residual."""
+    norm, attn = block.norm2, block.attn2
+    fs = plan.fsize
+    hj = join_frame(hidden_states.contiguous(), fs)
+    B, L, C = hj.shape
+    N = L // fs
+    keep_sorted, inv_sorted, seg_off = plan.frame_order()
+    Ml = keep_sorted.shape[1]
+    n = B * Ml
+    wq, bq = _panel_weight(attn.to_q)
+    wo, bo = _panel_weight(_out_linear(attn))
+    # (the panels of all samples are one row range: sample b at rows b * M_l -- what seg_off counts in)
+    xp = _lib.layernorm_gather(hj, keep_sorted, norm.weight, norm.bias, norm.eps)
+    q = _lib.linear_panels(xp, n, wq, C, bq)                               # (n, C)
+    k, vt = _cross_kv(attn.to_k, attn.to_v, _pad_keys(encoder_hidden_states, q.dtype), C, "panels")
+    o = _lib.attention_kv_segments(q, k, vt, attn.heads, seg_off, N, encoder_hidden_states.shape[1], _scale(attn, C))
+    y = _lib.linear_panels(_lib.to_panels(o), n, wo, C, bo).view(B, Ml, C)
+    return split_frame(_lib.unmerge_add(y, inv_sorted, hj), fs)
+
+
 # ----------------------------------------------------------------------------------------------------
 # patched block
 # ----------------------------------------------------------------------------------------------------
@@ -1718,8 +1784,10 @@ def make_diffusers_tome_block(block_class: Type[torch.nn.Module]) -> Type[torch.
                 norm_hidden_states = None
 
             # 1. self-attention on merged tokens (the hot path)                    # patch.py:148-169
-            # (merge_mlp: the feed-forward below reads the maps of THIS forward's compute_merge -- carried on a local)
-            plans = [] if getattr(self, "merge_mlp", False) is True else None
+            # (merge_mlp / merge_crossattn: the feed-forward and attn2 below read the maps of THIS forward's compute_merge --
+            # carried on a local)
+            plans = [] if (getattr(self, "merge_mlp", False) is True
+                           or getattr(self, "merge_crossattn", False) is True) else None
             seg_kw = {} if plans is None else {"plan_to": plans}
             if norm_hidden_states is None:
                 hidden_states = self_attention_segment(self, hidden_states, encoder_hidden_states, attention_mask,
@@ -1736,7 +1804,10 @@ def make_diffusers_tome_block(block_class: Type[torch.nn.Module]) -> Type[torch.
                 control = cross_control(self)                                      # p2p.register_cross_attention_control
                 route = attn2_route(self, hidden_states, encoder_hidden_states, encoder_attention_mask, cross_attention_kwargs,
                                     control)
-                if route.frame == "panels":
+                if cross_merge_route(self, hidden_states, plans[-1] if plans else None, route, encoder_hidden_states,
+                                     encoder_attention_mask) == "merged-panels":   # attn2 on the merged local tokens
+                    hidden_states = merged_cross_attention_residual(self, hidden_states, encoder_hidden_states, plans[-1])
+                elif route.frame == "panels":
                     hidden_states = norm_cross_attention_residual(self.norm2, self.attn2, hidden_states, encoder_hidden_states,
                                                                   route.ip, encoder_attention_mask, maps, words, control)
                 elif route.frame == "f32":
@@ -1898,6 +1969,7 @@ def remove_patch(model: torch.nn.Module):
             module.__dict__.pop("fp32_attention", None)        # update_patch's opt-in: a later apply_patch starts without it
             module.__dict__.pop("fp32_projections", None)      # (likewise)
             module.__dict__.pop("merge_mlp", None)             # (likewise)
+            module.__dict__.pop("merge_crossattn", None)       # (likewise)
             module.__dict__.pop("vtm_attention_maps", None)    # maps.register_attention_maps' switch ...
             module.__dict__.pop("attn2_probs", None)           # ... and the map of the block's last forward
             module.__dict__.pop("vtm_cross_control", None)     # p2p.register_cross_attention_control's schedule and edits
