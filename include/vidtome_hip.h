@@ -594,6 +594,53 @@ int vtm_local_blend(const float *acc, int64_t G, int64_t F, int64_t h, int64_t w
                     void *out, int dtype, int64_t C, int64_t H, int64_t W, int pool, float threshold, uint8_t *mask_out,
                     vtm_stream_t stream);
 
+/* vtm_attention_key_mass -- the per-key attention MASS of a self-attention call, the map self-attention guidance (SAG)
+ * thresholds, in fp32:
+ *     out[b * ldo + j] = sum_{i < Mq} (1 / h) * sum_head softmax_j(q[b, i, head] . k[b, j, head] * scale)[j],   j < Mk
+ * the column sums of the head-averaged probabilities; their mean over j is Mq / Mk (exactly 1 for self-attention).  q, ldq,
+ * k, ldk, dtype, B, h, Mq, Mqp, Mk, Mkp, d, scale exactly as for vtm_attention_probs (heads interleaved on the channel
+ * axis, rows addressed as (b * Mp + i) * ld, ld a multiple of 8, q and k 16-byte aligned, VTM_F16 / VTM_BF16 only, every
+ * head dim of vtm_attention, scale > 0) -- q and k may be row ranges of one (B, N, 3 C) q | k | v buffer (ld = 3 C).  There
+ * is no V operand and no bias.  Query rows >= Mq are padding: they are not read and contribute exactly 0 (a select on the
+ * row index); key rows >= Mk are never read.  Limits: 1 <= Mk <= 4096 (a workgroup's column accumulators live in LDS),
+ * 1 <= Mq <= 65536, any h > 0: nothing per head outlives its head.  out: fp32, sample b at b * ldo, ldo >= Mk; columns
+ * >= Mk are not written.  ws: a DEVICE workspace of vtm_attention_key_mass_ws_bytes(B, Mq, Mk) bytes, 0 for Mq <= 128
+ * (ws may then be NULL): a grid over (128-row query tile, sample) -- per head a sweep for the row maximum and denominator and
+ * a sweep that recomputes the scores and sums p / l down the tile's query rows, heads in ascending order; one tile writes
+ * out directly (one launch), more leave their column sums in ws and a second launch adds the tiles in ascending order; 1 / h
+ * is applied once.  Deterministic: no atomics, and the order of every addition depends on (h, Mq, Mk) alone -- a sample's
+ * bits depend neither on B, nor on the other samples, nor on the run.  On a bad argument nothing is launched and out is
+ * untouched. */
+size_t vtm_attention_key_mass_ws_bytes(int64_t B, int64_t Mq, int64_t Mk);
+int vtm_attention_key_mass(const void *q, int64_t ldq, const void *k, int64_t ldk, float *out, int64_t ldo, int dtype,
+                           int64_t B, int64_t h, int64_t Mq, int64_t Mqp, int64_t Mk, int64_t Mkp, int64_t d, float scale,
+                           void *ws, size_t ws_bytes, vtm_stream_t stream);
+
+/* vtm_sag_degrade -- the degrade step of self-attention guidance (Hong et al.; Diffusers' StableDiffusionSAGPipeline) for
+ * one chunk of frames, in one launch.  x: the whole-video latents, n_rows frames of (C, H, W) from the pointer given;
+ * frame_ids: a DEVICE pointer to F int32 rows of x (distinct, inside [0, n_rows): the caller's contract), or NULL for rows
+ * 0 .. F - 1; model_out: the chosen group's (F, C, H, W) rows of the UNet output; mass: DEVICE fp32 rows of
+ * ld_mass >= h_m * w_m, frame f at f * ld_mass (vtm_attention_key_mass of the mid block's (h_m, w_m) token grid); all
+ * latents contiguous NCHW of one dtype (VTM_F32, VTM_F16 or VTM_BF16).  Per frame f, channel c and pixel (y, x), in fp32:
+ *     x0, eps      = the pred_type formulas of vtm_guided_step (VTM_PRED_*) on x[row(f)] and m = model_out[f]
+ *     mask         = mass[f, (y * h_m / H) * w_m + x * w_m / W] > threshold          integer divisions: nearest-neighbour
+ *     blur         = sum_k taps[k] * ( sum_l taps[l] * x0[reflect(y + k - r), reflect(x + l - r)] )
+ *     out[f, c, y, x] = sqrt_alpha * (mask ? blur : x0) + sqrt_beta * eps            rounded once, to dtype
+ * taps: a HOST pointer to the 2 r + 1 fp32 taps, 0 <= r <= 4 (r = 0: the identity blur for a tap of 1); the horizontal pass
+ * runs first, each pass is fmaf(tap, value, acc) in ascending tap order from acc = 0; reflect is torch's "reflect" padding
+ * (the edge is not repeated), which needs H, W > r.  Three deliberate differences from the Diffusers pipeline: the mask
+ * SELECTS (it does not multiply: equal for finite values, and NaN / Inf do not leak across the mask); the nearest-neighbour
+ * source index is the integer floor(y * h_m / H), not a float scale; the blur is fp32 in two separable passes and rounded
+ * once at the store (Diffusers blurs in the model dtype).  One workgroup owns a (frame, channel) plane with x0 and the
+ * horizontal pass in LDS: H * W <= 16384 (128 x 128 latents; two fp32 planes are 128 KiB of the CU's 160 KiB).  out:
+ * chunk-local (F, C, H, W), must not overlap x (checked against the n_rows frames).  mask_out: DEVICE uint8 (F, H, W) that
+ * receives the mask as 0 / 1, or NULL.  No workspace, no atomics.  On a bad argument nothing is launched and out is
+ * untouched. */
+int vtm_sag_degrade(const void *x, int64_t n_rows, const int32_t *frame_ids, const void *model_out, const float *mass,
+                    int64_t ld_mass, int64_t h_m, int64_t w_m, int dtype, int64_t F, int64_t C, int64_t H, int64_t W,
+                    int pred_type, float sqrt_alpha, float sqrt_beta, const float *taps, int r, float threshold, void *out,
+                    uint8_t *mask_out, vtm_stream_t stream);
+
 /* vtm_attention_kv with a DEVICE-side query bound: sample b only has q_count[b] <= Mq meaningful query rows (the
  * compacted live queries of vtm_compact_queries); query blocks that start at or beyond the count exit at once, rows
  * beyond it are not meaningful.  The launch is sized for the host-known bound Mq -- no host round trip. */

@@ -96,6 +96,11 @@ _SIGNATURES = {
     "vtm_attention_word_map": ([_vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _vp, _i64, _i64, _vp, _i64,
                                 _i64, _vp, _i64, _vp, _int, _vp], _int),
     "vtm_local_blend": ([_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _int, _i64, _i64, _i64, _int, _f32, _vp, _vp], _int),
+    "vtm_attention_key_mass_ws_bytes": ([_i64, _i64, _i64], ctypes.c_size_t),
+    "vtm_attention_key_mass": ([_vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _vp,
+                                ctypes.c_size_t, _vp], _int),
+    "vtm_sag_degrade": ([_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _int, _i64, _i64, _i64, _i64, _int, _f32, _f32,
+                         ctypes.POINTER(_f32), _int, _f32, _vp, _vp, _vp], _int),
     "vtm_attention_kv_bounded": ([_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                   _f32, _vp, _vp, ctypes.c_size_t, _vp], _int),
     "vtm_attention_kv_shared_bounded": ([_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
@@ -1378,6 +1383,130 @@ def local_blend(acc: torch.Tensor, x: torch.Tensor, x_src: torch.Tensor, pool: i
     _check(lib().vtm_local_blend(acc.data_ptr(), G, F, h, w, x.data_ptr(), x_src.data_ptr(), out.data_ptr(), dtype_code(x), C,
                                  H, W, pool, float(threshold), _ptr(mask), _stream()), "vtm_local_blend")
     return (out, mask) if return_mask else out
+
+
+KEY_MASS_MAX_KEYS, KEY_MASS_MAX_QUERIES = 4096, 65536   # what vtm_attention_key_mass takes (csrc/attention_mass.hip)
+
+
+@_on_device
+def attention_key_mass(q: torch.Tensor, k: torch.Tensor, heads: int, Mq: int, Mk: int, scale: float,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The per-key attention mass of a self-attention call (vtm_attention_key_mass): q (B, Mqp, C) and k (B, Mkp, C) views
+    contiguous along the last axis as for attention_probs, fp16 / bf16 -- the q | k column ranges of one (B, N, 3 C) buffer
+    will do.  Returns sum_{i < Mq} mean_head softmax(q K^T * scale)[i, :], fp32 (B, Mk): a new tensor, or the first Mk columns
+    of ``out`` (fp32 (B, >= Mk) on q's device, unit stride along the row; columns >= Mk are not written).  Mk <= 4096,
+    Mq <= 65536, any head count; query rows >= Mq contribute exactly 0.  No V operand, no (B, Mq, Mk) intermediate;
+    deterministic, a sample's bits do not depend on B.  More than 128 queries go through a cached workspace."""
+    who = "attention_key_mass"
+    if not isinstance(q, torch.Tensor) or not isinstance(k, torch.Tensor) or q.dtype not in (torch.float16, torch.bfloat16) \
+            or k.dtype != q.dtype:
+        raise RuntimeError(f"{who}: q and k must share one of fp16 / bf16")
+    if q.dim() != 3 or k.dim() != 3 or not q.is_cuda or k.device != q.device:
+        raise RuntimeError(f"{who}: q must be (B, Mqp, C) and k (B, Mkp, C) on one GPU")
+    B, Mqp, C = q.shape
+    Mkp = k.shape[1]
+    heads, Mq, Mk = int(heads), int(Mq), int(Mk)
+    if k.shape[0] != B or k.shape[2] != C or heads < 1 or C % heads:
+        raise RuntimeError(f"{who}: k must be (B, Mkp, C) with C a multiple of heads")
+    if not (1 <= Mq <= Mqp and 1 <= Mk <= Mkp):
+        raise RuntimeError(f"{who}: Mq / Mk must lie inside q / k")
+    if Mk > KEY_MASS_MAX_KEYS or Mq > KEY_MASS_MAX_QUERIES:
+        raise RuntimeError(f"{who}: Mk = {Mk}, Mq = {Mq}: at most {KEY_MASS_MAX_KEYS} keys and {KEY_MASS_MAX_QUERIES} queries "
+                           "are taken")
+    for t, name, rows in ((q, "q", Mqp), (k, "k", Mkp)):
+        if t.stride(2) != 1 or t.stride(1) % 8 or t.stride(1) < C or (B > 1 and t.stride(0) != rows * t.stride(1)) \
+                or t.data_ptr() % 16:
+            raise RuntimeError(f"{who}: {name} must be 16-byte aligned rows (stride a multiple of 8), dense over the samples")
+    if out is None:
+        out = torch.empty((B, Mk), dtype=torch.float32, device=q.device)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != q.device or out.dim() != 2 \
+            or out.shape[0] != B or out.shape[1] < Mk or out.stride(1) != 1 or (B > 1 and out.stride(0) < out.shape[1]):
+        raise RuntimeError(f"{who}: out must be fp32 (B, >= Mk) on q's device, contiguous along its last axis")
+    nbytes = lib().vtm_attention_key_mass_ws_bytes(B, Mq, Mk)
+    ws = _workspace("key_mass", nbytes, q.device) if nbytes else None
+    _check(lib().vtm_attention_key_mass(q.data_ptr(), q.stride(1), k.data_ptr(), k.stride(1), out.data_ptr(),
+                                        out.stride(0) if B > 1 else out.shape[1], dtype_code(q), B, heads, Mq, Mqp, Mk, Mkp,
+                                        C // heads, float(scale), _ptr(ws), nbytes, _stream()), "vtm_attention_key_mass")
+    return out
+
+
+SAG_MAX_RADIUS, SAG_MAX_PLANE = 4, 16384   # what vtm_sag_degrade takes (csrc/sag.hip)
+
+
+def gaussian_taps(radius: int, sigma: float):
+    """The 2 radius + 1 taps exp(-0.5 (k / sigma)^2) of vtm_sag_degrade's blur: computed in float64, normalised to sum 1, then
+    rounded to fp32 (returned as Python floats that are fp32 values)."""
+    radius, sigma = int(radius), float(sigma)
+    if radius < 0 or not sigma > 0.0:
+        raise RuntimeError(f"gaussian_taps: radius = {radius}, sigma = {sigma}: a radius >= 0 and a sigma > 0 are taken")
+    w = [math.exp(-0.5 * (k / sigma) ** 2) for k in range(-radius, radius + 1)]
+    total = math.fsum(w)
+    return [_f32_round(v / total) for v in w]
+
+
+@_on_device
+def sag_degrade(x: torch.Tensor, model_out: torch.Tensor, mass: torch.Tensor, h_m: int, w_m: int, sqrt_alpha: float,
+                sqrt_beta: float, taps, threshold: float = 1.0, *, groups: int = 1, group: int = 0, frame_ids=None,
+                pred_type: int = PRED_EPSILON, out: Optional[torch.Tensor] = None, want_mask: bool = False):
+    """The degrade step of self-attention guidance for one chunk (vtm_sag_degrade, include/vidtome_hip.h): ``x``
+    (n_frames, C, H, W) the whole-video latents, ``model_out`` (groups * F, C, H, W) the UNet output of the chunk, group-major
+    -- group ``group`` of it is read; ``frame_ids`` as for guided_step; ``mass`` fp32 (F, >= h_m * w_m) on x's device, unit
+    stride along the row (attention_key_mass of the mid block's (h_m, w_m) grid); ``taps`` the 2 r + 1 blur taps, r <= 4
+    (gaussian_taps).  Returns out, a chunk-local (F, C, H, W) tensor of x's dtype (``out``: a contiguous tensor of that shape
+    that does not overlap x, or None for a new one), or (out, mask uint8 (F, H, W)) with ``want_mask``."""
+    who = "sag_degrade"
+    groups, group, pred_type, h_m, w_m = int(groups), int(group), int(pred_type), int(h_m), int(w_m)
+    for t, name in ((x, "x"), (model_out, "model_out")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4 or t.dtype not in _DT:
+            raise RuntimeError(f"{who}: {name} must be a (frames, C, H, W) fp16 / bf16 / fp32 tensor")
+    if pred_type not in (PRED_EPSILON, PRED_V, PRED_SAMPLE):
+        raise RuntimeError(f"{who}: unknown pred_type {pred_type}")
+    if groups < 1 or not 0 <= group < groups:
+        raise RuntimeError(f"{who}: groups = {groups}, group = {group}: a group index outside [0, groups)")
+    taps = [float(t) for t in taps]
+    if len(taps) % 2 != 1 or len(taps) > 2 * SAG_MAX_RADIUS + 1:
+        raise RuntimeError(f"{who}: {len(taps)} taps: 2 r + 1 of them are taken, r <= {SAG_MAX_RADIUS}")
+    r = len(taps) // 2
+    first, ids, F = _frame_rows(frame_ids, x.shape[0], who)
+    _, C, H, W = x.shape
+    if model_out.shape[0] != groups * F or tuple(model_out.shape[1:]) != (C, H, W):
+        raise RuntimeError(f"{who}: model_out {tuple(model_out.shape)} is not ({groups} groups * {F} frames, {C}, {H}, {W})")
+    if model_out.dtype != x.dtype or model_out.device != x.device:
+        raise RuntimeError(f"{who}: model_out ({model_out.dtype}, {model_out.device}) is not like x ({x.dtype}, {x.device})")
+    if H * W > SAG_MAX_PLANE:
+        raise RuntimeError(f"{who}: frames of {H} x {W} latents: a plane of at most {SAG_MAX_PLANE} elements (128 x 128) is "
+                           "taken, two fp32 planes of it live in a workgroup's LDS")
+    if H <= r or W <= r:
+        raise RuntimeError(f"{who}: reflect padding of radius {r} needs H, W > {r}")
+    if not isinstance(mass, torch.Tensor) or mass.dtype != torch.float32 or mass.device != x.device or mass.dim() != 2 \
+            or mass.shape[0] != F or mass.shape[1] < h_m * w_m or mass.stride(1) != 1 \
+            or (F > 1 and mass.stride(0) < mass.shape[1]) or h_m < 1 or w_m < 1 or h_m > H or w_m > W:
+        raise RuntimeError(f"{who}: mass must be fp32 ({F}, >= h_m * w_m = {h_m * w_m}) on x's device, contiguous along its "
+                           f"last axis, with the ({h_m}, {w_m}) grid inside ({H}, {W})")
+    _req(x, "x"), _req(model_out, "model_out")
+    if isinstance(ids, torch.Tensor) and _req(ids, "frame_ids").device != x.device:
+        raise RuntimeError(f"{who}: frame_ids lives on {ids.device}, x on {x.device}")
+    if out is None:
+        out = torch.empty((F, C, H, W), dtype=x.dtype, device=x.device)
+    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (F, C, H, W) or out.dtype != x.dtype \
+            or out.device != x.device or not out.is_contiguous():
+        raise RuntimeError(f"{who}: out must be a contiguous ({F}, {C}, {H}, {W}) tensor of x's dtype on x's device")
+    else:
+        x_lo, o_lo = x.data_ptr(), out.data_ptr()
+        if o_lo < x_lo + x.numel() * x.element_size() and x_lo < o_lo + out.numel() * out.element_size():
+            raise RuntimeError(f"{who}: out overlaps x")
+    mask = torch.empty((F, H, W), dtype=torch.uint8, device=x.device) if want_mask else None
+    if F == 0:
+        return (out, mask) if want_mask else out
+    if isinstance(ids, list):
+        ids = torch.tensor(ids, dtype=torch.int32, device=x.device)
+    E = C * H * W
+    _check(lib().vtm_sag_degrade(x.data_ptr() + first * E * x.element_size(), x.shape[0] - first, _ptr(ids),
+                                 model_out.data_ptr() + group * F * E * x.element_size(), mass.data_ptr(),
+                                 mass.stride(0) if F > 1 else mass.shape[1], h_m, w_m, dtype_code(x), F, C, H, W, pred_type,
+                                 float(sqrt_alpha), float(sqrt_beta), (_f32 * len(taps))(*taps), r, float(threshold),
+                                 out.data_ptr(), _ptr(mask), _stream()), "vtm_sag_degrade")
+    return (out, mask) if want_mask else out
 
 
 @_on_device

@@ -1,5 +1,5 @@
 // What the 16-bit attention kernels (attention.hip, attention16.hip, attention16g.hip, attention_sets.hip,
-// attention_bias.hip, attention_probs.hip, attention_words.hip) share of their tile handling: the buffer descriptor, the
+// attention_bias.hip, attention_probs.hip, attention_words.hip, attention_mass.hip) share of their tile handling: the buffer descriptor, the
 // K / V^T tile stage global memory -> staging registers -> LDS, the Q-fragment load, the score tile of the map kernels and,
 // for the two small cross-attention kernels, the pad initialisation, the split-P PV step and the 32-row output store.
 // Header-only; everything is __forceinline__ and every loop fully unrolled: the
@@ -180,7 +180,7 @@ __device__ __forceinline__ void load_q_frags(typename Frag<T>::vec (&qf)[(D + 15
 }
 
 // ---- the score tile of the map kernels ----
-// attention_words_kernel uses it; attention_probs_kernel carries the same text written out in its `scores` lambda: calling
+// attention_words_kernel and attention_mass_kernel use it; attention_probs_kernel carries the same text written out in its `scores` lambda: calling
 // this helper there kept every instantiation's VGPR / SGPR / LDS numbers but renumbered registers and moved a few
 // instructions, and that kernel's code is pinned (profiles/attention_words_resources.txt).  A change here has to be made
 // there too.

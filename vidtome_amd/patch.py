@@ -746,6 +746,64 @@ def unmerged_site(block: torch.nn.Module, x: torch.Tensor) -> bool:
     return downsample > info["args"]["max_downsample"]
 
 
+def sag_registered(block: torch.nn.Module) -> bool:
+    """``sag.register_self_attention_guidance`` selected the block: its attn1 leaves ``attn1_key_mass``."""
+    return block.__dict__.get("vtm_sag") is True
+
+
+def _sag_check(block: torch.nn.Module, x: torch.Tensor) -> None:
+    """Before the first launch of a registered block's attn1 segment: the key mass is that of the per-frame attention of a
+    plain attn1 call, and an edit is never silently dropped -- anything else raises."""
+    who = "vidtome_amd: this block is registered for self-attention guidance (register_self_attention_guidance) but "
+    if not unmerged_site(block, x):
+        raise RuntimeError(who + "its site merges tokens: the key mass would be over merged rows, not the frame's token grid "
+                                 "(SAG at merged sites is not supported; register the mid block)")
+    if x.shape[1] > _lib.KEY_MASS_MAX_KEYS:
+        raise RuntimeError(who + f"its frames have {x.shape[1]} tokens: vtm_attention_key_mass takes at most "
+                                 f"{_lib.KEY_MASS_MAX_KEYS} keys (a workgroup's column accumulators live in LDS)")
+    if pag.groups_of(block.attn1) is not None:
+        raise RuntimeError(who + "its attn1 is under perturbed attention (a PAG processor or register_perturbed_attention): "
+                                 "the perturbed samples have no attention map (SAG and PAG on one block are not supported)")
+    if _pnp_share_groups(block.attn1) != 1:
+        raise RuntimeError(who + "its attn1 shares the source sample's probabilities at this timestep (PnP injection): the "
+                                 "groups have no map of their own (SAG and PnP on one block are not supported)")
+
+
+def _key_mass_torch(q: torch.Tensor, k: torch.Tensor, heads: int, scale: float) -> torch.Tensor:
+    """fp32 torch restatement of vtm_attention_key_mass: sum over the queries of the head-averaged softmax, (B, Mk).  Head by
+    head: no (B, heads, N, N) tensor exists."""
+    B, _, C = q.shape
+    d = C // heads
+    acc = torch.zeros((B, k.shape[1]), dtype=torch.float32, device=q.device)
+    for h in range(heads):
+        s = torch.matmul(q[:, :, h * d:(h + 1) * d].float(), k[:, :, h * d:(h + 1) * d].float().transpose(1, 2)) * scale
+        acc += torch.softmax(s, dim=-1).sum(1)
+    return acc / heads
+
+
+def _module_path_key_mass(attn: torch.nn.Module, x: torch.Tensor) -> Optional[torch.Tensor]:
+    """The key mass of an attn1 call whose body does not hold 16-bit q | k rows for the kernel ("rows", "f32", "blas",
+    "module"): to_q / to_k through lora.linear_params on norm1's output, in fp32, then the torch restatement.  None (one
+    warning) when the projections are not readable or something stands between them and the scores; never raises."""
+    try:
+        ok = (x.dim() == 3 and all(hasattr(attn, a) for a in ("to_q", "to_k", "heads"))
+              and _readable_linear(attn.to_q) and _readable_linear(attn.to_k)
+              and not any(getattr(attn, a, None) is not None for a in ("group_norm", "spatial_norm", "norm_q", "norm_k"))
+              and lora.base_linear(attn.to_q).out_features % attn.heads == 0)
+        if ok:
+            with torch.no_grad():
+                xf = x.float()
+                q = _apply_linear(attn.to_q, xf, torch.float32)
+                k = _apply_linear(attn.to_k, xf, torch.float32)
+                return _key_mass_torch(q, k, attn.heads, _scale(attn, q.shape[-1]))
+    except Exception as e:   # (a forward never fails for its map)
+        _warn_once("sag-failed", f"vidtome_amd: attn1_key_mass is None: the key mass of an attn1 call failed ({e})")
+        return None
+    _warn_once("sag-unreadable", "vidtome_amd: attn1_key_mass is None for an attn1 call whose to_q / to_k are not plain "
+                                 "projections onto the scores")
+    return None
+
+
 def unmerged_self_attention_ok(block: torch.nn.Module, x: torch.Tensor, route: Optional[str] = None) -> bool:
     """``unmerged_self_attention_residual`` may run: the "panels" route (``route``: what ``attn1_route`` answered for a plain
     attn1 call, when the caller has asked already) behind a plain norm1, without PnP sharing, at a site that does not merge."""
@@ -768,6 +826,9 @@ def unmerged_self_attention_residual(block: torch.nn.Module, hidden_states: torc
     heads, scale = attn.heads, _scale(attn, C)
     hs = hidden_states.contiguous()
     n = BF * N
+    sag = sag_registered(block)
+    if sag:
+        _sag_check(block, hidden_states)                   # (no perturbed attention below: n_org is None)
     n_org = _pag_org(attn, BF)
 
     qkv_params = [_linear(m) for m in (attn.to_q, attn.to_k, attn.to_v)]
@@ -798,6 +859,10 @@ def unmerged_self_attention_residual(block: torch.nn.Module, hidden_states: torc
     qkv = _lib.linear_panels(xp, n, wqkv, 3 * C, bqkv).view(BF, N, 3 * C)
     # (BF, C, N rounded up to 8): V channel-major for the PV contraction, the key columns past N written as zeros
     vt = _lib.transpose_cols(qkv, 2 * C, C)
+    if sag:
+        # one launch on the q | k row ranges the core reads (N is inside the kernel's key limit: _sag_check)
+        with torch.no_grad():
+            block.attn1_key_mass = _lib.attention_key_mass(qkv[:, :, :C], qkv[:, :, C:2 * C], heads, N, N, scale)
     o = _lib.attention(qkv[:, :, :C], qkv[:, :, C:2 * C], vt, heads, N, scale, 1)
     op = _lib.to_panels(o.view(n, C))
     return _lib.linear_panels(op, n, wo, C, bo, resid=hs.view(n, C)).view(BF, N, C)
@@ -1693,6 +1758,10 @@ def patched_self_attention_segment(block: torch.nn.Module, hidden_states: torch.
         route = attn1_route(block, norm_hidden_states, encoder_hidden_states, attention_mask, cross_attention_kwargs,
                             gate_msa)
     _pag_check(block, norm_hidden_states, route)
+    if sag_registered(block):
+        # (these bodies hold no 16-bit q | k rows of the whole frame side by side: the restatement on norm1's output)
+        _sag_check(block, norm_hidden_states)
+        block.attn1_key_mass = _module_path_key_mass(block.attn1, norm_hidden_states)
     # ("module" and "blas" read the merged tokens; the other routes' projections gather through the map)
     m_a, u_a, merged = compute_merge(block, norm_hidden_states, block._tome_info, materialize=route in ("module", "blas"))
     plan = getattr(m_a, "plan", None)
@@ -1972,6 +2041,8 @@ def remove_patch(model: torch.nn.Module):
             module.__dict__.pop("merge_crossattn", None)       # (likewise)
             module.__dict__.pop("vtm_attention_maps", None)    # maps.register_attention_maps' switch ...
             module.__dict__.pop("attn2_probs", None)           # ... and the map of the block's last forward
+            module.__dict__.pop("vtm_sag", None)               # sag.register_self_attention_guidance's switch ...
+            module.__dict__.pop("attn1_key_mass", None)        # ... and the key mass of the block's last forward
             module.__dict__.pop("vtm_cross_control", None)     # p2p.register_cross_attention_control's schedule and edits
             module.__dict__.pop("vtm_local_blend", None)       # blend.register_local_blend's accumulator
             module.__dict__.pop(pag.MARK, None)                # pag.register_perturbed_attention's marker (on attn1)
