@@ -641,6 +641,38 @@ int vtm_sag_degrade(const void *x, int64_t n_rows, const int32_t *frame_ids, con
                     int pred_type, float sqrt_alpha, float sqrt_beta, const float *taps, int r, float threshold, void *out,
                     uint8_t *mask_out, vtm_stream_t stream);
 
+/* vtm_freeu -- FreeU (Si et al., "FreeU: Free Lunch in Diffusion U-Net"; Diffusers' enable_freeu with its threshold of 1) in
+ * place on x, the contiguous NCHW concatenation cat([hidden_states, res_hidden_states], 1) of B samples of C_h + C_s planes
+ * of (H, W) that an up-block resnet is about to read; dtype VTM_F32, VTM_F16 or VTM_BF16.  With P = H * W, in float64 terms:
+ *     backbone planes c < C_h / 2 (integer division):   out = v * g
+ *         version 1 (Diffusers):                g = b
+ *         version 2 (the original repository):  g[n, p] = 1 + (b - 1) (m[n, p] - min_p m[n]) / (max_p m[n] - min_p m[n]),
+ *                                               m[n, p] the mean of x[n, c, p] over ALL c < C_h; g = 1 where max == min
+ *                                               (the original divides 0 by 0 there: the one stated deviation)
+ *     planes C_h / 2 <= c < C_h:                        not touched, their bytes are never written
+ *     skip planes c >= C_h, a = 2 pi y / H, b' = 2 pi x / W:
+ *         S = sum v,  A_c, A_s = sum v cos a, sum v sin a,  B_c, B_s = sum v cos b', sum v sin b',
+ *         D_c, D_s = sum v cos(a + b'), sum v sin(a + b')                        (sums over the plane)
+ *         out[y, x] = v[y, x] + (s - 1) / P * (S + A_c cos a + A_s sin a + B_c cos b' + B_s sin b'
+ *                                                + D_c cos(a + b') + D_s sin(a + b'))
+ * which is Re ifftn(ifftshift(mask * fftshift(fftn(v)))) for mask = s on [H/2 - 1 : H/2 + 1, W/2 - 1 : W/2 + 1] and 1
+ * elsewhere: the four bins ky, kx in {0, -1}; it holds for every H, W >= 2, odd sizes and H = 2 included.  Limits:
+ * H, W >= 2, P <= 16384, C_h >= 2, C_s >= 1, B >= 0 (B == 0: VTM_OK, nothing is launched).  All arithmetic is fp32 and
+ * every stored value is rounded once; csrc/freeu.hip's header counts the roundings.  s == 1 gives the skip planes, and
+ * b == 1 with version 1 the backbone planes, no work at all: bit for bit the input.  Non-finite values propagate by IEEE
+ * rules through the plane that holds them (version 2: through that sample's map) and reach no other plane.  No atomics:
+ * a plane's bits depend on its own values (version 2: and its sample's map) alone, not on its position, B or the run.
+ * Version 1 is one launch.  Version 2 is three (the channel mean, min / max per sample, the apply launch) and needs ws, a
+ * 4-byte aligned DEVICE workspace of vtm_freeu_ws_bytes(B, P, version) bytes (0 for version 1: ws may be NULL).
+ * vtm_freeu_lanes(P): the lanes that own one plane of P elements, 16 / 64 / 256 / 1024 -- the kernel form, a function of
+ * P alone (0 for a P outside [4, 16384]).  On a bad argument -- a NULL or misaligned x, B < 0, a size outside the limits,
+ * another version or dtype, a missing or short ws, a grid beyond 2^31 - 1 workgroups -- nothing is launched and x is
+ * untouched. */
+int vtm_freeu_lanes(int64_t P);
+size_t vtm_freeu_ws_bytes(int64_t B, int64_t P, int version);
+int vtm_freeu(void *x, int dtype, int64_t B, int64_t C_h, int64_t C_s, int64_t H, int64_t W, float b, float s, int version,
+              void *ws, size_t ws_bytes, vtm_stream_t stream);
+
 /* vtm_attention_kv with a DEVICE-side query bound: sample b only has q_count[b] <= Mq meaningful query rows (the
  * compacted live queries of vtm_compact_queries); query blocks that start at or beyond the count exit at once, rows
  * beyond it are not meaningful.  The launch is sized for the host-known bound Mq -- no host round trip. */

@@ -12,10 +12,12 @@ from .blend import LocalBlend, register_local_blend, unregister_local_blend
 from .sampler import GuidedDDIM, GuidedDPMSolver
 from .pag import register_perturbed_attention, remove_perturbed_attention
 from .sag import SelfAttentionGuidance, register_self_attention_guidance, unregister_self_attention_guidance
+from .freeu import register_freeu, unregister_freeu
 
 __all__ = ["merge", "patch", "apply_patch", "remove_patch", "update_patch", "collect_from_patch",
            "register_attention_maps", "unregister_attention_maps",
            "CrossEdit", "register_cross_attention_control", "unregister_cross_attention_control",
            "LocalBlend", "register_local_blend", "unregister_local_blend",
            "GuidedDDIM", "GuidedDPMSolver", "register_perturbed_attention", "remove_perturbed_attention",
-           "SelfAttentionGuidance", "register_self_attention_guidance", "unregister_self_attention_guidance"]
+           "SelfAttentionGuidance", "register_self_attention_guidance", "unregister_self_attention_guidance",
+           "register_freeu", "unregister_freeu"]

@@ -101,6 +101,9 @@ _SIGNATURES = {
                                 ctypes.c_size_t, _vp], _int),
     "vtm_sag_degrade": ([_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _int, _i64, _i64, _i64, _i64, _int, _f32, _f32,
                          ctypes.POINTER(_f32), _int, _f32, _vp, _vp, _vp], _int),
+    "vtm_freeu_lanes": ([_i64], _int),
+    "vtm_freeu_ws_bytes": ([_i64, _i64, _int], ctypes.c_size_t),
+    "vtm_freeu": ([_vp, _int, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _int, _vp, ctypes.c_size_t, _vp], _int),
     "vtm_attention_kv_bounded": ([_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                   _f32, _vp, _vp, ctypes.c_size_t, _vp], _int),
     "vtm_attention_kv_shared_bounded": ([_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
@@ -1507,6 +1510,62 @@ def sag_degrade(x: torch.Tensor, model_out: torch.Tensor, mass: torch.Tensor, h_
                                  float(sqrt_alpha), float(sqrt_beta), (_f32 * len(taps))(*taps), r, float(threshold),
                                  out.data_ptr(), _ptr(mask), _stream()), "vtm_sag_degrade")
     return (out, mask) if want_mask else out
+
+
+FREEU_MAX_PLANE = 16384                         # what vtm_freeu takes (csrc/freeu.hip): H * W of a plane
+
+
+def freeu_lanes(P: int) -> int:
+    """The lanes that own one plane of ``P`` elements in vtm_freeu's apply launch (16 / 64 / 256 / 1024): the kernel form, the
+    library's own rule (vtm_freeu_lanes), a function of P alone.  0 for a P outside [4, FREEU_MAX_PLANE]."""
+    return int(lib().vtm_freeu_lanes(int(P)))
+
+
+def freeu_rounding_counts(P: int, C_h: int) -> Tuple[int, int]:
+    """(K_s, K_m) of csrc/freeu.hip's header, in units of 2^-24: the roundings between an input value and a stored skip-plane
+    value, folded for the error form ``K_s 2^-24 (|v| + |s - 1| 4 sum|v| / P)``, and the roundings between an input value
+    and an entry of version 2's channel-mean map."""
+    P, C_h = int(P), int(C_h)
+    G = freeu_lanes(P)
+    if G == 0 or C_h < 2:
+        raise ValueError(f"freeu_rounding_counts: P = {P}, C_h = {C_h}: 4 <= P <= {FREEU_MAX_PLANE} and C_h >= 2 are taken")
+    chunks = -(-P // 8)
+    R = 8 * -(-chunks // G) + int(math.log2(min(G, 64))) + (G // 64 if G > 64 else 0)
+    return -(-(7 * R + 180) // 4) + 1, -(-C_h // 16) + 15
+
+
+@_on_device
+def freeu(x: torch.Tensor, C_h: int, b: float, s: float, version: int = 1) -> torch.Tensor:
+    """FreeU in place on ``x`` (vtm_freeu, include/vidtome_hip.h): the contiguous (B, C_h + C_s, H, W) concatenation
+    cat([hidden_states, res_hidden_states], 1) of an up-block resnet, fp16 / bf16 / fp32 on the GPU.  Planes c < C_h // 2 are
+    scaled by ``b`` (``version`` 1, Diffusers) or by the original repository's per-pixel gain (``version`` 2), planes
+    C_h // 2 <= c < C_h are not touched, planes c >= C_h get their four lowest frequency bins scaled by ``s``.  Launches on
+    the current stream; version 2 takes its workspace from the per-stream cache.  Returns ``x``."""
+    who = "freeu"
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError(f"{who}: x must be a (B, C_h + C_s, H, W) tensor")
+    if x.dtype not in _DT:
+        raise ValueError(f"{who}: x is {x.dtype}: fp16, bf16 and fp32 are taken")
+    if not x.is_contiguous():
+        raise ValueError(f"{who}: x must be contiguous NCHW (strides {tuple(x.stride())} of shape {tuple(x.shape)} are not)")
+    C_h, version, b, s = int(C_h), int(version), float(b), float(s)
+    B, C, H, W = x.shape
+    if version not in (1, 2):
+        raise ValueError(f"{who}: version = {version}: 1 (Diffusers) or 2 (the original repository) is taken")
+    if C_h < 2 or C - C_h < 1:
+        raise ValueError(f"{who}: C_h = {C_h} of {C} channels: C_h >= 2 and C_s = C - C_h >= 1 are taken")
+    if H < 2 or W < 2 or H * W > FREEU_MAX_PLANE:
+        raise ValueError(f"{who}: x has planes of {H} x {W}: H, W >= 2 and H * W <= FREEU_MAX_PLANE = {FREEU_MAX_PLANE} are "
+                         "taken")
+    if not x.is_cuda:
+        raise ValueError(f"{who}: x lives on {x.device}: it must live on the GPU (vidtome_amd has no CPU path)")
+    if B == 0:
+        return x
+    nbytes = lib().vtm_freeu_ws_bytes(B, H * W, version)
+    ws = _workspace("freeu", nbytes, x.device) if nbytes else None
+    _check(lib().vtm_freeu(x.data_ptr(), dtype_code(x), B, C_h, C - C_h, H, W, b, s, version, _ptr(ws), nbytes, _stream()),
+           "vtm_freeu")
+    return x
 
 
 @_on_device

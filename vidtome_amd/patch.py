@@ -33,7 +33,7 @@ from typing import Any, Callable, Dict, NamedTuple, Optional, Tuple, Type
 import torch
 import torch.nn.functional as F
 
-from . import _lib, ip_adapter, lora, merge, pag
+from . import _lib, freeu, ip_adapter, lora, merge, pag
 from .utils import init_generator, isinstance_str, join_frame, split_frame
 
 # Attention over the merged sequence computes outputs only for the rows unmerge() reads (see MergePlan.q_rows);
@@ -2043,6 +2043,7 @@ def remove_patch(model: torch.nn.Module):
             module.__dict__.pop("attn2_probs", None)           # ... and the map of the block's last forward
             module.__dict__.pop("vtm_sag", None)               # sag.register_self_attention_guidance's switch ...
             module.__dict__.pop("attn1_key_mass", None)        # ... and the key mass of the block's last forward
+            freeu.release(module)                              # freeu.register_freeu's "vtm_freeu": hooks off, s1 .. b2 back
             module.__dict__.pop("vtm_cross_control", None)     # p2p.register_cross_attention_control's schedule and edits
             module.__dict__.pop("vtm_local_blend", None)       # blend.register_local_blend's accumulator
             module.__dict__.pop(pag.MARK, None)                # pag.register_perturbed_attention's marker (on attn1)
