@@ -859,6 +859,64 @@ int vtm_solver_step(const void *x, const void *model_out, const void *noise, con
                     float c_h2, float c_noise, void *x_out, float *h_out, void *eps_out, void *x0_out, vtm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * vtm_semantic_guidance -- semantic guidance (SEGA, Brack et al.; Diffusers' SemanticStableDiffusionPipeline, and with
+ * `regions` the masked form of LEditsPPPipelineStableDiffusion) for ONE CHUNK in one launch: the combined model output that
+ * vtm_guided_step / vtm_solver_step then take as a single group.  Every edit concept has its own group of the UNet output;
+ * its term is kept only where its magnitude reaches a quantile of its plane, which no set of group weights can express.
+ *   model_out  (groups * F, C, H, W) contiguous NCHW, group-major, dtype VTM_F32 / VTM_F16 / VTM_BF16; groups <=
+ *              VTM_SOLVER_MAX_GROUPS.
+ *   g_uncond   the group of the unconditional prediction u;  g_cond: the group of the conditional prediction c, or -1 for
+ *              no classifier-free term;  guidance_scale: s.
+ *   n_concepts E, 0 .. VTM_SEGA_MAX_CONCEPTS, each with HOST arrays copied into the kernel arguments:
+ *              group[e]; scale[e] = s_e, signed (a reversed edit is a negative scale); w_apply[e], w_acc[e] finite fp32;
+ *              mode[e] one of VTM_SEGA_*; and for the quantile q_e in [0, 1], with P = H W and pos = q_e (P - 1) in double,
+ *              rank_lo[e] = floor(pos) in [0, P) and rank_frac[e] = pos - rank_lo[e] in [0, 1) (not read for VTM_SEGA_REGION).
+ *   regions    DEVICE uint8 (E, F, H, W) of 0 / 1, or NULL; required when a concept with a non-zero weight names a region.
+ *   momentum   whole-video fp32 (n_rows, C, H, W) from the pointer given, or NULL; chunk frame f is row frame_ids[f] (DEVICE
+ *              int32, distinct, inside [0, n_rows): the caller's contract), or row f when frame_ids is NULL (vtm_solver_step's
+ *              h1).  mom_scale, mom_beta finite; mom_apply 0 / 1.
+ *   out        chunk-local (F, C, H, W) in dtype; must not overlap model_out.
+ *   mask_out   DEVICE uint8 (E, F, C, H, W), or NULL.
+ * Per frame f, channel ch and pixel p, in fp32 (inputs convert to fp32 exactly), every sum started from 0 in the order
+ * written:
+ *     d_e   = model_out[group[e] * F + f] - u
+ *     g_e   = scale[e] * d_e                 one subtraction, one product, each rounded to nearest, not contracted
+ *     a_e   = |g_e|                          VTM_SEGA_CHANNEL*: the population is the (f, ch) plane, P values
+ *           = sum over ch' = 0 .. C - 1 of |g_e[ch']|, ascending, each addition rounded, not contracted
+ *                                            VTM_SEGA_SUM*: one population per frame, the same mask for every channel
+ *     a_lo, a_hi = the values of ranks rank_lo and min(rank_lo + 1, P - 1) of the population in ascending order: exact order
+ *             statistics; NaNs rank ABOVE +inf (where np.sort puts them)
+ *     thr   = (float)((double)a_lo + rank_frac * ((double)a_hi - (double)a_lo))       IEEE double, not contracted
+ *     M_e   = a_e >= thr  [ AND regions[e, f, p] != 0 for the *_REGION modes ] ;  = regions[e, f, p] != 0 for VTM_SEGA_REGION,
+ *             which takes no quantile at all
+ *     gamma_app = sum over e ascending with w_apply[e] != 0 of  w_apply[e] * (M_e ? g_e : 0) ;  gamma_acc: the same with w_acc
+ *     m     = u + s * (c - u) + gamma_app + mom_scale * nu      (s term absent for g_cond < 0; nu term absent for a NULL
+ *                                                                momentum or mom_apply == 0)
+ *     nu'   = mom_beta * nu + (1 - mom_beta) * gamma_acc         in place, by the thread that read nu (1 - mom_beta in fp32)
+ *     out   = m rounded once to dtype ;   mask_out[e] = M_e as 0 / 1
+ * The mask SELECTS, it does not multiply: a term that is masked off is absent, whatever it holds.  A concept whose two weights
+ * are both 0 is never read (a group full of NaN stays out) and its mask_out rows are not written; a term whose weight is
+ * exactly 0 is absent from its sum.  A NaN in a_e is never selected, and a population whose chosen ranks hold a NaN (or an
+ * infinity: inf - inf and 0 * inf are NaN) has thr = NaN and selects nothing.  A plane's bits depend on its own frame's values alone -- not on F, the
+ * other frames, the chunking or the run (integer LDS atomics only, no global atomics, no workspace).  One workgroup owns a
+ * (frame, channel) plane with the population in LDS: 1 <= H W <= VTM_SEGA_MAX_PLANE; C >= 1 (<= 1024); F <= 2^20, F == 0 is
+ * VTM_OK and launches nothing.  On a bad argument (VTM_EINVAL) nothing is launched, out and momentum are untouched.
+ * ---------------------------------------------------------------------------------------------- */
+#define VTM_SEGA_MAX_CONCEPTS 6
+#define VTM_SEGA_MAX_PLANE 16384
+#define VTM_SEGA_CHANNEL 0          /* quantile of |g_e| per (frame, channel) plane */
+#define VTM_SEGA_SUM 1              /* quantile of the channel sum of |g_e| per frame */
+#define VTM_SEGA_REGION 2           /* the region alone */
+#define VTM_SEGA_CHANNEL_REGION 3   /* VTM_SEGA_CHANNEL and the region */
+#define VTM_SEGA_SUM_REGION 4       /* VTM_SEGA_SUM and the region */
+int vtm_semantic_guidance(const void *model_out, int dtype, int64_t F, int64_t C, int64_t H, int64_t W, int64_t groups,
+                          int64_t g_uncond, int64_t g_cond, float guidance_scale, int64_t n_concepts, const int32_t *group,
+                          const float *scale, const int32_t *rank_lo, const double *rank_frac, const float *w_apply,
+                          const float *w_acc, const int32_t *mode, const uint8_t *regions, float *momentum, int64_t n_rows,
+                          const int32_t *frame_ids, float mom_scale, float mom_beta, int mom_apply, void *out,
+                          uint8_t *mask_out, vtm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * vtm_layernorm -- the block's norm1 (vidtome/patch.py:139-146, the plain torch.nn.LayerNorm branch
  * `norm_hidden_states = self.norm1(hidden_states)`), the first operation of the patched segment and the
  * producer of the matching metric; also usable for norm2 / norm3 (patch.py:173-176, 187).

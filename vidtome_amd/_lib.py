@@ -129,6 +129,10 @@ _SIGNATURES = {
                          _vp, _vp, _vp, _vp], _int),
     "vtm_solver_step": ([_vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, ctypes.POINTER(_f32), _i64, _vp, _int, _f32, _f32, _f32,
                          _f32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp], _int),
+    "vtm_semantic_guidance": ([_vp, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _i64, ctypes.POINTER(ctypes.c_int32),
+                               ctypes.POINTER(_f32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double),
+                               ctypes.POINTER(_f32), ctypes.POINTER(_f32), ctypes.POINTER(ctypes.c_int32), _vp, _vp, _i64, _vp,
+                               _f32, _f32, _int, _vp, _vp, _vp], _int),
     "vtm_layernorm": ([_vp, _vp, _vp, _int, _i64, _i64, _f32, _vp, _vp], _int),
     "vtm_layernorm_gather": ([_vp, _vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _f32, _vp, _i64, _vp], _int),
     "vtm_geglu": ([_vp, _int, _i64, _i64, _vp, _vp], _int),
@@ -1510,6 +1514,108 @@ def sag_degrade(x: torch.Tensor, model_out: torch.Tensor, mass: torch.Tensor, h_
                                  float(sqrt_alpha), float(sqrt_beta), (_f32 * len(taps))(*taps), r, float(threshold),
                                  out.data_ptr(), _ptr(mask), _stream()), "vtm_sag_degrade")
     return (out, mask) if want_mask else out
+
+
+SEGA_MAX_CONCEPTS, SEGA_MAX_PLANE = 6, 16384    # include/vidtome_hip.h VTM_SEGA_MAX_CONCEPTS, VTM_SEGA_MAX_PLANE
+SEGA_CHANNEL, SEGA_SUM, SEGA_REGION, SEGA_CHANNEL_REGION, SEGA_SUM_REGION = range(5)   # VTM_SEGA_*: a concept's mask mode
+
+
+def sega_rank(q: float, P: int) -> Tuple[int, float]:
+    """(rank_lo, rank_frac) of vtm_semantic_guidance for the quantile ``q`` in [0, 1] of a population of ``P`` values:
+    pos = q (P - 1) in double, rank_lo = floor(pos), rank_frac = pos - rank_lo."""
+    q, P = float(q), int(P)
+    if not 0.0 <= q <= 1.0 or P < 1:
+        raise RuntimeError(f"sega_rank: q = {q}, P = {P}: a quantile inside [0, 1] of at least one value is taken")
+    pos = q * (P - 1)
+    lo = min(int(math.floor(pos)), P - 1)
+    return lo, pos - lo
+
+
+@_on_device
+def semantic_guidance(model_out: torch.Tensor, groups: int, g_uncond: int, g_cond: int, guidance_scale: float, group, scale,
+                      threshold, w_apply, w_acc, mode, *, regions: Optional[torch.Tensor] = None,
+                      momentum: Optional[torch.Tensor] = None, frame_ids=None, mom_scale: float = 0.0, mom_beta: float = 0.0,
+                      mom_apply: bool = False, out: Optional[torch.Tensor] = None, want_masks: bool = False):
+    """Semantic guidance for one chunk (vtm_semantic_guidance, include/vidtome_hip.h): ``model_out`` (groups * F, C, H, W),
+    group-major; ``g_uncond`` / ``g_cond`` (-1: no classifier-free term) the groups of u and c; per concept one host number
+    in each of ``group``, ``scale`` (signed), ``threshold`` (the quantile q in [0, 1]; the ranks are sega_rank's), ``w_apply``,
+    ``w_acc`` and ``mode`` (SEGA_*); ``regions`` uint8 (E, F, H, W), needed where a live concept's mode names a region;
+    ``momentum`` the whole-video fp32 (n_frames, C, H, W) buffer, updated in place at the rows ``frame_ids`` names (as for
+    guided_step; without momentum F is model_out's frame count and frame_ids only gives it).  Returns out, a chunk-local
+    (F, C, H, W) tensor of model_out's dtype (``out``: a contiguous tensor of that shape that does not overlap model_out, or
+    None for a new one), or (out, masks uint8 (E, F, C, H, W)) with ``want_masks`` -- rows of concepts whose two weights are
+    0 are not written."""
+    who = "semantic_guidance"
+    groups, g_uncond, g_cond = int(groups), int(g_uncond), int(g_cond)
+    if not isinstance(model_out, torch.Tensor) or model_out.dim() != 4 or model_out.dtype not in _DT:
+        raise RuntimeError(f"{who}: model_out must be a (groups * frames, C, H, W) fp16 / bf16 / fp32 tensor")
+    cols = [list(v) for v in (group, scale, threshold, w_apply, w_acc, mode)]
+    E = len(cols[0])
+    if any(len(c) != E for c in cols) or E > SEGA_MAX_CONCEPTS:
+        raise RuntimeError(f"{who}: {[len(c) for c in cols]} per-concept values: one of each for 0 .. {SEGA_MAX_CONCEPTS} concepts")
+    group, mode = [int(v) for v in cols[0]], [int(v) for v in cols[5]]
+    scale, threshold, w_apply, w_acc = ([float(v) for v in c] for c in cols[1:5])
+    if not 1 <= groups <= SOLVER_MAX_GROUPS or not 0 <= g_uncond < groups or not -1 <= g_cond < groups \
+            or any(not 0 <= g < groups for g in group):
+        raise RuntimeError(f"{who}: groups = {groups} (1 .. {SOLVER_MAX_GROUPS}), g_uncond = {g_uncond}, g_cond = {g_cond}, "
+                           f"group = {group}: a group index outside [0, groups)")
+    if any(m not in range(5) for m in mode):
+        raise RuntimeError(f"{who}: mode = {mode}: SEGA_CHANNEL .. SEGA_SUM_REGION (0 .. 4) are taken")
+    if any(not 0.0 <= q <= 1.0 for q in threshold):
+        raise RuntimeError(f"{who}: threshold = {threshold}: quantiles inside [0, 1] are taken")
+    guidance_scale, mom_scale, mom_beta = float(guidance_scale), float(mom_scale), float(mom_beta)
+    if not all(math.isfinite(v) for v in w_apply + w_acc + [guidance_scale, mom_scale, mom_beta]):
+        raise RuntimeError(f"{who}: the weights, guidance_scale, mom_scale and mom_beta must be finite")
+    if model_out.shape[0] % groups:
+        raise RuntimeError(f"{who}: model_out has {model_out.shape[0]} samples, not {groups} groups of frames")
+    n_chunk, C, H, W = model_out.shape[0] // groups, *model_out.shape[1:]
+    if momentum is not None:
+        if not isinstance(momentum, torch.Tensor) or momentum.dim() != 4 or momentum.dtype != torch.float32 \
+                or tuple(momentum.shape[1:]) != (C, H, W) or momentum.device != model_out.device:
+            raise RuntimeError(f"{who}: momentum must be an fp32 (frames, {C}, {H}, {W}) tensor on model_out's device")
+        first, ids, F = _frame_rows(frame_ids, momentum.shape[0], who)
+    else:
+        first, ids, F = 0, None, n_chunk if frame_ids is None else len(frame_ids)
+    if F != n_chunk:
+        raise RuntimeError(f"{who}: model_out {tuple(model_out.shape)} is not ({groups} groups * {F} frames, C, H, W)")
+    if C < 1 or H < 1 or W < 1 or H * W > SEGA_MAX_PLANE:
+        raise RuntimeError(f"{who}: frames of {C} x {H} x {W} latents: a plane of 1 .. {SEGA_MAX_PLANE} elements (128 x 128) is "
+                           "taken, it lives in a workgroup's LDS")
+    live = [e for e in range(E) if _f32_round(w_apply[e]) != 0.0 or _f32_round(w_acc[e]) != 0.0]
+    if any(mode[e] >= SEGA_REGION for e in live):
+        if not isinstance(regions, torch.Tensor) or regions.dtype != torch.uint8 or tuple(regions.shape) != (E, F, H, W) \
+                or regions.device != model_out.device:
+            raise RuntimeError(f"{who}: a region mode needs regions, a uint8 ({E}, {F}, {H}, {W}) tensor on model_out's device")
+    elif regions is not None and not isinstance(regions, torch.Tensor):
+        raise RuntimeError(f"{who}: regions must be a tensor")
+    _req(model_out, "model_out")
+    for t, name in ((regions, "regions"), (momentum, "momentum"), (ids if isinstance(ids, torch.Tensor) else None, "frame_ids")):
+        if t is not None and _req(t, name).device != model_out.device:
+            raise RuntimeError(f"{who}: {name} lives on {t.device}, model_out on {model_out.device}")
+    if out is None:
+        out = torch.empty((F, C, H, W), dtype=model_out.dtype, device=model_out.device)
+    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (F, C, H, W) or out.dtype != model_out.dtype \
+            or out.device != model_out.device or not out.is_contiguous():
+        raise RuntimeError(f"{who}: out must be a contiguous ({F}, {C}, {H}, {W}) tensor of model_out's dtype on its device")
+    else:
+        m_lo, o_lo = model_out.data_ptr(), out.data_ptr()
+        if o_lo < m_lo + model_out.numel() * model_out.element_size() and m_lo < o_lo + out.numel() * out.element_size():
+            raise RuntimeError(f"{who}: out overlaps model_out")
+    masks = torch.empty((E, F, C, H, W), dtype=torch.uint8, device=model_out.device) if want_masks else None
+    if F == 0:
+        return (out, masks) if want_masks else out
+    if isinstance(ids, list):
+        ids = torch.tensor(ids, dtype=torch.int32, device=model_out.device)
+    ranks = [sega_rank(q, H * W) for q in threshold]
+    i32, n = ctypes.c_int32 * max(E, 1), max(E, 1)
+    _check(lib().vtm_semantic_guidance(
+        model_out.data_ptr(), dtype_code(model_out), F, C, H, W, groups, g_uncond, g_cond, guidance_scale, E, i32(*group),
+        (_f32 * n)(*scale), i32(*(r[0] for r in ranks)), (ctypes.c_double * n)(*(r[1] for r in ranks)), (_f32 * n)(*w_apply),
+        (_f32 * n)(*w_acc), i32(*mode), _ptr(regions),
+        momentum.data_ptr() + first * C * H * W * 4 if momentum is not None else None,
+        momentum.shape[0] - first if momentum is not None else 0, _ptr(ids), mom_scale, mom_beta, int(bool(mom_apply)),
+        out.data_ptr(), _ptr(masks), _stream()), "vtm_semantic_guidance")
+    return (out, masks) if want_masks else out
 
 
 FREEU_MAX_PLANE = 16384                         # what vtm_freeu takes (csrc/freeu.hip): H * W of a plane
