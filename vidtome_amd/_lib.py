@@ -756,6 +756,59 @@ def _frame_rows(frame_ids, n_frames: int, who: str):
     return 0, ids, len(ids)
 
 
+def _step_operands(who: str, x, model_out, groups: int, pred_type: int, rescale: float, frame_ids, noise, noise_coef, out, want,
+                   any_output: bool, check_groups, check_rescale, check_more=None, extra=()):
+    """What guided_step and solver_step check and allocate alike, in the order they always did; the wrapper's own checks run
+    in between: ``check_groups()`` after the operand types, ``check_rescale(E)`` once the shapes fit, ``check_more()`` after
+    the noise.  ``noise_coef``: the name of the non-zero coefficient that needs ``noise``, or None; ``want`` = (want_x,
+    want_eps, want_x0); ``extra``: further (tensor or None, name) pairs that must live on x's device.  Returns
+    (F, E, device frame ids or None, out, eps, x0, the chunk's first element in a whole-video tensor)."""
+    for t, name in ((x, "x"), (model_out, "model_out")):
+        if not isinstance(t, torch.Tensor) or t.dim() < 2 or t.dtype not in _DT:
+            raise RuntimeError(f"{who}: {name} must be a (frames, ...) fp16 / bf16 / fp32 tensor")
+    if pred_type not in (PRED_EPSILON, PRED_V, PRED_SAMPLE):
+        raise RuntimeError(f"{who}: unknown pred_type {pred_type}")
+    check_groups()
+    if not rescale >= 0.0:
+        raise RuntimeError(f"{who}: rescale = {rescale} is negative or NaN")
+    first, ids, F = _frame_rows(frame_ids, x.shape[0], who)
+    E = math.prod(x.shape[1:])
+    if model_out.shape[0] != groups * F or math.prod(model_out.shape[1:]) != E:
+        raise RuntimeError(f"{who}: model_out {tuple(model_out.shape)} is not ({groups} groups * {F} frames, {E} elements)")
+    if model_out.dtype != x.dtype:
+        raise RuntimeError(f"{who}: dtype mismatch: x {x.dtype}, model_out {model_out.dtype}")
+    check_rescale(E)
+    if noise_coef and noise is None:
+        raise RuntimeError(f"{who}: {noise_coef} != 0 needs noise")
+    if noise is not None and (not isinstance(noise, torch.Tensor) or noise.dtype != x.dtype or noise.numel() != F * E
+                              or noise.shape[0] != F):
+        raise RuntimeError(f"{who}: noise must be a ({F}, ...) {x.dtype} tensor of the chunk's {F * E} elements")
+    if check_more:
+        check_more()
+    if not any_output:
+        raise RuntimeError(f"{who}: no output asked for")
+    if out is not None and (not isinstance(out, torch.Tensor) or out.shape != x.shape or out.dtype != x.dtype
+                            or out.device != x.device):
+        raise RuntimeError(f"{who}: out must be a tensor like x (it may be x)")
+    if E < 1 and F:
+        raise RuntimeError(f"{who}: empty frames")
+    _req(x, "x"), _req(model_out, "model_out")
+    for t, name in ((noise, "noise"), (out, "out"), *extra, (ids if isinstance(ids, torch.Tensor) else None, "frame_ids")):
+        if t is not None and _req(t, name).device != x.device:
+            raise RuntimeError(f"{who}: {name} lives on {t.device}, x on {x.device}")
+    if model_out.device != x.device:
+        raise RuntimeError(f"{who}: model_out lives on {model_out.device}, x on {x.device}")
+    if isinstance(ids, list):
+        ids = torch.tensor(ids, dtype=torch.int32, device=x.device)
+    want_x, want_eps, want_x0 = want
+    if want_x and out is None:
+        out = torch.empty_like(x) if (frame_ids is None) else x
+    local = (F,) + tuple(model_out.shape[1:])
+    eps = torch.empty(local, dtype=x.dtype, device=x.device) if want_eps else None
+    x0 = torch.empty(local, dtype=x.dtype, device=x.device) if want_x0 else None
+    return F, E, ids, out, eps, x0, first * E
+
+
 @_on_device
 def guided_step(x: torch.Tensor, model_out: torch.Tensor, sqrt_alpha: float, sqrt_beta: float, c_x0: float, c_eps: float,
                 sigma: float = 0.0, *, groups: int = 2, g_uncond: Optional[int] = None, g_cond: Optional[int] = None,
@@ -775,58 +828,28 @@ def guided_step(x: torch.Tensor, model_out: torch.Tensor, sqrt_alpha: float, sqr
         g_uncond = max(groups - 2, 0)
     if g_cond is None:
         g_cond = groups - 1 if groups >= 2 else -1
-    g_uncond, g_cond, pred_type = int(g_uncond), int(g_cond), int(pred_type)
-    for t, name in ((x, "x"), (model_out, "model_out")):
-        if not isinstance(t, torch.Tensor) or t.dim() < 2 or t.dtype not in _DT:
-            raise RuntimeError(f"{who}: {name} must be a (frames, ...) fp16 / bf16 / fp32 tensor")
-    if pred_type not in (PRED_EPSILON, PRED_V, PRED_SAMPLE):
-        raise RuntimeError(f"{who}: unknown pred_type {pred_type}")
-    if groups < 1 or not 0 <= g_uncond < groups or not -1 <= g_cond < groups:
-        raise RuntimeError(f"{who}: groups = {groups}, g_uncond = {g_uncond}, g_cond = {g_cond}: a group index outside [0, groups)")
-    if g_uncond == g_cond:
-        raise RuntimeError(f"{who}: g_uncond == g_cond == {g_cond}")
-    sigma, rescale = float(sigma), float(rescale)
-    if not rescale >= 0.0:
-        raise RuntimeError(f"{who}: rescale = {rescale} is negative or NaN")
-    first, ids, F = _frame_rows(frame_ids, x.shape[0], who)
-    E = math.prod(x.shape[1:])
-    if model_out.shape[0] != groups * F or math.prod(model_out.shape[1:]) != E:
-        raise RuntimeError(f"{who}: model_out {tuple(model_out.shape)} is not ({groups} groups * {F} frames, {E} elements)")
-    if model_out.dtype != x.dtype:
-        raise RuntimeError(f"{who}: dtype mismatch: x {x.dtype}, model_out {model_out.dtype}")
-    if rescale > 0.0 and (g_cond < 0 or E < 2):
-        raise RuntimeError(f"{who}: rescale > 0 needs a conditional group and frames of at least 2 elements")
-    if sigma != 0.0 and noise is None:
-        raise RuntimeError(f"{who}: sigma != 0 needs noise")
-    if noise is not None and (not isinstance(noise, torch.Tensor) or noise.dtype != x.dtype or noise.numel() != F * E
-                              or noise.shape[0] != F):
-        raise RuntimeError(f"{who}: noise must be a ({F}, ...) {x.dtype} tensor of the chunk's {F * E} elements")
-    if not (want_x or want_eps or want_x0):
-        raise RuntimeError(f"{who}: no output asked for")
-    if out is not None and (not isinstance(out, torch.Tensor) or out.shape != x.shape or out.dtype != x.dtype
-                            or out.device != x.device):
-        raise RuntimeError(f"{who}: out must be a tensor like x (it may be x)")
-    if E < 1 and F:
-        raise RuntimeError(f"{who}: empty frames")
-    _req(x, "x"), _req(model_out, "model_out")
-    for t, name in ((noise, "noise"), (out, "out"), (ids if isinstance(ids, torch.Tensor) else None, "frame_ids")):
-        if t is not None and _req(t, name).device != x.device:
-            raise RuntimeError(f"{who}: {name} lives on {t.device}, x on {x.device}")
-    if model_out.device != x.device:
-        raise RuntimeError(f"{who}: model_out lives on {model_out.device}, x on {x.device}")
-    if isinstance(ids, list):
-        ids = torch.tensor(ids, dtype=torch.int32, device=x.device)
-    if want_x and out is None:
-        out = torch.empty_like(x) if (frame_ids is None) else x
-    local = (F,) + tuple(model_out.shape[1:])
-    eps = torch.empty(local, dtype=x.dtype, device=x.device) if want_eps else None
-    x0 = torch.empty(local, dtype=x.dtype, device=x.device) if want_x0 else None
+    g_uncond, g_cond, pred_type, sigma, rescale = int(g_uncond), int(g_cond), int(pred_type), float(sigma), float(rescale)
+
+    def check_groups():
+        if groups < 1 or not 0 <= g_uncond < groups or not -1 <= g_cond < groups:
+            raise RuntimeError(f"{who}: groups = {groups}, g_uncond = {g_uncond}, g_cond = {g_cond}: a group index outside "
+                               "[0, groups)")
+        if g_uncond == g_cond:
+            raise RuntimeError(f"{who}: g_uncond == g_cond == {g_cond}")
+
+    def check_rescale(E):
+        if rescale > 0.0 and (g_cond < 0 or E < 2):
+            raise RuntimeError(f"{who}: rescale > 0 needs a conditional group and frames of at least 2 elements")
+
+    F, E, ids, out, eps, x0, skip = _step_operands(
+        who, x, model_out, groups, pred_type, rescale, frame_ids, noise, "sigma" if sigma != 0.0 else None, out,
+        (want_x, want_eps, want_x0), want_x or want_eps or want_x0, check_groups, check_rescale)
     if F == 0:
         return (out if want_x else None), eps, x0
-    skip = first * E * x.element_size()
+    skip *= x.element_size()
     _check(lib().vtm_guided_step(x.data_ptr() + skip, model_out.data_ptr(), _ptr(noise if sigma != 0.0 else None),
-                                 dtype_code(x), F, E, groups, g_uncond, g_cond, _ptr(ids), pred_type, float(guidance), rescale,
-                                 float(sqrt_alpha), float(sqrt_beta), float(c_x0), float(c_eps), sigma,
+                                 dtype_code(x), F, E, groups, g_uncond, g_cond, _ptr(ids), pred_type, float(guidance),
+                                 rescale, float(sqrt_alpha), float(sqrt_beta), float(c_x0), float(c_eps), sigma,
                                  out.data_ptr() + skip if want_x else None, _ptr(eps), _ptr(x0), _stream()),
            "vtm_guided_step")
     return (out if want_x else None), eps, x0
@@ -852,67 +875,39 @@ def solver_step(x: torch.Tensor, model_out: torch.Tensor, weights, sqrt_alpha: f
     weights = [float(v) for v in weights]
     groups, pred_type = len(weights), int(pred_type)
     g_ref = groups - 1 if g_ref is None else int(g_ref)
-    for t, name in ((x, "x"), (model_out, "model_out")):
-        if not isinstance(t, torch.Tensor) or t.dim() < 2 or t.dtype not in _DT:
-            raise RuntimeError(f"{who}: {name} must be a (frames, ...) fp16 / bf16 / fp32 tensor")
-    if pred_type not in (PRED_EPSILON, PRED_V, PRED_SAMPLE):
-        raise RuntimeError(f"{who}: unknown pred_type {pred_type}")
-    if not 1 <= groups <= SOLVER_MAX_GROUPS or not all(math.isfinite(v) for v in weights):
-        raise RuntimeError(f"{who}: {groups} weights {weights}: 1 .. {SOLVER_MAX_GROUPS} finite numbers, one per group")
     c_x, c_x0, c_h1, c_h2, c_noise, rescale = (float(v) for v in (c_x, c_x0, c_h1, c_h2, c_noise, rescale))
-    if not rescale >= 0.0:
-        raise RuntimeError(f"{who}: rescale = {rescale} is negative or NaN")
-    first, ids, F = _frame_rows(frame_ids, x.shape[0], who)
-    E = math.prod(x.shape[1:])
-    if model_out.shape[0] != groups * F or math.prod(model_out.shape[1:]) != E:
-        raise RuntimeError(f"{who}: model_out {tuple(model_out.shape)} is not ({groups} groups * {F} frames, {E} elements)")
-    if model_out.dtype != x.dtype:
-        raise RuntimeError(f"{who}: dtype mismatch: x {x.dtype}, model_out {model_out.dtype}")
-    if rescale > 0.0 and (not 0 <= g_ref < groups or _f32_round(weights[g_ref]) == 0.0 or E < 2):
-        raise RuntimeError(f"{who}: rescale > 0 needs g_ref = {g_ref} inside [0, {groups}) with a non-zero weight, and frames of "
-                           "at least 2 elements")
-    if c_noise != 0.0 and noise is None:
-        raise RuntimeError(f"{who}: c_noise != 0 needs noise")
-    if noise is not None and (not isinstance(noise, torch.Tensor) or noise.dtype != x.dtype or noise.numel() != F * E
-                              or noise.shape[0] != F):
-        raise RuntimeError(f"{who}: noise must be a ({F}, ...) {x.dtype} tensor of the chunk's {F * E} elements")
-    for t, name, c in ((h1, "h1", c_h1), (h2, "h2", c_h2), (h_out, "h_out", 0.0)):
-        if t is None and c != 0.0:
-            raise RuntimeError(f"{who}: c_{name} != 0 needs {name}")
-        if t is not None and (not isinstance(t, torch.Tensor) or t.shape != x.shape or t.dtype != torch.float32
-                              or t.device != x.device):
-            raise RuntimeError(f"{who}: {name} must be an fp32 tensor shaped like x, on its device")
-    if not (want_x or want_eps or want_x0 or h_out is not None):
-        raise RuntimeError(f"{who}: no output asked for")
-    if out is not None and (not isinstance(out, torch.Tensor) or out.shape != x.shape or out.dtype != x.dtype
-                            or out.device != x.device):
-        raise RuntimeError(f"{who}: out must be a tensor like x (it may be x)")
-    if E < 1 and F:
-        raise RuntimeError(f"{who}: empty frames")
-    _req(x, "x"), _req(model_out, "model_out")
-    for t, name in ((noise, "noise"), (out, "out"), (h1, "h1"), (h2, "h2"), (h_out, "h_out"),
-                    (ids if isinstance(ids, torch.Tensor) else None, "frame_ids")):
-        if t is not None and _req(t, name).device != x.device:
-            raise RuntimeError(f"{who}: {name} lives on {t.device}, x on {x.device}")
-    if model_out.device != x.device:
-        raise RuntimeError(f"{who}: model_out lives on {model_out.device}, x on {x.device}")
-    if isinstance(ids, list):
-        ids = torch.tensor(ids, dtype=torch.int32, device=x.device)
-    if want_x and out is None:
-        out = torch.empty_like(x) if (frame_ids is None) else x
-    local = (F,) + tuple(model_out.shape[1:])
-    eps = torch.empty(local, dtype=x.dtype, device=x.device) if want_eps else None
-    x0 = torch.empty(local, dtype=x.dtype, device=x.device) if want_x0 else None
+
+    def check_groups():
+        if not 1 <= groups <= SOLVER_MAX_GROUPS or not all(math.isfinite(v) for v in weights):
+            raise RuntimeError(f"{who}: {groups} weights {weights}: 1 .. {SOLVER_MAX_GROUPS} finite numbers, one per group")
+
+    def check_rescale(E):
+        if rescale > 0.0 and (not 0 <= g_ref < groups or _f32_round(weights[g_ref]) == 0.0 or E < 2):
+            raise RuntimeError(f"{who}: rescale > 0 needs g_ref = {g_ref} inside [0, {groups}) with a non-zero weight, and "
+                               "frames of at least 2 elements")
+
+    def check_history():
+        for t, name, c in ((h1, "h1", c_h1), (h2, "h2", c_h2), (h_out, "h_out", 0.0)):
+            if t is None and c != 0.0:
+                raise RuntimeError(f"{who}: c_{name} != 0 needs {name}")
+            if t is not None and (not isinstance(t, torch.Tensor) or t.shape != x.shape or t.dtype != torch.float32
+                                  or t.device != x.device):
+                raise RuntimeError(f"{who}: {name} must be an fp32 tensor shaped like x, on its device")
+
+    F, E, ids, out, eps, x0, skip = _step_operands(
+        who, x, model_out, groups, pred_type, rescale, frame_ids, noise, "c_noise" if c_noise != 0.0 else None, out,
+        (want_x, want_eps, want_x0), want_x or want_eps or want_x0 or h_out is not None, check_groups, check_rescale,
+        check_history, ((h1, "h1"), (h2, "h2"), (h_out, "h_out")))
     if F == 0:
         return (out if want_x else None), eps, x0
-    skip, hskip = first * E * x.element_size(), first * E * 4
 
     def hist(t, used=True):
-        return t.data_ptr() + hskip if (t is not None and used) else None
-    _check(lib().vtm_solver_step(x.data_ptr() + skip, model_out.data_ptr(), _ptr(noise if c_noise != 0.0 else None),
+        return t.data_ptr() + skip * 4 if (t is not None and used) else None
+    skip_x = skip * x.element_size()
+    _check(lib().vtm_solver_step(x.data_ptr() + skip_x, model_out.data_ptr(), _ptr(noise if c_noise != 0.0 else None),
                                  hist(h1, c_h1 != 0.0), hist(h2, c_h2 != 0.0), dtype_code(x), F, E, groups,
                                  (_f32 * groups)(*weights), g_ref, _ptr(ids), pred_type, rescale, float(sqrt_alpha),
-                                 float(sqrt_beta), c_x, c_x0, c_h1, c_h2, c_noise, out.data_ptr() + skip if want_x else None,
+                                 float(sqrt_beta), c_x, c_x0, c_h1, c_h2, c_noise, out.data_ptr() + skip_x if want_x else None,
                                  hist(h_out), _ptr(eps), _ptr(x0), _stream()), "vtm_solver_step")
     return (out if want_x else None), eps, x0
 
@@ -1451,6 +1446,26 @@ def gaussian_taps(radius: int, sigma: float):
     return [_f32_round(v / total) for v in w]
 
 
+def _chunk_out(who: str, out, shape, ref: torch.Tensor, ref_name: str, like: str, ids):
+    """The chunk-local result of sag_degrade / semantic_guidance: ``out`` when given -- a contiguous tensor of ``shape`` with
+    ``ref``'s dtype and device that does not overlap ref -- else a new one; and the frame ids _frame_rows left, on ref's
+    device (a list is uploaded).  Returns (out, ids)."""
+    if isinstance(ids, torch.Tensor) and _req(ids, "frame_ids").device != ref.device:
+        raise RuntimeError(f"{who}: frame_ids lives on {ids.device}, {ref_name} on {ref.device}")
+    if out is None:
+        out = torch.empty(shape, dtype=ref.dtype, device=ref.device)
+    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != ref.dtype or out.device != ref.device \
+            or not out.is_contiguous():
+        raise RuntimeError(f"{who}: out must be a contiguous ({', '.join(map(str, shape))}) tensor of {like}")
+    else:
+        r_lo, o_lo = ref.data_ptr(), out.data_ptr()
+        if o_lo < r_lo + ref.numel() * ref.element_size() and r_lo < o_lo + out.numel() * out.element_size():
+            raise RuntimeError(f"{who}: out overlaps {ref_name}")
+    if isinstance(ids, list):
+        ids = torch.tensor(ids, dtype=torch.int32, device=ref.device)
+    return out, ids
+
+
 @_on_device
 def sag_degrade(x: torch.Tensor, model_out: torch.Tensor, mass: torch.Tensor, h_m: int, w_m: int, sqrt_alpha: float,
                 sqrt_beta: float, taps, threshold: float = 1.0, *, groups: int = 1, group: int = 0, frame_ids=None,
@@ -1491,22 +1506,10 @@ def sag_degrade(x: torch.Tensor, model_out: torch.Tensor, mass: torch.Tensor, h_
         raise RuntimeError(f"{who}: mass must be fp32 ({F}, >= h_m * w_m = {h_m * w_m}) on x's device, contiguous along its "
                            f"last axis, with the ({h_m}, {w_m}) grid inside ({H}, {W})")
     _req(x, "x"), _req(model_out, "model_out")
-    if isinstance(ids, torch.Tensor) and _req(ids, "frame_ids").device != x.device:
-        raise RuntimeError(f"{who}: frame_ids lives on {ids.device}, x on {x.device}")
-    if out is None:
-        out = torch.empty((F, C, H, W), dtype=x.dtype, device=x.device)
-    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (F, C, H, W) or out.dtype != x.dtype \
-            or out.device != x.device or not out.is_contiguous():
-        raise RuntimeError(f"{who}: out must be a contiguous ({F}, {C}, {H}, {W}) tensor of x's dtype on x's device")
-    else:
-        x_lo, o_lo = x.data_ptr(), out.data_ptr()
-        if o_lo < x_lo + x.numel() * x.element_size() and x_lo < o_lo + out.numel() * out.element_size():
-            raise RuntimeError(f"{who}: out overlaps x")
+    out, ids = _chunk_out(who, out, (F, C, H, W), x, "x", "x's dtype on x's device", ids)
     mask = torch.empty((F, H, W), dtype=torch.uint8, device=x.device) if want_mask else None
     if F == 0:
         return (out, mask) if want_mask else out
-    if isinstance(ids, list):
-        ids = torch.tensor(ids, dtype=torch.int32, device=x.device)
     E = C * H * W
     _check(lib().vtm_sag_degrade(x.data_ptr() + first * E * x.element_size(), x.shape[0] - first, _ptr(ids),
                                  model_out.data_ptr() + group * F * E * x.element_size(), mass.data_ptr(),
@@ -1589,23 +1592,13 @@ def semantic_guidance(model_out: torch.Tensor, groups: int, g_uncond: int, g_con
     elif regions is not None and not isinstance(regions, torch.Tensor):
         raise RuntimeError(f"{who}: regions must be a tensor")
     _req(model_out, "model_out")
-    for t, name in ((regions, "regions"), (momentum, "momentum"), (ids if isinstance(ids, torch.Tensor) else None, "frame_ids")):
+    for t, name in ((regions, "regions"), (momentum, "momentum")):
         if t is not None and _req(t, name).device != model_out.device:
             raise RuntimeError(f"{who}: {name} lives on {t.device}, model_out on {model_out.device}")
-    if out is None:
-        out = torch.empty((F, C, H, W), dtype=model_out.dtype, device=model_out.device)
-    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (F, C, H, W) or out.dtype != model_out.dtype \
-            or out.device != model_out.device or not out.is_contiguous():
-        raise RuntimeError(f"{who}: out must be a contiguous ({F}, {C}, {H}, {W}) tensor of model_out's dtype on its device")
-    else:
-        m_lo, o_lo = model_out.data_ptr(), out.data_ptr()
-        if o_lo < m_lo + model_out.numel() * model_out.element_size() and m_lo < o_lo + out.numel() * out.element_size():
-            raise RuntimeError(f"{who}: out overlaps model_out")
+    out, ids = _chunk_out(who, out, (F, C, H, W), model_out, "model_out", "model_out's dtype on its device", ids)
     masks = torch.empty((E, F, C, H, W), dtype=torch.uint8, device=model_out.device) if want_masks else None
     if F == 0:
         return (out, masks) if want_masks else out
-    if isinstance(ids, list):
-        ids = torch.tensor(ids, dtype=torch.int32, device=model_out.device)
     ranks = [sega_rank(q, H * W) for q in threshold]
     i32, n = ctypes.c_int32 * max(E, 1), max(E, 1)
     _check(lib().vtm_semantic_guidance(

@@ -551,7 +551,7 @@ Family make_family() {
     f.rec_bytes = (size_t)rec_size(D) * sizeof(float);
     f.xcd_min_nqb = XCD_MIN_NQB;
     f.ws_devplan_min_tiles = 16;
-    if constexpr (lds_for(D) > 64 * 1024) f.lds_opt_in = opt_in_lds<attention_kernel<T, D, FOLD>, lds_for(D)>;
+    if constexpr (lds_for(D) > 64 * 1024) f.lds_opt_in = vtm::opt_in_lds<attention_kernel<T, D, FOLD>, lds_for(D)>;
     f.main = launch_main<T, D, FOLD>;
     f.combine = launch_combine<T, D>;
     return f;

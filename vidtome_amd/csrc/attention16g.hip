@@ -431,7 +431,7 @@ Family make_family() {
     // last round of the LIVE items mostly idle -- 34 816 rows, 0.78 live: 849 items on 256 slots took 4 rounds for 3.3 rounds
     // of work), or else takes the plain host plan
     f.host_split_all = false;
-    if constexpr (lds16g(NG) > 64 * 1024) f.lds_opt_in = opt_in_lds<attention16g_kernel<T, 40, NG>, lds16g(NG)>;
+    if constexpr (lds16g(NG) > 64 * 1024) f.lds_opt_in = vtm::opt_in_lds<attention16g_kernel<T, 40, NG>, lds16g(NG)>;
     f.main = launch_main<T, NG>;
     f.combine = launch_combine<T, NG>;
     return f;

@@ -412,7 +412,7 @@ Family make_family() {
     // the pieces are cut from 32-key tiles
     f.key_tile = KT;
     f.xcd_min_nqb = F_XCD_MIN_NQB;
-    if constexpr (flds_bytes(D) > 64 * 1024) f.lds_opt_in = opt_in_lds<attention_f32_kernel<D>, flds_bytes(D)>;
+    if constexpr (flds_bytes(D) > 64 * 1024) f.lds_opt_in = vtm::opt_in_lds<attention_f32_kernel<D>, flds_bytes(D)>;
     f.main = launch_main<D>;
     f.combine = launch_combine<D>;
     return f;

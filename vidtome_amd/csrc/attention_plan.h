@@ -8,7 +8,6 @@
 #include "attention_common.h"
 
 #include <algorithm>
-#include <atomic>
 #include <type_traits>
 
 namespace vtm_att {
@@ -351,19 +350,6 @@ inline size_t devplan_ws_bytes(int slots, size_t rec_bytes) { return DEVPLAN_HEA
 // the PlanArgs of a planned launch, for a family's launch thunks
 inline PlanArgs plan_args(const Call &c, const Launch &g) {
     return {g.nqb, g.whole, g.split_major, g.partial, c.q_count, static_cast<const DevPlan *>(g.plan), g.nsplit, g.xcd_groups};
-}
-
-// once per (kernel, device): lets Kernel use LDS bytes of dynamic LDS, beyond the default 64 KB (a Family's lds_opt_in)
-template <auto Kernel, size_t LDS>
-hipError_t opt_in_lds() {
-    static_assert(LDS > 64 * 1024, "up to 64 KB of dynamic LDS need no opt-in");
-    static std::atomic<bool> done[vtm::MAX_DEVICES];
-    const int dev = vtm::current_device();
-    if (done[dev].load(std::memory_order_acquire)) return hipSuccess;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
-    if (e == hipSuccess) done[dev].store(true, std::memory_order_release);
-    return e;
 }
 
 // The launch protocol of every family.  A query-bounded launch of at least two rounds is planned ON THE DEVICE from the

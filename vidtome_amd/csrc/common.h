@@ -68,6 +68,27 @@ inline int device_cus() {
     return n;
 }
 
+// once per (kernel, device): lets Kernel use LDS bytes of dynamic LDS, beyond the default 64 KB.  A failure is the caller's
+// to report: "<export>: LDS attribute: <hip error string>", VTM_ELAUNCH.
+template <auto Kernel, size_t LDS>
+hipError_t opt_in_lds() {
+    static_assert(LDS > 64 * 1024, "up to 64 KB of dynamic LDS need no opt-in");
+    static std::atomic<bool> done[MAX_DEVICES];
+    const int dev = current_device();
+    if (done[dev].load(std::memory_order_acquire)) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
+    if (e == hipSuccess) done[dev].store(true, std::memory_order_release);
+    return e;
+}
+
+// out, F rows of E elements of the model dtype, does not overlap the n rows at p
+inline bool rows_apart(const void *out, int64_t F, const void *p, int64_t n, int64_t E, int dtype) {
+    const int64_t es = dtype == VTM_F32 ? 4 : 2;
+    const char *p0 = (const char *)p, *p1 = p0 + n * E * es, *o0 = (const char *)out, *o1 = o0 + F * E * es;
+    return o1 <= p0 || p1 <= o0;
+}
+
 // 16-byte global accesses with an optional streaming (non-temporal) policy.  Measured on the HBM-bound kernels
 // (profiles/r03_hbm_nt.txt): beyond the 256 MB Infinity Cache non-temporal loads / stores are +5 ... +15 % (no line is
 // kept that nobody will read again before it is evicted); for working sets the cache holds they are -10 % (the next

@@ -58,9 +58,8 @@
 // The planes C_h / 2 <= c < C_h get no work item; neither do the skip planes when s == 1 nor the backbone planes of
 // version 1 when b == 1: those bytes are never written.
 #include "common.h"
-#include "step_chunk.h"
+#include "step_core.h"
 
-#include <atomic>
 
 namespace {
 
@@ -83,7 +82,7 @@ struct Apply {
 
 template <typename T>
 __device__ __forceinline__ void load8(const T *p, int n, bool vec, float *v) {
-    constexpr int N = 16 / sizeof(T);           // step_chunk.h's chunk: 8 16-bit elements or 4 fp32
+    constexpr int N = 16 / sizeof(T);           // step_core.h's chunk: 8 16-bit elements or 4 fp32
 #pragma unroll
     for (int h = 0; h < CHUNK / N; ++h) {
         const int nh = n - h * N;
@@ -295,14 +294,8 @@ int launch_apply(void *x, const Apply &a, hipStream_t s) {
     constexpr int NT = G > WG_MIN ? G : WG_MIN;
     const int lds = (a.H + a.W) * (int)sizeof(float2) + (G > 64 ? 7 * (G / 64) * (int)sizeof(float) : 0);
     if (lds > 64 * 1024) {
-        static std::atomic<bool> attr_set[vtm::MAX_DEVICES];
-        const int dev = vtm::current_device();
-        if (!attr_set[dev].load(std::memory_order_acquire)) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(freeu_apply_kernel<T, G>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, FREEU_LDS_MAX);
-            if (e != hipSuccess) return vtm::fail(VTM_ELAUNCH, "vtm_freeu: LDS attribute: %s", hipGetErrorString(e));
-            attr_set[dev].store(true, std::memory_order_release);
-        }
+        const hipError_t e = vtm::opt_in_lds<freeu_apply_kernel<T, G>, FREEU_LDS_MAX>();
+        if (e != hipSuccess) return vtm::fail(VTM_ELAUNCH, "vtm_freeu: LDS attribute: %s", hipGetErrorString(e));
     }
     const int64_t blocks = vtm::cdiv(a.items, NT / G);
     hipLaunchKernelGGL((freeu_apply_kernel<T, G>), dim3((unsigned)blocks), dim3(NT), lds, s, (T *)x, a);

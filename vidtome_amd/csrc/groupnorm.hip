@@ -324,14 +324,8 @@ int launch_groupnorm(const void *x, const void *add, const void *gamma, const vo
     if (VTM_GN_THREADS) threads = VTM_GN_THREADS;
     threads = (int)std::min<int64_t>(threads, std::max<int64_t>(64, vtm::cdiv(vtm::cdiv(n, V), 64) * 64));
     if (lds > 64 * 1024) {
-        static std::atomic<bool> attr_set[vtm::MAX_DEVICES];
-        const int dev = vtm::current_device();
-        if (!attr_set[dev].load(std::memory_order_acquire)) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(groupnorm_silu_kernel<T>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, GN_LDS_MAX);
-            if (e != hipSuccess) return vtm::fail(VTM_ELAUNCH, "vtm_groupnorm_silu: LDS attribute: %s", hipGetErrorString(e));
-            attr_set[dev].store(true, std::memory_order_release);
-        }
+        const hipError_t e = vtm::opt_in_lds<groupnorm_silu_kernel<T>, GN_LDS_MAX>();
+        if (e != hipSuccess) return vtm::fail(VTM_ELAUNCH, "vtm_groupnorm_silu: LDS attribute: %s", hipGetErrorString(e));
     }
     hipLaunchKernelGGL(groupnorm_silu_kernel<T>, dim3((unsigned)(B * groups)), dim3(threads), lds, s, (const T *)x, (const T *)add,
                        (const T *)gamma, (const T *)beta, (int)C, (int)HW, (int)groups, eps, act, (int)(data / sizeof(T)), (T *)out);

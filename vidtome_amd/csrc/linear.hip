@@ -25,7 +25,6 @@
 #include "common.h"
 #include "ablate.h"
 
-#include <atomic>
 #include <cstdlib>
 
 namespace {
@@ -502,14 +501,8 @@ template <typename T, bool TRANS>
 int launch_ws(const void *x0, int64_t P0, const void *x1, int64_t P1, int64_t B, const int32_t *rows, int64_t rows_ld,
               const int32_t *rows2, int64_t n, const void *W, const void *bias, int64_t N, void *out, int64_t ldo, int64_t obs,
               hipStream_t s) {
-    static std::atomic<bool> attr_set[vtm::MAX_DEVICES];
-    const int dev = vtm::current_device();
-    if (!attr_set[dev].load(std::memory_order_acquire)) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(linear_rows_ws_kernel<T, TRANS>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, WS_LDS_BYTES);
-        if (e != hipSuccess) return vtm::fail(VTM_ELAUNCH, "vtm_linear_rows: LDS attribute: %s", hipGetErrorString(e));
-        attr_set[dev].store(true, std::memory_order_release);
-    }
+    const hipError_t e = vtm::opt_in_lds<linear_rows_ws_kernel<T, TRANS>, WS_LDS_BYTES>();
+    if (e != hipSuccess) return vtm::fail(VTM_ELAUNCH, "vtm_linear_rows: LDS attribute: %s", hipGetErrorString(e));
     // every wave gets the same number of 32-token blocks, as few as fill the chip's CUs once
     const int64_t RB = vtm::cdiv(n, 32), halves = N / WS_TN;
     int64_t bpw = vtm::cdiv(RB * halves * B, (int64_t)vtm::device_cus() * WS_NW);

@@ -1,6 +1,6 @@
 // vtm_sag_degrade: the degrade step of self-attention guidance for one chunk in one launch -- threshold the per-key attention
 // mass of the mid block (vtm_attention_key_mass), upsample that mask nearest-neighbour to the latent grid, predict the clean
-// sample x0 and the noise eps from x_t and one group's model output (the three formulas of vtm_guided_step), blur x0 with a
+// sample x0 and the noise eps from x_t and one group's model output (step_core.h's predict), blur x0 with a
 // (2 r + 1)^2 Gaussian inside the mask, and re-noise: out = sqrt_alpha * (mask ? blur(x0) : x0) + sqrt_beta * eps.
 //
 // One workgroup owns one (frame, channel) plane, as groupnorm.hip keeps a group: x0 of the plane goes to LDS (plane A), a
@@ -11,9 +11,7 @@
 // reaches exactly the pixels whose blur window holds it.
 // One launch, no workspace, no atomics: a plane's bits depend on that plane's operands alone.
 #include "common.h"
-#include "step_chunk.h"
-
-#include <atomic>
+#include "step_core.h"
 
 namespace {
 
@@ -30,16 +28,16 @@ struct Degrade {
 // torch's "reflect": -1 -> 1, n -> n - 2 (n > r makes one fold enough)
 __device__ __forceinline__ int reflect(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * (n - 1) - i : i); }
 
-// the predicted clean sample and the predicted noise of vtm_guided_step's three prediction types
+// step_core.h's predict(), for the pass that needs the clean sample alone and for the store, which needs the noise alone
 __device__ __forceinline__ float predict_x0(const Degrade &g, float xv, float m) {
-    if (g.pred == VTM_PRED_EPSILON) return (xv - g.sqrt_beta * m) / g.sqrt_alpha;
-    if (g.pred == VTM_PRED_V) return g.sqrt_alpha * xv - g.sqrt_beta * m;
-    return m;
+    float x0, eps;
+    vtm::predict(g.pred, g.sqrt_alpha, g.sqrt_beta, xv, m, x0, eps);
+    return x0;
 }
 __device__ __forceinline__ float predict_eps(const Degrade &g, float xv, float m) {
-    if (g.pred == VTM_PRED_EPSILON) return m;
-    if (g.pred == VTM_PRED_V) return g.sqrt_alpha * m + g.sqrt_beta * xv;
-    return (xv - g.sqrt_alpha * m) / g.sqrt_beta;
+    float x0, eps;
+    vtm::predict(g.pred, g.sqrt_alpha, g.sqrt_beta, xv, m, x0, eps);
+    return eps;
 }
 
 template <typename T>
@@ -85,14 +83,8 @@ int launch_degrade(const void *x, const void *model_out, const float *mass, int6
     const int HW = g.H * g.W;
     const int lds = 2 * HW * (int)sizeof(float);
     if (lds > 64 * 1024) {
-        static std::atomic<bool> attr_set[vtm::MAX_DEVICES];
-        const int dev = vtm::current_device();
-        if (!attr_set[dev].load(std::memory_order_acquire)) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(sag_degrade_kernel<T>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, SAG_LDS_MAX);
-            if (e != hipSuccess) return vtm::fail(VTM_ELAUNCH, "vtm_sag_degrade: LDS attribute: %s", hipGetErrorString(e));
-            attr_set[dev].store(true, std::memory_order_release);
-        }
+        const hipError_t e = vtm::opt_in_lds<sag_degrade_kernel<T>, SAG_LDS_MAX>();
+        if (e != hipSuccess) return vtm::fail(VTM_ELAUNCH, "vtm_sag_degrade: LDS attribute: %s", hipGetErrorString(e));
     }
     // several planes per CU where the LDS allows: 256 threads up to 32 x 32 planes, else 1024
     const int threads = HW <= 64 ? 64 : (HW <= 4096 ? 256 : 1024);
@@ -108,9 +100,7 @@ VTM_EXPORT int vtm_sag_degrade(const void *x, int64_t n_rows, const int32_t *fra
                                int64_t H, int64_t W, int pred_type, float sqrt_alpha, float sqrt_beta, const float *taps,
                                int r, float threshold, void *out, uint8_t *mask_out, vtm_stream_t stream) {
     const char *who = "vtm_sag_degrade";
-    VTM_REQUIRE(dtype == VTM_F32 || dtype == VTM_F16 || dtype == VTM_BF16, "%s: unsupported dtype %d", who, dtype);
-    VTM_REQUIRE(pred_type == VTM_PRED_EPSILON || pred_type == VTM_PRED_V || pred_type == VTM_PRED_SAMPLE,
-                "%s: unknown pred_type %d", who, pred_type);
+    if (const int rc = vtm::check_dtype_pred(who, dtype, pred_type)) return rc;
     VTM_REQUIRE(x && model_out && mass && taps && out, "%s: x, model_out, mass, taps and out are required", who);
     VTM_REQUIRE(r >= 0 && r <= SAG_MAX_R, "%s: r = %d, a blur radius of 0 .. %d is taken", who, r, SAG_MAX_R);
     VTM_REQUIRE(F >= 0 && F <= (1 << 20) && C >= 1 && C <= (1 << 10) && H >= 1 && W >= 1 && n_rows >= (frame_ids ? 1 : F),
@@ -126,11 +116,7 @@ VTM_EXPORT int vtm_sag_degrade(const void *x, int64_t n_rows, const int32_t *fra
                 (long long)w_m, (long long)ld_mass);
     VTM_REQUIRE(sqrt_alpha == sqrt_alpha && sqrt_beta == sqrt_beta && threshold == threshold,
                 "%s: sqrt_alpha, sqrt_beta and threshold must not be NaN", who);
-    {
-        const int64_t es = dtype == VTM_F32 ? 4 : 2, E = C * H * W;
-        const char *x0 = (const char *)x, *x1 = x0 + n_rows * E * es, *o0 = (const char *)out, *o1 = o0 + F * E * es;
-        VTM_REQUIRE(o1 <= x0 || x1 <= o0, "%s: out overlaps x", who);
-    }
+    VTM_REQUIRE(vtm::rows_apart(out, F, x, n_rows, C * H * W, dtype), "%s: out overlaps x", who);
     if (F == 0) return VTM_OK;
     Degrade g{pred_type, r, (int)H, (int)W, (int)h_m, (int)w_m, sqrt_alpha, sqrt_beta, threshold, {}};
     for (int t = 0; t <= 2 * r; ++t) g.taps[t] = taps[t];

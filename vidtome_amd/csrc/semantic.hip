@@ -34,9 +34,8 @@
 // (the library is built with -ffp-contract=off).
 // One launch, no workspace, no global atomics.
 #include "common.h"
-#include "step_chunk.h"
+#include "step_core.h"
 
-#include <atomic>
 #include <cmath>
 
 namespace {
@@ -230,14 +229,8 @@ int launch_semantic(const void *model_out, int64_t F, int64_t C, int P, const Se
                     const int32_t *frame_ids, void *out, uint8_t *mask_out, hipStream_t st) {
     const int lds = (HEAD_WORDS + P) * 4;
     if (lds > 64 * 1024) {
-        static std::atomic<bool> attr_set[vtm::MAX_DEVICES];
-        const int dev = vtm::current_device();
-        if (!attr_set[dev].load(std::memory_order_acquire)) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(semantic_kernel<T>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
-            if (e != hipSuccess) return vtm::fail(VTM_ELAUNCH, "vtm_semantic_guidance: LDS attribute: %s", hipGetErrorString(e));
-            attr_set[dev].store(true, std::memory_order_release);
-        }
+        const hipError_t e = vtm::opt_in_lds<semantic_kernel<T>, LDS_MAX>();
+        if (e != hipSuccess) return vtm::fail(VTM_ELAUNCH, "vtm_semantic_guidance: LDS attribute: %s", hipGetErrorString(e));
     }
     const int threads = P <= 64 ? 64 : (P <= 1024 ? 256 : 1024);
     hipLaunchKernelGGL(semantic_kernel<T>, dim3((unsigned)(F * C)), dim3(threads), lds, st, (const T *)model_out, F, (int)C, P, s,
@@ -294,11 +287,7 @@ VTM_EXPORT int vtm_semantic_guidance(const void *model_out, int dtype, int64_t F
         s.orig[k] = e, s.group[k] = group[e], s.mode[k] = mode[e], s.rank_lo[k] = rank_lo[e];
         s.scale[k] = scale[e], s.w_apply[k] = w_apply[e], s.w_acc[k] = w_acc[e], s.rank_frac[k] = rank_frac[e];
     }
-    {
-        const int64_t es = dtype == VTM_F32 ? 4 : 2, E = C * H * W;
-        const char *m0 = (const char *)model_out, *m1 = m0 + groups * F * E * es, *o0 = (const char *)out, *o1 = o0 + F * E * es;
-        VTM_REQUIRE(o1 <= m0 || m1 <= o0 || F == 0, "%s: out overlaps model_out", who);
-    }
+    VTM_REQUIRE(vtm::rows_apart(out, F, model_out, groups * F, C * H * W, dtype), "%s: out overlaps model_out", who);
     if (F == 0) return VTM_OK;
     hipStream_t st = vtm::as_stream(stream);
     return vtm::with_dtype(dtype, who, [&](auto t) {

@@ -41,6 +41,41 @@ def _host_list(values, name: str) -> list:
         raise ValueError(f"GuidedDDIM: {name} must be a sequence or a tensor") from None
 
 
+def _checked_step(who: str, x, model_out, noise, groups, frame_ids, want, coefficients, on_groups=None, before_gpu=None):
+    """What the ``step`` of both samplers checks, in the order it always did: the names in ``want``; the step's
+    ``coefficients()``; x, model_out and noise as (frames, ...) tensors; the group count (then ``on_groups(groups)``, the
+    sampler's own look at it); one dtype (then ``before_gpu()``); all on the GPU.  Returns (want as a tuple, the coefficients,
+    F, groups, what on_groups gave)."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if any(w not in WANT for w in want) or len(set(want)) != len(want):
+        raise ValueError(f"{who}.step: want names {want}, known: {WANT}")
+    coef = coefficients()
+    tensors = ((x, "x"), (model_out, "model_out")) + (((noise, "noise"),) if noise is not None else ())
+    for t, name in tensors:
+        if not isinstance(t, torch.Tensor) or t.dim() < 2:
+            raise RuntimeError(f"{who}.step: {name} must be a (frames, ...) tensor")
+    F = x.shape[0] if frame_ids is None else len(frame_ids)
+    groups = int(groups)
+    if groups < 1 or model_out.shape[0] != groups * F:
+        raise RuntimeError(f"{who}.step: model_out has {model_out.shape[0]} samples, not {groups} groups x {F} frames")
+    own = on_groups(groups) if on_groups else None
+    if model_out.dtype != x.dtype or (noise is not None and noise.dtype != x.dtype):
+        raise RuntimeError(f"{who}.step: dtype mismatch: x {x.dtype}, model_out {model_out.dtype}"
+                           + (f", noise {noise.dtype}" if noise is not None else ""))
+    if before_gpu:
+        before_gpu()
+    for t, name in tensors:
+        if not t.is_cuda:
+            raise RuntimeError(f"{who}.step: {name} must live on the GPU (vidtome_amd has no CPU path)")
+    return want, coef, F, groups, own
+
+
+def _asked(res, want):
+    """(out, eps, x0) of a step as ``step`` returns it: out, or (out, *asked) in ``want``'s order."""
+    asked = dict(eps=res[1], x0=res[2])
+    return res[0] if not want else (res[0],) + tuple(asked[w] for w in want)
+
+
 class GuidedDDIM:
     """DDIM over ``alphas_cumprod`` (indexed by timestep) along ``timesteps`` (descending, as a Diffusers scheduler holds them
     after ``set_timesteps``).  ``guidance_rescale`` applies where there is guidance (``groups >= 2``); ``eta`` is Diffusers'."""
@@ -107,32 +142,15 @@ class GuidedDDIM:
         a NEW tensor when ``frame_ids`` is None (all of it is written), otherwise x itself, updated IN PLACE in the chunk's rows
         -- a new tensor would hold rows nobody wrote.  Returns out, or (out, *asked) with ``want`` naming "eps" and / or "x0":
         chunk-local (F, C, H, W) tensors of the epsilon and the clean-sample prediction."""
-        want = (want,) if isinstance(want, str) else tuple(want)
-        if any(w not in WANT for w in want) or len(set(want)) != len(want):
-            raise ValueError(f"GuidedDDIM.step: want names {want}, known: {WANT}")
-        _, _, sqrt_alpha, sqrt_beta, c_x0, c_eps, sigma = self.coefficients(i, inversion)
-        tensors = ((x, "x"), (model_out, "model_out")) + (((noise, "noise"),) if noise is not None else ())
-        for t, name in tensors:
-            if not isinstance(t, torch.Tensor) or t.dim() < 2:
-                raise RuntimeError(f"GuidedDDIM.step: {name} must be a (frames, ...) tensor")
-        F = x.shape[0] if frame_ids is None else len(frame_ids)
-        groups = int(groups)
-        if groups < 1 or model_out.shape[0] != groups * F:
-            raise RuntimeError(f"GuidedDDIM.step: model_out has {model_out.shape[0]} samples, not {groups} groups x {F} frames")
-        if model_out.dtype != x.dtype or (noise is not None and noise.dtype != x.dtype):
-            raise RuntimeError(f"GuidedDDIM.step: dtype mismatch: x {x.dtype}, model_out {model_out.dtype}"
-                               + (f", noise {noise.dtype}" if noise is not None else ""))
-        for t, name in tensors:
-            if not t.is_cuda:
-                raise RuntimeError(f"GuidedDDIM.step: {name} must live on the GPU (vidtome_amd has no CPU path)")
+        want, (_, _, sqrt_alpha, sqrt_beta, c_x0, c_eps, sigma), F, groups, _ = _checked_step(
+            "GuidedDDIM", x, model_out, noise, groups, frame_ids, want, lambda: self.coefficients(i, inversion))
         if sigma != 0.0 and noise is None:
             noise = torch.randn((F,) + tuple(model_out.shape[1:]), dtype=x.dtype, device=x.device, generator=generator)
         res = _lib.guided_step(x, model_out, sqrt_alpha, sqrt_beta, c_x0, c_eps, sigma, groups=groups, frame_ids=frame_ids,
                                pred_type=PREDICTION_TYPES[self.prediction_type], guidance=self.guidance_scale,
                                rescale=self.guidance_rescale if groups >= 2 else 0.0, noise=noise, out=out,
                                want_eps="eps" in want, want_x0="x0" in want)
-        asked = dict(eps=res[1], x0=res[2])
-        return res[0] if not want else (res[0],) + tuple(asked[w] for w in want)
+        return _asked(res, want)
 
 
 ALGORITHM_TYPES = ("dpmsolver++", "sde-dpmsolver++")
@@ -311,28 +329,10 @@ class GuidedDPMSolver:
         W, group-major), ``frame_ids``, ``out`` (it may be x; without it a NEW tensor when ``frame_ids`` is None, otherwise x
         itself IN PLACE), ``want`` and the result are ``GuidedDDIM.step``'s.  With "sde-dpmsolver++" and no ``noise`` (F, C, H,
         W), randn of the chunk's shape is drawn from ``generator``."""
-        want = (want,) if isinstance(want, str) else tuple(want)
-        if any(w not in WANT for w in want) or len(set(want)) != len(want):
-            raise ValueError(f"GuidedDPMSolver.step: want names {want}, known: {WANT}")
-        sqrt_alpha, sqrt_beta, c_x, c_x0, c_h1, c_h2, c_noise = self.coefficients(i)
-        tensors = ((x, "x"), (model_out, "model_out")) + (((noise, "noise"),) if noise is not None else ())
-        for t, name in tensors:
-            if not isinstance(t, torch.Tensor) or t.dim() < 2:
-                raise RuntimeError(f"GuidedDPMSolver.step: {name} must be a (frames, ...) tensor")
-        F = x.shape[0] if frame_ids is None else len(frame_ids)
-        groups = int(groups)
-        if groups < 1 or model_out.shape[0] != groups * F:
-            raise RuntimeError(f"GuidedDPMSolver.step: model_out has {model_out.shape[0]} samples, not {groups} groups x {F} "
-                               "frames")
-        weights = self.weights(groups)
-        if model_out.dtype != x.dtype or (noise is not None and noise.dtype != x.dtype):
-            raise RuntimeError(f"GuidedDPMSolver.step: dtype mismatch: x {x.dtype}, model_out {model_out.dtype}"
-                               + (f", noise {noise.dtype}" if noise is not None else ""))
+        want, (sqrt_alpha, sqrt_beta, c_x, c_x0, c_h1, c_h2, c_noise), F, groups, weights = _checked_step(
+            "GuidedDPMSolver", x, model_out, noise, groups, frame_ids, want, lambda: self.coefficients(i), self.weights,
+            lambda: self._in_sequence(int(i)))
         i = int(i)
-        self._in_sequence(i)
-        for t, name in tensors:
-            if not t.is_cuda:
-                raise RuntimeError(f"GuidedDPMSolver.step: {name} must live on the GPU (vidtome_amd has no CPU path)")
         if len(self.history) != self.solver_order - 1 or any(h.shape != x.shape or h.device != x.device for h in self.history):
             if i != 0:
                 raise RuntimeError(f"GuidedDPMSolver.step: the history of step {i} does not fit x {tuple(x.shape)} on {x.device}")
@@ -349,5 +349,4 @@ class GuidedDPMSolver:
                                pred_type=PREDICTION_TYPES[self.prediction_type],
                                rescale=self.guidance_rescale if groups >= 2 else 0.0, noise=noise, out=out,
                                want_eps="eps" in want, want_x0="x0" in want)
-        asked = dict(eps=res[1], x0=res[2])
-        return res[0] if not want else (res[0],) + tuple(asked[w] for w in want)
+        return _asked(res, want)
