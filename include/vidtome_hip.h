@@ -859,6 +859,45 @@ int vtm_solver_step(const void *x, const void *model_out, const void *noise, con
                     float c_h2, float c_noise, void *x_out, float *h_out, void *eps_out, void *x0_out, vtm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * vtm_invert_step -- edit-friendly DDPM inversion (Huberman-Spiegelglas et al.; LEDITS++, Diffusers'
+ * LEditsPPPipelineStableDiffusion.invert; inversion.EditFriendlyInversion): the INVERSE of vtm_solver_step for ONE CHUNK in one
+ * launch.  vtm_solver_step computes x_out = mu + c_noise * noise; here x (the current noise level) and `target` (the next
+ * level, noised independently by vtm_noise_levels) are given and that line is solved for the noise.  Sizes, dtypes, frame_ids,
+ * model_out, w, g_ref, the rescale, the prediction types, the history, the launch shapes and the reduction order are
+ * vtm_solver_step's; the arguments are its own plus target and z_out, minus noise and x_out.
+ *   x          whole-video (n_frames, E) in `dtype`, rows frame_ids[f]: the level this step starts from.  Read only.
+ *   target     whole-video, rows as x's: the level this step lands on.  Read, then CORRECTED IN PLACE.  Required when
+ *              c_noise != 0; neither read nor written when c_noise == 0 (the step that lands on alphas_cumprod = 1).
+ *   z_out      whole-video, rows as x's, in `dtype`: the step's noise map.  Required.  x, target and z_out are three buffers.
+ *   h1, h2, h_out, eps_out, x0_out  as in vtm_solver_step.
+ * Per frame and element, in fp32, with the operations of vtm_solver_step in the same order:
+ *     m, x0, eps  as in vtm_solver_step
+ *     mu      = c_x * x + c_x0 * x0 + c_h1 * h1 + c_h2 * h2            (a term whose coefficient is 0 is absent)
+ *     z_out   = (target - mu) / c_noise                                  rounded ONCE to `dtype`;   +0 when c_noise == 0
+ *     target  = mu + c_noise * fp32(z_out)                               rounded once
+ *     h_out = x0 (fp32, not rounded) ;   eps_out = eps ;   x0_out = x0
+ * The last line is vtm_solver_step's own x_out with noise = z_out, operation for operation (one shared helper, no contraction
+ * into fma): vtm_solver_step on the same x, model_out and history with noise = z_out returns the corrected target and the same
+ * h_out BIT FOR BIT.  Any E >= 1, F <= 2^20; F == 0 is VTM_OK.  One launch, no workspace, no atomics.  On a bad argument
+ * (VTM_EINVAL) nothing is launched.
+ * ---------------------------------------------------------------------------------------------- */
+int vtm_invert_step(const void *x, const void *model_out, const float *h1, const float *h2, int dtype, int64_t F, int64_t E,
+                    int64_t groups, const float *w, int64_t g_ref, const int32_t *frame_ids, int pred_type, float rescale,
+                    float sqrt_alpha, float sqrt_beta, float c_x, float c_x0, float c_h1, float c_h2, float c_noise,
+                    void *target, void *z_out, float *h_out, void *eps_out, void *x0_out, vtm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * vtm_noise_levels -- the forward noising of a video to ALL levels of a schedule in one launch, in place on independent
+ * N(0, 1) draws:   levels[k, p] = sqrt_alpha[k] * x0[p] + sqrt_beta[k] * levels[k, p]     for k < n, p < P.
+ *   x0      (P) contiguous in `dtype`: the clean video.        levels  (n, P) contiguous in `dtype`, not x0.
+ *   coef    DEVICE fp32 (n, 2): (sqrt_alpha[k], sqrt_beta[k]).
+ * In fp32, every stored value rounded once.  16-byte accesses when P is a multiple of 16 bytes of `dtype` and both pointers
+ * are 16-byte aligned, element accesses otherwise; which of the two changes no bit.  n <= 2^20, P >= 1; n == 0 is VTM_OK.
+ * On a bad argument (VTM_EINVAL) nothing is launched.
+ * ---------------------------------------------------------------------------------------------- */
+int vtm_noise_levels(const void *x0, void *levels, const float *coef, int dtype, int64_t n, int64_t P, vtm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * vtm_semantic_guidance -- semantic guidance (SEGA, Brack et al.; Diffusers' SemanticStableDiffusionPipeline, and with
  * `regions` the masked form of LEditsPPPipelineStableDiffusion) for ONE CHUNK in one launch: the combined model output that
  * vtm_guided_step / vtm_solver_step then take as a single group.  Every edit concept has its own group of the UNet output;

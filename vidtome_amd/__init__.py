@@ -10,6 +10,7 @@ from .maps import register_attention_maps, unregister_attention_maps
 from .p2p import CrossEdit, register_cross_attention_control, unregister_cross_attention_control
 from .blend import LocalBlend, register_local_blend, unregister_local_blend
 from .sampler import GuidedDDIM, GuidedDPMSolver
+from .inversion import EditFriendlyInversion
 from .pag import register_perturbed_attention, remove_perturbed_attention
 from .sag import SelfAttentionGuidance, register_self_attention_guidance, unregister_self_attention_guidance
 from .freeu import register_freeu, unregister_freeu
@@ -21,4 +22,4 @@ __all__ = ["merge", "patch", "apply_patch", "remove_patch", "update_patch", "col
            "LocalBlend", "register_local_blend", "unregister_local_blend",
            "GuidedDDIM", "GuidedDPMSolver", "register_perturbed_attention", "remove_perturbed_attention",
            "SelfAttentionGuidance", "register_self_attention_guidance", "unregister_self_attention_guidance",
-           "register_freeu", "unregister_freeu", "EditConcept", "SemanticGuidance"]
+           "register_freeu", "unregister_freeu", "EditConcept", "SemanticGuidance", "EditFriendlyInversion"]

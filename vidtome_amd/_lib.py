@@ -129,6 +129,9 @@ _SIGNATURES = {
                          _vp, _vp, _vp, _vp], _int),
     "vtm_solver_step": ([_vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, ctypes.POINTER(_f32), _i64, _vp, _int, _f32, _f32, _f32,
                          _f32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp], _int),
+    "vtm_invert_step": ([_vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, ctypes.POINTER(_f32), _i64, _vp, _int, _f32, _f32, _f32, _f32,
+                         _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp], _int),
+    "vtm_noise_levels": ([_vp, _vp, _vp, _int, _i64, _i64, _vp], _int),
     "vtm_semantic_guidance": ([_vp, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _i64, ctypes.POINTER(ctypes.c_int32),
                                ctypes.POINTER(_f32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double),
                                ctypes.POINTER(_f32), ctypes.POINTER(_f32), ctypes.POINTER(ctypes.c_int32), _vp, _vp, _i64, _vp,
@@ -859,6 +862,34 @@ SOLVER_STEP_THREADS = 1024                      # csrc/solver_step.hip: threads 
 SOLVER_MAX_GROUPS = 8                           # include/vidtome_hip.h VTM_SOLVER_MAX_GROUPS
 
 
+def _solver_checks(who: str, x, weights, pred_type, g_ref, rescale: float, fp32_like_x):
+    """What solver_step and invert_step check about the weights, the rescale reference and their whole-video fp32 operands:
+    -> (weights, groups, pred_type, g_ref, check_groups, check_rescale, check_history), the three checks as ``_step_operands``
+    calls them.  ``fp32_like_x``: (tensor or None, name, the coefficient that needs it) triples."""
+    weights = [float(v) for v in weights]
+    groups, pred_type = len(weights), int(pred_type)
+    g_ref = groups - 1 if g_ref is None else int(g_ref)
+
+    def check_groups():
+        if not 1 <= groups <= SOLVER_MAX_GROUPS or not all(math.isfinite(v) for v in weights):
+            raise RuntimeError(f"{who}: {groups} weights {weights}: 1 .. {SOLVER_MAX_GROUPS} finite numbers, one per group")
+
+    def check_rescale(E):
+        if rescale > 0.0 and (not 0 <= g_ref < groups or _f32_round(weights[g_ref]) == 0.0 or E < 2):
+            raise RuntimeError(f"{who}: rescale > 0 needs g_ref = {g_ref} inside [0, {groups}) with a non-zero weight, and "
+                               "frames of at least 2 elements")
+
+    def check_history():
+        for t, name, c in fp32_like_x:
+            if t is None and c != 0.0:
+                raise RuntimeError(f"{who}: c_{name} != 0 needs {name}")
+            if t is not None and (not isinstance(t, torch.Tensor) or t.shape != x.shape or t.dtype != torch.float32
+                                  or t.device != x.device):
+                raise RuntimeError(f"{who}: {name} must be an fp32 tensor shaped like x, on its device")
+
+    return weights, groups, pred_type, g_ref, check_groups, check_rescale, check_history
+
+
 @_on_device
 def solver_step(x: torch.Tensor, model_out: torch.Tensor, weights, sqrt_alpha: float, sqrt_beta: float, c_x: float, c_x0: float,
                 c_h1: float = 0.0, c_h2: float = 0.0, c_noise: float = 0.0, *, h1: Optional[torch.Tensor] = None,
@@ -872,27 +903,9 @@ def solver_step(x: torch.Tensor, model_out: torch.Tensor, weights, sqrt_alpha: f
     x with the clean-sample predictions of the two previous steps, needed where ``c_h1`` / ``c_h2`` is not 0; ``h_out``: where
     this step's goes (it may be h1 or h2)."""
     who = "solver_step"
-    weights = [float(v) for v in weights]
-    groups, pred_type = len(weights), int(pred_type)
-    g_ref = groups - 1 if g_ref is None else int(g_ref)
     c_x, c_x0, c_h1, c_h2, c_noise, rescale = (float(v) for v in (c_x, c_x0, c_h1, c_h2, c_noise, rescale))
-
-    def check_groups():
-        if not 1 <= groups <= SOLVER_MAX_GROUPS or not all(math.isfinite(v) for v in weights):
-            raise RuntimeError(f"{who}: {groups} weights {weights}: 1 .. {SOLVER_MAX_GROUPS} finite numbers, one per group")
-
-    def check_rescale(E):
-        if rescale > 0.0 and (not 0 <= g_ref < groups or _f32_round(weights[g_ref]) == 0.0 or E < 2):
-            raise RuntimeError(f"{who}: rescale > 0 needs g_ref = {g_ref} inside [0, {groups}) with a non-zero weight, and "
-                               "frames of at least 2 elements")
-
-    def check_history():
-        for t, name, c in ((h1, "h1", c_h1), (h2, "h2", c_h2), (h_out, "h_out", 0.0)):
-            if t is None and c != 0.0:
-                raise RuntimeError(f"{who}: c_{name} != 0 needs {name}")
-            if t is not None and (not isinstance(t, torch.Tensor) or t.shape != x.shape or t.dtype != torch.float32
-                                  or t.device != x.device):
-                raise RuntimeError(f"{who}: {name} must be an fp32 tensor shaped like x, on its device")
+    weights, groups, pred_type, g_ref, check_groups, check_rescale, check_history = _solver_checks(
+        who, x, weights, pred_type, g_ref, rescale, ((h1, "h1", c_h1), (h2, "h2", c_h2), (h_out, "h_out", 0.0)))
 
     F, E, ids, out, eps, x0, skip = _step_operands(
         who, x, model_out, groups, pred_type, rescale, frame_ids, noise, "c_noise" if c_noise != 0.0 else None, out,
@@ -910,6 +923,76 @@ def solver_step(x: torch.Tensor, model_out: torch.Tensor, weights, sqrt_alpha: f
                                  float(sqrt_beta), c_x, c_x0, c_h1, c_h2, c_noise, out.data_ptr() + skip_x if want_x else None,
                                  hist(h_out), _ptr(eps), _ptr(x0), _stream()), "vtm_solver_step")
     return (out if want_x else None), eps, x0
+
+
+@_on_device
+def invert_step(x: torch.Tensor, model_out: torch.Tensor, weights, sqrt_alpha: float, sqrt_beta: float, c_x: float, c_x0: float,
+                c_h1: float = 0.0, c_h2: float = 0.0, c_noise: float = 0.0, *, target: Optional[torch.Tensor] = None,
+                z_out: Optional[torch.Tensor] = None, h1: Optional[torch.Tensor] = None, h2: Optional[torch.Tensor] = None,
+                h_out: Optional[torch.Tensor] = None, g_ref: Optional[int] = None, frame_ids=None,
+                pred_type: int = PRED_EPSILON, rescale: float = 0.0, want_eps: bool = False, want_x0: bool = False):
+    """One chunk's step of edit-friendly inversion (vtm_invert_step, include/vidtome_hip.h), the inverse of ``solver_step``:
+    ``x`` the current level and ``target`` the next one, whole-video tensors of one shape and dtype; ``z_out`` like them
+    receives the step's noise in the chunk's rows, and ``target`` is corrected IN PLACE there, to exactly what ``solver_step``
+    computes from the same operands with ``noise = z_out[rows]``.  With ``c_noise == 0`` z_out's rows become +0 and target
+    (it may be None) is left alone.  ``model_out``, ``weights``, ``g_ref``, ``h1`` / ``h2`` / ``h_out``, ``frame_ids``,
+    ``pred_type`` and ``rescale`` as in ``solver_step``.  Returns (eps or None, x0 or None), chunk-local."""
+    who = "invert_step"
+    c_x, c_x0, c_h1, c_h2, c_noise, rescale = (float(v) for v in (c_x, c_x0, c_h1, c_h2, c_noise, rescale))
+    weights, groups, pred_type, g_ref, check_groups, check_rescale, check_history = _solver_checks(
+        who, x, weights, pred_type, g_ref, rescale, ((h1, "h1", c_h1), (h2, "h2", c_h2), (h_out, "h_out", 0.0)))
+
+    def check_more():
+        check_history()
+        if z_out is None or (target is None and c_noise != 0.0):
+            raise RuntimeError(f"{who}: z_out is required, and c_noise != 0 needs target")
+        for t, name in ((target, "target"), (z_out, "z_out")):
+            if t is not None and (not isinstance(t, torch.Tensor) or t.shape != x.shape or t.dtype != x.dtype
+                                  or t.device != x.device):
+                raise RuntimeError(f"{who}: {name} must be a tensor like x, on its device")
+        if len({t.data_ptr() for t in (x, target, z_out) if t is not None}) != 2 + (target is not None):
+            raise RuntimeError(f"{who}: x, target and z_out must be three buffers")
+
+    F, E, ids, _, eps, x0, skip = _step_operands(
+        who, x, model_out, groups, pred_type, rescale, frame_ids, None, None, None, (False, want_eps, want_x0), True,
+        check_groups, check_rescale, check_more, ((h1, "h1"), (h2, "h2"), (h_out, "h_out"), (target, "target"), (z_out, "z_out")))
+    if F == 0:
+        return eps, x0
+
+    def row(t, size, used=True):
+        return t.data_ptr() + skip * size if (t is not None and used) else None
+    el = x.element_size()
+    _check(lib().vtm_invert_step(row(x, el), model_out.data_ptr(), row(h1, 4, c_h1 != 0.0), row(h2, 4, c_h2 != 0.0),
+                                 dtype_code(x), F, E, groups, (_f32 * groups)(*weights), g_ref, _ptr(ids), pred_type, rescale,
+                                 float(sqrt_alpha), float(sqrt_beta), c_x, c_x0, c_h1, c_h2, c_noise,
+                                 row(target, el, c_noise != 0.0), row(z_out, el), row(h_out, 4), _ptr(eps), _ptr(x0), _stream()),
+           "vtm_invert_step")
+    return eps, x0
+
+
+@_on_device
+def noise_levels(x0: torch.Tensor, levels: torch.Tensor, coef: torch.Tensor) -> torch.Tensor:
+    """levels[k] = coef[k, 0] * x0 + coef[k, 1] * levels[k] in place, all levels in one launch (vtm_noise_levels): ``levels``
+    (n, *x0.shape) holds independent N(0, 1) draws in x0's dtype, ``coef`` is a device fp32 (n, 2) table of (sqrt_alpha,
+    sqrt_beta).  Returns levels."""
+    who = "noise_levels"
+    for t, name in ((x0, "x0"), (levels, "levels"), (coef, "coef")):
+        if not isinstance(t, torch.Tensor):
+            raise RuntimeError(f"{who}: {name} must be a tensor")
+    if x0.dtype not in _DT or levels.dtype != x0.dtype:
+        raise RuntimeError(f"{who}: x0 and levels must share one of fp16 / bf16 / fp32, not {x0.dtype} and {levels.dtype}")
+    if levels.dim() != x0.dim() + 1 or tuple(levels.shape[1:]) != tuple(x0.shape) or x0.numel() < 1:
+        raise RuntimeError(f"{who}: levels {tuple(levels.shape)} is not (n, *x0.shape) for x0 {tuple(x0.shape)}")
+    n = levels.shape[0]
+    if coef.dtype != torch.float32 or tuple(coef.shape) != (n, 2):
+        raise RuntimeError(f"{who}: coef must be an fp32 ({n}, 2) tensor of (sqrt_alpha, sqrt_beta)")
+    _req(x0, "x0"), _req(levels, "levels"), _req(coef, "coef")
+    if levels.device != x0.device or coef.device != x0.device:
+        raise RuntimeError(f"{who}: levels lives on {levels.device}, coef on {coef.device}, x0 on {x0.device}")
+    if n:
+        _check(lib().vtm_noise_levels(x0.data_ptr(), levels.data_ptr(), coef.data_ptr(), dtype_code(x0), n, x0.numel(),
+                                      _stream()), "vtm_noise_levels")
+    return levels
 
 
 @_on_device

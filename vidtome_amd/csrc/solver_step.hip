@@ -6,56 +6,23 @@
 // this step's x0 goes to h_out.  Everything is fp32 and every stored value is rounded once.
 //
 // The cut into 16-byte chunks of the model dtype, the two launch shapes and the reduction order are step_core.h's; this file
-// says what m is (combine) and what the update adds up (Solver::update).  A chunk of the fp32 history is 16 or 32 bytes (4 / 8
+// says what the update adds up (Solver::update); what m is (combine) and the deterministic part of the sum (solver_sum) are
+// solver_core.h's, shared with the inverse step (invert_step.hip).  A chunk of the fp32 history is 16 or 32 bytes (4 / 8
 // elements): one or two 16-byte accesses.
 #include "common.h"
-#include "step_core.h"
+#include "solver_core.h"
 
 namespace {
 
+using vtm::combine;
 using vtm::load_chunk;
+using vtm::load_history;
+using vtm::Solve;
 using vtm::store_chunk;
+using vtm::store_history;
 
 constexpr int SS_THREADS = 1024;              // rescale: threads of a frame's workgroup (_lib.SOLVER_STEP_THREADS)
 static_assert(SS_THREADS == vtm::STEP_THREADS, "the per-frame launch is step_core.h's");
-constexpr int MAX_GROUPS = VTM_SOLVER_MAX_GROUPS;
-
-struct Solve {
-    int pred, g_ref, terms;                   // terms: the groups of non-zero weight,
-    int g[MAX_GROUPS];                        // ... ascending,
-    float w[MAX_GROUPS];                      // ... and their weights
-    float rescale, sqrt_alpha, sqrt_beta, c_x, c_x0, c_h1, c_h2, c_noise;
-};
-
-// the chunk's n <= N fp32 history elements: N / 4 chunks of fp32
-template <int N, bool VEC>
-__device__ __forceinline__ void load_history(const float *p, int n, float *v) {
-#pragma unroll
-    for (int q = 0; q < N; q += 4) load_chunk<float, VEC>(p + q, n - q, v + q);
-}
-
-template <int N, bool VEC>
-__device__ __forceinline__ void store_history(float *p, int n, const float *v) {
-#pragma unroll
-    for (int q = 0; q < N; q += 4) store_chunk<float, VEC>(p + q, n - q, v + q);
-}
-
-// m = sum of w[g] * model_out[g] over the groups of non-zero weight, ascending, from 0: the same operations wherever m is
-// needed, so every pass sees the same m.  mo points at the chunk in group 0; group g lies g * stride elements further.
-template <typename T, bool VEC>
-__device__ __forceinline__ void combine(const Solve &s, const T *mo, int64_t stride, int n, float *m) {
-    constexpr int N = 16 / sizeof(T);
-    float v[N];
-#pragma unroll
-    for (int k = 0; k < N; ++k) m[k] = 0.0f;
-#pragma unroll 1
-    for (int t = 0; t < s.terms; ++t) {
-        const float w = s.w[t];
-        load_chunk<T, VEC>(mo + s.g[t] * stride, n, v);
-#pragma unroll
-        for (int k = 0; k < N; ++k) m[k] = m[k] + w * v[k];
-    }
-}
 
 // step_core.h's policy: the launch's operands.  Group g of model_out lies g * stride elements behind group 0; all but
 // model_out and x may be null.  x_out may be x and h_out may be h1 or h2: a chunk is read before it is written, by the same
@@ -95,11 +62,7 @@ struct Solver {
             float mv = mk[k];
             if constexpr (RESCALE) mv = mv * factor;
             vtm::predict(s.pred, s.sqrt_alpha, s.sqrt_beta, xv[k], mv, x0[k], ep[k]);
-            float acc = 0.0f;
-            if (s.c_x != 0.0f) acc = acc + s.c_x * xv[k];
-            if (s.c_x0 != 0.0f) acc = acc + s.c_x0 * x0[k];
-            if (h1) acc = acc + s.c_h1 * p1[k];
-            if (h2) acc = acc + s.c_h2 * p2[k];
+            float acc = vtm::solver_sum(s, xv[k], x0[k], h1 != nullptr, p1[k], h2 != nullptr, p2[k]);
             if (noise) acc = acc + s.c_noise * nz[k];
             xn[k] = acc;
         }
@@ -140,27 +103,14 @@ VTM_EXPORT int vtm_solver_step(const void *x, const void *model_out, const void 
                                void *eps_out, void *x0_out, vtm_stream_t stream) {
     const char *who = "vtm_solver_step";
     if (const int rc = vtm::check_dtype_pred(who, dtype, pred_type)) return rc;
-    VTM_REQUIRE(x && model_out && w, "%s: x, model_out and w are required", who);
-    // (F bounds the grid of the per-frame launch: 1024 F threads must stay below 2^32)
-    VTM_REQUIRE(F >= 0 && F <= (1 << 20) && E >= 1 && groups >= 1 && groups <= MAX_GROUPS,
-                "%s: bad sizes F = %lld, E = %lld, groups = %lld (1 .. %d)", who, (long long)F, (long long)E, (long long)groups,
-                MAX_GROUPS);
-    VTM_REQUIRE(!(rescale < 0.0f) && rescale == rescale, "%s: rescale = %g is negative or NaN", who, (double)rescale);
-    VTM_REQUIRE(!(rescale > 0.0f) || (g_ref >= 0 && g_ref < groups && w[g_ref] != 0.0f && E >= 2),
-                "%s: rescale > 0 needs g_ref = %lld inside [0, %lld) with a non-zero weight, and E >= 2", who, (long long)g_ref,
-                (long long)groups);
+    if (const int rc = vtm::check_solver_sizes(who, x, model_out, w, F, E, groups, rescale, g_ref)) return rc;
     VTM_REQUIRE(c_noise == 0.0f ? true : noise != nullptr, "%s: c_noise != 0 needs noise", who);
     VTM_REQUIRE(c_h1 == 0.0f ? true : h1 != nullptr, "%s: c_h1 != 0 needs h1", who);
     VTM_REQUIRE(c_h2 == 0.0f ? true : h2 != nullptr, "%s: c_h2 != 0 needs h2", who);
     VTM_REQUIRE(x_out || h_out || eps_out || x0_out, "%s: no output", who);
     if (F == 0) return VTM_OK;
 
-    Solve s{pred_type, rescale > 0.0f ? (int)g_ref : 0, 0, {}, {}, rescale, sqrt_alpha, sqrt_beta, c_x, c_x0, c_h1, c_h2, c_noise};
-    for (int g = 0; g < groups; ++g)
-        if (w[g] != 0.0f) {                                         // a group of weight 0 is never read
-            s.g[s.terms] = g;
-            s.w[s.terms++] = w[g];
-        }
+    const Solve s = vtm::make_solve(pred_type, rescale, g_ref, groups, w, sqrt_alpha, sqrt_beta, c_x, c_x0, c_h1, c_h2, c_noise);
     // a coefficient of 0: the term is absent, its operand is not read
     const void *noise_used = c_noise != 0.0f ? noise : nullptr;
     const float *h1_used = c_h1 != 0.0f ? h1 : nullptr, *h2_used = c_h2 != 0.0f ? h2 : nullptr;
