@@ -686,14 +686,86 @@ def _attention_out(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, Mq: int, 
     return (torch.zeros if Mqp != Mq else torch.empty)((B, Mqp, C), dtype=q.dtype, device=q.device)
 
 
+def _out_like_q(who: str, out: torch.Tensor, q: torch.Tensor) -> None:
+    if out.shape != q.shape or out.dtype != q.dtype or out.device != q.device or not out.is_contiguous():
+        raise RuntimeError(f"{who}: out must be a contiguous tensor of q's shape, dtype and device")
+
+
+_MODULE_PATH = " (fp32 models keep the module path)"
+
+
+def _half_operands(who: str, q, k, vt=None, hint: str = "") -> None:
+    """The side calls take fp16 / bf16 operands of one dtype (anything else, a non-tensor included, is refused here)."""
+    ops = (q, k) if vt is None else (q, k, vt)
+    if not all(isinstance(t, torch.Tensor) for t in ops) or q.dtype not in (torch.float16, torch.bfloat16) \
+            or any(t.dtype != q.dtype for t in ops):
+        raise RuntimeError(f"{who}: {'q and k' if vt is None else 'q, k and vt'} must share one of fp16 / bf16{hint}")
+
+
+def _kv_shapes(who: str, q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor):
+    """(B, Mqp, C, Mkp) of q (B, Mqp, C), k (B, Mkp, C) and vt (B, C, ldvt)."""
+    B, Mqp, C = q.shape
+    if k.shape[0] != B or vt.shape[0] != B or k.shape[2] != C or vt.shape[1] != C:
+        raise RuntimeError(f"{who}: k must be (B, Mkp, C) and vt (B, C, ldvt)")
+    return B, Mqp, C, k.shape[1]
+
+
+MAX_KEY_SETS = 8
+
+
+def _key_sets(who: str, sets):
+    """``sets``, a sequence of 1 .. MAX_KEY_SETS (start, length, weight), as a list of (int, int, float) and as the
+    (starts, lens, weights) arrays the exports take."""
+    sets = [(int(s), int(n), float(w)) for s, n, w in sets]
+    n = len(sets)
+    if not 1 <= n <= MAX_KEY_SETS:
+        raise RuntimeError(f"{who}: 1 .. {MAX_KEY_SETS} key sets, got {n}")
+    return sets, ((_i64 * n)(*[s for s, _, _ in sets]), (_i64 * n)(*[m for _, m, _ in sets]),
+                  (_f32 * n)(*[w for _, _, w in sets]))
+
+
+def _key_rows(who: str, t, must_be: str, q: torch.Tensor, B: int, Mk: int, optional: bool = False):
+    """(pointer, row length, batch stride) of fp32 per-key rows on q's device, THE statement of how they are handed over:
+    (B, >= Mk) with a row per sample or (1, >= Mk) with one row for all, unit stride along the row; a batch stride of 0 is an
+    expanded row.  ``must_be``: how the message opens ("bias must be").  ``optional``: None gives (None, 0, 0)."""
+    if t is None and optional:
+        return None, 0, 0
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != q.device or t.dim() != 2 \
+            or t.shape[0] not in (1, B) or t.shape[1] < Mk or t.stride(1) != 1 \
+            or (t.shape[0] == B and B > 1 and 0 < t.stride(0) < t.shape[1]):
+        raise RuntimeError(f"{who}: {must_be} fp32 on q's device, (B, >= Mk) or (1, >= Mk), contiguous along its last axis")
+    return t.data_ptr(), t.shape[1], (t.stride(0) if t.shape[0] == B and B > 1 else 0)
+
+
+def _qk_views(who: str, q, k, heads: int, Mq: int, Mk: int, dense_single: bool):
+    """The q (B, Mqp, C) / k (B, Mkp, C) views of the map calls: fp16 / bf16 on one GPU, C a multiple of heads, Mq / Mk
+    inside, 16-byte aligned rows, the samples a dense stride apart -- which a single sample need not show unless
+    ``dense_single``.  Returns (B, Mqp, C, Mkp, heads, Mq, Mk), the last three as ints."""
+    _half_operands(who, q, k)
+    if q.dim() != 3 or k.dim() != 3 or not q.is_cuda or k.device != q.device:
+        raise RuntimeError(f"{who}: q must be (B, Mqp, C) and k (B, Mkp, C) on one GPU")
+    B, Mqp, C = q.shape
+    Mkp = k.shape[1]
+    heads, Mq, Mk = int(heads), int(Mq), int(Mk)
+    if k.shape[0] != B or k.shape[2] != C or heads < 1 or C % heads:
+        raise RuntimeError(f"{who}: k must be (B, Mkp, C) with C a multiple of heads")
+    if not (1 <= Mq <= Mqp and 1 <= Mk <= Mkp):
+        raise RuntimeError(f"{who}: Mq / Mk must lie inside q / k")
+    for t, name, rows in ((q, "q", Mqp), (k, "k", Mkp)):
+        if t.stride(2) != 1 or t.stride(1) % 8 or t.stride(1) < C or t.data_ptr() % 16 \
+                or ((dense_single or B > 1) and t.stride(0) != rows * t.stride(1)):
+            raise RuntimeError(f"{who}: {name} must be 16-byte aligned rows (stride a multiple of 8), dense over the samples")
+    return B, Mqp, C, Mkp, heads, Mq, Mk
+
+
 @_on_device
 def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, M: int, scale: float,
               share_groups: int = 1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """q, k: (B, Mp, C) views with arbitrary last-dim-contiguous row stride; vt: (B, C, ldvt) = v transposed.
     Returns out (B, Mp, C) (rows >= M untouched/zero).  ``out``: a dense (B, Mp, C) tensor of q's dtype to write into (a
     sample range of a larger buffer) instead of a new one; its rows >= M are left alone."""
-    if out is not None and (out.shape != q.shape or out.dtype != q.dtype or out.device != q.device or not out.is_contiguous()):
-        raise RuntimeError("attention: out must be a contiguous tensor of q's shape, dtype and device")
+    if out is not None:
+        _out_like_q("attention", out, q)
     B, Mp, C = q.shape
     d = C // heads
     new = _attention_out(q, k, vt, M, Mp, alloc=out is None)
@@ -1024,8 +1096,8 @@ def attention_kv(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int,
     ``share_groups`` > 1: the probabilities of the first B / share_groups samples serve every group (pnp_utils.py:57-67);
     with ``q_count`` the caller vouches that every sample of a group has the same live rows (align_batch) -- no key folding.
     ``out``: a dense (B, Mqp, C) tensor of q's dtype to write into (a sample range of a larger buffer) instead of a new one."""
-    if out is not None and (out.shape != q.shape or out.dtype != q.dtype or out.device != q.device or not out.is_contiguous()):
-        raise RuntimeError("attention_kv: out must be a contiguous tensor of q's shape, dtype and device")
+    if out is not None:
+        _out_like_q("attention_kv", out, q)
     if share_groups != 1 and k_fold is not None:
         raise RuntimeError("attention_kv: shared probabilities do not go with folded keys")
     if k_fold is not None and q.dtype == torch.float32:
@@ -1070,9 +1142,6 @@ def attention_kv(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int,
     return out
 
 
-MAX_KEY_SETS = 8
-
-
 @_on_device
 def attention_kv_range(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, Mq: int, start: int, Mk: int,
                        scale: float) -> torch.Tensor:
@@ -1105,27 +1174,17 @@ def attention_kv_sets(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads:
     (start, length, weight): set s is the key range [start, start + length) of k / vt, start a multiple of 8; the result
     is sum_s weight_s * softmax(q K_s^T * scale) V_s, (B, Mqp, C).  fp16 / bf16 operands only.  One set of weight 1 IS the
     plain core and goes to attention_kv (the same launch and bits as a block without the extra sets)."""
-    sets = [(int(s), int(n), float(w)) for s, n, w in sets]
-    if not 1 <= len(sets) <= MAX_KEY_SETS:
-        raise RuntimeError(f"attention_kv_sets: 1 .. {MAX_KEY_SETS} key sets, got {len(sets)}")
-    if q.dtype not in (torch.float16, torch.bfloat16) or k.dtype != q.dtype or vt.dtype != q.dtype:
-        raise RuntimeError("attention_kv_sets: q, k and vt must share one of fp16 / bf16 (fp32 models keep the module path)")
-    B, Mqp, C = q.shape
-    Mkp = k.shape[1]
-    d = C // heads
-    _attention_out(q, k, vt, Mq, Mkp, alloc=False)
-    if k.shape[0] != B or vt.shape[0] != B or k.shape[2] != C or vt.shape[1] != C:
-        raise RuntimeError("attention_kv_sets: k must be (B, Mkp, C) and vt (B, C, ldvt)")
+    who = "attention_kv_sets"
+    sets, arrays = _key_sets(who, sets)
+    _half_operands(who, q, k, vt, _MODULE_PATH)
+    _attention_out(q, k, vt, Mq, k.shape[1], alloc=False)
+    B, Mqp, C, Mkp = _kv_shapes(who, q, k, vt)
     if len(sets) == 1 and sets[0][2] == 1.0:
         return attention_kv_range(q, k, vt, heads, Mq, sets[0][0], sets[0][1], scale)
     out = _attention_out(q, k, vt, Mq, Mkp)
-    n = len(sets)
-    starts = (_i64 * n)(*[s for s, _, _ in sets])
-    lens = (_i64 * n)(*[m for _, m, _ in sets])
-    weights = (_f32 * n)(*[w for _, _, w in sets])
     _check(lib().vtm_attention_kv_sets(q.data_ptr(), q.stride(1), k.data_ptr(), k.stride(1), vt.data_ptr(), vt.stride(1),
-                                       out.data_ptr(), C, dtype_code(q), B, heads, Mq, Mqp, Mkp, d, float(scale), n, starts,
-                                       lens, weights, _stream()), "vtm_attention_kv_sets")
+                                       out.data_ptr(), C, dtype_code(q), B, heads, Mq, Mqp, Mkp, C // heads, float(scale),
+                                       len(sets), *arrays, _stream()), "vtm_attention_kv_sets")
     return out
 
 
@@ -1137,36 +1196,28 @@ def attention_kv_sets_masked(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor,
     Diffusers' ``ip_adapter_masks`` give -- or (B, R, ld) with a table per sample; ld >= Mq, the weights are shared by the
     heads.  The result is sum_s weight_s * mask[set_mask[s]][query] * softmax(q K_s^T * scale) V_s, the masked term weighted
     in fp32.  With every ``set_mask[s] == -1`` this IS attention_kv_sets(q, k, vt, heads, Mq, sets, scale)."""
-    sets = [(int(s), int(n), float(w)) for s, n, w in sets]
+    who = "attention_kv_sets_masked"
+    sets = list(sets)
     rows = [int(r) for r in set_mask]
     if len(rows) != len(sets):
-        raise RuntimeError(f"attention_kv_sets_masked: {len(sets)} sets but {len(rows)} mask rows")
+        raise RuntimeError(f"{who}: {len(sets)} sets but {len(rows)} mask rows")
     if all(r == -1 for r in rows):
         return attention_kv_sets(q, k, vt, heads, Mq, sets, scale)
-    if not 1 <= len(sets) <= MAX_KEY_SETS:
-        raise RuntimeError(f"attention_kv_sets_masked: 1 .. {MAX_KEY_SETS} key sets, got {len(sets)}")
-    if q.dtype not in (torch.float16, torch.bfloat16) or k.dtype != q.dtype or vt.dtype != q.dtype:
-        raise RuntimeError("attention_kv_sets_masked: q, k and vt must share one of fp16 / bf16")
-    B, Mqp, C = q.shape
-    Mkp = k.shape[1]
-    d = C // heads
-    if k.shape[0] != B or vt.shape[0] != B or k.shape[2] != C or vt.shape[1] != C:
-        raise RuntimeError("attention_kv_sets_masked: k must be (B, Mkp, C) and vt (B, C, ldvt)")
+    sets, arrays = _key_sets(who, sets)
+    _half_operands(who, q, k, vt)
+    B, Mqp, C, Mkp = _kv_shapes(who, q, k, vt)
     if not isinstance(mask, torch.Tensor) or mask.dtype != torch.float32 or mask.device != q.device \
             or mask.dim() not in (2, 3) or not mask.is_contiguous() or mask.shape[-1] < Mq \
             or (mask.dim() == 3 and mask.shape[0] != B):
-        raise RuntimeError("attention_kv_sets_masked: mask must be contiguous fp32 on q's device, (R, >= Mq) or (B, R, >= Mq)")
+        raise RuntimeError(f"{who}: mask must be contiguous fp32 on q's device, (R, >= Mq) or (B, R, >= Mq)")
     R, ld = mask.shape[-2], mask.shape[-1]
     if not all(-1 <= r < R for r in rows):
-        raise RuntimeError(f"attention_kv_sets_masked: mask rows {rows} do not lie in the table of {R} rows")
+        raise RuntimeError(f"{who}: mask rows {rows} do not lie in the table of {R} rows")
     out = _attention_out(q, k, vt, Mq, Mkp)
     n = len(sets)
-    starts = (_i64 * n)(*[s for s, _, _ in sets])
-    lens = (_i64 * n)(*[m for _, m, _ in sets])
-    weights = (_f32 * n)(*[w for _, _, w in sets])
     _check(lib().vtm_attention_kv_sets_masked(q.data_ptr(), q.stride(1), k.data_ptr(), k.stride(1), vt.data_ptr(),
-                                              vt.stride(1), out.data_ptr(), C, dtype_code(q), B, heads, Mq, Mqp, Mkp, d,
-                                              float(scale), n, starts, lens, weights, (_int * n)(*rows), mask.data_ptr(), ld,
+                                              vt.stride(1), out.data_ptr(), C, dtype_code(q), B, heads, Mq, Mqp, Mkp,
+                                              C // heads, float(scale), n, *arrays, (_int * n)(*rows), mask.data_ptr(), ld,
                                               R * ld if mask.dim() == 3 else 0, _stream()), "vtm_attention_kv_sets_masked")
     return out
 
@@ -1180,38 +1231,30 @@ def attention_kv_sets_src(q: torch.Tensor, q_src: torch.Tensor, k: torch.Tensor,
     be another sample range of q's buffer.  ``out``: a dense (B, Mqp, C) tensor to write into (rows >= Mq stay as they are)
     instead of a new one.  With every ``set_src[s] == 0`` this IS attention_kv_sets' launch (the library sends it to the
     same kernel)."""
-    sets = [(int(s), int(n), float(w)) for s, n, w in sets]
+    who = "attention_kv_sets_src"
+    sets = list(sets)
     src = [int(s) for s in set_src]
     if len(src) != len(sets):
-        raise RuntimeError(f"attention_kv_sets_src: {len(sets)} sets but {len(src)} set_src entries")
-    if not 1 <= len(sets) <= MAX_KEY_SETS:
-        raise RuntimeError(f"attention_kv_sets_src: 1 .. {MAX_KEY_SETS} key sets, got {len(sets)}")
+        raise RuntimeError(f"{who}: {len(sets)} sets but {len(src)} set_src entries")
+    sets, arrays = _key_sets(who, sets)
     if any(s not in (0, 1) for s in src):
-        raise RuntimeError(f"attention_kv_sets_src: set_src entries are 0 (q) or 1 (q_src), got {src}")
-    if q.dtype not in (torch.float16, torch.bfloat16) or k.dtype != q.dtype or vt.dtype != q.dtype:
-        raise RuntimeError("attention_kv_sets_src: q, k and vt must share one of fp16 / bf16")
-    B, Mqp, C = q.shape
-    Mkp = k.shape[1]
-    d = C // heads
-    _attention_out(q, k, vt, Mq, Mkp, alloc=False)
-    if k.shape[0] != B or vt.shape[0] != B or k.shape[2] != C or vt.shape[1] != C:
-        raise RuntimeError("attention_kv_sets_src: k must be (B, Mkp, C) and vt (B, C, ldvt)")
+        raise RuntimeError(f"{who}: set_src entries are 0 (q) or 1 (q_src), got {src}")
+    _half_operands(who, q, k, vt)
+    _attention_out(q, k, vt, Mq, k.shape[1], alloc=False)
+    B, Mqp, C, Mkp = _kv_shapes(who, q, k, vt)
     if not isinstance(q_src, torch.Tensor) or q_src.dtype != q.dtype or q_src.device != q.device or q_src.dim() != 3 \
             or q_src.shape[0] != B or q_src.shape[2] != C or q_src.shape[1] < Mq or q_src.stride(2) != 1 \
             or q_src.stride(1) % 8 or q_src.stride(0) != q_src.shape[1] * q_src.stride(1) or q_src.data_ptr() % 16:
-        raise RuntimeError("attention_kv_sets_src: q_src must be (B, >= Mq, C) of q's dtype on q's device, 16-byte aligned "
-                           "rows (stride a multiple of 8), dense over the samples")
+        raise RuntimeError(f"{who}: q_src must be (B, >= Mq, C) of q's dtype on q's device, 16-byte aligned rows (stride a "
+                           "multiple of 8), dense over the samples")
     if out is None:
         out = _attention_out(q, k, vt, Mq, Mkp)
-    elif out.shape != q.shape or out.dtype != q.dtype or out.device != q.device or not out.is_contiguous():
-        raise RuntimeError("attention_kv_sets_src: out must be a contiguous tensor of q's shape, dtype and device")
+    else:
+        _out_like_q(who, out, q)
     n = len(sets)
-    starts = (_i64 * n)(*[s for s, _, _ in sets])
-    lens = (_i64 * n)(*[m for _, m, _ in sets])
-    weights = (_f32 * n)(*[w for _, _, w in sets])
     _check(lib().vtm_attention_kv_sets_src(q.data_ptr(), q.stride(1), q_src.data_ptr(), q_src.stride(1), q_src.shape[1],
                                            k.data_ptr(), k.stride(1), vt.data_ptr(), vt.stride(1), out.data_ptr(), C,
-                                           dtype_code(q), B, heads, Mq, Mqp, Mkp, d, float(scale), n, starts, lens, weights,
+                                           dtype_code(q), B, heads, Mq, Mqp, Mkp, C // heads, float(scale), n, *arrays,
                                            (_int * n)(*src), _stream()), "vtm_attention_kv_sets_src")
     return out
 
@@ -1258,24 +1301,15 @@ def attention_kv_bias(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads:
     ``bias`` is fp32 on q's device, (B, Mk') with a row per sample or (1, Mk') with one row for all, Mk' >= Mk, contiguous
     along the last axis; the values are shared by the heads and the queries and are finite or -inf (-inf: probability exactly
     0).  The result is softmax(q K^T * scale + bias) V, (B, Mqp, C).  fp16 / bf16 operands only."""
-    if q.dtype not in (torch.float16, torch.bfloat16) or k.dtype != q.dtype or vt.dtype != q.dtype:
-        raise RuntimeError("attention_kv_bias: q, k and vt must share one of fp16 / bf16 (fp32 models keep the module path)")
-    B, Mqp, C = q.shape
-    Mkp = k.shape[1]
-    d = C // heads
+    who = "attention_kv_bias"
+    _half_operands(who, q, k, vt, _MODULE_PATH)
+    B, Mqp, C, Mkp = _kv_shapes(who, q, k, vt)
     Mk = int(Mk)
-    if k.shape[0] != B or vt.shape[0] != B or k.shape[2] != C or vt.shape[1] != C:
-        raise RuntimeError("attention_kv_bias: k must be (B, Mkp, C) and vt (B, C, ldvt)")
-    if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or bias.device != q.device or bias.dim() != 2 \
-            or bias.shape[0] not in (1, B) or bias.shape[1] < Mk or bias.stride(1) != 1 \
-            or (bias.shape[0] == B and B > 1 and 0 < bias.stride(0) < bias.shape[1]):   # (stride 0: an expanded row)
-        raise RuntimeError("attention_kv_bias: bias must be fp32 on q's device, (B, >= Mk) or (1, >= Mk), contiguous along "
-                           "its last axis")
+    bias_rows = _key_rows(who, bias, "bias must be", q, B, Mk)
     out = _attention_out(q, k, vt, Mq, Mkp)
-    batch_stride = bias.stride(0) if bias.shape[0] == B and B > 1 else 0
     _check(lib().vtm_attention_kv_bias(q.data_ptr(), q.stride(1), k.data_ptr(), k.stride(1), vt.data_ptr(), vt.stride(1),
-                                       out.data_ptr(), C, dtype_code(q), B, heads, Mq, Mqp, Mk, Mkp, d, float(scale),
-                                       bias.data_ptr(), bias.shape[1], batch_stride, _stream()), "vtm_attention_kv_bias")
+                                       out.data_ptr(), C, dtype_code(q), B, heads, Mq, Mqp, Mk, Mkp, C // heads, float(scale),
+                                       *bias_rows, _stream()), "vtm_attention_kv_bias")
     return out
 
 
@@ -1312,8 +1346,7 @@ def attention_kv_segments(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, he
     (n_seg + 1) int32 on q's device, absolute row offsets that never decrease; ``max_seg_rows`` a host bound on every
     segment's length.  Row i of segment s is softmax(q[i] K_s^T * scale) V_s; the result is (rows, C), rows outside every
     segment are not written (``out``: the buffer to write into).  fp16 / bf16 operands only."""
-    if q.dtype not in (torch.float16, torch.bfloat16) or k.dtype != q.dtype or vt.dtype != q.dtype:
-        raise RuntimeError("attention_kv_segments: q, k and vt must share one of fp16 / bf16")
+    _half_operands("attention_kv_segments", q, k, vt)
     if q.dim() != 2 or k.dim() != 3 or vt.dim() != 3 or not q.is_cuda or k.device != q.device or vt.device != q.device:
         raise RuntimeError("attention_kv_segments: q must be (rows, C), k (n_seg, Mkp, C) and vt (n_seg, C, ldvt) on one GPU")
     rows, C = q.shape
@@ -1343,47 +1376,14 @@ def attention_probs(q: torch.Tensor, k: torch.Tensor, heads: int, Mq: int, Mk: i
     views contiguous along the last axis as for attention_kv_bias, fp16 / bf16; ``bias`` None or what attention_kv_bias
     takes.  Returns mean_head softmax(q K^T * scale + bias) of the first Mq query rows and Mk <= 256 keys, a new
     (B, Mq, Mk) float32 tensor.  No V operand, no (B, heads, Mq, Mk) intermediate; deterministic."""
-    if not isinstance(q, torch.Tensor) or not isinstance(k, torch.Tensor) or q.dtype not in (torch.float16, torch.bfloat16) \
-            or k.dtype != q.dtype:
-        raise RuntimeError("attention_probs: q and k must share one of fp16 / bf16")
-    if q.dim() != 3 or k.dim() != 3 or not q.is_cuda or k.device != q.device:
-        raise RuntimeError("attention_probs: q must be (B, Mqp, C) and k (B, Mkp, C) on one GPU")
-    B, Mqp, C = q.shape
-    Mkp = k.shape[1]
-    heads, Mq, Mk = int(heads), int(Mq), int(Mk)
-    if k.shape[0] != B or k.shape[2] != C or heads < 1 or C % heads:
-        raise RuntimeError("attention_probs: k must be (B, Mkp, C) with C a multiple of heads")
-    if not (1 <= Mq <= Mqp and 1 <= Mk <= Mkp):
-        raise RuntimeError("attention_probs: Mq / Mk must lie inside q / k")
-    for t, name, rows in ((q, "q", Mqp), (k, "k", Mkp)):
-        if t.stride(2) != 1 or t.stride(1) % 8 or t.stride(1) < C or t.stride(0) != rows * t.stride(1) or t.data_ptr() % 16:
-            raise RuntimeError(f"attention_probs: {name} must be 16-byte aligned rows (stride a multiple of 8), dense over "
-                               "the samples")
-    if bias is not None and (
-            not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or bias.device != q.device or bias.dim() != 2
-            or bias.shape[0] not in (1, B) or bias.shape[1] < Mk or bias.stride(1) != 1
-            or (bias.shape[0] == B and B > 1 and 0 < bias.stride(0) < bias.shape[1])):   # (stride 0: an expanded row)
-        raise RuntimeError("attention_probs: bias must be None or fp32 on q's device, (B, >= Mk) or (1, >= Mk), contiguous "
-                           "along its last axis")
+    who = "attention_probs"
+    B, Mqp, C, Mkp, heads, Mq, Mk = _qk_views(who, q, k, heads, Mq, Mk, dense_single=True)
+    bias_rows = _key_rows(who, bias, "bias must be None or", q, B, Mk, optional=True)
     out = torch.empty((B, Mq, Mk), dtype=torch.float32, device=q.device)
-    ld_bias = 0 if bias is None else bias.shape[1]
-    batch_stride = bias.stride(0) if bias is not None and bias.shape[0] == B and B > 1 else 0
     _check(lib().vtm_attention_probs(q.data_ptr(), q.stride(1), k.data_ptr(), k.stride(1), out.data_ptr(), Mk, dtype_code(q),
-                                     B, heads, Mq, Mqp, Mk, Mkp, C // heads, float(scale), _ptr(bias), ld_bias, batch_stride,
-                                     _stream()), "vtm_attention_probs")
+                                     B, heads, Mq, Mqp, Mk, Mkp, C // heads, float(scale), *bias_rows, _stream()),
+           "vtm_attention_probs")
     return out
-
-
-def _key_rows(who: str, t: Optional[torch.Tensor], name: str, q: torch.Tensor, B: int, Mk: int):
-    """(pointer, row length, batch stride) of fp32 per-key rows (B or 1, >= Mk) on q's device, as the bias of
-    attention_kv_bias is handed over; None gives (None, 0, 0)."""
-    if t is None:
-        return None, 0, 0
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != q.device or t.dim() != 2 \
-            or t.shape[0] not in (1, B) or t.shape[1] < Mk or t.stride(1) != 1 \
-            or (t.shape[0] == B and B > 1 and 0 < t.stride(0) < t.shape[1]):   # (stride 0: an expanded row)
-        raise RuntimeError(f"{who}: {name} must be fp32 on q's device, (B, >= Mk) or (1, >= Mk), contiguous along its last axis")
-    return t.data_ptr(), t.shape[1], (t.stride(0) if t.shape[0] == B and B > 1 else 0)
 
 
 @_on_device
@@ -1397,26 +1397,11 @@ def attention_word_map(q: torch.Tensor, k: torch.Tensor, heads: int, Mq: int, Mk
     inside ``out``: the caller's business) or to row b.  ``accumulate``: add to what ``out`` holds, else overwrite.  Returns
     ``out``.  One launch; no (B, Mq, Mk) map, deterministic."""
     who = "attention_word_map"
-    if not isinstance(q, torch.Tensor) or not isinstance(k, torch.Tensor) or q.dtype not in (torch.float16, torch.bfloat16) \
-            or k.dtype != q.dtype:
-        raise RuntimeError(f"{who}: q and k must share one of fp16 / bf16")
-    if q.dim() != 3 or k.dim() != 3 or not q.is_cuda or k.device != q.device:
-        raise RuntimeError(f"{who}: q must be (B, Mqp, C) and k (B, Mkp, C) on one GPU")
-    B, Mqp, C = q.shape
-    Mkp = k.shape[1]
-    heads, Mq, Mk = int(heads), int(Mq), int(Mk)
-    if k.shape[0] != B or k.shape[2] != C or heads < 1 or C % heads:
-        raise RuntimeError(f"{who}: k must be (B, Mkp, C) with C a multiple of heads")
-    if not (1 <= Mq <= Mqp and 1 <= Mk <= Mkp):
-        raise RuntimeError(f"{who}: Mq / Mk must lie inside q / k")
-    for t, name, rows in ((q, "q", Mqp), (k, "k", Mkp)):
-        if t.stride(2) != 1 or t.stride(1) % 8 or t.stride(1) < C or (B > 1 and t.stride(0) != rows * t.stride(1)) \
-                or t.data_ptr() % 16:
-            raise RuntimeError(f"{who}: {name} must be 16-byte aligned rows (stride a multiple of 8), dense over the samples")
+    B, Mqp, C, Mkp, heads, Mq, Mk = _qk_views(who, q, k, heads, Mq, Mk, dense_single=False)
     if weights is None:
         raise RuntimeError(f"{who}: weights are required")
-    b_ptr, ld_bias, b_stride = _key_rows(who, bias, "bias", q, B, Mk)
-    w_ptr, ld_w, w_stride = _key_rows(who, weights, "weights", q, B, Mk)
+    b_ptr, ld_bias, b_stride = _key_rows(who, bias, "bias must be", q, B, Mk, optional=True)
+    w_ptr, ld_w, w_stride = _key_rows(who, weights, "weights must be", q, B, Mk)
     if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != q.device or out.dim() != 2 \
             or out.shape[1] < Mq or out.stride(1) != 1 or (out.shape[0] > 1 and out.stride(0) < out.shape[1]):
         raise RuntimeError(f"{who}: out must be fp32 (rows, >= Mq) on q's device, contiguous along its last axis")
@@ -1483,25 +1468,10 @@ def attention_key_mass(q: torch.Tensor, k: torch.Tensor, heads: int, Mq: int, Mk
     Mq <= 65536, any head count; query rows >= Mq contribute exactly 0.  No V operand, no (B, Mq, Mk) intermediate;
     deterministic, a sample's bits do not depend on B.  More than 128 queries go through a cached workspace."""
     who = "attention_key_mass"
-    if not isinstance(q, torch.Tensor) or not isinstance(k, torch.Tensor) or q.dtype not in (torch.float16, torch.bfloat16) \
-            or k.dtype != q.dtype:
-        raise RuntimeError(f"{who}: q and k must share one of fp16 / bf16")
-    if q.dim() != 3 or k.dim() != 3 or not q.is_cuda or k.device != q.device:
-        raise RuntimeError(f"{who}: q must be (B, Mqp, C) and k (B, Mkp, C) on one GPU")
-    B, Mqp, C = q.shape
-    Mkp = k.shape[1]
-    heads, Mq, Mk = int(heads), int(Mq), int(Mk)
-    if k.shape[0] != B or k.shape[2] != C or heads < 1 or C % heads:
-        raise RuntimeError(f"{who}: k must be (B, Mkp, C) with C a multiple of heads")
-    if not (1 <= Mq <= Mqp and 1 <= Mk <= Mkp):
-        raise RuntimeError(f"{who}: Mq / Mk must lie inside q / k")
+    B, Mqp, C, Mkp, heads, Mq, Mk = _qk_views(who, q, k, heads, Mq, Mk, dense_single=False)
     if Mk > KEY_MASS_MAX_KEYS or Mq > KEY_MASS_MAX_QUERIES:
         raise RuntimeError(f"{who}: Mk = {Mk}, Mq = {Mq}: at most {KEY_MASS_MAX_KEYS} keys and {KEY_MASS_MAX_QUERIES} queries "
                            "are taken")
-    for t, name, rows in ((q, "q", Mqp), (k, "k", Mkp)):
-        if t.stride(2) != 1 or t.stride(1) % 8 or t.stride(1) < C or (B > 1 and t.stride(0) != rows * t.stride(1)) \
-                or t.data_ptr() % 16:
-            raise RuntimeError(f"{who}: {name} must be 16-byte aligned rows (stride a multiple of 8), dense over the samples")
     if out is None:
         out = torch.empty((B, Mk), dtype=torch.float32, device=q.device)
     elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != q.device or out.dim() != 2 \

@@ -15,10 +15,8 @@
 //     as long as no finite score has been seen the exponent is taken against 0 instead of the running maximum -inf, so
 //     leading masked tiles give 0, not NaN.  A sample whose keys are ALL -inf ends as 0 / 0 = NaN, as torch's SDPA does;
 //   * no key split, no workspace, no combine kernel: the key axis is a few hundred keys, the launch streams q and out.
-#include "attention_plan.h"
+#include "attention_checks.h"
 #include "attention_stage.h"
-
-#include <cmath>
 
 namespace vtm_att {
 // the bias rows of one vtm_attention_kv_bias call (Call::key_bias): sample b reads bias[b * batch_stride + key]
@@ -195,27 +193,17 @@ VTM_EXPORT int vtm_attention_kv_bias(const void *q, int64_t ldq, const void *k, 
     VTM_REQUIRE(q && k && vt && out, "%s: null pointer", who);
     VTM_REQUIRE(bias, "%s: null bias", who);
     VTM_REQUIRE(B > 0 && h > 0 && Mq > 0 && Mqp >= Mq && Mk > 0 && Mkp >= Mk && Mkp % 8 == 0 && d > 0, "%s: bad sizes", who);
-    VTM_REQUIRE(scale > 0.0f && std::isfinite(scale), "%s: scale must be positive and finite", who);
-    if (dtype == VTM_F32)
-        return vtm::fail(VTM_EINVAL, "%s: fp32 operands are not taken (dtype must be VTM_F16 or VTM_BF16)", who);
-    if (dtype != VTM_F16 && dtype != VTM_BF16) return vtm::fail(VTM_EINVAL, "%s: dtype must be VTM_F16 or VTM_BF16", who);
+    if (int rc = check_scale(who, scale)) return rc;
+    if (int rc = check_half_dtype(who, dtype)) return rc;
     VTM_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 8 == 0 && ldo % 4 == 0 && ldvt >= Mk,
                 "%s: leading dimensions must keep 16-byte alignment (ldvt >= Mk, %% 8)", who);
-    // K / V^T tiles are addressed with 32-bit byte offsets inside one (sample, head) slice (buffer loads)
-    VTM_REQUIRE((Mkp * ldk + d) * 2 < (1ll << 31) && (d * ldvt + Mkp) * 2 < (1ll << 31),
-                "%s: a (sample, head) slice of K or V^T must stay below 2 GiB", who);
-    VTM_REQUIRE(ld_bias >= Mk, "%s: ld_bias = %lld is shorter than a row of Mk = %lld values", who, (long long)ld_bias,
-                (long long)Mk);
-    // one row for every sample (stride 0), or per-sample rows that do not overlap
-    VTM_REQUIRE(bias_batch_stride == 0 || bias_batch_stride >= ld_bias,
-                "%s: bias_batch_stride = %lld must be 0 or at least ld_bias = %lld", who, (long long)bias_batch_stride,
-                (long long)ld_bias);
+    if (int rc = check_kv_slices(who, "sample", Mkp, ldk, d, ldvt)) return rc;
+    if (int rc = check_key_rows(who, "bias", "values", ld_bias, bias_batch_stride, Mk)) return rc;
     const KeyBias kb{bias, ld_bias, bias_batch_stride};
     Call c{q, ldq, k, ldk, vt, ldvt, out, ldo, dtype, B, h, Mq, Mqp, Mk, Mkp, scale, 1, nullptr, 0,
            nullptr, vtm::as_stream(stream), false, nullptr, nullptr, 0};
     c.key_bias = &kb;
-    return with_head_dim(d, [&](auto dim) {
-        constexpr int D = decltype(dim)::value;
-        return planned_launch(c, dtype == VTM_F16 ? bias_family<__half, D>() : bias_family<vtm_bf16, D>());
+    return with_half_head_dim(dtype, d, [&](auto t, auto dim) {
+        return planned_launch(c, bias_family<decltype(t), decltype(dim)::value>());
     });
 }

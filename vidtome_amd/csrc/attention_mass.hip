@@ -10,8 +10,8 @@
 //     in flight in registers while the current one is computed;
 //   * S^T = K Q^T on v_mfma_f32_32x32x16 (one query per lane); score = fma(S^T, scale * log2(e), slot), base-2 softmax; the
 //     slot row is 0 for a key that exists and -inf behind the last key, which is all the bounds logic the scores need;
-//   * per head, sweep 1 over the key tiles: the online row maximum and denominator, kept in two REGISTERS of the lane that
-//     owns the query -- nothing per head outlives its head, so there is no head limit;
+//   * per head, sweep 1 over the key tiles: the online row maximum and denominator (online_sum, attention_stage.h), kept in
+//     two REGISTERS of the lane that owns the query -- nothing per head outlives its head, so there is no head limit;
 //   * per head, sweep 2 over the key tiles: the tile's scores again, p = exp2(s - m) * (1 / l), SELECTED to 0 for a query
 //     row >= Mq (pad rows may hold NaN: they are not read, and what their lanes compute is not used), then summed down the
 //     query rows: each wave turns its 32 x 32 blocks round through LDS (rows of 33 floats) and a lane adds the 16 rows of its
@@ -25,10 +25,8 @@
 // No atomics; the order of every addition depends on (h, Mq, Mk) alone, so a sample's bits depend neither on B, nor on the
 // other samples, nor on the run.
 // Cost: K is re-staged from L2 twice per head and query tile; q is read once per step of its head.
-#include "attention_plan.h"
+#include "attention_checks.h"
 #include "attention_stage.h"
-
-#include <cmath>
 
 namespace {
 
@@ -67,9 +65,7 @@ __global__ __launch_bounds__(MASS_NT, 2) void attention_mass_kernel(const T *__r
     const T *kb0 = k + b * Mkp * ldk;
     const int ntiles = (Mk + KV - 1) / KV;
 
-    // the K pad columns meet Q's zero padding, but garbage there could be NaN; tile stores never touch them
-    for (int i = tid; i < KV * (K_STRIDE - D); i += NT)
-        sK[(i / (K_STRIDE - D)) * K_STRIDE + D + i % (K_STRIDE - D)] = (elem)0.0f;
+    zero_k_pads<T, D, NT>(sK, tid);
     if (tid < KV) {
         sSlot[0][tid] = 0.0f;
         sSlot[1][tid] = (ntiles - 1) * KV + tid < Mk ? 0.0f : -INFINITY;
@@ -108,19 +104,7 @@ __global__ __launch_bounds__(MASS_NT, 2) void attention_mass_kernel(const T *__r
             l_run = 0.0f;
         }
         qk_scores_biased<T, D, NT>(s, sK, sSlot[ct == ntiles - 1 ? 1 : 0], qf, 0, scale_log2e, l31, hi);
-        float mt = fmaxf(s[0][0], s[1][0]);
-#pragma unroll
-        for (int r = 1; r < 16; ++r) mt = fmaxf(fmaxf(mt, s[0][r]), s[1][r]);
-        mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
-        const float m_new = fmaxf(m_run, mt);
-        const float m_use = m_new == -INFINITY ? 0.0f : m_new;   // (as attention_probs_kernel; every tile has a key)
-        float sum = 0.0f;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sum += __builtin_amdgcn_exp2f(s[kb][r] - m_use);
-        l_run = l_run * __builtin_amdgcn_exp2f(m_run - m_use) + sum;   // nothing seen before: l_run is 0
-        m_run = m_new;
+        const float m_use = online_sum(s, m_run, l_run);   // (as attention_probs_kernel; every tile has a key)
         if (ct == ntiles - 1) {
             m_head = m_use;
             il_head = 1.0f / (l_run + __shfl_xor(l_run, 32, 64));
@@ -213,33 +197,23 @@ VTM_EXPORT int vtm_attention_key_mass(const void *q, int64_t ldq, const void *k,
                                       int64_t d, float scale, void *ws, size_t ws_bytes, vtm_stream_t stream) {
     const char *who = "vtm_attention_key_mass";
     VTM_REQUIRE(q && k && out, "%s: null pointer", who);
-    VTM_REQUIRE(((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k)) & 15) == 0 &&
-                    (reinterpret_cast<uintptr_t>(out) & 3) == 0, "%s: q and k must be 16-byte aligned", who);
-    VTM_REQUIRE(B > 0 && h > 0 && Mq > 0 && Mqp >= Mq && Mk > 0 && Mkp >= Mk && d > 0, "%s: bad sizes", who);
+    if (int rc = check_qk_aligned(who, q, k, (reinterpret_cast<uintptr_t>(out) & 3) == 0)) return rc;
+    if (int rc = check_map_sizes(who, B, h, Mq, Mqp, Mk, Mkp, d)) return rc;
     VTM_REQUIRE(Mk <= MASS_MAX_KEYS, "%s: Mk = %lld, at most %d keys are taken", who, (long long)Mk, MASS_MAX_KEYS);
     VTM_REQUIRE(Mq <= MASS_MAX_QUERIES, "%s: Mq = %lld, at most %lld queries are taken", who, (long long)Mq,
                 (long long)MASS_MAX_QUERIES);
     VTM_REQUIRE(h < (1ll << 20), "%s: h = %lld is not a head count", who, (long long)h);
-    VTM_REQUIRE(scale > 0.0f && std::isfinite(scale), "%s: scale must be positive and finite", who);
-    if (dtype == VTM_F32)
-        return vtm::fail(VTM_EINVAL, "%s: fp32 operands are not taken (dtype must be VTM_F16 or VTM_BF16)", who);
-    if (dtype != VTM_F16 && dtype != VTM_BF16) return vtm::fail(VTM_EINVAL, "%s: dtype must be VTM_F16 or VTM_BF16", who);
-    VTM_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldq >= h * d && ldk >= h * d && ldo >= Mk,
-                "%s: ldq and ldk must be multiples of 8 and hold h * d channels, ldo >= Mk", who);
-    // K tiles are addressed with 32-bit byte offsets inside one (sample, head) slice (buffer loads)
-    VTM_REQUIRE((Mk * ldk + d) * 2 < (1ll << 31), "%s: a (sample, head) slice of K must stay below 2 GiB", who);
+    if (int rc = check_scale(who, scale)) return rc;
+    if (int rc = check_half_dtype(who, dtype)) return rc;
+    if (int rc = check_qk_rows(who, ldq, ldk, h, d, Mk, ldo, Mk, "ldo >= Mk")) return rc;
     VTM_REQUIRE(B * vtm::cdiv(Mq, MASS_QB) < (1ll << 31) && B < 65536, "%s: grid too large", who);
     const size_t need = mass_ws_bytes(B, Mq, Mk);
     VTM_REQUIRE(need == 0 || (ws != nullptr && ws_bytes >= need && (reinterpret_cast<uintptr_t>(ws) & 3) == 0),
                 "%s: workspace of %zu bytes needed (vtm_attention_key_mass_ws_bytes), %zu given", who, need,
                 ws ? ws_bytes : (size_t)0);
     hipStream_t s = vtm::as_stream(stream);
-    return with_head_dim(d, [&](auto dim) {
-        constexpr int D = decltype(dim)::value;
-        if (dtype == VTM_F16)
-            launch_mass<__half, D>(q, ldq, k, ldk, out, ldo, B, h, Mq, Mqp, Mk, Mkp, scale, (float *)ws, s);
-        else
-            launch_mass<vtm_bf16, D>(q, ldq, k, ldk, out, ldo, B, h, Mq, Mqp, Mk, Mkp, scale, (float *)ws, s);
+    return with_half_head_dim(dtype, d, [&](auto t, auto dim) {
+        launch_mass<decltype(t), decltype(dim)::value>(q, ldq, k, ldk, out, ldo, B, h, Mq, Mqp, Mk, Mkp, scale, (float *)ws, s);
         return vtm::launch_status(who);
     });
 }

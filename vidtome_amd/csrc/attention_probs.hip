@@ -11,9 +11,9 @@
 //     the current one is computed.  The sample's bias row (<= 256 keys) sits in LDS for the whole launch, pre-multiplied by
 //     log2(e); slots >= Mk hold -inf, which is all the bounds logic the scores need;
 //   * S^T = K Q^T on v_mfma_f32_32x32x16 (one query per lane); score = fma(S^T, scale * log2(e), slot), base-2 softmax;
-//   * sweep 1 (heads outer, tiles inner): the online row maximum and denominator of every head; at a head's last tile the
-//     maximum and 1 / denominator go to LDS, one slot per (head, query row) -- the stats of h heads live there, not in a
-//     dynamically indexed register array;
+//   * sweep 1 (heads outer, tiles inner): the online row maximum and denominator of every head (online_sum,
+//     attention_stage.h); at a head's last tile the maximum and 1 / denominator go to LDS, one slot per (head, query row)
+//     -- the stats of h heads live there, not in a dynamically indexed register array;
 //   * sweep 2 (tiles outer, heads inner): the tile's scores again, exp2(s - m_head) * (1 / l_head) added into the tile's 32
 //     fp32 mean accumulators head after head in ascending order, one multiplication by 1 / h, and the tile is written once,
 //     turned round through LDS (the K tile's bytes, free between two tiles) so that a half-wave stores 32 consecutive keys
@@ -23,10 +23,8 @@
 //   * one launch, no atomics, no workspace: the same operands give the same bits.
 // Cost: K is re-staged from L2 twice per head and q is read once per step of its head (2 ntiles times, from L2 after the
 // first).
-#include "attention_plan.h"
+#include "attention_checks.h"
 #include "attention_stage.h"
-
-#include <cmath>
 
 namespace {
 
@@ -66,11 +64,7 @@ __global__ __launch_bounds__(PROBS_NT, 2) void attention_probs_kernel(
     const T *kb0 = k + b * Mkp * ldk;
     const int row = wave * QW + l31;
 
-    // the K pad columns meet Q's zero padding, but garbage there could be NaN; tile stores never touch them
-    auto zero_pads = [&]() {
-        for (int i = tid; i < KV * (K_STRIDE - D); i += NT)
-            sK[(i / (K_STRIDE - D)) * K_STRIDE + D + i % (K_STRIDE - D)] = (elem)0.0f;
-    };
+    auto zero_pads = [&]() { zero_k_pads<T, D, NT>(sK, tid); };   // (again after every flush, which writes over them)
     zero_pads();
     {
         float v = -INFINITY;
@@ -134,20 +128,7 @@ __global__ __launch_bounds__(PROBS_NT, 2) void attention_probs_kernel(
                 l_run = 0.0f;
             }
             scores(ct, s);
-            float mt = fmaxf(s[0][0], s[1][0]);
-#pragma unroll
-            for (int r = 1; r < 16; ++r) mt = fmaxf(fmaxf(mt, s[0][r]), s[1][r]);
-            mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
-            const float m_new = fmaxf(m_run, mt);
-            // (only masked keys so far: -inf - (-inf) would be NaN; against 0 every p of such a query is exp2(-inf) = 0)
-            const float m_use = m_new == -INFINITY ? 0.0f : m_new;
-            float sum = 0.0f;
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) sum += __builtin_amdgcn_exp2f(s[kb][r] - m_use);
-            l_run = l_run * __builtin_amdgcn_exp2f(m_run - m_use) + sum;   // nothing finite seen before: l_run is 0
-            m_run = m_new;
+            const float m_use = online_sum(s, m_run, l_run);
             if (ct == ntiles - 1) {
                 const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
                 if (hi == 0) {
@@ -253,35 +234,20 @@ VTM_EXPORT int vtm_attention_probs(const void *q, int64_t ldq, const void *k, in
                                    vtm_stream_t stream) {
     const char *who = "vtm_attention_probs";
     VTM_REQUIRE(q && k && out, "%s: null pointer", who);
-    VTM_REQUIRE(((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k)) & 15) == 0 &&
-                    (reinterpret_cast<uintptr_t>(out) & 3) == 0, "%s: q and k must be 16-byte aligned", who);
-    VTM_REQUIRE(B > 0 && h > 0 && Mq > 0 && Mqp >= Mq && Mk > 0 && Mkp >= Mk && d > 0, "%s: bad sizes", who);
+    if (int rc = check_qk_aligned(who, q, k, (reinterpret_cast<uintptr_t>(out) & 3) == 0)) return rc;
+    if (int rc = check_map_sizes(who, B, h, Mq, Mqp, Mk, Mkp, d)) return rc;
     VTM_REQUIRE(Mk <= PROBS_MAX_KEYS, "%s: Mk = %lld, at most %d keys are taken", who, (long long)Mk, PROBS_MAX_KEYS);
     VTM_REQUIRE(h <= PROBS_MAX_HEADS, "%s: h = %lld, at most %d heads are taken", who, (long long)h, PROBS_MAX_HEADS);
-    VTM_REQUIRE(scale > 0.0f && std::isfinite(scale), "%s: scale must be positive and finite", who);
-    if (dtype == VTM_F32)
-        return vtm::fail(VTM_EINVAL, "%s: fp32 operands are not taken (dtype must be VTM_F16 or VTM_BF16)", who);
-    if (dtype != VTM_F16 && dtype != VTM_BF16) return vtm::fail(VTM_EINVAL, "%s: dtype must be VTM_F16 or VTM_BF16", who);
-    VTM_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldq >= h * d && ldk >= h * d && ldo >= Mk,
-                "%s: ldq and ldk must be multiples of 8 and hold h * d channels, ldo >= Mk", who);
-    // K tiles are addressed with 32-bit byte offsets inside one (sample, head) slice (buffer loads)
-    VTM_REQUIRE((Mk * ldk + d) * 2 < (1ll << 31), "%s: a (sample, head) slice of K must stay below 2 GiB", who);
+    if (int rc = check_scale(who, scale)) return rc;
+    if (int rc = check_half_dtype(who, dtype)) return rc;
+    if (int rc = check_qk_rows(who, ldq, ldk, h, d, Mk, ldo, Mk, "ldo >= Mk")) return rc;
     VTM_REQUIRE(B * vtm::cdiv(Mq, PROBS_QB) < (1ll << 31), "%s: grid too large", who);
-    if (bias != nullptr) {
-        VTM_REQUIRE(ld_bias >= Mk, "%s: ld_bias = %lld is shorter than a row of Mk = %lld values", who, (long long)ld_bias,
-                    (long long)Mk);
-        // one row for every sample (stride 0), or per-sample rows that do not overlap
-        VTM_REQUIRE(bias_batch_stride == 0 || bias_batch_stride >= ld_bias,
-                    "%s: bias_batch_stride = %lld must be 0 or at least ld_bias = %lld", who, (long long)bias_batch_stride,
-                    (long long)ld_bias);
-    }
+    if (bias != nullptr)
+        if (int rc = check_key_rows(who, "bias", "values", ld_bias, bias_batch_stride, Mk)) return rc;
     hipStream_t s = vtm::as_stream(stream);
-    return with_head_dim(d, [&](auto dim) {
-        constexpr int D = decltype(dim)::value;
-        if (dtype == VTM_F16)
-            launch_probs<__half, D>(q, ldq, k, ldk, out, ldo, B, h, Mq, Mqp, Mk, Mkp, scale, bias, bias_batch_stride, s);
-        else
-            launch_probs<vtm_bf16, D>(q, ldq, k, ldk, out, ldo, B, h, Mq, Mqp, Mk, Mkp, scale, bias, bias_batch_stride, s);
+    return with_half_head_dim(dtype, d, [&](auto t, auto dim) {
+        launch_probs<decltype(t), decltype(dim)::value>(q, ldq, k, ldk, out, ldo, B, h, Mq, Mqp, Mk, Mkp, scale, bias,
+                                                        bias_batch_stride, s);
         return vtm::launch_status(who);
     });
 }

@@ -20,10 +20,8 @@
 //   * no key split, no workspace, no combine kernel: the key axis is a few hundred keys, the launch streams q and out.
 // A segment's rows are clamped to [0, rows_total) before anything is addressed: offsets that break the contract (decreasing,
 // negative, beyond rows_total) give rows nobody computes, never an access outside q / out.
-#include "attention_plan.h"
+#include "attention_checks.h"
 #include "attention_stage.h"
-
-#include <cmath>
 
 namespace vtm_att {
 // the segments of one vtm_attention_kv_segments call (Call::B = their number, Call::M = the bound on their length)
@@ -204,23 +202,18 @@ VTM_EXPORT int vtm_attention_kv_segments(const void *q, int64_t ldq, const void 
     VTM_REQUIRE(rows_total > 0 && n_seg > 0 && max_seg_rows > 0 && h > 0 && Mk > 0 && Mkp >= Mk && Mkp % 8 == 0 && d > 0,
                 "%s: bad sizes", who);
     VTM_REQUIRE(rows_total < (1ll << 31), "%s: rows_total = %lld does not fit the int32 offsets", who, (long long)rows_total);
-    VTM_REQUIRE(scale > 0.0f && std::isfinite(scale), "%s: scale must be positive and finite", who);
-    if (dtype == VTM_F32)
-        return vtm::fail(VTM_EINVAL, "%s: fp32 operands are not taken (dtype must be VTM_F16 or VTM_BF16)", who);
-    if (dtype != VTM_F16 && dtype != VTM_BF16) return vtm::fail(VTM_EINVAL, "%s: dtype must be VTM_F16 or VTM_BF16", who);
+    if (int rc = check_scale(who, scale)) return rc;
+    if (int rc = check_half_dtype(who, dtype)) return rc;
     VTM_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 8 == 0 && ldo % 4 == 0 && ldvt >= Mk && ldq >= h * d && ldo >= h * d &&
                     ldk >= h * d,
                 "%s: leading dimensions must hold a row and keep 16-byte alignment (ldvt >= Mk, %% 8)", who);
-    // K / V^T tiles are addressed with 32-bit byte offsets inside one (segment, head) slice (buffer loads)
-    VTM_REQUIRE((Mkp * ldk + d) * 2 < (1ll << 31) && (d * ldvt + Mkp) * 2 < (1ll << 31),
-                "%s: a (segment, head) slice of K or V^T must stay below 2 GiB", who);
+    if (int rc = check_kv_slices(who, "segment", Mkp, ldk, d, ldvt)) return rc;
     const QuerySegments segs{seg_off, rows_total};
     // the planner's "samples" are the segments, its query rows the bound on a segment's length
     Call c{q, ldq, k, ldk, vt, ldvt, out, ldo, dtype, n_seg, h, max_seg_rows, max_seg_rows, Mk, Mkp, scale, 1, nullptr, 0,
            nullptr, vtm::as_stream(stream), false, nullptr, nullptr, 0};
     c.segments = &segs;
-    return with_head_dim(d, [&](auto dim) {
-        constexpr int D = decltype(dim)::value;
-        return planned_launch(c, dtype == VTM_F16 ? segments_family<__half, D>() : segments_family<vtm_bf16, D>());
+    return with_half_head_dim(dtype, d, [&](auto t, auto dim) {
+        return planned_launch(c, segments_family<decltype(t), decltype(dim)::value>());
     });
 }

@@ -20,7 +20,7 @@
 //     are zeroed as values): the key axis is 2 - 10 tiles long, bounds logic is not what this kernel waits for;
 //   * per set: running max, denominator and fp32 accumulators of its own; at the end of the set they are folded into a
 //     second fp32 accumulator as w_s / l_s; that sum is rounded to the output type once.
-#include "attention_plan.h"
+#include "attention_checks.h"
 #include "attention_stage.h"
 
 #include <cmath>
@@ -284,15 +284,11 @@ int sets_launch(const char *who, const void *q, int64_t ldq, const void *k, int6
     VTM_REQUIRE(q && k && vt && out && set_start && set_len && set_weight, "%s: null pointer", who);
     VTM_REQUIRE(n_sets >= 1 && n_sets <= MAX_KEY_SETS, "%s: n_sets must be 1 .. %d, got %d", who, MAX_KEY_SETS, n_sets);
     VTM_REQUIRE(B > 0 && h > 0 && Mq > 0 && Mqp >= Mq && Mkp > 0 && d > 0, "%s: bad sizes", who);
-    VTM_REQUIRE(scale > 0.0f && std::isfinite(scale), "%s: scale must be positive and finite", who);
-    if (dtype == VTM_F32)
-        return vtm::fail(VTM_EINVAL, "%s: fp32 operands are not taken (dtype must be VTM_F16 or VTM_BF16)", who);
-    if (dtype != VTM_F16 && dtype != VTM_BF16) return vtm::fail(VTM_EINVAL, "%s: dtype must be VTM_F16 or VTM_BF16", who);
+    if (int rc = check_scale(who, scale)) return rc;
+    if (int rc = check_half_dtype(who, dtype)) return rc;
     VTM_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 8 == 0 && ldo % 4 == 0,
                 "%s: leading dimensions must keep 16-byte alignment", who);
-    // K / V^T tiles are addressed with 32-bit byte offsets inside one (sample, head) slice (buffer loads)
-    VTM_REQUIRE((Mkp * ldk + d) * 2 < (1ll << 31) && (d * ldvt + Mkp) * 2 < (1ll << 31),
-                "%s: a (sample, head) slice of K or V^T must stay below 2 GiB", who);
+    if (int rc = check_kv_slices(who, "sample", Mkp, ldk, d, ldvt)) return rc;
     KeySets sets;
     sets.n = n_sets;
     int64_t keys = 0;
@@ -318,9 +314,8 @@ int sets_launch(const char *who, const void *q, int64_t ldq, const void *k, int6
     c.set_masks = masks;
     c.set_src = src;
     const SetsKind kind = masks != nullptr ? SETS_MASKED : src != nullptr ? SETS_SRC : SETS_PLAIN;
-    return with_head_dim(d, [&](auto dim) {
-        constexpr int D = decltype(dim)::value;
-        return planned_launch(c, dtype == VTM_F16 ? sets_family<__half, D>(kind) : sets_family<vtm_bf16, D>(kind));
+    return with_half_head_dim(dtype, d, [&](auto t, auto dim) {
+        return planned_launch(c, sets_family<decltype(t), decltype(dim)::value>(kind));
     });
 }
 

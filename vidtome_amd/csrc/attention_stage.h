@@ -1,7 +1,8 @@
 // What the 16-bit attention kernels (attention.hip, attention16.hip, attention16g.hip, attention_sets.hip,
 // attention_bias.hip, attention_probs.hip, attention_words.hip, attention_mass.hip) share of their tile handling: the buffer descriptor, the
-// K / V^T tile stage global memory -> staging registers -> LDS, the Q-fragment load, the score tile of the map kernels and,
-// for the two small cross-attention kernels, the pad initialisation, the split-P PV step and the 32-row output store.
+// K / V^T tile stage global memory -> staging registers -> LDS, the Q-fragment load, the score tile of the map kernels with
+// its online-softmax step, the K pad initialisation and, for the two small cross-attention kernels, the V^T pad
+// initialisation, the split-P PV step and the 32-row output store.
 // Header-only; everything is __forceinline__ and every loop fully unrolled: the
 // kernels that use a piece keep the registers they had with its text written out, and where they did not, they do not use it
 // (profiles/attention_stage_resources.txt).
@@ -214,11 +215,51 @@ __device__ __forceinline__ void qk_scores_biased(f32x16 (&s)[2], const typename 
         }
 }
 
+// The online-softmax step of a score tile `s` (the layout above), per query: the running maximum `m_run` joined with the
+// tile's over the lane's 32 scores and both half-waves into `m_new`; returns the base the tile's exponents are taken
+// against.  While only masked keys have been seen that base is 0: -inf - (-inf) would be NaN, and against 0 every p of such
+// a query is exp2(-inf) = 0.
+__device__ __forceinline__ float online_max(const f32x16 (&s)[2], float m_run, float &m_new) {
+    float mt = fmaxf(s[0][0], s[1][0]);
+#pragma unroll
+    for (int r = 1; r < 16; ++r) mt = fmaxf(fmaxf(mt, s[0][r]), s[1][r]);
+    mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
+    m_new = fmaxf(m_run, mt);
+    return m_new == -INFINITY ? 0.0f : m_new;
+}
+
+// online_max plus the denominator: `l_run`, this lane's share of the sum, is rescaled to the new base and takes the tile's
+// exponentials (nothing finite seen before: l_run is 0); m_run becomes the new maximum.  Returns the base.
+__device__ __forceinline__ float online_sum(const f32x16 (&s)[2], float &m_run, float &l_run) {
+    float m_new;
+    const float m_use = online_max(s, m_run, m_new);
+    float sum = 0.0f;
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sum += __builtin_amdgcn_exp2f(s[kb][r] - m_use);
+    l_run = l_run * __builtin_amdgcn_exp2f(m_run - m_use) + sum;
+    m_run = m_new;
+    return m_use;
+}
+
+// ---- LDS pads ----
+
+// The K pad columns meet Q's zero padding, but garbage there could be NaN; tile stores never touch them.
+template <typename T, int D, int NT>
+__device__ __forceinline__ void zero_k_pads(typename Frag<T>::elem *sK, int tid) {
+    using elem = typename Frag<T>::elem;
+    constexpr int K_STRIDE = KvStage<T, D, NT>::K_STRIDE;
+    for (int i = tid; i < KV * (K_STRIDE - D); i += NT)
+        sK[(i / (K_STRIDE - D)) * K_STRIDE + D + i % (K_STRIDE - D)] = (elem)0.0f;
+}
+
 // ---- the single-buffered tile of attention_sets_kernel / attention_bias_kernel: V^T in 32-row blocks, nothing rides in
 // the pads ----
 
-// One-time LDS init: the K pad columns meet Q's zero padding and the V^T pad rows feed O^T rows nobody stores, but garbage
-// there could be NaN; tile stores never touch them.
+// One-time LDS init: the K pad columns as in zero_k_pads, and the V^T pad rows, which feed O^T rows nobody stores but could
+// hold NaN just the same.  The K loop stays written out: with a call of zero_k_pads in its place attention_sets_kernel's
+// code came out different (profiles/attention_contract_codeobj.txt).  A change there has to be made here too.
 template <typename T, int D, int NT>
 __device__ __forceinline__ void zero_kv_pads(typename Frag<T>::elem *sK, typename Frag<T>::elem *sV, int tid) {
     using elem = typename Frag<T>::elem;

@@ -14,7 +14,7 @@
 //   * no load of a step stands inside a branch (see `issue` below): what a ragged tile, a dead query or a padded
 //     contraction must not see is fetched from a place that exists and replaced by zeros when it is used;
 //   * scores as in attention_probs_kernel (qk_scores_biased, attention_stage.h), base-2 online softmax whose running
-//     maximum carries TWO sums, the weighted numerator and the denominator, rescaled together;
+//     maximum (online_max, there too) carries TWO sums, the weighted numerator and the denominator, rescaled together;
 //   * at a head's last tile numerator * (1 / denominator) is added to a per-lane fp32 accumulator, heads in ascending
 //     order; the accumulator is multiplied by 1 / h once and each query row is stored once (lanes 0-31 of a wave: 32
 //     consecutive floats);
@@ -22,10 +22,8 @@
 //     contributes exactly 0 (weights are finite), a sample whose keys are ALL -inf gives 0 * (1 / 0) = NaN for that sample;
 //   * one launch, no atomics, no workspace; every output element has one writer: the same operands and the same prior
 //     `out` give the same bits.
-#include "attention_plan.h"
+#include "attention_checks.h"
 #include "attention_stage.h"
-
-#include <cmath>
 
 namespace {
 
@@ -60,9 +58,7 @@ __global__ __launch_bounds__(WORDS_NT, 2) void attention_words_kernel(
     const T *qrow = q + (b * Mp + (q_ok ? qi : 0)) * ldq;
     const T *kb0 = k + b * Mkp * ldk;
 
-    // the K pad columns meet Q's zero padding, but garbage there could be NaN; tile stores never touch them
-    for (int i = tid; i < KV * (K_STRIDE - D); i += NT)
-        sK[(i / (K_STRIDE - D)) * K_STRIDE + D + i % (K_STRIDE - D)] = (elem)0.0f;
+    zero_k_pads<T, D, NT>(sK, tid);
     {
         float v = -INFINITY, w = 0.0f;
         if (tid < Mk) {
@@ -114,13 +110,8 @@ __global__ __launch_bounds__(WORDS_NT, 2) void attention_words_kernel(
             n_run = 0.0f;
         }
         qk_scores_biased<T, D, NT>(s, sK, sB, qf, ct, scale_log2e, l31, hi);
-        float mt = fmaxf(s[0][0], s[1][0]);
-#pragma unroll
-        for (int r = 1; r < 16; ++r) mt = fmaxf(fmaxf(mt, s[0][r]), s[1][r]);
-        mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
-        const float m_new = fmaxf(m_run, mt);
-        // (only masked keys so far: -inf - (-inf) would be NaN; against 0 every p of such a query is exp2(-inf) = 0)
-        const float m_use = m_new == -INFINITY ? 0.0f : m_new;
+        float m_new;
+        const float m_use = online_max(s, m_run, m_new);
         float sum = 0.0f, num = 0.0f;
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb)
@@ -187,41 +178,23 @@ VTM_EXPORT int vtm_attention_word_map(const void *q, int64_t ldq, const void *k,
                                       int accumulate, vtm_stream_t stream) {
     const char *who = "vtm_attention_word_map";
     VTM_REQUIRE(q && k && weights && out, "%s: null pointer", who);
-    VTM_REQUIRE(((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k)) & 15) == 0 &&
-                    ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(weights)) & 3) == 0 &&
-                    (reinterpret_cast<uintptr_t>(out_rows) & 7) == 0, "%s: q and k must be 16-byte aligned", who);
-    VTM_REQUIRE(B > 0 && h > 0 && Mq > 0 && Mqp >= Mq && Mk > 0 && Mkp >= Mk && d > 0, "%s: bad sizes", who);
+    const bool rest_aligned = ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(weights)) & 3) == 0 &&
+                              (reinterpret_cast<uintptr_t>(out_rows) & 7) == 0;
+    if (int rc = check_qk_aligned(who, q, k, rest_aligned)) return rc;
+    if (int rc = check_map_sizes(who, B, h, Mq, Mqp, Mk, Mkp, d)) return rc;
     VTM_REQUIRE(h < (1ll << 20), "%s: h = %lld heads", who, (long long)h);
     VTM_REQUIRE(Mk <= WORDS_MAX_KEYS, "%s: Mk = %lld, at most %d keys are taken", who, (long long)Mk, WORDS_MAX_KEYS);
-    VTM_REQUIRE(scale > 0.0f && std::isfinite(scale), "%s: scale must be positive and finite", who);
-    if (dtype == VTM_F32)
-        return vtm::fail(VTM_EINVAL, "%s: fp32 operands are not taken (dtype must be VTM_F16 or VTM_BF16)", who);
-    if (dtype != VTM_F16 && dtype != VTM_BF16) return vtm::fail(VTM_EINVAL, "%s: dtype must be VTM_F16 or VTM_BF16", who);
-    VTM_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldq >= h * d && ldk >= h * d && ldo >= Mq,
-                "%s: ldq and ldk must be multiples of 8 and hold h * d channels, ldo >= Mq", who);
-    // K tiles are addressed with 32-bit byte offsets inside one (sample, head) slice (buffer loads)
-    VTM_REQUIRE((Mk * ldk + d) * 2 < (1ll << 31), "%s: a (sample, head) slice of K must stay below 2 GiB", who);
+    if (int rc = check_scale(who, scale)) return rc;
+    if (int rc = check_half_dtype(who, dtype)) return rc;
+    if (int rc = check_qk_rows(who, ldq, ldk, h, d, Mk, ldo, Mq, "ldo >= Mq")) return rc;
     VTM_REQUIRE(B * vtm::cdiv(Mq, WORDS_QB) < (1ll << 31), "%s: grid too large", who);
-    if (bias != nullptr) {
-        VTM_REQUIRE(ld_bias >= Mk, "%s: ld_bias = %lld is shorter than a row of Mk = %lld values", who, (long long)ld_bias,
-                    (long long)Mk);
-        // one row for every sample (stride 0), or per-sample rows that do not overlap
-        VTM_REQUIRE(bias_batch_stride == 0 || bias_batch_stride >= ld_bias,
-                    "%s: bias_batch_stride = %lld must be 0 or at least ld_bias = %lld", who, (long long)bias_batch_stride,
-                    (long long)ld_bias);
-    }
-    VTM_REQUIRE(ld_w >= Mk, "%s: ld_w = %lld is shorter than a row of Mk = %lld weights", who, (long long)ld_w, (long long)Mk);
-    VTM_REQUIRE(w_batch_stride == 0 || w_batch_stride >= ld_w, "%s: w_batch_stride = %lld must be 0 or at least ld_w = %lld",
-                who, (long long)w_batch_stride, (long long)ld_w);
+    if (bias != nullptr)
+        if (int rc = check_key_rows(who, "bias", "values", ld_bias, bias_batch_stride, Mk)) return rc;
+    if (int rc = check_key_rows(who, "w", "weights", ld_w, w_batch_stride, Mk)) return rc;
     hipStream_t s = vtm::as_stream(stream);
-    return with_head_dim(d, [&](auto dim) {
-        constexpr int D = decltype(dim)::value;
-        if (dtype == VTM_F16)
-            launch_words<__half, D>(q, ldq, k, ldk, out, ldo, B, h, Mq, Mqp, Mk, Mkp, scale, bias, bias_batch_stride, weights,
-                                    w_batch_stride, out_rows, accumulate != 0, s);
-        else
-            launch_words<vtm_bf16, D>(q, ldq, k, ldk, out, ldo, B, h, Mq, Mqp, Mk, Mkp, scale, bias, bias_batch_stride, weights,
-                                      w_batch_stride, out_rows, accumulate != 0, s);
+    return with_half_head_dim(dtype, d, [&](auto t, auto dim) {
+        launch_words<decltype(t), decltype(dim)::value>(q, ldq, k, ldk, out, ldo, B, h, Mq, Mqp, Mk, Mkp, scale, bias,
+                                                        bias_batch_stride, weights, w_batch_stride, out_rows, accumulate != 0, s);
         return vtm::launch_status(who);
     });
 }
