@@ -146,7 +146,7 @@ def census(S, tile=TILE, wave=WAVE, thr=DEFER_THR, dead=None, masked_below=-np.i
 
 
 def online_softmax64(S_sets, V_sets=None, *, tile=TILE, wave=WAVE, thr=DEFER_THR, dead=None, drop_alpha=False,
-                     no_set_reset=False, exp_against_zero=False):
+                     no_set_reset=False, exp_against_zero=False, stale_shift=False):
     """The kernels' state machine in float64: for every set s (S_sets[s]: queries x keys of the set, log2 units; V_sets[s]:
     keys x columns, or None) walk the tiles, keep (m_run, l_run, o) per row, follow the maximum only where the wave's branch
     is taken, take the exponent against m_run (against 0 while it is -inf) and fold the set as o / l.  Returns a list of
@@ -156,7 +156,10 @@ def online_softmax64(S_sets, V_sets=None, *, tile=TILE, wave=WAVE, thr=DEFER_THR
       drop_alpha        a taken rescale of a finite state does not multiply o and l_run (the word map's numerator is o);
       no_set_reset      m_run and l_run are carried across the end of a set (o is cleared by the fold itself);
       exp_against_zero  every exponent is taken against 0 instead of the running maximum.  Softmax is shift-invariant, so
-                        this shows only through the range of the format p is computed in: p passes through fp32 here."""
+                        this shows only through the range of the format p is computed in: p passes through fp32 here;
+      stale_shift       the tile after a taken rescale of a finite state still takes its exponents against the maximum
+                        from before that rescale (the kernels that carry the shift in the query's spare k-slot and do
+                        not write it back after a raise)."""
     Mq = S_sets[0].shape[0]
     rows = Mq + (-Mq % wave)
     nw = rows // wave
@@ -168,6 +171,7 @@ def online_softmax64(S_sets, V_sets=None, *, tile=TILE, wave=WAVE, thr=DEFER_THR
         o = None if V is None else np.zeros((rows, V.shape[1]))
         if not no_set_reset:
             m, l = np.full(rows, -np.inf), np.zeros(rows)
+        stale, m_stale = np.zeros(rows, dtype=bool), np.zeros(rows)
         for t0 in range(0, P.shape[1], tile):
             s = P[:, t0:t0 + tile]
             mt = s.max(1)
@@ -178,11 +182,16 @@ def online_softmax64(S_sets, V_sets=None, *, tile=TILE, wave=WAVE, thr=DEFER_THR
             alpha[fin] = np.exp2(m[fin] - m_new[fin])
             if drop_alpha:
                 alpha[fin & take_row] = 1.0
+            raised = fin & take_row
+            m_before = m
             m = m_new
             l = l * alpha
             m_use = np.where(np.isneginf(m), 0.0, m)
             if exp_against_zero:
                 m_use = np.zeros(rows)
+            if stale_shift:
+                m_use = np.where(stale, m_stale, m_use)
+                stale, m_stale = raised, m_before
             with np.errstate(over="ignore"):
                 p = np.exp2(s - m_use[:, None])
                 if exp_against_zero:

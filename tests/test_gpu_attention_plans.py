@@ -329,11 +329,17 @@ def _fold_bias_word(lg, dtype):
 
 
 def run_case(L, oracle, call, dtype, d, B, h, Mq, Mk, expect, share=1, counts=None, ws="lib", mult=None, seed=0,
-             min_live_per_tier=1):
+             min_live_per_tier=1, hook=None):
     """One raw library call.  `call`: kv / bounded / shared_bounded / folded; `counts`: per-sample query counts (None =
     unbounded); `ws`: "lib" (the size the library asks for), None (no workspace) or a byte count; `mult` (folded keys):
     (B, Mk) multiplicities, 0 = no such key -- the oracle attends over the sequence with the copies.  `expect` =
-    (family, plan, combine).  Returns the Selection."""
+    (family, plan, combine).  Returns the Selection.
+
+    `hook` (tests/test_gpu_core_softmax_corners.py) brings operands and a comparison of its own and leaves everything
+    else -- windows, garbage, canaries, the selection and the workspace check -- to this function:
+    hook.operands(sel, q, k, v, rows, cnt, kc) writes the live windows of q / k / v in place of the planted keys below and
+    adds the rows it wants compared; hook.compare(sel, launch, out, vt, rows, cnt, kc) stands in for the oracle comparison
+    (`launch()` runs the call again on what vt holds by then, checks 1 and 2 included, and returns its output)."""
     n_cus = cus()
     f32 = dtype == torch.float32
     C = h * d
@@ -377,7 +383,9 @@ def run_case(L, oracle, call, dtype, d, B, h, Mq, Mk, expect, share=1, counts=No
     tiers = sorted({ns for _, ns, _ in sel.split})
     for ns in tiers:
         assert sum(1 for _, n in live_split if n == ns) >= min_live_per_tier, ("no live item splits", ns)
-    for bs in range(src):
+    if hook is not None:
+        hook.operands(sel, q, k, v, rows, cnt, kc)
+    for bs in range(src if hook is None else 0):
         mk = kc[bs]
         targets = {}
         for ns in tiers or [1]:
@@ -424,37 +432,42 @@ def run_case(L, oracle, call, dtype, d, B, h, Mq, Mk, expect, share=1, counts=No
     # output window (B, Mqp, C) with ldo > C inside a buffer with a guard block behind the last row
     ldo = C + 24
     canary = CANARY32 if f32 else CANARY
-    obuf = torch.full(((B * Mqp + GUARD_ROWS) * ldo,), canary, dtype=torch.int32 if f32 else torch.int16, device=DEV)
-    wsb, nb = None, 0
-    if ws is not None:
-        nb = _ws_size(L, call, d, B, h, Mq, Mk, counts, ws, f32)
-        wsb = torch.full((nb + 65536,), -1, dtype=torch.int8, device=DEV)
+    nb = 0 if ws is None else _ws_size(L, call, d, B, h, Mq, Mk, counts, ws, f32)
     qc = None if counts is None else torch.tensor(counts, dtype=torch.int32, device=DEV)
     kcd = torch.tensor(kc, dtype=torch.int32, device=DEV) if mult is not None else None
     lib, s = L.lib(), L._stream()
     P = lambda t: None if t is None else t.data_ptr()
-    head = (P(q), 2 * C, P(k), 3 * C, P(vt), ldvt, P(obuf), ldo, DT_CODE[dtype], B, h, Mq, Mqp, Mk, Mkp, d, float(scale))
-    if call == "kv":
-        rc = lib.vtm_attention_kv(*head, share, P(wsb), nb, s)
-    elif call == "bounded":
-        rc = lib.vtm_attention_kv_bounded(*head, P(qc), P(wsb), nb, s)
-    elif call == "shared_bounded":
-        rc = lib.vtm_attention_kv_shared_bounded(*head, share, P(qc), P(wsb), nb, s)
-    else:
-        rc = lib.vtm_attention_kv_folded(*head, P(qc), P(kcd), P(kbias), Mk, P(wsb), nb, s)
-    L._check(rc, call)
-    torch.cuda.synchronize()
-    # 1. nothing written outside the (B, Mqp, C) window
-    ob = obuf.view(B * Mqp + GUARD_ROWS, ldo)
-    assert bool((ob[:B * Mqp, C:] == canary).all()), "a write into the gap columns past C"
-    assert bool((ob[B * Mqp:] == canary).all()), "a write behind the last output row"
-    if f32:
-        assert bool((ob[:B * Mqp].view(B, Mqp, ldo)[:, Mq:] == canary).all()), "a write into the rows Mq .. Mqp"
-    # 2. the plan the launch took
-    if wsb is not None:
-        _check_workspace(sel, wsb, nb)
+
+    def launch():
+        obuf = torch.full(((B * Mqp + GUARD_ROWS) * ldo,), canary, dtype=torch.int32 if f32 else torch.int16, device=DEV)
+        wsb = None if ws is None else torch.full((nb + 65536,), -1, dtype=torch.int8, device=DEV)
+        head = (P(q), 2 * C, P(k), 3 * C, P(vt), ldvt, P(obuf), ldo, DT_CODE[dtype], B, h, Mq, Mqp, Mk, Mkp, d, float(scale))
+        if call == "kv":
+            rc = lib.vtm_attention_kv(*head, share, P(wsb), nb, s)
+        elif call == "bounded":
+            rc = lib.vtm_attention_kv_bounded(*head, P(qc), P(wsb), nb, s)
+        elif call == "shared_bounded":
+            rc = lib.vtm_attention_kv_shared_bounded(*head, share, P(qc), P(wsb), nb, s)
+        else:
+            rc = lib.vtm_attention_kv_folded(*head, P(qc), P(kcd), P(kbias), Mk, P(wsb), nb, s)
+        L._check(rc, call)
+        torch.cuda.synchronize()
+        # 1. nothing written outside the (B, Mqp, C) window
+        ob = obuf.view(B * Mqp + GUARD_ROWS, ldo)
+        assert bool((ob[:B * Mqp, C:] == canary).all()), "a write into the gap columns past C"
+        assert bool((ob[B * Mqp:] == canary).all()), "a write behind the last output row"
+        if f32:
+            assert bool((ob[:B * Mqp].view(B, Mqp, ldo)[:, Mq:] == canary).all()), "a write into the rows Mq .. Mqp"
+        # 2. the plan the launch took
+        if wsb is not None:
+            _check_workspace(sel, wsb, nb)
+        return ob[:B * Mqp, :C].contiguous().view(dtype).view(B, Mqp, C)
+
+    out = launch()
+    if hook is not None:
+        hook.compare(sel, launch, out, vt, rows, cnt, kc)
+        return sel
     # 3. the oracle, over each sample's own keys (folded: with the copies)
-    out = ob[:B * Mqp, :C].contiguous().view(dtype).view(B, Mqp, C)
     worst, scale_max = 0.0, 0.0 if f32 else 1.0       # (fp32: of max|ref| over the launch, not of max(1, .))
     for b in range(B):
         bs = b % src
@@ -562,8 +575,8 @@ PLANS = ("single", "tail", "device", "nows", "split_all")
 EXPECT = {"single": "single", "tail": "tail", "device": "device", "nows": "single", "split_all": "split_all"}
 
 
-def _plan_case(L, oracle, kind, dtype, d, plan, fold=False, ng=1, src=1, h=8):
-    n_cus = cus()
+def plan_args(kind, d, plan, n_cus, fold=False, ng=1, src=1, h=8):
+    """The run_case arguments of one (family, plan) case on a device of `n_cus` CUs (host arithmetic only)."""
     F = Family(kind, d, ng)
     share = ng
     if plan in ("device", "nows") and ng == 1:
@@ -597,8 +610,24 @@ def _plan_case(L, oracle, kind, dtype, d, plan, fold=False, ng=1, src=1, h=8):
     if EXPECT[plan] != "single":
         combine = "f32" if kind == "f32" else "16" if kind != "k" else ("plain" if (pv16_for(d) or EXPECT[plan] != "tail") else "parts")
     mult = _mult(B, Mk, d + B) if fold else None
-    return run_case(L, oracle, call, dtype, d, B, h, Mq, Mk, (kind, EXPECT[plan], combine), share=share, counts=counts,
-                    ws=ws, mult=mult, seed=zlib.crc32(f"{kind}/{plan}/{ng}/{src}".encode()) % 1000)
+    return dict(call=call, d=d, B=B, h=h, Mq=Mq, Mk=Mk, expect=(kind, EXPECT[plan], combine), share=share, counts=counts,
+                ws=ws, mult=mult, seed=zlib.crc32(f"{kind}/{plan}/{ng}/{src}".encode()) % 1000)
+
+
+def ws_size_restated(call, d, B, h, Mq, Mk, counts, ws, f32, n_cus):
+    """_ws_size from the restated planners (test_workspace_sizes_equal_the_restated_plans and
+    test_binding_workspace_holds_the_fp32_plans hold them to the library's exports)."""
+    if ws != "lib":
+        return int(ws)
+    size = ws_bytes_f32 if f32 else (lambda B, h, Mq, Mk, d, bounded, n: ws_bytes_any(B, h, Mq, Mk, d, bounded, n))
+    nb = size(B, h, Mq, Mk, d, False, n_cus)
+    if counts is not None:
+        nb = max(nb, size(B, h, Mq, Mk, d, True, n_cus))
+    return max(nb, 65536)
+
+
+def _plan_case(L, oracle, kind, dtype, d, plan, fold=False, ng=1, src=1, h=8):
+    return run_case(L, oracle, dtype=dtype, **plan_args(kind, d, plan, cus(), fold=fold, ng=ng, src=src, h=h))
 
 
 DTYPES = [torch.float16, torch.bfloat16]
