@@ -898,6 +898,57 @@ int vtm_invert_step(const void *x, const void *model_out, const float *h1, const
 int vtm_noise_levels(const void *x0, void *levels, const float *coef, int dtype, int64_t n, int64_t P, vtm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Frame-keyed noise -- N(0, 1) noise addressed the way every other caller-side operand is: per frame.  The normal of element
+ * e of whole-video frame `frame` at step `step` is a PURE FUNCTION of (seed, tag, step, frame, e) -- a counter-based generator,
+ * no state and no stream position -- so a stochastic step's bits depend neither on how the video is cut into chunks, nor on
+ * the chunks' order, nor on the rank or the stream that runs a chunk (noise.FrameNoise).  The keying is part of this contract:
+ *     generator  Philox4x32-10 (Salmon et al., SC'11; Random123's philox4x32, 10 rounds): multipliers 0xD2511F53, 0xCD9E8D57,
+ *                Weyl constants 0x9E3779B9, 0xBB67AE85; per round
+ *                c = [hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)], then k0 += W0, k1 += W1.
+ *     key        (seed & 0xffffffff, seed >> 32)
+ *     counter    (e >> 2, frame, step, tag)   e: the element's offset inside its frame (E = C * H * W elements);
+ *                frame: the whole-video row, frame0 + (frame_ids ? frame_ids[f] : f);  tag: names the use (VTM_NOISE_*; a
+ *                caller's own tags start at VTM_NOISE_USER).  Element e takes normal number e & 3 of its quad.
+ *     normals    from the outputs o0 .. o3, for the pairs (a, b) = (o0, o1) and (o2, o3):
+ *                u1 = ((a >> 9) + 0.5f) * 2^-23 (exact in fp32, inside (0, 1));  u2 = (b >> 8) * 2^-24;
+ *                r = sqrtf(-2 logf(u1));  the pair's normals are r * cospif(2 u2), r * sinpif(2 u2)
+ *                -- the precise fp32 functions, no fast-math.  u1 >= 2^-24, so |z| <= sqrt(48 ln 2) = 5.7682 by construction.
+ * In a 16-bit model dtype the fp32 normal is rounded ONCE to the dtype before any use, so a keyed step computes exactly what
+ * the tensor-noise step computes from vtm_frame_noise's output.
+ *
+ * vtm_frame_noise -- out (S, F, E) contiguous in `dtype`: out[s, f, e] = the normal of element e of frame frame0 + row(f) at
+ *   step step0 + s (mod 2^32).  frame_ids: DEVICE int32 (F entries) or NULL (row f); frame0 in [0, 2^31).  One thread per quad,
+ *   one quad-wide store (16 bytes fp32, 8 bytes 16-bit) when E % 4 == 0 and out is aligned to it, element stores otherwise;
+ *   which of the two changes no bit.  E in [1, 2^34], F <= 2^20, S * F * ceil(E / 4) < 2^32 - 256; S == 0 or F == 0 is VTM_OK.
+ * vtm_philox_bits -- the integer core alone: out[i] = Philox4x32-10(ctr[i], key of seed) for n counters of four uint32 (both
+ *   DEVICE, 16-byte aligned), so the generator can be pinned exactly on the device.
+ * vtm_guided_step_keyed / vtm_solver_step_keyed -- vtm_guided_step / vtm_solver_step with (seed, step, tag, frame0) in place
+ *   of the noise pointer: the noise of the chunk is drawn where it is used (no randn launch, no (F, E) read), otherwise the
+ *   same expression, operation for operation, and the same launch shapes; every other argument is the tensor form's.  frame0:
+ *   the whole-video row of row 0 of x / x_out / h1 / h2 / h_out -- a caller that steps an ascending run of frames offsets those
+ *   pointers to the run's first row, sends no frame_ids, and names the first row here; 0 otherwise.  With sigma == 0
+ *   (c_noise == 0) the term is absent and the key is not used.  One launch, no workspace, no atomics; on a bad argument
+ *   (VTM_EINVAL) nothing is launched.
+ * ---------------------------------------------------------------------------------------------- */
+#define VTM_NOISE_INIT   0   /* the initial latents */
+#define VTM_NOISE_STEP   1   /* a sampler's stochastic term; counter.step = the step index i */
+#define VTM_NOISE_LEVELS 2   /* edit-friendly inversion's independent levels; counter.step = the level index k */
+#define VTM_NOISE_USER   16  /* the first tag that is the caller's */
+int vtm_frame_noise(void *out, int dtype, int64_t S, int64_t F, int64_t E, const int32_t *frame_ids, int64_t frame0,
+                    uint64_t seed, uint32_t step0, uint32_t tag, vtm_stream_t stream);
+int vtm_philox_bits(const uint32_t *ctr, int64_t n, uint64_t seed, uint32_t *out, vtm_stream_t stream);
+int vtm_guided_step_keyed(const void *x, const void *model_out, uint64_t seed, uint32_t step, uint32_t tag, int64_t frame0,
+                          int dtype, int64_t F, int64_t E, int64_t groups, int64_t g_uncond, int64_t g_cond,
+                          const int32_t *frame_ids, int pred_type, float guidance, float rescale, float sqrt_alpha,
+                          float sqrt_beta, float c_x0, float c_eps, float sigma, void *x_out, void *eps_out, void *x0_out,
+                          vtm_stream_t stream);
+int vtm_solver_step_keyed(const void *x, const void *model_out, uint64_t seed, uint32_t step, uint32_t tag, int64_t frame0,
+                          const float *h1, const float *h2, int dtype, int64_t F, int64_t E, int64_t groups, const float *w,
+                          int64_t g_ref, const int32_t *frame_ids, int pred_type, float rescale, float sqrt_alpha,
+                          float sqrt_beta, float c_x, float c_x0, float c_h1, float c_h2, float c_noise, void *x_out,
+                          float *h_out, void *eps_out, void *x0_out, vtm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * vtm_semantic_guidance -- semantic guidance (SEGA, Brack et al.; Diffusers' SemanticStableDiffusionPipeline, and with
  * `regions` the masked form of LEditsPPPipelineStableDiffusion) for ONE CHUNK in one launch: the combined model output that
  * vtm_guided_step / vtm_solver_step then take as a single group.  Every edit concept has its own group of the UNet output;

@@ -11,6 +11,7 @@ from .p2p import CrossEdit, register_cross_attention_control, unregister_cross_a
 from .blend import LocalBlend, register_local_blend, unregister_local_blend
 from .sampler import GuidedDDIM, GuidedDPMSolver
 from .inversion import EditFriendlyInversion
+from .noise import FrameNoise
 from .pag import register_perturbed_attention, remove_perturbed_attention
 from .sag import SelfAttentionGuidance, register_self_attention_guidance, unregister_self_attention_guidance
 from .freeu import register_freeu, unregister_freeu
@@ -22,4 +23,4 @@ __all__ = ["merge", "patch", "apply_patch", "remove_patch", "update_patch", "col
            "LocalBlend", "register_local_blend", "unregister_local_blend",
            "GuidedDDIM", "GuidedDPMSolver", "register_perturbed_attention", "remove_perturbed_attention",
            "SelfAttentionGuidance", "register_self_attention_guidance", "unregister_self_attention_guidance",
-           "register_freeu", "unregister_freeu", "EditConcept", "SemanticGuidance", "EditFriendlyInversion"]
+           "register_freeu", "unregister_freeu", "EditConcept", "SemanticGuidance", "EditFriendlyInversion", "FrameNoise"]

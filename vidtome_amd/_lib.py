@@ -12,6 +12,7 @@ from __future__ import annotations
 import ctypes
 import functools
 import math
+import operator
 import os
 import struct
 import threading
@@ -30,6 +31,7 @@ PROBS_MAX_KEYS, PROBS_MAX_HEADS = 256, 40   # what vtm_attention_probs takes (cs
 _DT = {torch.float32: VTM_F32, torch.float16: VTM_F16, torch.bfloat16: VTM_BF16}
 
 _vp, _i64, _int, _f32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float
+_u64, _u32 = ctypes.c_uint64, ctypes.c_uint32
 _lib: Optional[ctypes.CDLL] = None
 
 _SIGNATURES = {
@@ -132,6 +134,12 @@ _SIGNATURES = {
     "vtm_invert_step": ([_vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, ctypes.POINTER(_f32), _i64, _vp, _int, _f32, _f32, _f32, _f32,
                          _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp], _int),
     "vtm_noise_levels": ([_vp, _vp, _vp, _int, _i64, _i64, _vp], _int),
+    "vtm_frame_noise": ([_vp, _int, _i64, _i64, _i64, _vp, _i64, _u64, _u32, _u32, _vp], _int),
+    "vtm_philox_bits": ([_vp, _i64, _u64, _vp, _vp], _int),
+    "vtm_guided_step_keyed": ([_vp, _vp, _u64, _u32, _u32, _i64, _int, _i64, _i64, _i64, _i64, _i64, _vp, _int, _f32, _f32, _f32,
+                               _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp], _int),
+    "vtm_solver_step_keyed": ([_vp, _vp, _u64, _u32, _u32, _i64, _vp, _vp, _int, _i64, _i64, _i64, ctypes.POINTER(_f32), _i64, _vp,
+                               _int, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp], _int),
     "vtm_semantic_guidance": ([_vp, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _i64, ctypes.POINTER(ctypes.c_int32),
                                ctypes.POINTER(_f32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double),
                                ctypes.POINTER(_f32), ctypes.POINTER(_f32), ctypes.POINTER(ctypes.c_int32), _vp, _vp, _i64, _vp,
@@ -800,6 +808,25 @@ PRED_EPSILON, PRED_V, PRED_SAMPLE = 0, 1, 2     # include/vidtome_hip.h VTM_PRED
 GUIDED_STEP_THREADS = 1024                      # csrc/guided_step.hip: threads of the per-frame (rescale) workgroup
 
 
+NOISE_INIT, NOISE_STEP, NOISE_LEVELS, NOISE_USER = 0, 1, 2, 16     # include/vidtome_hip.h VTM_NOISE_*
+
+
+def _noise_key(who: str, key, noise=None):
+    """``key`` of a keyed call, checked: None, or (seed in [0, 2^64), step in [0, 2^32), tag in [0, 2^32)) as ints; it
+    stands in place of ``noise``."""
+    if key is None:
+        return None
+    if noise is not None:
+        raise RuntimeError(f"{who}: both a noise tensor and a noise key")
+    try:
+        seed, step, tag = (operator.index(v) for v in key)
+    except (TypeError, ValueError):
+        raise RuntimeError(f"{who}: key must be three integers (seed, step, tag)") from None
+    if not 0 <= seed < 2 ** 64 or not 0 <= step < 2 ** 32 or not 0 <= tag < 2 ** 32:
+        raise RuntimeError(f"{who}: key (seed {seed}, step {step}, tag {tag}) outside [0, 2^64) x [0, 2^32) x [0, 2^32)")
+    return seed, step, tag
+
+
 def guided_step_chunk(dtype: torch.dtype) -> int:
     """Elements of a 16-byte chunk, the unit csrc/guided_step.hip moves and hands to a lane (4 fp32, 8 fp16 / bf16)."""
     return 16 // torch.empty((), dtype=dtype).element_size()
@@ -889,15 +916,17 @@ def guided_step(x: torch.Tensor, model_out: torch.Tensor, sqrt_alpha: float, sqr
                 sigma: float = 0.0, *, groups: int = 2, g_uncond: Optional[int] = None, g_cond: Optional[int] = None,
                 frame_ids=None, pred_type: int = PRED_EPSILON, guidance: float = 7.5, rescale: float = 0.0,
                 noise: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, want_x: bool = True,
-                want_eps: bool = False, want_x0: bool = False):
+                want_eps: bool = False, want_x0: bool = False, key=None):
     """One chunk's guided DDIM step (vtm_guided_step, include/vidtome_hip.h): ``x`` (n_frames, ...) the whole-video latents,
     ``model_out`` (groups * F, ...) the UNet output of the chunk, group-major; the chunk's frame f is row ``frame_ids[f]`` of x
     (a host sequence / CPU tensor, checked and uploaded unless it is an ascending run; or a device int32 tensor, taken as it
     is; None: the chunk is the whole video).  ``g_uncond`` / ``g_cond`` default to the last two groups (one group: no
     guidance, g_cond = -1).  ``out`` receives x' in the chunk's rows and may be x; None allocates a new tensor when the chunk
     is the whole video and otherwise means x (in place: a new tensor would have rows that nobody wrote).  Returns
-    (out or None, eps or None, x0 or None) -- eps / x0 chunk-local (F, ...), allocated when asked for."""
+    (out or None, eps or None, x0 or None) -- eps / x0 chunk-local (F, ...), allocated when asked for.  ``key`` = (seed, step,
+    tag) in place of ``noise``: the frame-keyed noise of those frames, drawn inside the launch (vtm_guided_step_keyed)."""
     who = "guided_step"
+    key = _noise_key(who, key, noise)
     groups = int(groups)
     if g_uncond is None:
         g_uncond = max(groups - 2, 0)
@@ -917,11 +946,19 @@ def guided_step(x: torch.Tensor, model_out: torch.Tensor, sqrt_alpha: float, sqr
             raise RuntimeError(f"{who}: rescale > 0 needs a conditional group and frames of at least 2 elements")
 
     F, E, ids, out, eps, x0, skip = _step_operands(
-        who, x, model_out, groups, pred_type, rescale, frame_ids, noise, "sigma" if sigma != 0.0 else None, out,
+        who, x, model_out, groups, pred_type, rescale, frame_ids, noise, "sigma" if sigma != 0.0 and key is None else None, out,
         (want_x, want_eps, want_x0), want_x or want_eps or want_x0, check_groups, check_rescale)
     if F == 0:
         return (out if want_x else None), eps, x0
+    frame0 = skip // E
     skip *= x.element_size()
+    if key is not None:
+        _check(lib().vtm_guided_step_keyed(x.data_ptr() + skip, model_out.data_ptr(), *key, frame0, dtype_code(x), F, E, groups,
+                                           g_uncond, g_cond, _ptr(ids), pred_type, float(guidance), rescale, float(sqrt_alpha),
+                                           float(sqrt_beta), float(c_x0), float(c_eps), sigma,
+                                           out.data_ptr() + skip if want_x else None, _ptr(eps), _ptr(x0), _stream()),
+               "vtm_guided_step_keyed")
+        return (out if want_x else None), eps, x0
     _check(lib().vtm_guided_step(x.data_ptr() + skip, model_out.data_ptr(), _ptr(noise if sigma != 0.0 else None),
                                  dtype_code(x), F, E, groups, g_uncond, g_cond, _ptr(ids), pred_type, float(guidance),
                                  rescale, float(sqrt_alpha), float(sqrt_beta), float(c_x0), float(c_eps), sigma,
@@ -967,20 +1004,23 @@ def solver_step(x: torch.Tensor, model_out: torch.Tensor, weights, sqrt_alpha: f
                 c_h1: float = 0.0, c_h2: float = 0.0, c_noise: float = 0.0, *, h1: Optional[torch.Tensor] = None,
                 h2: Optional[torch.Tensor] = None, h_out: Optional[torch.Tensor] = None, g_ref: Optional[int] = None,
                 frame_ids=None, pred_type: int = PRED_EPSILON, rescale: float = 0.0, noise: Optional[torch.Tensor] = None,
-                out: Optional[torch.Tensor] = None, want_x: bool = True, want_eps: bool = False, want_x0: bool = False):
+                out: Optional[torch.Tensor] = None, want_x: bool = True, want_eps: bool = False, want_x0: bool = False,
+                key=None):
     """One chunk's step of a multistep solver (vtm_solver_step, include/vidtome_hip.h): ``x``, ``model_out``, ``frame_ids``,
-    ``noise``, ``out`` and the result (out or None, eps or None, x0 or None) as in ``guided_step``.  ``weights``: one host
+    ``noise`` or ``key`` (vtm_solver_step_keyed), ``out`` and the result (out or None, eps or None, x0 or None) as in
+    ``guided_step``.  ``weights``: one host
     number per group of model_out (their count is the number of groups; a group of weight 0 is never read); ``g_ref``: the
     group whose per-frame std ``rescale`` restores (default: the last).  ``h1`` / ``h2``: whole-video fp32 tensors shaped like
     x with the clean-sample predictions of the two previous steps, needed where ``c_h1`` / ``c_h2`` is not 0; ``h_out``: where
     this step's goes (it may be h1 or h2)."""
     who = "solver_step"
+    key = _noise_key(who, key, noise)
     c_x, c_x0, c_h1, c_h2, c_noise, rescale = (float(v) for v in (c_x, c_x0, c_h1, c_h2, c_noise, rescale))
     weights, groups, pred_type, g_ref, check_groups, check_rescale, check_history = _solver_checks(
         who, x, weights, pred_type, g_ref, rescale, ((h1, "h1", c_h1), (h2, "h2", c_h2), (h_out, "h_out", 0.0)))
 
     F, E, ids, out, eps, x0, skip = _step_operands(
-        who, x, model_out, groups, pred_type, rescale, frame_ids, noise, "c_noise" if c_noise != 0.0 else None, out,
+        who, x, model_out, groups, pred_type, rescale, frame_ids, noise, "c_noise" if c_noise != 0.0 and key is None else None, out,
         (want_x, want_eps, want_x0), want_x or want_eps or want_x0 or h_out is not None, check_groups, check_rescale,
         check_history, ((h1, "h1"), (h2, "h2"), (h_out, "h_out")))
     if F == 0:
@@ -989,6 +1029,13 @@ def solver_step(x: torch.Tensor, model_out: torch.Tensor, weights, sqrt_alpha: f
     def hist(t, used=True):
         return t.data_ptr() + skip * 4 if (t is not None and used) else None
     skip_x = skip * x.element_size()
+    if key is not None:
+        _check(lib().vtm_solver_step_keyed(x.data_ptr() + skip_x, model_out.data_ptr(), *key, skip // E, hist(h1, c_h1 != 0.0),
+                                           hist(h2, c_h2 != 0.0), dtype_code(x), F, E, groups, (_f32 * groups)(*weights), g_ref,
+                                           _ptr(ids), pred_type, rescale, float(sqrt_alpha), float(sqrt_beta), c_x, c_x0, c_h1,
+                                           c_h2, c_noise, out.data_ptr() + skip_x if want_x else None, hist(h_out), _ptr(eps),
+                                           _ptr(x0), _stream()), "vtm_solver_step_keyed")
+        return (out if want_x else None), eps, x0
     _check(lib().vtm_solver_step(x.data_ptr() + skip_x, model_out.data_ptr(), _ptr(noise if c_noise != 0.0 else None),
                                  hist(h1, c_h1 != 0.0), hist(h2, c_h2 != 0.0), dtype_code(x), F, E, groups,
                                  (_f32 * groups)(*weights), g_ref, _ptr(ids), pred_type, rescale, float(sqrt_alpha),
@@ -1065,6 +1112,56 @@ def noise_levels(x0: torch.Tensor, levels: torch.Tensor, coef: torch.Tensor) -> 
         _check(lib().vtm_noise_levels(x0.data_ptr(), levels.data_ptr(), coef.data_ptr(), dtype_code(x0), n, x0.numel(),
                                       _stream()), "vtm_noise_levels")
     return levels
+
+
+@_on_device
+def frame_noise(out: torch.Tensor, seed: int, step0: int, tag: int, frame_ids=None, n_frames: Optional[int] = None
+                ) -> torch.Tensor:
+    """Frame-keyed N(0, 1) noise (vtm_frame_noise, include/vidtome_hip.h "Frame-keyed noise") into ``out`` (S, F, ...),
+    contiguous fp16 / bf16 / fp32 on the GPU: out[s, f] is the noise of whole-video frame ``frame_ids[f]`` (a host sequence,
+    checked against ``n_frames`` when that is given; or a device int32 tensor, taken as it is; None: frame f, and ``n_frames``
+    when given must be F) at step
+    ``step0 + s``.  One launch.  Returns out."""
+    who = "frame_noise"
+    if not isinstance(out, torch.Tensor) or out.dim() < 3 or out.dtype not in _DT:
+        raise RuntimeError(f"{who}: out must be a (steps, frames, ...) fp16 / bf16 / fp32 tensor")
+    seed, step0, tag = _noise_key(who, (seed, step0, tag))
+    S, F = out.shape[0], out.shape[1]
+    E = math.prod(out.shape[2:])
+    if frame_ids is None:
+        if n_frames is not None and int(n_frames) != F:
+            raise RuntimeError(f"{who}: n_frames = {n_frames} for out's {F} frames (without frame_ids they are frames 0 .. F - 1)")
+        first, ids = 0, None
+    else:
+        first, ids, n = _frame_rows(frame_ids, 2 ** 31 if n_frames is None else int(n_frames), who)
+        if n != F:
+            raise RuntimeError(f"{who}: {n} frame_ids for out's {F} frames")
+    if E < 1 and S and F:
+        raise RuntimeError(f"{who}: empty frames")
+    _req(out, "out")
+    if isinstance(ids, torch.Tensor) and _req(ids, "frame_ids").device != out.device:
+        raise RuntimeError(f"{who}: frame_ids lives on {ids.device}, out on {out.device}")
+    if isinstance(ids, list):
+        ids = torch.tensor(ids, dtype=torch.int32, device=out.device)
+    if S and F:
+        _check(lib().vtm_frame_noise(out.data_ptr(), dtype_code(out), S, F, E, _ptr(ids), first, seed, step0, tag, _stream()),
+               "vtm_frame_noise")
+    return out
+
+
+@_on_device
+def philox_bits(counters: torch.Tensor, seed: int) -> torch.Tensor:
+    """Philox4x32-10 of every row of ``counters`` (n, 4) under the key of ``seed`` (vtm_philox_bits): a new (n, 4) tensor.
+    Both are device int32 tensors holding the uint32 bit patterns (torch's uint32 support is partial)."""
+    who = "philox_bits"
+    if not isinstance(counters, torch.Tensor) or counters.dtype != torch.int32 or counters.dim() != 2 or counters.shape[1] != 4:
+        raise RuntimeError(f"{who}: counters must be an (n, 4) int32 tensor of uint32 bit patterns")
+    seed = _noise_key(who, (seed, 0, 0))[0]
+    _req(counters, "counters")
+    out = torch.empty_like(counters)
+    if counters.shape[0]:
+        _check(lib().vtm_philox_bits(counters.data_ptr(), counters.shape[0], seed, out.data_ptr(), _stream()), "vtm_philox_bits")
+    return out
 
 
 @_on_device

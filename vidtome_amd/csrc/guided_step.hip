@@ -35,13 +35,14 @@ __device__ __forceinline__ float guide(const Step &s, float mu, float mc) { retu
 
 // step_core.h's policy: the launch's operands.  mu / mc: the unconditional and the conditional group of model_out (mc null
 // without guidance); noise and any output may be null.  x_out may be x: a chunk is read before it is written, by the same
-// thread.
-template <typename T>
+// thread.  KEYED (vtm_guided_step_keyed): there is no noise tensor, the chunk's noise is drawn from kn where it is used.
+template <typename T, bool KEYED = false>
 struct Guided {
     static constexpr int N = 16 / sizeof(T);
     const Step &s;
     const T *x, *mu, *mc, *noise;
     T *x_out, *eps_out, *x0_out;
+    vtm::KeyedNoise kn{};
 
     template <bool VEC>
     __device__ __forceinline__ void m(int64_t local, int n, float *out) const {
@@ -59,18 +60,19 @@ struct Guided {
 
     // factor: the frame's rescale factor (1 and unused without rescale)
     template <bool VEC, bool RESCALE>
-    __device__ __forceinline__ void update(float factor, int64_t local, int64_t video, int n) const {
+    __device__ __forceinline__ void update(float factor, int64_t local, int64_t video, int n, int64_t row, int64_t e) const {
         float mk[N], xv[N], nz[N], x0[N], ep[N], xn[N];
         m<VEC>(local, n, mk);
         load_chunk<T, VEC>(x + video, n, xv);
-        if (noise) load_chunk<T, VEC>(noise + local, n, nz);
+        if constexpr (KEYED) vtm::normal_chunk<T>(kn, row, e, nz);
+        else if (noise) load_chunk<T, VEC>(noise + local, n, nz);
 #pragma unroll
         for (int k = 0; k < N; ++k) {
             float mv = mk[k];
             if constexpr (RESCALE) mv = mv * factor;
             vtm::predict(s.pred, s.sqrt_alpha, s.sqrt_beta, xv[k], mv, x0[k], ep[k]);
             xn[k] = s.c_x0 * x0[k] + s.c_eps * ep[k];
-            if (noise) xn[k] = xn[k] + s.sigma * nz[k];
+            if (KEYED || noise) xn[k] = xn[k] + s.sigma * nz[k];
         }
         if (x_out) store_chunk<T, VEC>(x_out + video, n, xn);
         if (eps_out) store_chunk<T, VEC>(eps_out + local, n, ep);
@@ -101,13 +103,35 @@ __global__ __launch_bounds__(GS_THREADS) void guided_step_rescale_kernel(const T
                               E, frame_ids);
 }
 
-}  // namespace
+// the keyed forms of the two kernels: the noise pointer gives way to the key
+template <typename T, bool VEC>
+__global__ __launch_bounds__(EW_THREADS) void guided_keyed_kernel(const T *x, const T *__restrict__ model_out,
+                                                                  vtm::KeyedNoise kn, int64_t F, int64_t E, int64_t g_uncond,
+                                                                  int64_t g_cond, const int32_t *__restrict__ frame_ids, Step s,
+                                                                  T *x_out, T *__restrict__ eps_out, T *__restrict__ x0_out) {
+    vtm::step_elementwise<T, VEC>(Guided<T, true>{s, x, model_out + g_uncond * F * E,
+                                                  s.guided ? model_out + g_cond * F * E : nullptr, nullptr, x_out, eps_out,
+                                                  x0_out, kn},
+                                  F, E, frame_ids);
+}
 
-VTM_EXPORT int vtm_guided_step(const void *x, const void *model_out, const void *noise, int dtype, int64_t F, int64_t E,
-                               int64_t groups, int64_t g_uncond, int64_t g_cond, const int32_t *frame_ids, int pred_type,
-                               float guidance, float rescale, float sqrt_alpha, float sqrt_beta, float c_x0, float c_eps,
-                               float sigma, void *x_out, void *eps_out, void *x0_out, vtm_stream_t stream) {
-    const char *who = "vtm_guided_step";
+template <typename T, bool VEC>
+__global__ __launch_bounds__(GS_THREADS) void guided_keyed_rescale_kernel(const T *x, const T *__restrict__ model_out,
+                                                                          vtm::KeyedNoise kn, int64_t F, int64_t E,
+                                                                          int64_t g_uncond, int64_t g_cond,
+                                                                          const int32_t *__restrict__ frame_ids, Step s,
+                                                                          T *x_out, T *__restrict__ eps_out,
+                                                                          T *__restrict__ x0_out) {
+    vtm::step_rescale<T, VEC>(Guided<T, true>{s, x, model_out + g_uncond * F * E, model_out + g_cond * F * E, nullptr, x_out,
+                                              eps_out, x0_out, kn},
+                              E, frame_ids);
+}
+
+// the body of both exports; kn: the keyed export's noise (noise is then null), null for the tensor form
+int guided_step(const char *who, const void *x, const void *model_out, const void *noise, const vtm::KeyedNoise *kn, int dtype,
+                int64_t F, int64_t E, int64_t groups, int64_t g_uncond, int64_t g_cond, const int32_t *frame_ids, int pred_type,
+                float guidance, float rescale, float sqrt_alpha, float sqrt_beta, float c_x0, float c_eps, float sigma,
+                void *x_out, void *eps_out, void *x0_out, vtm_stream_t stream) {
     if (const int rc = vtm::check_dtype_pred(who, dtype, pred_type)) return rc;
     VTM_REQUIRE(x && model_out, "%s: x and model_out are required", who);
     // (F bounds the grid of the per-frame launch: 1024 F threads must stay below 2^32)
@@ -118,7 +142,7 @@ VTM_EXPORT int vtm_guided_step(const void *x, const void *model_out, const void 
     VTM_REQUIRE(g_cond >= -1 && g_cond < groups, "%s: g_cond = %lld outside [0, %lld) and not -1", who, (long long)g_cond,
                 (long long)groups);
     VTM_REQUIRE(g_cond != g_uncond, "%s: g_uncond == g_cond == %lld", who, (long long)g_cond);
-    VTM_REQUIRE(sigma == 0.0f ? true : noise != nullptr, "%s: sigma != 0 needs noise", who);
+    VTM_REQUIRE(sigma == 0.0f ? true : (noise != nullptr || kn), "%s: sigma != 0 needs noise", who);
     VTM_REQUIRE(!(rescale < 0.0f) && rescale == rescale, "%s: rescale = %g is negative or NaN", who, (double)rescale);
     VTM_REQUIRE(!(rescale > 0.0f) || (g_cond >= 0 && E >= 2), "%s: rescale > 0 needs a conditional group and E >= 2", who);
     VTM_REQUIRE(x_out || eps_out || x0_out, "%s: no output", who);
@@ -128,7 +152,14 @@ VTM_EXPORT int vtm_guided_step(const void *x, const void *model_out, const void 
     const void *noise_used = sigma != 0.0f ? noise : nullptr;       // sigma == 0: the term is absent, noise is not read
     const int rc = vtm::with_dtype(dtype, who, [&](auto t) {
         using T = decltype(t);
-        vtm::launch_step<T>(rescale > 0.0f, {guided_step_kernel<T, false>, guided_step_kernel<T, true>},
+        if (kn && sigma != 0.0f)
+            vtm::launch_step<T>(rescale > 0.0f, {guided_keyed_kernel<T, false>, guided_keyed_kernel<T, true>},
+                                {guided_keyed_rescale_kernel<T, false>, guided_keyed_rescale_kernel<T, true>}, F, E,
+                                {x, model_out, x_out, eps_out, x0_out}, vtm::as_stream(stream), (const T *)x,
+                                (const T *)model_out, *kn, F, E, g_uncond, g_cond, frame_ids, s, (T *)x_out, (T *)eps_out,
+                                (T *)x0_out);
+        else
+            vtm::launch_step<T>(rescale > 0.0f, {guided_step_kernel<T, false>, guided_step_kernel<T, true>},
                             {guided_step_rescale_kernel<T, false>, guided_step_rescale_kernel<T, true>}, F, E,
                             {x, model_out, noise_used, x_out, eps_out, x0_out}, vtm::as_stream(stream), (const T *)x,
                             (const T *)model_out, (const T *)noise_used, F, E, g_uncond, g_cond, frame_ids, s, (T *)x_out,
@@ -137,4 +168,26 @@ VTM_EXPORT int vtm_guided_step(const void *x, const void *model_out, const void 
     });
     if (rc != VTM_OK) return rc;
     return vtm::launch_status(who);
+}
+
+}  // namespace
+
+VTM_EXPORT int vtm_guided_step(const void *x, const void *model_out, const void *noise, int dtype, int64_t F, int64_t E,
+                               int64_t groups, int64_t g_uncond, int64_t g_cond, const int32_t *frame_ids, int pred_type,
+                               float guidance, float rescale, float sqrt_alpha, float sqrt_beta, float c_x0, float c_eps,
+                               float sigma, void *x_out, void *eps_out, void *x0_out, vtm_stream_t stream) {
+    return guided_step("vtm_guided_step", x, model_out, noise, nullptr, dtype, F, E, groups, g_uncond, g_cond, frame_ids,
+                       pred_type, guidance, rescale, sqrt_alpha, sqrt_beta, c_x0, c_eps, sigma, x_out, eps_out, x0_out, stream);
+}
+
+VTM_EXPORT int vtm_guided_step_keyed(const void *x, const void *model_out, uint64_t seed, uint32_t step, uint32_t tag,
+                                     int64_t frame0, int dtype, int64_t F, int64_t E, int64_t groups, int64_t g_uncond,
+                                     int64_t g_cond, const int32_t *frame_ids, int pred_type, float guidance, float rescale,
+                                     float sqrt_alpha, float sqrt_beta, float c_x0, float c_eps, float sigma, void *x_out,
+                                     void *eps_out, void *x0_out, vtm_stream_t stream) {
+    const char *who = "vtm_guided_step_keyed";
+    if (const int rc = vtm::check_keyed(who, frame0, E)) return rc;
+    const vtm::KeyedNoise kn{vtm::noise_key(seed, step, tag), (uint32_t)frame0};
+    return guided_step(who, x, model_out, nullptr, &kn, dtype, F, E, groups, g_uncond, g_cond, frame_ids, pred_type, guidance,
+                       rescale, sqrt_alpha, sqrt_beta, c_x0, c_eps, sigma, x_out, eps_out, x0_out, stream);
 }

@@ -48,7 +48,7 @@ struct Inverter {
 
     // factor: the frame's rescale factor (1 and unused without rescale)
     template <bool VEC, bool RESCALE>
-    __device__ __forceinline__ void update(float factor, int64_t local, int64_t video, int n) const {
+    __device__ __forceinline__ void update(float factor, int64_t local, int64_t video, int n, int64_t, int64_t) const {
         float mk[N], xv[N], tv[N], p1[N], p2[N], x0[N], ep[N], z[N], tn[N];
         m<VEC>(local, n, mk);
         load_chunk<T, VEC>(x + video, n, xv);

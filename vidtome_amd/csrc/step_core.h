@@ -6,9 +6,10 @@
 // of the launch's operands that says what only that step knows:
 //     p.m<VEC>(local, n, m)                       the chunk's combined model output m
 //     p.ref<VEC>(local, n, r)                     the chunk of the group whose per-frame std the rescale restores
-//     p.update<VEC, RESCALE>(factor, local, video, n)   one chunk of the update: predict(), the step's own sum, the stores
+//     p.update<VEC, RESCALE>(factor, local, video, n, row, e)   one chunk of the update: predict(), the step's own sum, the stores
 //     p.s.rescale                                 Diffusers' guidance_rescale
-// local = f * E + e is the chunk's offset in a chunk-local (F, E) operand, video = frame_ids[f] * E + e in a whole-video one.
+// local = f * E + e is the chunk's offset in a chunk-local (F, E) operand, video = row * E + e in a whole-video one, whose row
+// is frame_ids[f] (f without ids).
 //   step_elementwise   rescale == 0: a grid-stride loop over the F * chunks-per-frame chunks.
 //   step_rescale       rescale  > 0: one STEP_THREADS workgroup per frame, three passes over the frame (after the first they come
 //                      from L2): the means of ref and m; their squared deviations; the update.  Lane t adds its chunks t,
@@ -17,6 +18,7 @@
 // One launch (launch_step), no workspace, no atomics.  Everything is fp32 and every stored value is rounded once.
 #pragma once
 #include "common.h"
+#include "philox.h"
 
 #include <algorithm>
 #include <initializer_list>
@@ -62,6 +64,24 @@ __device__ __forceinline__ void store_chunk(T *p, int n, const float *v) {
         for (int k = 0; k < N; ++k)
             if (k < n) p[k] = from_f32<T>(v[k]);
     }
+}
+
+// Where a keyed step's noise comes from (philox.h) instead of a chunk-local tensor.  frame0: the whole-video row of row 0 of
+// the launch's whole-video operands (a caller that steps an ascending run of frames offsets those pointers and sends no ids).
+struct KeyedNoise {
+    NoiseKey key;
+    uint32_t frame0;
+};
+
+// the chunk at element e of row `row` of keyed noise as fp32, each normal rounded ONCE to T first: the values load_chunk reads
+// from a stored noise tensor of the model dtype.  (Elements past the frame's end are never used.)
+template <typename T>
+__device__ __forceinline__ void normal_chunk(const KeyedNoise &kn, int64_t row, int64_t e, float *v) {
+    constexpr int N = 16 / sizeof(T);
+#pragma unroll
+    for (int q = 0; q < N / 4; ++q) normal_quad(kn.key, (uint32_t)(e >> 2) + q, kn.frame0 + (uint32_t)row, v + 4 * q);
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = vtm::to_f32(from_f32<T>(v[k]));
 }
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -119,7 +139,7 @@ __device__ __forceinline__ void step_elementwise(const P &p, int64_t F, int64_t 
         const int64_t f = i / chunks, e = (i - f * chunks) * N;
         const int n = (int)std::min<int64_t>(N, E - e);
         const int64_t row = frame_ids ? (int64_t)frame_ids[f] : f;
-        p.template update<VEC, false>(1.0f, f * E + e, row * E + e, n);
+        p.template update<VEC, false>(1.0f, f * E + e, row * E + e, n, row, e);
     }
 }
 
@@ -166,7 +186,7 @@ __device__ __forceinline__ void step_rescale(const P &p, int64_t E, const int32_
     const int64_t row = frame_ids ? (int64_t)frame_ids[f] : f;
     for (int64_t i = threadIdx.x; i < chunks; i += STEP_THREADS) {
         const int64_t e = i * N;
-        p.template update<VEC, true>(factor, f * E + e, row * E + e, (int)std::min<int64_t>(N, E - e));
+        p.template update<VEC, true>(factor, f * E + e, row * E + e, (int)std::min<int64_t>(N, E - e), row, e);
     }
 }
 
@@ -189,6 +209,13 @@ inline int check_dtype_pred(const char *who, int dtype, int pred_type) {
     VTM_REQUIRE(dtype == VTM_F32 || dtype == VTM_F16 || dtype == VTM_BF16, "%s: unsupported dtype %d", who, dtype);
     VTM_REQUIRE(pred_type == VTM_PRED_EPSILON || pred_type == VTM_PRED_V || pred_type == VTM_PRED_SAMPLE,
                 "%s: unknown pred_type %d", who, pred_type);
+    return VTM_OK;
+}
+
+// what a keyed export requires beyond its tensor form: the counter's words are 32 bits (quad e >> 2, frame)
+inline int check_keyed(const char *who, int64_t frame0, int64_t E) {
+    VTM_REQUIRE(frame0 >= 0 && frame0 <= INT32_MAX, "%s: frame0 = %lld outside [0, 2^31)", who, (long long)frame0);
+    VTM_REQUIRE(E <= (int64_t(1) << 34), "%s: E = %lld: a frame's quad index must fit 32 bits", who, (long long)E);
     return VTM_OK;
 }
 

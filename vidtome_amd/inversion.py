@@ -28,6 +28,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib
+from .noise import LEVELS, FrameNoise
 from .sampler import PREDICTION_TYPES, GuidedDPMSolver, _checked_step
 
 
@@ -62,10 +63,18 @@ class EditFriendlyInversion:
         """[(sqrt(a_k), sqrt(1 - a_k))] for the n levels the solver steps from, in host float64."""
         return [self.solver._level(k)[:2] for k in range(len(self.solver.timesteps))]
 
-    def noise_levels(self, x0: torch.Tensor, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    def noise_levels(self, x0: torch.Tensor, generator: Optional[torch.Generator] = None,
+                     noise: Optional[FrameNoise] = None) -> torch.Tensor:
         """The video ``x0`` (n_frames, ...) noised to every level, one vtm_noise_levels launch over randn drawn from
         ``generator``: a NEW (n + 1, n_frames, ...) tensor, ``levels[k] = sqrt(a_k) x0 + sqrt(1 - a_k) N(0, 1)`` for k < n and
-        ``levels[n] = x0``.  Also allocates ``noise`` and prepares the solver's history, on the current stream."""
+        ``levels[n] = x0``.  Also allocates ``noise`` and prepares the solver's history, on the current stream.
+        ``noise=FrameNoise(seed)`` in place of ``generator``: the draws are keyed by (seed, LEVELS, level k, frame, element) --
+        one vtm_frame_noise launch -- so a frame's levels depend neither on the video's length nor on a generator's state."""
+        if noise is not None and not isinstance(noise, FrameNoise):
+            raise TypeError("EditFriendlyInversion.noise_levels: noise must be a FrameNoise")
+        if noise is not None and generator is not None:
+            raise ValueError("EditFriendlyInversion.noise_levels: noise=FrameNoise(...) draws nothing from a generator: pass one "
+                             "of the two")
         if not isinstance(x0, torch.Tensor) or x0.dim() < 2:
             raise RuntimeError("EditFriendlyInversion.noise_levels: x0 must be a (frames, ...) tensor")
         if not x0.is_cuda:
@@ -74,7 +83,10 @@ class EditFriendlyInversion:
             raise RuntimeError("EditFriendlyInversion.noise_levels: x0 must be a contiguous fp16 / bf16 / fp32 tensor")
         n = len(self.solver.timesteps)
         levels = torch.empty((n + 1,) + tuple(x0.shape), dtype=x0.dtype, device=x0.device)
-        levels[:n].normal_(generator=generator)
+        if noise is None:
+            levels[:n].normal_(generator=generator)
+        elif n:
+            noise.with_tag(LEVELS).normal(tuple(x0.shape[1:]), 0, n_frames=x0.shape[0], steps=n, out=levels[:n])
         coef = torch.tensor(self.level_coefficients(), dtype=torch.float32).to(x0.device)
         _lib.noise_levels(x0, levels[:n], coef)
         levels[n].copy_(x0)

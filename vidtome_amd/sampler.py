@@ -27,6 +27,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib
+from .noise import FrameNoise
 
 PREDICTION_TYPES = {"epsilon": _lib.PRED_EPSILON, "v_prediction": _lib.PRED_V, "sample": _lib.PRED_SAMPLE}
 WANT = ("eps", "x0")
@@ -68,6 +69,15 @@ def _checked_step(who: str, x, model_out, noise, groups, frame_ids, want, coeffi
         if not t.is_cuda:
             raise RuntimeError(f"{who}.step: {name} must live on the GPU (vidtome_amd has no CPU path)")
     return want, coef, F, groups, own
+
+
+def _keyed(who: str, noise, generator):
+    """``noise`` of a step -> (the tensor or None, the FrameNoise or None)."""
+    if not isinstance(noise, FrameNoise):
+        return noise, None
+    if generator is not None:
+        raise ValueError(f"{who}.step: noise=FrameNoise(...) draws nothing from a generator: pass one of the two")
+    return None, noise
 
 
 def _asked(res, want):
@@ -129,27 +139,30 @@ class GuidedDDIM:
         return a_from, a_to, math.sqrt(a_from), math.sqrt(1.0 - a_from), math.sqrt(a_to), c_eps, sigma
 
     def step(self, x: torch.Tensor, model_out: torch.Tensor, i: int, *, groups: int = 2, frame_ids=None,
-             inversion: bool = False, noise: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None,
+             inversion: bool = False, noise=None, generator: Optional[torch.Generator] = None,
              out: Optional[torch.Tensor] = None, want: Sequence[str] = ()):
         """Step ``i`` for one chunk, one vtm_guided_step launch on the current stream.  ``x`` (n_frames, C, H, W): the
         whole-video latents; ``model_out`` (groups * F, C, H, W): the UNet output of the chunk, group-major, its last two
         groups the unconditional and the conditional prediction (generate.py:276; under PnP the source group comes first and
         is not read); ``groups = 1``: no guidance (inversion).  ``frame_ids``: the chunk's F frame indices into x (what
         ``scheduler.get_chunks`` gives, any host sequence, or a device int32 tensor, which is not checked); None: the chunk is
-        the whole video.  With ``eta > 0`` and no ``noise`` (F, C, H, W), randn of the chunk's shape is drawn from ``generator``.
+        the whole video.  With ``eta > 0`` and no ``noise`` (F, C, H, W), randn of the chunk's shape is drawn from ``generator``
+        -- noise that depends on the chunking.  ``noise=FrameNoise(seed)`` instead keys the noise by (seed, i, frame, element):
+        one vtm_guided_step_keyed launch that draws it in place, the same bits under any chunking, order, rank or stream.
 
         ``out`` receives x' in the chunk's rows and may be x (every element is read before it is written).  Without ``out``:
         a NEW tensor when ``frame_ids`` is None (all of it is written), otherwise x itself, updated IN PLACE in the chunk's rows
         -- a new tensor would hold rows nobody wrote.  Returns out, or (out, *asked) with ``want`` naming "eps" and / or "x0":
         chunk-local (F, C, H, W) tensors of the epsilon and the clean-sample prediction."""
+        noise, keyed = _keyed("GuidedDDIM", noise, generator)
         want, (_, _, sqrt_alpha, sqrt_beta, c_x0, c_eps, sigma), F, groups, _ = _checked_step(
             "GuidedDDIM", x, model_out, noise, groups, frame_ids, want, lambda: self.coefficients(i, inversion))
-        if sigma != 0.0 and noise is None:
+        if sigma != 0.0 and noise is None and keyed is None:
             noise = torch.randn((F,) + tuple(model_out.shape[1:]), dtype=x.dtype, device=x.device, generator=generator)
         res = _lib.guided_step(x, model_out, sqrt_alpha, sqrt_beta, c_x0, c_eps, sigma, groups=groups, frame_ids=frame_ids,
                                pred_type=PREDICTION_TYPES[self.prediction_type], guidance=self.guidance_scale,
                                rescale=self.guidance_rescale if groups >= 2 else 0.0, noise=noise, out=out,
-                               want_eps="eps" in want, want_x0="x0" in want)
+                               want_eps="eps" in want, want_x0="x0" in want, key=keyed.key(i) if keyed else None)
         return _asked(res, want)
 
 
@@ -323,12 +336,14 @@ class GuidedDPMSolver:
                                "step 0 restarts it)")
 
     def step(self, x: torch.Tensor, model_out: torch.Tensor, i: int, *, groups: int = 2, frame_ids=None,
-             noise: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None,
+             noise=None, generator: Optional[torch.Generator] = None,
              out: Optional[torch.Tensor] = None, want: Sequence[str] = ()):
         """Step ``i`` for one chunk, one vtm_solver_step launch on the current stream.  ``x``, ``model_out`` (groups * F, C, H,
         W, group-major), ``frame_ids``, ``out`` (it may be x; without it a NEW tensor when ``frame_ids`` is None, otherwise x
         itself IN PLACE), ``want`` and the result are ``GuidedDDIM.step``'s.  With "sde-dpmsolver++" and no ``noise`` (F, C, H,
-        W), randn of the chunk's shape is drawn from ``generator``."""
+        W), randn of the chunk's shape is drawn from ``generator``; ``noise=FrameNoise(seed)`` keys it per frame instead (one
+        vtm_solver_step_keyed launch), as in ``GuidedDDIM.step``."""
+        noise, keyed = _keyed("GuidedDPMSolver", noise, generator)
         want, (sqrt_alpha, sqrt_beta, c_x, c_x0, c_h1, c_h2, c_noise), F, groups, weights = _checked_step(
             "GuidedDPMSolver", x, model_out, noise, groups, frame_ids, want, lambda: self.coefficients(i), self.weights,
             lambda: self._in_sequence(int(i)))
@@ -338,7 +353,7 @@ class GuidedDPMSolver:
                 raise RuntimeError(f"GuidedDPMSolver.step: the history of step {i} does not fit x {tuple(x.shape)} on {x.device}")
             self.prepare(x)
         self._current = i
-        if c_noise != 0.0 and noise is None:
+        if c_noise != 0.0 and noise is None and keyed is None:
             noise = torch.randn((F,) + tuple(model_out.shape[1:]), dtype=x.dtype, device=x.device, generator=generator)
         ring = len(self.history)
         res = _lib.solver_step(x, model_out, weights, sqrt_alpha, sqrt_beta, c_x, c_x0, c_h1, c_h2, c_noise,
@@ -348,5 +363,5 @@ class GuidedDPMSolver:
                                g_ref=groups - 1 if self.rescale_group is None else self.rescale_group, frame_ids=frame_ids,
                                pred_type=PREDICTION_TYPES[self.prediction_type],
                                rescale=self.guidance_rescale if groups >= 2 else 0.0, noise=noise, out=out,
-                               want_eps="eps" in want, want_x0="x0" in want)
+                               want_eps="eps" in want, want_x0="x0" in want, key=keyed.key(i) if keyed else None)
         return _asked(res, want)
