@@ -1183,6 +1183,46 @@ int vtm_groupnorm_silu(const void *x, const void *add, const void *gamma, const 
 int vtm_resnet_tail(const void *shortcut, const void *hidden, int dtype, int64_t B, int64_t M, int64_t inject_rows,
                     int64_t period, double scale, void *out, vtm_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Attention broadcast -- vtm_residual_record / vtm_residual_replay / vtm_residual_replay_layernorm.  Beyond the reference:
+ * Pyramid Attention Broadcast (Zhao et al. 2024) on the patched block.  In a window of timesteps a block's attn1 / attn2
+ * segment is computed every k-th step and replayed in between (broadcast.py decides the steps on the host).  What is kept of
+ * a segment is its contribution to the residual stream, the residual add included, per frame of the WHOLE video:
+ *   d = T(f32(h_after) - f32(h_before)),      replayed as      h' = T(f32(h) + f32(d)),
+ * T the model dtype, one rounding each.  The delta is the same whichever route computed the segment (several routes never
+ * materialise the attention output before the residual add).
+ * The batch is group-major: sample b = g * Fg + f, G groups of the chunk's Fg frames, E = N * C elements per frame.  A cache
+ * is (G, num_frames, E) contiguous in `dtype`; frame f of the chunk is cache row (g, id(f)), id(f) = frame_ids[f], or f when
+ * frame_ids is NULL.  frame_ids: device int32 (Fg,), the ids distinct and in [0, num_frames): they are NOT checked on the
+ * device -- an id outside the range reads or writes outside the cache -- the caller validates them on the host.
+ * vtm_residual_record: cache[(g * num_frames + id(f)) * E + e] = T(f32(h_out[b, e]) - f32(h_in[b, e])).  Rows the ids do not
+ *   name are not touched.  cache must not overlap h_in / h_out (VTM_EINVAL).
+ * vtm_residual_replay: out[b, e] = T(f32(h[b, e]) + f32(cache1[..])); with cache2 (may be NULL) then
+ *   out[b, e] = T(f32(that rounded value) + f32(cache2[..])) -- two segments in a row, the intermediate rounding kept.
+ *   out may be h itself (any other overlap: VTM_EINVAL).
+ * Both: VTM_F32 / VTM_F16 / VTM_BF16; 1 <= Fg <= num_frames, G, E >= 1 (else VTM_EINVAL).  A grid-stride launch over
+ * 16-byte chunks, moved with one 16-byte access when E is a multiple of the chunk (4 fp32 / 8 16-bit elements) and every
+ * pointer is 16-byte aligned, element by element otherwise; which of the two changes no bit.
+ * vtm_residual_replay_layernorm: the replay above to out_rows (G Fg N, C) -- may be h -- AND, in the same launch, the
+ *   LayerNorm of those rows over C (gamma, beta: (C) in `dtype` or NULL) to out_panels in the k-panel layout
+ *   [C / 8][panel_rows][8] vtm_ff_geglu reads, panel_rows = vtm_panel_rows(G Fg N); panel rows >= G Fg N are not written.
+ *   Every written panel row is BIT-EQUAL to vtm_layernorm_panels(out_rows): the row lives in registers, two-pass fp32
+ *   statistics, and the summation order is that of the kernel vtm_layernorm_panels launches for the same (G Fg N, C)
+ *   (lanes-per-row at C = 320 / 640 and at C = 1280 from 32768 rows, a wave per row otherwise).  VTM_F16 / VTM_BF16 only
+ *   (the panel GEMMs are 16-bit); C % 64 == 0, C <= 2048 -- the widths the fused feed-forward takes; every pointer 16-byte
+ *   aligned; plain (cached) loads and stores.  Anything else: VTM_EINVAL.
+ * No workspace, no atomics: a frame's bits depend on that frame's operands alone, so any chunking of a video gives the same
+ * bits per frame.  Cache rows are written on `stream`; launches on two streams must name disjoint frames.
+ * ---------------------------------------------------------------------------------------------- */
+int vtm_residual_record(const void *h_in, const void *h_out, void *cache, const int32_t *frame_ids, int dtype, int64_t G,
+                        int64_t Fg, int64_t num_frames, int64_t E, vtm_stream_t stream);
+int vtm_residual_replay(const void *h, const void *cache1, const void *cache2, const int32_t *frame_ids, int dtype, int64_t G,
+                        int64_t Fg, int64_t num_frames, int64_t E, void *out, vtm_stream_t stream);
+int vtm_residual_replay_layernorm(const void *h, const void *cache1, const void *cache2, const int32_t *frame_ids,
+                                  const void *gamma, const void *beta, float eps, int dtype, int64_t G, int64_t Fg,
+                                  int64_t num_frames, int64_t N, int64_t C, void *out_rows, void *out_panels,
+                                  int64_t panel_rows, vtm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,7 @@ from .pag import register_perturbed_attention, remove_perturbed_attention
 from .sag import SelfAttentionGuidance, register_self_attention_guidance, unregister_self_attention_guidance
 from .freeu import register_freeu, unregister_freeu
 from .semantic import EditConcept, SemanticGuidance
+from .broadcast import AttentionBroadcast, register_attention_broadcast, unregister_attention_broadcast
 
 __all__ = ["merge", "patch", "apply_patch", "remove_patch", "update_patch", "collect_from_patch",
            "register_attention_maps", "unregister_attention_maps",
@@ -23,4 +24,5 @@ __all__ = ["merge", "patch", "apply_patch", "remove_patch", "update_patch", "col
            "LocalBlend", "register_local_blend", "unregister_local_blend",
            "GuidedDDIM", "GuidedDPMSolver", "register_perturbed_attention", "remove_perturbed_attention",
            "SelfAttentionGuidance", "register_self_attention_guidance", "unregister_self_attention_guidance",
-           "register_freeu", "unregister_freeu", "EditConcept", "SemanticGuidance", "EditFriendlyInversion", "FrameNoise"]
+           "register_freeu", "unregister_freeu", "EditConcept", "SemanticGuidance", "EditFriendlyInversion", "FrameNoise",
+           "AttentionBroadcast", "register_attention_broadcast", "unregister_attention_broadcast"]

@@ -159,6 +159,10 @@ _SIGNATURES = {
     "vtm_resnet_tail": ([_vp, _vp, _int, _i64, _i64, _i64, _i64, ctypes.c_double, _vp, _vp], _int),
     "vtm_linear_f32": ([_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _int, _vp, _vp, _int, _i64,
                         _i64, _int, _vp], _int),
+    "vtm_residual_record": ([_vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _vp], _int),
+    "vtm_residual_replay": ([_vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _vp, _vp], _int),
+    "vtm_residual_replay_layernorm": ([_vp, _vp, _vp, _vp, _vp, _vp, _f32, _int, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _i64,
+                                       _vp], _int),
 }
 
 
@@ -2065,6 +2069,89 @@ def linear_panels(x_panels: torch.Tensor, n: int, w_panels: torch.Tensor, N: int
                                    _ptr(bias), _ptr(resid), dtype_code(x_panels), out.data_ptr(), out.stride(0), _stream()),
            "vtm_linear_panels")
     return out
+
+
+# ---- attention broadcast (csrc/broadcast.hip): a segment's per-frame residual delta, recorded and replayed ----
+def _broadcast_operands(who: str, h: torch.Tensor, caches, frame_ids: Optional[torch.Tensor]):
+    """(G, Fg, num_frames, E) of a group-major batch ``h`` (G Fg, ...) against whole-video caches (G, num_frames, ...) of the
+    same trailing shape, dtype and device.  ``frame_ids``: None (the chunk is frames 0 .. Fg - 1 = the whole video) or a device
+    int32 (Fg,) tensor of distinct ids in [0, num_frames) -- NOT checked, here or on the device: the caller validates them."""
+    _req(h, "h")
+    first = caches[0]
+    for c in caches:
+        _req(c, "cache")
+        if c.dim() < 3 or c.shape != first.shape or c.dtype != h.dtype or c.device != h.device or c.shape[2:] != h.shape[1:]:
+            raise RuntimeError(f"{who}: a cache must be (G, num_frames, {', '.join(map(str, h.shape[1:]))}) {h.dtype} on "
+                               f"{h.device}, got {tuple(c.shape)} {c.dtype} on {c.device}")
+    G, num_frames = first.shape[:2]
+    if frame_ids is None:
+        Fg = num_frames
+    else:
+        if not frame_ids.is_cuda or frame_ids.device != h.device or frame_ids.dtype != torch.int32 or frame_ids.dim() != 1 \
+                or not frame_ids.is_contiguous():
+            raise RuntimeError(f"{who}: frame_ids must be a contiguous 1-D int32 tensor on {h.device}")
+        Fg = frame_ids.numel()
+    if h.dim() < 2 or not 1 <= Fg <= num_frames or h.shape[0] != G * Fg:
+        raise RuntimeError(f"{who}: the batch has {h.shape[0]} samples, the caches hold G = {G} groups and the call carries "
+                           f"Fg = {Fg} of {num_frames} frames (G Fg samples, group-major)")
+    return G, Fg, num_frames, h[0].numel()
+
+
+@_on_device
+def residual_record(h_in: torch.Tensor, h_out: torch.Tensor, cache: torch.Tensor,
+                    frame_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """cache[g, id(f)] = (h_out.float() - h_in.float()).to(dtype)[g * Fg + f]: vtm_residual_record (include/vidtome_hip.h).
+    Cache rows the ids do not name are left as they are.  Returns ``cache``."""
+    who = "residual_record"
+    G, Fg, num_frames, E = _broadcast_operands(who, h_in, (cache,), frame_ids)
+    _req(h_out, "h_out")
+    if h_out.shape != h_in.shape or h_out.dtype != h_in.dtype or h_out.device != h_in.device:
+        raise RuntimeError(f"{who}: h_out must be like h_in")
+    _check(lib().vtm_residual_record(_ptr(h_in), _ptr(h_out), _ptr(cache), _ptr(frame_ids), dtype_code(h_in), G, Fg, num_frames,
+                                     E, _stream()), "vtm_residual_record")
+    return cache
+
+
+@_on_device
+def residual_replay(h: torch.Tensor, cache1: torch.Tensor, cache2: Optional[torch.Tensor] = None,
+                    frame_ids: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(h.float() + cache1[g, id(f)].float()).to(dtype), then the same with ``cache2`` on the rounded sum: vtm_residual_replay.
+    ``out`` may be ``h``."""
+    who = "residual_replay"
+    G, Fg, num_frames, E = _broadcast_operands(who, h, (cache1,) if cache2 is None else (cache1, cache2), frame_ids)
+    if out is None:
+        out = torch.empty_like(h)
+    elif out.shape != h.shape or out.dtype != h.dtype or out.device != h.device or not out.is_contiguous():
+        raise RuntimeError(f"{who}: out must be like h")
+    _check(lib().vtm_residual_replay(_ptr(h), _ptr(cache1), _ptr(cache2), _ptr(frame_ids), dtype_code(h), G, Fg, num_frames, E,
+                                     _ptr(out), _stream()), "vtm_residual_replay")
+    return out
+
+
+@_on_device
+def residual_replay_layernorm(h: torch.Tensor, cache1: torch.Tensor, cache2: Optional[torch.Tensor],
+                              frame_ids: Optional[torch.Tensor], weight: Optional[torch.Tensor], bias: Optional[torch.Tensor],
+                              eps: float, out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``residual_replay`` of h (G Fg, N, C) to token rows and, in the same launch, the LayerNorm of those rows as k-panels
+    (C / 8, panel_rows(G Fg N), 8), every written row bit-equal to ``layernorm_panels`` of the rows: (rows, panels).
+    fp16 / bf16, C a multiple of 64, at most 2048 (vtm_residual_replay_layernorm)."""
+    who = "residual_replay_layernorm"
+    if h.dim() != 3:
+        raise RuntimeError(f"{who}: h must be (G Fg, N, C)")
+    G, Fg, num_frames, _ = _broadcast_operands(who, h, (cache1,) if cache2 is None else (cache1, cache2), frame_ids)
+    _, N, C = h.shape
+    for name, p in (("weight", weight), ("bias", bias)):
+        if p is not None and (p.dtype != h.dtype or p.numel() != C or p.device != h.device or not p.is_contiguous()):
+            raise RuntimeError(f"{who}: {name} must be a contiguous ({C},) {h.dtype} tensor on {h.device}")
+    if out is None:
+        out = torch.empty_like(h)
+    elif out.shape != h.shape or out.dtype != h.dtype or out.device != h.device or not out.is_contiguous():
+        raise RuntimeError(f"{who}: out must be like h")
+    panels = torch.empty((C // 8, panel_rows(G * Fg * N), 8), dtype=h.dtype, device=h.device)
+    _check(lib().vtm_residual_replay_layernorm(_ptr(h), _ptr(cache1), _ptr(cache2), _ptr(frame_ids), _ptr(weight), _ptr(bias),
+                                               float(eps), dtype_code(h), G, Fg, num_frames, N, C, _ptr(out), _ptr(panels),
+                                               panels.shape[1], _stream()), "vtm_residual_replay_layernorm")
+    return out, panels
 
 
 @_on_device

@@ -19,7 +19,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libvidtome_hip.so")
-SOURCES = ["api.hip", "normalize.hip", "match.hip", "match_filter.hip", "sort.hip", "order.hip", "frame_order.hip", "plan.hip", "gather.hip", "attention.hip", "attention16.hip", "attention16g.hip", "attention_f32.hip", "attention_sets.hip", "attention_bias.hip", "attention_segments.hip", "attention_probs.hip", "attention_words.hip", "attention_mass.hip", "cross_edit.hip", "local_blend.hip", "sag.hip", "freeu.hip", "ddim.hip", "guided_step.hip", "solver_step.hip", "invert_step.hip", "frame_noise.hip", "semantic.hip", "layernorm.hip", "geglu.hip", "linear.hip", "linear_f32.hip", "ff.hip", "lora.hip", "groupnorm.hip"]
+SOURCES = ["api.hip", "normalize.hip", "match.hip", "match_filter.hip", "sort.hip", "order.hip", "frame_order.hip", "plan.hip", "gather.hip", "attention.hip", "attention16.hip", "attention16g.hip", "attention_f32.hip", "attention_sets.hip", "attention_bias.hip", "attention_segments.hip", "attention_probs.hip", "attention_words.hip", "attention_mass.hip", "cross_edit.hip", "local_blend.hip", "sag.hip", "freeu.hip", "ddim.hip", "guided_step.hip", "solver_step.hip", "invert_step.hip", "frame_noise.hip", "semantic.hip", "layernorm.hip", "broadcast.hip", "geglu.hip", "linear.hip", "linear_f32.hip", "ff.hip", "lora.hip", "groupnorm.hip"]
 ARCH = "gfx950"
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
          "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-function",

@@ -1834,6 +1834,50 @@ def _lib_layernorm_ok(norm: torch.nn.Module, x: torch.Tensor) -> bool:
             and x.dtype in (torch.float16, torch.bfloat16, torch.float32))
 
 
+_NO_BROADCAST = (None, "", "compute", "compute")
+
+
+def broadcast_modes(block: torch.nn.Module):
+    """(bc, name, attn1's mode, attn2's mode) of this forward under ``broadcast.register_attention_broadcast``: each mode
+    "compute" (the segment as ever), "record" (the same, then one vtm_residual_record launch) or "reuse" (the segment is
+    replaced by the replay of its cached delta).  An unregistered block: ``_NO_BROADCAST``, nothing looked at.  Launches
+    nothing.  Raises, with the block's name, where a registered consumer would silently miss what a skipped segment makes."""
+    hit = block.__dict__.get("vtm_broadcast")
+    if hit is None:
+        return _NO_BROADCAST
+    bc, name = hit
+    who = f"vidtome_amd: block '{name}' is registered for attention broadcast (register_attention_broadcast) but "
+    if block.use_ada_layer_norm or block.use_ada_layer_norm_zero:
+        raise RuntimeError(who + "is an AdaLayerNorm / AdaLayerNormZero block: its segments are modulated per timestep "
+                                 "(attention broadcast on such a block is not supported)")
+    mode1, mode2 = bc.step_modes(name)
+    if block.attn2 is None:
+        mode2 = "compute"
+    if mode2 == "reuse":
+        for on, what in ((getattr(block, "vtm_attention_maps", False), "attention maps (register_attention_maps)"),
+                         (local_blend_of(block) is not None, "LocalBlend (register_local_blend)"),
+                         (block.__dict__.get("vtm_cross_control") is not None,
+                          "cross-attention control (register_cross_attention_control)")):
+            if on:
+                raise RuntimeError(who + f"also for {what}: this step replays attn2, which computes no map")
+    if mode1 == "reuse" and sag_registered(block):
+        raise RuntimeError(who + "also for self-attention guidance (register_self_attention_guidance): this step replays "
+                                 "attn1, which computes no key mass")
+    return bc, name, mode1, mode2
+
+
+def broadcast_feed_forward_residual(bc, name: str, norm: torch.nn.Module, ff: torch.nn.Module, hidden_states: torch.Tensor
+                                    ) -> torch.Tensor:
+    """The whole block on a step that replays both attentions, where ``fused_ff_ok`` holds: h2 = h + d1 + d2 and norm3(h2) as
+    k-panels from ONE launch (vtm_residual_replay_layernorm), then ``norm_feed_forward_residual``'s two GEMMs on them."""
+    C = hidden_states.shape[-1]
+    w1, b1, D, w2, b2 = _ff_panel_weights(ff)
+    h2, xp = bc.replay_layernorm(name, hidden_states, norm)
+    n = h2.numel() // C
+    hp = _lib.ff_geglu(xp, n, w1, D, b1)
+    return _lib.linear_panels(hp, n, w2, C, b2, resid=h2.view(n, C)).view(hidden_states.shape)
+
+
 def make_diffusers_tome_block(block_class: Type[torch.nn.Module]) -> Type[torch.nn.Module]:
     """vidtome/patch.py:119-203: patched class made on the fly, named ToMeBlock, keeps ``_parent``."""
 
@@ -1843,31 +1887,47 @@ def make_diffusers_tome_block(block_class: Type[torch.nn.Module]) -> Type[torch.
         def forward(self, hidden_states, attention_mask=None, encoder_hidden_states=None,
                     encoder_attention_mask=None, timestep=None, cross_attention_kwargs=None,
                     class_labels=None) -> torch.Tensor:
-            gate_msa = None
-            if self.use_ada_layer_norm:                                            # patch.py:139-146
-                norm_hidden_states = self.norm1(hidden_states, timestep)
-            elif self.use_ada_layer_norm_zero:
-                norm_hidden_states, gate_msa, shift_mlp, scale_mlp, gate_mlp = self.norm1(
-                    hidden_states, timestep, class_labels, hidden_dtype=hidden_states.dtype)
+            bc, bc_name, mode1, mode2 = broadcast_modes(self)                      # broadcast.register_attention_broadcast
+            if mode1 == "reuse":
+                # attn1 is replayed: no norm1, no compute_merge (no draw, no global-token update), so no MergePlan either --
+                # merge_mlp / merge_crossattn take their plain paths ("no local map")
+                if mode2 == "reuse" and fused_ff_ok(self.norm3, self.ff, hidden_states):
+                    return broadcast_feed_forward_residual(bc, bc_name, self.norm3, self.ff, hidden_states)
+                hidden_states = bc.replay(bc_name, ("attn1", "attn2") if mode2 == "reuse" else ("attn1",), hidden_states)
+                plans = None
             else:
-                norm_hidden_states = None
+                segment_input = hidden_states
+                gate_msa = None
+                if self.use_ada_layer_norm:                                        # patch.py:139-146
+                    norm_hidden_states = self.norm1(hidden_states, timestep)
+                elif self.use_ada_layer_norm_zero:
+                    norm_hidden_states, gate_msa, shift_mlp, scale_mlp, gate_mlp = self.norm1(
+                        hidden_states, timestep, class_labels, hidden_dtype=hidden_states.dtype)
+                else:
+                    norm_hidden_states = None
 
-            # 1. self-attention on merged tokens (the hot path)                    # patch.py:148-169
-            # (merge_mlp / merge_crossattn: the feed-forward and attn2 below read the maps of THIS forward's compute_merge --
-            # carried on a local)
-            plans = [] if (getattr(self, "merge_mlp", False) is True
-                           or getattr(self, "merge_crossattn", False) is True) else None
-            seg_kw = {} if plans is None else {"plan_to": plans}
-            if norm_hidden_states is None:
-                hidden_states = self_attention_segment(self, hidden_states, encoder_hidden_states, attention_mask,
-                                                       cross_attention_kwargs, **seg_kw)
-            else:
-                hidden_states = patched_self_attention_segment(
-                    self, hidden_states, norm_hidden_states, encoder_hidden_states, attention_mask,
-                    cross_attention_kwargs, gate_msa, **seg_kw)
+                # 1. self-attention on merged tokens (the hot path)                # patch.py:148-169
+                # (merge_mlp / merge_crossattn: the feed-forward and attn2 below read the maps of THIS forward's
+                # compute_merge -- carried on a local)
+                plans = [] if (getattr(self, "merge_mlp", False) is True
+                               or getattr(self, "merge_crossattn", False) is True) else None
+                seg_kw = {} if plans is None else {"plan_to": plans}
+                if norm_hidden_states is None:
+                    hidden_states = self_attention_segment(self, hidden_states, encoder_hidden_states, attention_mask,
+                                                           cross_attention_kwargs, **seg_kw)
+                else:
+                    hidden_states = patched_self_attention_segment(
+                        self, hidden_states, norm_hidden_states, encoder_hidden_states, attention_mask,
+                        cross_attention_kwargs, gate_msa, **seg_kw)
+                if mode1 == "record":
+                    bc.record(bc_name, "attn1", segment_input, hidden_states)
 
             cross_attention_kwargs = cross_attention_kwargs if cross_attention_kwargs is not None else {}
-            if self.attn2 is not None:                                             # patch.py:171-185
+            if mode2 == "reuse":                                                   # attn2 is replayed (with attn1's, above)
+                if mode1 != "reuse":
+                    hidden_states = bc.replay(bc_name, ("attn2",), hidden_states)
+            elif self.attn2 is not None:                                           # patch.py:171-185
+                segment_input = hidden_states
                 maps = self if getattr(self, "vtm_attention_maps", False) else None   # maps.register_attention_maps
                 words = local_blend_of(self)                                       # blend.register_local_blend
                 control = cross_control(self)                                      # p2p.register_cross_attention_control
@@ -1892,6 +1952,8 @@ def make_diffusers_tome_block(block_class: Type[torch.nn.Module]) -> Type[torch.
                     hidden_states = cross_attention(self.attn2, norm_hidden_states, encoder_hidden_states,
                                                     encoder_attention_mask, probs_to=maps, words_to=words, ctl=control,
                                                     route=route, **cross_attention_kwargs) + hidden_states
+                if mode2 == "record":
+                    bc.record(bc_name, "attn2", segment_input, hidden_states)
 
             route = ff_route(self, hidden_states, plans[-1] if plans else None)
             if route != "plain":                                                   # the feed-forward on the merged local tokens
@@ -2047,6 +2109,7 @@ def remove_patch(model: torch.nn.Module):
             module.__dict__.pop("vtm_cross_control", None)     # p2p.register_cross_attention_control's schedule and edits
             module.__dict__.pop("vtm_local_blend", None)       # blend.register_local_blend's accumulator
             module.__dict__.pop(pag.MARK, None)                # pag.register_perturbed_attention's marker (on attn1)
+            module.__dict__.pop("vtm_broadcast", None)         # broadcast.register_attention_broadcast's schedule and caches
     _lib.release_workspaces()            # the cached scratch buffers of the patched path (re-created on demand)
     return roots[-1]                     # the reference returns its loop variable: the last tree walked
 
