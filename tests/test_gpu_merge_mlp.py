@@ -435,7 +435,7 @@ def test_whole_block_through_the_public_api(L, dtype, merge_global):
             assert routes == ["merged-panels"] * len(chunks), routes
             on_small, _ = _forward(unet, UNMERGED, small, cond)
             on_single, _ = _forward(unet, MERGING, single, cond)
-            assert routes[len(chunks):] == ["plain", "plain"], routes
+            assert routes[len(chunks):] == ["panels", "panels"], routes
         finally:
             vpatch.ff_route = orig_route
         assert torch.equal(state_on, state_off), "the flag moved the generator"

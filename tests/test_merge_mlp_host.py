@@ -172,20 +172,20 @@ def test_route_is_plain_without_the_flag_a_local_map_or_with_ada_zero(built):
     unet, blk = _patched()
     x = _tokens()
     assert vpatch.fused_ff_ok(blk.norm3, blk.ff, x)
-    assert vpatch.ff_route(blk, x, _plan()) == "plain"                     # flag unset
+    assert vpatch.ff_route(blk, x, _plan()) == "panels"                    # flag unset
     vidtome_amd.update_patch(unet, merge_mlp=False)
-    assert vpatch.ff_route(blk, x, _plan()) == "plain"
+    assert vpatch.ff_route(blk, x, _plan()) == "panels"
     vidtome_amd.update_patch(unet, merge_mlp=1)                            # the opt-in is True itself, like fp32_projections
-    assert vpatch.ff_route(blk, x, _plan()) == "plain"
+    assert vpatch.ff_route(blk, x, _plan()) == "panels"
     vidtome_amd.update_patch(unet, merge_mlp=True)
     assert vpatch.ff_route(blk, x, _plan()) == "merged-panels"
-    assert vpatch.ff_route(blk, x, None) == "plain"                        # a site that does not merge: no plan
-    assert vpatch.ff_route(blk, x, _plan(local=False)) == "plain"          # single-frame chunk, local_merge_ratio <= 0
+    assert vpatch.ff_route(blk, x, None) == "panels"                       # a site that does not merge: no plan
+    assert vpatch.ff_route(blk, x, _plan(local=False)) == "panels"         # single-frame chunk, local_merge_ratio <= 0
     half = _plan()
     half.inv_local = None
-    assert vpatch.ff_route(blk, x, half) == "plain"
+    assert vpatch.ff_route(blk, x, half) == "panels"
     blk.use_ada_layer_norm_zero = True
-    assert vpatch.ff_route(blk, x, _plan()) == "plain"
+    assert vpatch.ff_route(blk, x, _plan()) == "module"
     blk.use_ada_layer_norm_zero = False
     blk.use_ada_layer_norm = True                                          # AdaLayerNorm keeps a plain norm3
     assert vpatch.ff_route(blk, x, _plan()) == "merged-panels"

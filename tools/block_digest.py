@@ -24,7 +24,13 @@ Cases (fp16 unless named; batch 2, 4 frames, latent 16 x 16, local_merge_ratio 0
                250 tokens: maps registered (plain, masked, IP-Adapter), a LocalBlend registered (plain, IP-Adapter),
                cross-attention control at an injecting step (four groups: the source, an identity, an edited one, one without an
                edit) with maps and blend registered, and control outside its schedule with maps, with a blend, with both.  These
-               lines carry two more hashes: ``attn2_probs`` and the LocalBlend accumulator"""
+               lines carry two more hashes: ``attn2_probs`` and the LocalBlend accumulator
+  ff/*         the block's feed-forward tail through the block forward and the public API alone (FF_CASES; the route and the
+               tail's wrappers of each row: tests/test_gpu_ff_route.py): every row of ``patch.ff_route``'s table without and with
+               ``merge_mlp``, an AdaLayerNormZero stand-in at a site that does not merge, and attention broadcast
+               (FF_BROADCAST_CASES: one line per step -- a record step, then the reuse of attn1, of attn2 or of both).  The one
+               forward that raises is a line too, its wrappers up to there and the exception's type: an fp16 block with fp32
+               feed-forward weights, whose mixed-dtype GEMM torch refuses on the host"""
 import argparse
 import hashlib
 import os
@@ -38,7 +44,8 @@ B, FRAMES, LATENT = 2, 4, (16, 16)
 SPIED = ("layernorm", "layernorm_panels", "gather_rows", "gather_panels", "to_panels", "transpose_cols", "linear_rows",
          "linear_panels", "linear_f32", "attention", "attention_kv", "attention_kv_bias", "attention_kv_sets",
          "attention_kv_sets_masked", "attention_kv_sets_src", "cross_edit_values", "attention_probs", "attention_word_map",
-         "compact_queries", "fold_keys", "compose", "anchor_maps", "unmerge_add", "ff_geglu", "geglu")
+         "compact_queries", "fold_keys", "compose", "anchor_maps", "unmerge_add", "ff_geglu", "geglu", "layernorm_gather",
+         "residual_record", "residual_replay", "residual_replay_layernorm")
 
 # name -> (dtype, C, heads, options); the expected route of each row is tests/test_gpu_attn1_route.py's table
 ROUTE_CASES = {
@@ -392,6 +399,135 @@ def run_f32_blocks(vidtome_amd, out):
     vidtome_amd.remove_patch(unet)
 
 
+# feed-forward rows: name -> (dtype, C, heads, options)
+FF_CASES = {
+    "fp16 C=320": (torch.float16, 320, 8, {}),
+    "bf16 C=640": (torch.bfloat16, 640, 8, {}),
+    "fp16 C=160 heads 4": (torch.float16, 160, 4, {}),
+    "FF_MODE=blas": (torch.float16, 320, 8, {"ff_mode": "blas"}),
+    "fp32": (torch.float32, 320, 8, {"counting": True}),
+    "fp32 fp32_projections": (torch.float32, 320, 8, {"fp32_projections": True}),
+    "a non-GEGLU ff": (torch.float16, 320, 8, {"plain_ff": True}),
+    "a LayerNorm subclass as norm3": (torch.float16, 320, 8, {"other_norm3": True}),
+    "fp32 ff weights in an fp16 block": (torch.float16, 320, 8, {"f32_ff": True, "raises": True}),
+    # (at a site that does not merge: the gate of attn1 is per frame row, patch.py:165, and so fits un-merged tokens alone)
+    "AdaLayerNormZero": (torch.float16, 320, 8, {"ada_zero": True, "unmerged": True}),
+    "AdaLayerNormZero merge_mlp": (torch.float16, 320, 8, {"ada_zero": True, "unmerged": True, "merge_mlp": True}),
+    "merge_mlp fp16": (torch.float16, 320, 8, {"merge_mlp": True}),
+    "merge_mlp FF_MODE=blas": (torch.float16, 320, 8, {"merge_mlp": True, "ff_mode": "blas"}),
+    "merge_mlp fp32 fp32_projections": (torch.float32, 320, 8, {"merge_mlp": True, "fp32_projections": True}),
+    "merge_mlp single-frame chunk": (torch.float16, 320, 8, {"merge_mlp": True, "frames": 1}),
+    "merge_mlp un-merged site": (torch.float16, 320, 8, {"merge_mlp": True, "unmerged": True}),
+}
+# broadcast rows: name -> (FF_CASES row of the block, attn1_every, attn2_every); steps 0 (record) and 1 (reuse) of each
+FF_BROADCAST_CASES = {
+    "attn1 reuse": ("fp16 C=320", 2, None),
+    "attn2 reuse": ("fp16 C=320", None, 2),
+    "both reuse fp16": ("fp16 C=320", 2, 2),
+    "both reuse FF_MODE=blas": ("FF_MODE=blas", 2, 2),
+    "both reuse fp32 fp32_projections": ("fp32 fp32_projections", 2, 2),
+}
+
+
+class OtherNorm(torch.nn.LayerNorm):
+    """Computes a LayerNorm, but is not the class the fused paths read."""
+
+
+class PlainFF(torch.nn.Module):
+    """A feed-forward that is not the GEGLU one."""
+
+    def __init__(self, C):
+        super().__init__()
+        self.net = torch.nn.ModuleList([torch.nn.Linear(C, C)])
+
+    def forward(self, x):
+        return self.net[0](x)
+
+
+class AdaZeroNorm1(torch.nn.Module):
+    """An AdaLayerNormZero norm1: a LayerNorm of its input and four seeded (B F, C) tensors -- gate_msa, shift_mlp, scale_mlp,
+    gate_mlp."""
+
+    def __init__(self, n, C, dtype, seed=17):
+        super().__init__()
+        g = torch.Generator().manual_seed(seed)
+        self.parts = [(torch.randn(n, C, generator=g) * 0.25).to(device=DEV, dtype=dtype) for _ in range(4)]
+
+    def forward(self, x, timestep=None, class_labels=None, hidden_dtype=None):
+        return (torch.nn.functional.layer_norm(x, x.shape[-1:]), *self.parts)
+
+
+def ff_case(vidtome_amd, name):
+    """(model, block, hidden states, text conditioning, restore) of one FF_CASES row: a full block (77 text tokens of width 768)
+    set up through ``apply_patch`` / ``update_patch`` alone; call ``restore()`` afterwards."""
+    from vidtome_amd import patch as vpatch, sites as S
+    dt, C, heads, opt = FF_CASES[name]
+    frames = opt.get("frames", FRAMES)
+    text = torch.randn(B * frames, 77, 768, generator=torch.Generator().manual_seed(3)).to(device=DEV, dtype=dt)
+    torch.manual_seed(123)
+    unet, site, blk = site_block(vidtome_amd, S, dt, C, heads, unmerged=opt.get("unmerged", False), full=True)
+    if opt.get("fp32_projections"):
+        vidtome_amd.update_patch(unet, fp32_projections=True)
+    if opt.get("merge_mlp"):
+        vidtome_amd.update_patch(unet, merge_mlp=True)
+    if opt.get("counting"):                                  # (attn2 of a plain fp32 block is the module's own forward)
+        blk.attn2.__class__ = type("Attention", (CountingAttention, type(blk.attn2)), {})
+    if opt.get("plain_ff"):
+        blk.ff = PlainFF(C).to(device=DEV, dtype=dt)
+    if opt.get("other_norm3"):
+        norm3 = OtherNorm(C).to(device=DEV, dtype=dt)
+        norm3.load_state_dict(blk.norm3.state_dict())
+        blk.norm3 = norm3
+    if opt.get("f32_ff"):
+        blk.ff.float()
+    if opt.get("ada_zero"):
+        blk.norm1, blk.use_ada_layer_norm_zero = AdaZeroNorm1(B * frames, C, dt), True
+    keep_ff = vpatch.FF_MODE
+    vpatch.FF_MODE = opt.get("ff_mode", "panels")
+    h = S.synthetic_hidden(site, B, frames, LATENT, dt, DEV, seed=50, clip_seed=7)
+
+    def restore():
+        vpatch.FF_MODE = keep_ff
+        vidtome_amd.remove_patch(unet)
+    return unet, blk, h, text, restore
+
+
+def run_ff(vidtome_amd, out):
+    """The feed-forward tail of every FF_CASES row, and of every FF_BROADCAST_CASES row at its two steps."""
+    from vidtome_amd import _lib
+
+    def forward(tag, blk, h, text, raises=False):
+        with torch.no_grad(), Spy(_lib) as spy:
+            try:
+                y = blk(h, encoder_hidden_states=text)
+            except RuntimeError as e:                        # (raised on the host: see the docstring)
+                if not raises:
+                    raise
+                out.append(f"{tag} | {' '.join(spy.calls)} | raised {type(e).__name__}")
+                return
+        if raises:
+            raise SystemExit(f"block_digest: {tag} was to raise")
+        emit(out, tag, spy, y, blk)
+
+    for name in FF_CASES:
+        unet, blk, h, text, restore = ff_case(vidtome_amd, name)
+        try:
+            forward(f"ff/{name} block forward", blk, h, text, FF_CASES[name][3].get("raises", False))
+        finally:
+            restore()
+    for name, (row, every1, every2) in FF_BROADCAST_CASES.items():
+        unet, blk, h, text, restore = ff_case(vidtome_amd, row)
+        try:
+            bc = vidtome_amd.AttentionBroadcast([999, 666, 333, 0], FRAMES, attn1_every=every1, attn2_every=every2,
+                                                attn1_window=(0, 1000), attn2_window=(0, 1000))
+            vidtome_amd.register_attention_broadcast(unet, bc)
+            for step in (0, 1):
+                bc.set_step(step)
+                forward(f"ff/broadcast {name} step {step} ({' '.join(bc.modes(step))})", blk, h, text)
+        finally:
+            restore()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--package", default=ROOT, help="directory holding the vidtome_amd package to import")
@@ -419,6 +555,7 @@ def main():
     run_cross(vidtome_amd, out)
     run_f32_blocks(vidtome_amd, out)
     run_cross_side(vidtome_amd, out)
+    run_ff(vidtome_amd, out)
     torch.cuda.synchronize()
     out.append("occurred in chunks/*: " + "; ".join(sorted(seen)))
     text = "\n".join(out) + "\n"

@@ -884,6 +884,35 @@ def self_attention_segment(block: torch.nn.Module, hidden_states: torch.Tensor, 
                                           plan_to=plan_to)
 
 
+def cross_attention_segment(block: torch.nn.Module, hidden_states: torch.Tensor, encoder_hidden_states, encoder_attention_mask,
+                            cross_attention_kwargs, timestep, plan: Optional["MergePlan"]) -> torch.Tensor:
+    """patch.py:171-185: norm2 -> attn2 -> + residual on the body ``attn2_route`` and ``cross_merge_route`` name.  ``plan``:
+    the MergePlan of this forward's attn1 segment (None: nothing merged, or nobody asked for it)."""
+    cross_attention_kwargs = cross_attention_kwargs if cross_attention_kwargs is not None else {}
+    maps = block if getattr(block, "vtm_attention_maps", False) else None      # maps.register_attention_maps
+    words = local_blend_of(block)                                              # blend.register_local_blend
+    control = cross_control(block)                                             # p2p.register_cross_attention_control
+    route = attn2_route(block, hidden_states, encoder_hidden_states, encoder_attention_mask, cross_attention_kwargs, control)
+    if cross_merge_route(block, hidden_states, plan, route, encoder_hidden_states,
+                         encoder_attention_mask) == "merged-panels":           # attn2 on the merged local tokens
+        return merged_cross_attention_residual(block, hidden_states, encoder_hidden_states, plan)
+    if route.frame == "panels":
+        return norm_cross_attention_residual(block.norm2, block.attn2, hidden_states, encoder_hidden_states, route.ip,
+                                             encoder_attention_mask, maps, words, control)
+    if route.frame == "f32":
+        return norm_cross_attention_f32(block.norm2, block.attn2, hidden_states, encoder_hidden_states, probs_to=maps,
+                                        words_to=words)
+    # "blas", "module": both read normed tokens
+    norm_hidden_states = (block.norm2(hidden_states, timestep) if block.use_ada_layer_norm
+                          else layer_norm(block.norm2, hidden_states))
+    if control is None and norm_hidden_states.dtype != hidden_states.dtype:
+        # (the route reads the tokens' dtype: a norm2 that changes it is routed on its output)
+        route = attn2_route(block, norm_hidden_states, encoder_hidden_states, encoder_attention_mask, cross_attention_kwargs,
+                            normed=True)
+    return cross_attention(block.attn2, norm_hidden_states, encoder_hidden_states, encoder_attention_mask, probs_to=maps,
+                           words_to=words, ctl=control, route=route, **cross_attention_kwargs) + hidden_states
+
+
 def self_attention_rows(attn: torch.nn.Module, x0: torch.Tensor, x1: Optional[torch.Tensor],
                         rows: Optional[torch.Tensor], q_rows: Optional[torch.Tensor] = None,
                         q_count: Optional[torch.Tensor] = None, plan: Optional["MergePlan"] = None,
@@ -1551,17 +1580,26 @@ def _geglu_ff(ff: torch.nn.Module):
     return None
 
 
+def _geglu_dims(ff: torch.nn.Module, x: torch.Tensor):
+    """(GEGLU projection, output Linear, C, D) of ``_geglu_ff`` -- the two BASE Linears (shapes and dtypes of the effective
+    weights) -- where they chain C -> 2 D -> D -> C over the channels of ``x``; else None."""
+    lin = _geglu_ff(ff)
+    if lin is not None:
+        proj, out = (lora.base_linear(m) for m in lin)
+        C, D = x.shape[-1], proj.out_features // 2
+        if proj.in_features == C and proj.out_features == 2 * D and out.in_features == D and out.out_features == C:
+            return proj, out, C, D
+    return None
+
+
 def fused_ff_ok(norm: torch.nn.Module, ff: torch.nn.Module, x: torch.Tensor) -> bool:
     if FF_MODE != "panels" or not x.is_cuda or x.dtype not in (torch.float16, torch.bfloat16):
         return False
-    lin = _geglu_ff(ff)
-    if lin is None or not _plain_layernorm(norm, x):
+    dims = _geglu_dims(ff, x)
+    if dims is None or not _plain_layernorm(norm, x):
         return False
-    proj, out = (lora.base_linear(m) for m in lin)
-    C = x.shape[-1]
-    D = proj.out_features // 2
-    return (C % 64 == 0 and C <= 2048 and proj.in_features == C and D % 64 == 0 and out.in_features == D
-            and out.out_features == C and proj.weight.dtype == x.dtype and out.weight.dtype == x.dtype)
+    proj, out, C, D = dims
+    return C % 64 == 0 and C <= 2048 and D % 64 == 0 and proj.weight.dtype == x.dtype and out.weight.dtype == x.dtype
 
 
 def _ff_panel_weights(ff: torch.nn.Module):
@@ -1582,31 +1620,38 @@ def _ff_panel_weights(ff: torch.nn.Module):
     return w1, b1, D, w2, b2
 
 
+def _ff_panels(weights, xp: torch.Tensor, n: int, resid: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The two GEMMs of a feed-forward ``fused_ff_ok`` accepted, over the k-panels ``xp`` of its n LayerNorm'ed rows: the GEGLU
+    projection with the gated activation in its epilogue -> k-panels, the output Linear + bias (+ ``resid`` (n, C)) -> (n, C)
+    token rows.  The one place vtm_ff_geglu is reached from; the panels come from vtm_layernorm_panels
+    (``norm_feed_forward_residual``), vtm_layernorm_gather (``merged_feed_forward_residual``) or
+    vtm_residual_replay_layernorm (``broadcast_feed_forward_residual``).  ``weights``: ``_ff_panel_weights(ff)``, which each
+    caller takes AHEAD of its LayerNorm launch -- a first call packs there (vtm_to_panels), and launch order is kept."""
+    w1, b1, D, w2, b2 = weights
+    hp = _lib.ff_geglu(xp, n, w1, D, b1)
+    return _lib.linear_panels(hp, n, w2, xp.shape[0] * 8, b2, resid=resid)        # (C / 8 panels in, C columns out)
+
+
 def norm_feed_forward_residual(norm: torch.nn.Module, ff: torch.nn.Module, hidden_states: torch.Tensor) -> torch.Tensor:
     """patch.py:187-199 for the plain-LayerNorm block: ``ff(norm3(hidden_states)) + hidden_states`` as three launches:
     LayerNorm -> k-panels, GEGLU projection with the gated activation in its epilogue -> k-panels, output Linear + bias +
     residual -> token rows.  The caller has checked ``fused_ff_ok``."""
-    C = hidden_states.shape[-1]
-    w1, b1, D, w2, b2 = _ff_panel_weights(ff)
+    weights = _ff_panel_weights(ff)
     hs = hidden_states.contiguous()
-    n = hs.numel() // C
+    n = hs.numel() // hs.shape[-1]
     xp = _lib.layernorm_panels(hs, norm.weight, norm.bias, norm.eps)
-    hp = _lib.ff_geglu(xp, n, w1, D, b1)
-    return _lib.linear_panels(hp, n, w2, C, b2, resid=hs.view(n, C)).view(hidden_states.shape)
+    return _ff_panels(weights, xp, n, hs.view(n, -1)).view(hidden_states.shape)
 
 
 def f32_ff_ok(block: torch.nn.Module, norm: torch.nn.Module, ff: torch.nn.Module, x: torch.Tensor) -> bool:
     """The feed-forward of an fp32 block with the ``fp32_projections`` opt-in on the fp32 GEMMs (norm_feed_forward_f32)."""
     if not (_fp32_projections(block) and x.is_cuda and x.dtype == torch.float32 and _f32_layernorm_ok(norm, x)):
         return False
-    lin = _geglu_ff(ff)
-    if lin is None:
+    dims = _geglu_dims(ff, x)
+    if dims is None:
         return False
-    proj, out = (lora.base_linear(m) for m in lin)
-    C = x.shape[-1]
-    D = proj.out_features // 2
-    return (proj.in_features == C and proj.out_features == 2 * D and D % 8 == 0 and out.in_features == D
-            and out.out_features == C and _linear_dtype_ok(lin[0], torch.float32) and _linear_dtype_ok(lin[1], torch.float32))
+    proj, out, C, D = dims
+    return D % 8 == 0 and _linear_dtype_ok(proj, torch.float32) and _linear_dtype_ok(out, torch.float32)
 
 
 def norm_feed_forward_f32(norm: torch.nn.Module, ff: torch.nn.Module, hidden_states: torch.Tensor) -> torch.Tensor:
@@ -1639,23 +1684,63 @@ def feed_forward(ff: torch.nn.Module, x: torch.Tensor) -> torch.Tensor:
 
 def ff_route(block: torch.nn.Module, hidden_states: torch.Tensor, plan: Optional["MergePlan"]) -> str:
     """How the block computes its feed-forward on hidden states like ``hidden_states`` (B F, N, C) behind the attn1 segment
-    whose compute_merge gave ``plan`` (None: nothing merged).  Launches nothing.
-      "plain"          today's feed-forward over every token (the forward's own choice among norm_feed_forward_residual,
-                       norm_feed_forward_f32 and the module): the block's ``merge_mlp`` opt-in (``update_patch(model,
-                       merge_mlp=True)``) is unset, or there is no local map -- a site that does not merge, a single-frame
-                       chunk, local_merge_ratio <= 0 -- or the block is an AdaLayerNormZero one (its shift / scale / gate are
-                       per frame row)
-      "merged-panels"  ``u(ff(norm3(m(h)))) + h`` over the local levels' closures (tomesd's merge_mlp) as vtm_layernorm_gather
-                       -> vtm_ff_geglu -> vtm_linear_panels -> vtm_unmerge_add: where ``fused_ff_ok`` holds
-      "merged"         the same on every other feed-forward (fp32 models, VIDTOME_FF=blas, a ``ff`` that is not the GEGLU
-                       one, projections the panel path does not read): gathered LayerNorm with token rows out (or
-                       vtm_gather_rows + the norm module), ``feed_forward``, vtm_unmerge_add
+    whose compute_merge gave ``plan`` (None: nothing merged).  Launches nothing; decided once per forward, and
+    ``feed_forward_segment`` calls the body.  The first row that holds, "on the merged tokens" meaning: the block's
+    ``merge_mlp`` opt-in (``update_patch(model, merge_mlp=True)``) is True itself AND there is a local map (``plan.keep`` and
+    ``plan.inv_local``: not a site that does not merge, a single-frame chunk, local_merge_ratio <= 0 or a replayed attn1) AND
+    the block is no AdaLayerNormZero one (its shift / scale / gate are per frame row):
+      "merged-panels"  on the merged tokens, and ``fused_ff_ok``: ``u(ff(norm3(m(h)))) + h`` over the local levels' closures
+                       (tomesd's merge_mlp) as vtm_layernorm_gather -> vtm_ff_geglu -> vtm_linear_panels -> vtm_unmerge_add
+                       (``merged_feed_forward_residual``)
+      "merged"         on the merged tokens, every other feed-forward (fp32 models, VIDTOME_FF=blas, a ``ff`` that is not the
+                       GEGLU one, projections the panel path does not read): gathered LayerNorm with token rows out (or
+                       vtm_gather_rows + the norm module), ``feed_forward``, vtm_unmerge_add (the same body)
+      "panels"         over every token, no AdaLayerNormZero block, and ``fused_ff_ok``: vtm_layernorm_panels -> vtm_ff_geglu
+                       -> vtm_linear_panels with the residual (``norm_feed_forward_residual``)
+      "f32"            over every token, no AdaLayerNormZero block, and ``f32_ff_ok`` (an fp32 block with ``fp32_projections``):
+                       vtm_layernorm and the two fp32 GEMMs (``norm_feed_forward_f32``)
+      "module"         everything else, every AdaLayerNormZero block among it: ``layer_norm``, the shift / scale,
+                       ``feed_forward``, the gate, the residual (``module_feed_forward_residual``)
+    So an fp32 block with ``fp32_projections`` AND ``merge_mlp`` is "merged" where it merges, not "f32" (there is no merged
+    fp32-GEMM body); an AdaLayerNorm (non-zero) block keeps a plain norm3 and may be "panels" or "merged-panels"; and
+    ``fused_ff_ok`` is evaluated at most once.
     The global level plays no part: its merged sequence holds other chunks' anchor rows, whose feed-forward output nobody
     would read.  The matching is the one attn1 used in this forward; nothing is drawn."""
-    if (getattr(block, "merge_mlp", False) is not True or block.use_ada_layer_norm_zero or plan is None
-            or plan.keep is None or plan.inv_local is None):
-        return "plain"
-    return "merged-panels" if fused_ff_ok(block.norm3, block.ff, hidden_states) else "merged"
+    if block.use_ada_layer_norm_zero:
+        return "module"
+    merged = (getattr(block, "merge_mlp", False) is True and plan is not None and plan.keep is not None
+              and plan.inv_local is not None)
+    if fused_ff_ok(block.norm3, block.ff, hidden_states):
+        return "merged-panels" if merged else "panels"
+    if merged:
+        return "merged"
+    return "f32" if f32_ff_ok(block, block.norm3, block.ff, hidden_states) else "module"
+
+
+def module_feed_forward_residual(norm: torch.nn.Module, ff: torch.nn.Module, hidden_states: torch.Tensor, ada=None
+                                 ) -> torch.Tensor:
+    """patch.py:187-199 as written, the "module" feed-forward of ``ff_route``: ``ff(norm3(h)) + h`` through ``layer_norm`` and
+    ``feed_forward``.  ``ada``: an AdaLayerNormZero block's (shift_mlp, scale_mlp, gate_mlp) of this forward's norm1, each
+    (B F, C); None on every other block."""
+    norm_hidden_states = layer_norm(norm, hidden_states)
+    if ada is None:
+        return feed_forward(ff, norm_hidden_states) + hidden_states
+    shift_mlp, scale_mlp, gate_mlp = ada
+    norm_hidden_states = norm_hidden_states * (1 + scale_mlp[:, None]) + shift_mlp[:, None]
+    return gate_mlp.unsqueeze(1) * feed_forward(ff, norm_hidden_states) + hidden_states
+
+
+def feed_forward_segment(block: torch.nn.Module, hidden_states: torch.Tensor, plan: Optional["MergePlan"], route: str,
+                         ada=None) -> torch.Tensor:
+    """The block's feed-forward segment on the body ``route`` (what ``ff_route`` answered for this call) names; ``ada`` goes to
+    the "module" body alone -- no other route is taken on an AdaLayerNormZero block."""
+    if route in ("merged-panels", "merged"):
+        return merged_feed_forward_residual(block, hidden_states, plan, route)
+    if route == "panels":
+        return norm_feed_forward_residual(block.norm3, block.ff, hidden_states)
+    if route == "f32":
+        return norm_feed_forward_f32(block.norm3, block.ff, hidden_states)
+    return module_feed_forward_residual(block.norm3, block.ff, hidden_states, ada)
 
 
 def merged_feed_forward_residual(block: torch.nn.Module, hidden_states: torch.Tensor, plan: "MergePlan", route: str
@@ -1670,10 +1755,9 @@ def merged_feed_forward_residual(block: torch.nn.Module, hidden_states: torch.Te
     Ml = keep.shape[1]
     if route == "merged-panels":
         # (the panels of all samples are one row range: sample b at rows b * M_l, like norm_feed_forward_residual's b * L)
-        w1, b1, D, w2, b2 = _ff_panel_weights(ff)
+        weights = _ff_panel_weights(ff)
         xp = _lib.layernorm_gather(hj, keep, norm.weight, norm.bias, norm.eps)
-        hp = _lib.ff_geglu(xp, B * Ml, w1, D, b1)
-        y = _lib.linear_panels(hp, B * Ml, w2, C, b2).view(B, Ml, C)
+        y = _ff_panels(weights, xp, B * Ml).view(B, Ml, C)
     else:
         if _lib_layernorm_ok(norm, hj):
             xn = _lib.layernorm_gather(hj, keep, norm.weight, norm.bias, norm.eps, panels=False)
@@ -1868,14 +1952,13 @@ def broadcast_modes(block: torch.nn.Module):
 
 def broadcast_feed_forward_residual(bc, name: str, norm: torch.nn.Module, ff: torch.nn.Module, hidden_states: torch.Tensor
                                     ) -> torch.Tensor:
-    """The whole block on a step that replays both attentions, where ``fused_ff_ok`` holds: h2 = h + d1 + d2 and norm3(h2) as
-    k-panels from ONE launch (vtm_residual_replay_layernorm), then ``norm_feed_forward_residual``'s two GEMMs on them."""
-    C = hidden_states.shape[-1]
-    w1, b1, D, w2, b2 = _ff_panel_weights(ff)
+    """The whole block on a step that replays both attentions, where ``ff_route`` answers "panels": h2 = h + d1 + d2 and
+    norm3(h2) as k-panels from ONE launch (vtm_residual_replay_layernorm), then ``norm_feed_forward_residual``'s two GEMMs on
+    them."""
+    weights = _ff_panel_weights(ff)
     h2, xp = bc.replay_layernorm(name, hidden_states, norm)
-    n = h2.numel() // C
-    hp = _lib.ff_geglu(xp, n, w1, D, b1)
-    return _lib.linear_panels(hp, n, w2, C, b2, resid=h2.view(n, C)).view(hidden_states.shape)
+    n = h2.numel() // h2.shape[-1]
+    return _ff_panels(weights, xp, n, h2.view(n, -1)).view(hidden_states.shape)
 
 
 def make_diffusers_tome_block(block_class: Type[torch.nn.Module]) -> Type[torch.nn.Module]:
@@ -1888,20 +1971,24 @@ def make_diffusers_tome_block(block_class: Type[torch.nn.Module]) -> Type[torch.
                     encoder_attention_mask=None, timestep=None, cross_attention_kwargs=None,
                     class_labels=None) -> torch.Tensor:
             bc, bc_name, mode1, mode2 = broadcast_modes(self)                      # broadcast.register_attention_broadcast
+            plan = ada = route = None
             if mode1 == "reuse":
                 # attn1 is replayed: no norm1, no compute_merge (no draw, no global-token update), so no MergePlan either --
-                # merge_mlp / merge_crossattn take their plain paths ("no local map")
-                if mode2 == "reuse" and fused_ff_ok(self.norm3, self.ff, hidden_states):
-                    return broadcast_feed_forward_residual(bc, bc_name, self.norm3, self.ff, hidden_states)
+                # merge_mlp / merge_crossattn take their paths over every token ("no local map")
+                if mode2 == "reuse":
+                    # (attn2's delta rides in the same launch; with the "panels" feed-forward, norm3 does too.  The replay
+                    # changes neither shape nor dtype: the route asked here is the feed-forward's below)
+                    route = ff_route(self, hidden_states, None)
+                    if route == "panels":
+                        return broadcast_feed_forward_residual(bc, bc_name, self.norm3, self.ff, hidden_states)
                 hidden_states = bc.replay(bc_name, ("attn1", "attn2") if mode2 == "reuse" else ("attn1",), hidden_states)
-                plans = None
             else:
                 segment_input = hidden_states
                 gate_msa = None
                 if self.use_ada_layer_norm:                                        # patch.py:139-146
                     norm_hidden_states = self.norm1(hidden_states, timestep)
                 elif self.use_ada_layer_norm_zero:
-                    norm_hidden_states, gate_msa, shift_mlp, scale_mlp, gate_mlp = self.norm1(
+                    norm_hidden_states, gate_msa, *ada = self.norm1(
                         hidden_states, timestep, class_labels, hidden_dtype=hidden_states.dtype)
                 else:
                     norm_hidden_states = None
@@ -1919,56 +2006,25 @@ def make_diffusers_tome_block(block_class: Type[torch.nn.Module]) -> Type[torch.
                     hidden_states = patched_self_attention_segment(
                         self, hidden_states, norm_hidden_states, encoder_hidden_states, attention_mask,
                         cross_attention_kwargs, gate_msa, **seg_kw)
+                plan = plans[-1] if plans else None
                 if mode1 == "record":
                     bc.record(bc_name, "attn1", segment_input, hidden_states)
 
-            cross_attention_kwargs = cross_attention_kwargs if cross_attention_kwargs is not None else {}
+            # 2. cross-attention                                                   # patch.py:171-185
             if mode2 == "reuse":                                                   # attn2 is replayed (with attn1's, above)
                 if mode1 != "reuse":
                     hidden_states = bc.replay(bc_name, ("attn2",), hidden_states)
-            elif self.attn2 is not None:                                           # patch.py:171-185
+            elif self.attn2 is not None:
                 segment_input = hidden_states
-                maps = self if getattr(self, "vtm_attention_maps", False) else None   # maps.register_attention_maps
-                words = local_blend_of(self)                                       # blend.register_local_blend
-                control = cross_control(self)                                      # p2p.register_cross_attention_control
-                route = attn2_route(self, hidden_states, encoder_hidden_states, encoder_attention_mask, cross_attention_kwargs,
-                                    control)
-                if cross_merge_route(self, hidden_states, plans[-1] if plans else None, route, encoder_hidden_states,
-                                     encoder_attention_mask) == "merged-panels":   # attn2 on the merged local tokens
-                    hidden_states = merged_cross_attention_residual(self, hidden_states, encoder_hidden_states, plans[-1])
-                elif route.frame == "panels":
-                    hidden_states = norm_cross_attention_residual(self.norm2, self.attn2, hidden_states, encoder_hidden_states,
-                                                                  route.ip, encoder_attention_mask, maps, words, control)
-                elif route.frame == "f32":
-                    hidden_states = norm_cross_attention_f32(self.norm2, self.attn2, hidden_states, encoder_hidden_states,
-                                                             probs_to=maps, words_to=words)
-                else:                                                              # "blas", "module": both read normed tokens
-                    norm_hidden_states = (self.norm2(hidden_states, timestep) if self.use_ada_layer_norm
-                                          else layer_norm(self.norm2, hidden_states))
-                    if control is None and norm_hidden_states.dtype != hidden_states.dtype:
-                        # (the route reads the tokens' dtype: a norm2 that changes it is routed on its output)
-                        route = attn2_route(self, norm_hidden_states, encoder_hidden_states, encoder_attention_mask,
-                                            cross_attention_kwargs, normed=True)
-                    hidden_states = cross_attention(self.attn2, norm_hidden_states, encoder_hidden_states,
-                                                    encoder_attention_mask, probs_to=maps, words_to=words, ctl=control,
-                                                    route=route, **cross_attention_kwargs) + hidden_states
+                hidden_states = cross_attention_segment(self, hidden_states, encoder_hidden_states, encoder_attention_mask,
+                                                        cross_attention_kwargs, timestep, plan)
                 if mode2 == "record":
                     bc.record(bc_name, "attn2", segment_input, hidden_states)
 
-            route = ff_route(self, hidden_states, plans[-1] if plans else None)
-            if route != "plain":                                                   # the feed-forward on the merged local tokens
-                return merged_feed_forward_residual(self, hidden_states, plans[-1], route)
-            if not self.use_ada_layer_norm_zero and fused_ff_ok(self.norm3, self.ff, hidden_states):   # patch.py:187-199
-                return norm_feed_forward_residual(self.norm3, self.ff, hidden_states)
-            if not self.use_ada_layer_norm_zero and f32_ff_ok(self, self.norm3, self.ff, hidden_states):
-                return norm_feed_forward_f32(self.norm3, self.ff, hidden_states)
-            norm_hidden_states = layer_norm(self.norm3, hidden_states)
-            if self.use_ada_layer_norm_zero:
-                norm_hidden_states = norm_hidden_states * (1 + scale_mlp[:, None]) + shift_mlp[:, None]
-            ff_output = feed_forward(self.ff, norm_hidden_states)
-            if self.use_ada_layer_norm_zero:
-                ff_output = gate_mlp.unsqueeze(1) * ff_output
-            return ff_output + hidden_states
+            # 3. feed-forward                                                      # patch.py:187-199
+            if route is None:
+                route = ff_route(self, hidden_states, plan)
+            return feed_forward_segment(self, hidden_states, plan, route, ada)
 
     return ToMeBlock
 
